@@ -18,6 +18,12 @@ the model; `replica_value` beside it = N independent models, one per rank (no da
 coincide and `value` is the plain build; `single_model` keeps the ring code's N=1 figure.  `init_db` (N=1) times the
 reference's real entry point, KModel::init on a KMC database of the same stream in tmpfs (kmodel.hpp:57-86), host feed
 included.
+
+A plain run (no --full) does only what the headline needs: it sets up, warms up, times the `--steps` insert steps and
+the `--steps` query steps, writes the outputs of the last step if --dump-outputs is given, and prints the line (at N>1
+the single-model leg is the headline and runs too).  Everything else -- roofline and per-kernel figures, init_db,
+query_genome, query_strings, the N=1 single_model figure, the other partition, the C++ multi-GPU entry, the CPU
+baseline -- runs only with --full (and its --no-* switches apply there).
 """
 import argparse
 import json
@@ -49,6 +55,9 @@ def parse():
     ap.add_argument("--cs", type=int, default=1023)
     ap.add_argument("--nh", type=int, default=7)
     ap.add_argument("--nb", type=int, default=5)
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (roofline, init_db, genome, strings, single_model at N=1, "
+                                                         "other partition, C++ multi-GPU entry, CPU baseline); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed in its last step as DIR/<name>.npy (float32/float64)")
     ap.add_argument("--cpu-sample", type=int, default=4_000_000, help="k-mers of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-init-db", action="store_true", help="skip the KModel::init(database) leg")
@@ -451,6 +460,34 @@ def single_model_leg(a, m, km, cnt, q, out, rank, world, dev, rehearsal, distrib
             "stats": {"n_km": st.n_km, "attempts": st.attempts, "successes": st.successes, "rest_entries": st.rest_entries}}
 
 
+DUMP_BYTES = 56 << 20                                               # what --dump-outputs writes at most, whatever nb is (limit: 64 MB)
+
+
+def dump_outputs(path, m, out):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step, as .npy files two builds can be compared by.
+    The model: of every coupled tag / value array, km_back and the filters, a fixed seeded sample of its bytes (float32) and
+    (size, popcount, CRC-32) of the whole array (model_array_digests, float64, one row per array in file order), plus
+    (n_km, successes, rest_entries, rest_bytes).  The answers of the last kmer_to_occ step: a fixed seeded sample (float32)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    st = m.stats()
+    arrays = ([("tag", a) for a in range(st.nb)] + [("value", a) for a in range(st.nb)] + [("km_back", 0)]
+              + [("bf", i) for i in range(st.bf_num)] + [("bf_back", i) for i in range(st.bf_num)])
+    nq = min(out.numel(), 1 << 21)
+    per_array = max(1, min(1 << 20, (DUMP_BYTES // 4 - nq) // len(arrays)))
+    idx = np.sort(np.random.default_rng([0x6B6D78, 0]).integers(0, out.numel(), nq))
+    np.save(os.path.join(path, "query_occ.npy"), out[torch.from_numpy(idx).to(out.device)].cpu().numpy().astype(np.float32))
+    popcount = np.array([bin(v).count("1") for v in range(256)], dtype=np.int64)
+    digests = []
+    for j, (which, i) in enumerate(arrays):
+        b = m.download(which, i)
+        digests.append([b.size, int(np.bincount(b, minlength=256) @ popcount), zlib.crc32(b)])
+        sel = np.sort(np.random.default_rng([0x6B6D78, 1 + j]).integers(0, max(b.size, 1), min(per_array, b.size)))
+        np.save(os.path.join(path, f"model_{which}_{i}.npy"), b[sel].astype(np.float32))
+    np.save(os.path.join(path, "model_array_digests.npy"), np.array(digests, dtype=np.float64))
+    np.save(os.path.join(path, "model_counts.npy"), np.array([st.n_km, st.successes, st.rest_entries, st.rest_bytes], dtype=np.float64))
+
+
 _REAL_STDOUT = None
 
 
@@ -559,11 +596,13 @@ def main():
     t_q = time.perf_counter() - t0
     (t_ins, t_q), (n_all, nq_all) = kd.reduce_job([t_ins, t_q], [n, q.numel()], device="cpu" if rehearsal else dev)   # MAX of times, SUM of units
     st = m.stats()
+    if rank == 0 and world == 1 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, m, out)
 
     # ---- roofline leg: same steps again with HIP events around every launch of each kernel class
     roof = None
     extra = {}
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         m.set_profile(True)
         m.kernel_times(reset=True)
         for _ in range(a.steps):
@@ -658,24 +697,24 @@ def main():
                                            "gather_GBps_at_32B": (1 << 27) * G / tg / 1e9,
                                            "atomic_GBps_at_32B": (1 << 27) * G / ta / 1e9}}
     init_db = {}
-    if rank == 0 and world == 1 and not a.no_init_db and a.k <= 31:
+    if rank == 0 and world == 1 and a.full and not a.no_init_db and a.k <= 31:
         try:
             init_db = init_db_leg(a, km, cnt)
         except Exception as e:  # noqa: BLE001
             init_db = {"init_db_error": repr(e)}
-    if rank == 0 and world == 1 and not a.no_init_db and a.k <= 31:
+    if rank == 0 and world == 1 and a.full and not a.no_init_db and a.k <= 31:
         try:
             init_db.update(init_db_leg(a, km, cnt, layout="kmc2"))
             init_db["init_db_kmc2_over_kmc1"] = init_db["init_db_kmc2_value"] / init_db["init_db_value"] if init_db.get("init_db_value") else None
         except Exception as e:  # noqa: BLE001
             init_db["init_db_kmc2_error"] = repr(e)
-    if rank == 0 and world == 1 and a.genome_bases > 0 and a.k <= 31:
+    if rank == 0 and world == 1 and a.full and a.genome_bases > 0 and a.k <= 31:
         try:
             init_db.update(genome_leg(a, dev, a.genome_bases))
             init_db["query_genome_over_random"] = init_db["query_genome_value"] / (nq_all * a.steps / t_q)
         except Exception as e:  # noqa: BLE001
             init_db["genome_error"] = repr(e)
-    if rank == 0 and world == 1 and not a.no_query_strings and a.k <= 31:
+    if rank == 0 and world == 1 and a.full and not a.no_query_strings and a.k <= 31:
         try:
             query_step()
             torch.cuda.synchronize()
@@ -683,8 +722,9 @@ def main():
         except Exception as e:  # noqa: BLE001
             init_db["query_strings_error"] = repr(e)
     # ---- ONE model over all ranks' streams; a watchdog ends the job with what is measured if the exchange hangs
+    # (the headline at N > 1; at N = 1 a figure beside it, --full only)
     single = None
-    if not a.no_single_model:
+    if not a.no_single_model and (world > 1 or a.full):
         import threading
         done = threading.Event()
 
@@ -707,8 +747,10 @@ def main():
             single = single_model_leg(a, m, km, cnt, q, out, rank, world, dev, rehearsal, distributed)
         except Exception as e:  # noqa: BLE001
             single = {"error": repr(e)}
+        if rank == 0 and world > 1 and a.dump_outputs and "value" in single:
+            dump_outputs(a.dump_outputs, m, out)                 # the headline's model (rank 0's replica) and rank 0's answers
         # N > 1: the OTHER partition too, a few builds, beside the headline (not in it): the first run on a node times both
-        if world > 1 and "value" in single and not a.no_other_partition:
+        if world > 1 and a.full and "value" in single and not a.no_other_partition:
             import copy
             b = copy.copy(a)
             b.partition = "range" if a.partition == "ring" else "ring"
@@ -724,7 +766,7 @@ def main():
         # (rehearsal on one GPU: only with KMX_BENCH_CXX_MULTI=1, every handle on cuda:0 -- the code path, not a rate)
         # It runs in a CHILD of rank 0 (a fresh process: its own HIP context, its own RCCL communicators, a time limit): whatever
         # happens there -- a refused peer mapping, a hung collective -- costs this leg, not the run.
-        if world > 1 and (not rehearsal or os.environ.get("KMX_BENCH_CXX_MULTI") == "1") and not a.no_cxx_multi and single is not None and a.k <= 31:
+        if world > 1 and a.full and (not rehearsal or os.environ.get("KMX_BENCH_CXX_MULTI") == "1") and not a.no_cxx_multi and single is not None and a.k <= 31:
             if rank == 0:
                 devs = [0] * world if rehearsal else list(range(world))
                 cmd = [sys.executable, os.path.abspath(__file__), "--cxx-multi-child", ",".join(str(d) for d in devs), "--kmers", str(a.n), "--kmer-len", str(a.k),
@@ -741,7 +783,7 @@ def main():
         done.set()
         wd.cancel()
     cpu = None
-    if rank == 0 and world == 1 and a.cpu_sample > 0:
+    if rank == 0 and world == 1 and a.full and a.cpu_sample > 0:
         try:
             cpu = cpu_baseline(a)
         except Exception as e:  # noqa: BLE001

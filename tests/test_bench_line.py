@@ -37,3 +37,13 @@ def test_a_failed_single_model_leg_leaves_no_headline():
 def test_a_switched_off_single_model_leg_keeps_the_replica_headline():
     out = bench.promote_single_model(copy.deepcopy(LINE), None, 8)
     assert out["value"] == 8.0e9 and "replica_value" not in out
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """Without --full only the headline runs; --dump-outputs is off unless given a directory."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 7, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"

@@ -5,7 +5,7 @@ tag=$1
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/${tag}.txt
 : > "$out"
-args="--steps 6 --warmup 1 --no-init-db --no-query-strings --no-single-model --cpu-sample 0 --genome-bases 0"
+args="--full --steps 6 --warmup 1 --no-init-db --no-query-strings --no-single-model --cpu-sample 0 --genome-bases 0"
 for rep in 1 2 3; do
 for pr in 0 1; do
 	KMX_TEST_HOOKS=1 KMX_PREGATHER_PROBE=$pr python "$root/bench.py" $args > "$root/gpurun_out/${tag}_p${pr}.json" 2> /dev/null

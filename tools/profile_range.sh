@@ -7,7 +7,7 @@ tag=$1; part=${2:-range}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/prof_$tag
 rm -rf "$out"; mkdir -p "$out"
-args="--partition $part --steps 1 --warmup 0 --no-init-db --cpu-sample 0 --no-query-strings --no-roofline --single-model-steps 2"
+args="--full --partition $part --steps 1 --warmup 0 --no-init-db --cpu-sample 0 --no-query-strings --no-roofline --single-model-steps 2"
 python "$root/bench.py" $args > "$root/gpurun_out/${tag}_plain_run.json" 2> "$root/gpurun_out/${tag}_plain.err"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out" -- python "$root/bench.py" $args > "$root/gpurun_out/${tag}_run.json" 2> "$root/gpurun_out/${tag}.err"
