@@ -120,6 +120,7 @@ public:
 	void init_KModel(std::string db_file) { init(db_file); }                 // README.md:76
 
 	// kmodel.hpp:90 -- t_num is accepted for source compatibility; the batch runs on the GPU
+	// Safe to call from several threads on one object at once: the library serialises queries per handle.
 	std::vector<int> kmer_to_occ(std::vector<std::string> kmer_v, int t_num = 4)
 	{
 		(void)t_num;
@@ -156,7 +157,7 @@ public:
 		return occ_v;
 	}
 
-	// kmodel.hpp:100
+	// kmodel.hpp:100 -- safe from several threads at once (an OpenMP loop over it, like the reference's): serialised per handle
 	int kmer_to_occ(std::string kmer, uint32_t r_occ = 0)
 	{
 		(void)r_occ;

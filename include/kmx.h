@@ -196,7 +196,10 @@ int kmx_dev_view(kmx_model *m, int which, int index, void **ptr, uint64_t *bytes
 /* dst |= src over n 32-bit words (merging partial filters)                                                              */
 int kmx_or_words_dev(kmx_model *m, void *d_dst, const void *d_src, uint64_t n_words);
 
-/* vector<int> KModel::kmer_to_occ(vector<string>, t_num)                   kmodel.hpp:90-98   */
+/* vector<int> KModel::kmer_to_occ(vector<string>, t_num)                   kmodel.hpp:90-98
+ * Threads: the four query functions below may be called on one handle from any number of host threads at once (the
+ * reference calls kmer_to_occ from an OpenMP loop); the library serialises them per handle, one query at a time.
+ * A build, load, save or destroy of a handle must not overlap anything else on that handle.                              */
 int kmx_query_packed(kmx_model *m, const uint64_t *kmers, uint64_t n, int32_t *out);
 int kmx_query_packed_dev(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out);
 /* n records of `stride` bytes holding `len` characters each (not NUL-terminated), 2 <= len <= 64.  Strings of

@@ -317,6 +317,9 @@ struct kmx_model {
 	size_t prof_used = 0;
 	double kc_seconds[KC_N] = {0};
 	uint64_t kc_launches[KC_N] = {0};
+	// queries on one handle may come from several host threads (the reference's kmer_to_occ is called from an OpenMP loop):
+	// one query at a time holds this for its whole length -- qfeed, prof's vectors and h_stats[ST_QUERY_*] are shared
+	std::mutex query_mu;
 };
 
 static void prof_begin(KernelProf *p, int cls, hipStream_t st)
@@ -1903,9 +1906,11 @@ static int kmx_kmc_read_impl(const char *db_prefix, uint64_t *kmers, uint32_t *c
 }
 
 // ------------------------------------------------------------------------------------------ query
-static int kmx_query_packed_dev_impl(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out)
+// Every query entry point holds m->query_mu from its first look at the handle to its return: the slots of m->qfeed (and
+// ensure_query_feed's reallocation of them), m->prof's event and span vectors and h_stats[ST_QUERY_*] are used by one
+// caller at a time.  The *_locked functions below expect the caller to hold it.
+static int query_packed_dev_locked(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
 	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	HIPCHK(hipSetDevice(m->device));
 	if (m->prof.count && m->d_stats) {                            // accounting (kmx_set_profile(m, 2)): never the timed kernel
@@ -1921,9 +1926,17 @@ static int kmx_query_packed_dev_impl(kmx_model *m, const uint64_t *d_kmers, uint
 	return KMX_OK;
 }
 
+static int kmx_query_packed_dev_impl(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	return query_packed_dev_locked(m, d_kmers, n, d_out);
+}
+
 static int kmx_query_packed_impl(kmx_model *m, const uint64_t *kmers, uint64_t n, int32_t *out)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
 	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	if (!n) return KMX_OK;
 	HIPCHK(hipSetDevice(m->device));
@@ -1931,7 +1944,7 @@ static int kmx_query_packed_impl(kmx_model *m, const uint64_t *kmers, uint64_t n
 	HIPCHK(dk.alloc(n * m->W * 8));
 	HIPCHK(dout.alloc(n * 4));
 	int rc = hipMemcpyAsync(dk.p, kmers, n * m->W * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess ? KMX_OK : fail(KMX_E_NODEVICE, "H2D copy failed");
-	if (!rc) rc = kmx_query_packed_dev(m, dk.as<uint64_t>(), n, dout.as<int32_t>());
+	if (!rc) rc = query_packed_dev_locked(m, dk.as<uint64_t>(), n, dout.as<int32_t>());
 	if (!rc && hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) rc = fail(KMX_E_NODEVICE, "D2H copy failed");
 	if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(KMX_E_NODEVICE, "query failed");
 	return rc;
@@ -1949,6 +1962,7 @@ static int kmx_query_packed_impl(kmx_model *m, const uint64_t *kmers, uint64_t n
 static const u64 kQuerySub = u64(1) << 14;                     // strings per task
 static const size_t kQuerySlotBytes = size_t(32) << 20;        // input bytes per slot
 
+// (caller holds m->query_mu: without it, another caller's copies could still be using the slots freed here)
 static int ensure_query_feed(kmx_model *m, size_t in_bytes, size_t answers)
 {
 	auto &F = m->qfeed;
@@ -1990,6 +2004,7 @@ static int ensure_query_feed(kmx_model *m, size_t in_bytes, size_t answers)
 
 // n items of item_bytes each through the pipeline.  stage(worker, lo, hi, dst): items [lo, hi) -> dst (their place in the
 // slot); launch(slot, count): the kernel from d_in[slot] to d_out[slot] on the model's stream; answers -> out[0 .. n).
+// The caller holds m->query_mu.
 template <typename STAGE, typename LAUNCH>
 static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE stage, LAUNCH launch, int32_t *out)
 {
@@ -2091,6 +2106,7 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 static int query_text(kmx_model *m, const KmxStrBatch &sb, uint64_t n, int32_t *out)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);                  // both passes (packed, then the dirty strings' bytes) under one hold
 	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	const int len = sb.len, W = m->W;
 	if (len < 2 || len > 64 || sb.stride < len) return fail(KMX_E_ARG, "k-mer strings must hold 2..64 characters (got %d, stride %d)", len, sb.stride);
@@ -2400,6 +2416,7 @@ static int kmx_load_impl(const char *dir, kmx_model **out)
 static int kmx_get_stats_impl(kmx_model *m, kmx_stats *st)
 {
 	if (!m || !st) return fail(KMX_E_ARG, "null argument");
+	std::lock_guard<std::mutex> lk(m->query_mu);                  // h_stats[ST_QUERY_*] are written by queries
 	memset(st, 0, sizeof *st);
 	st->n_total = m->n_total; st->n_km = m->n_km;
 	for (int i = 0; i < 3; i++) { st->n_bf[i] = m->n_bf[i]; st->byte_bf[i] = m->byte_bf[i]; st->byte_bf_back[i] = m->byte_bf_back[i]; }
@@ -2549,6 +2566,7 @@ static int kmx_set_profile_impl(kmx_model *m, int on)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
 	if (on < 0 || on > 2) return fail(KMX_E_ARG, "kmx_set_profile: 0 (off), 1 (timing) or 2 (accounting), got %d", on);
+	std::lock_guard<std::mutex> lk(m->query_mu);                  // a running query reads prof.on / prof.count
 	m->prof.on = on == 1;                                         // 1: per-class timing of the product's kernels
 	m->prof.count = on == 2;                                      // 2: no timing; the fused launches run their accounting variant (kmx_stats piped_*)
 	return KMX_OK;
@@ -2557,6 +2575,7 @@ static int kmx_set_profile_impl(kmx_model *m, int on)
 static int kmx_get_kernel_times_impl(kmx_model *m, double *seconds, uint64_t *launches, int reset)
 {
 	if (!m || !seconds || !launches) return fail(KMX_E_ARG, "null argument");
+	std::lock_guard<std::mutex> lk(m->query_mu);                  // prof_collect empties the span vector queries push to
 	HIPCHK(hipSetDevice(m->device));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	prof_collect(m);

@@ -11,10 +11,10 @@ from kmcex_amd import api
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _compile(tmp_path, source=os.path.join(ROOT, "examples", "kmcex_main.cpp"), name="kmcEx"):
+def _compile(tmp_path, source=os.path.join(ROOT, "examples", "kmcex_main.cpp"), name="kmcEx", extra=()):
     api.load_library()
     exe = str(tmp_path / name)
-    subprocess.check_call(["g++", "-O3", "-m64", "-std=c++11", "-I" + os.path.join(ROOT, "include"), source,
+    subprocess.check_call(["g++", "-O3", "-m64", *extra, "-std=c++11", "-I" + os.path.join(ROOT, "include"), source,
                            "-L" + os.path.join(ROOT, "kmcex_amd"), "-lkmx", "-Wl,-rpath," + os.path.join(ROOT, "kmcex_amd"), "-o", exe])
     return exe
 
@@ -79,6 +79,31 @@ def test_facade_vector_of_strings_gives_reference_answers(tmp_path):
     p = subprocess.run([exe, tiny, os.path.join(tiny, "queries.txt")], capture_output=True, text=True)
     assert p.returncode == 0, p.stdout[-300:] + p.stderr
     assert p.stdout.split() == open(os.path.join(tiny, "occ.txt")).read().split()
+
+
+def _compile_concurrent(tmp_path):
+    """tests/facade_concurrent.cpp with the reference's flags plus OpenMP (makefile:4 builds kmcEx with -fopenmp)"""
+    return _compile(tmp_path, os.path.join(ROOT, "tests", "facade_concurrent.cpp"), "facade_concurrent", extra=("-fopenmp", "-pthread"))
+
+
+def test_facade_concurrent_program_compiles(tmp_path):
+    _compile_concurrent(tmp_path)
+
+
+@pytest.mark.gpu
+def test_facade_concurrent_callers_give_reference_answers(tmp_path):
+    """The reference's own batch pattern on ONE object -- `#pragma omp parallel for` over kmer_to_occ(string), 8 threads
+    (kmodel.hpp:90-98) -- and 4 std::threads sending their own vector<string> slices (one with other lengths mixed in) through
+    include/kmodel.hpp on the REFERENCE's model files: both answer lists are the reference's occ.txt, line for line."""
+    exe = _compile_concurrent(tmp_path)
+    tiny = os.path.join(ROOT, "tests", "golden", "tiny")
+    p = subprocess.run([exe, tiny, os.path.join(tiny, "queries.txt")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-300:] + p.stderr
+    want = open(os.path.join(tiny, "occ.txt")).read().split()
+    got = p.stdout.split()
+    assert len(got) == 2 * len(want)
+    assert got[:len(want)] == want, "omp parallel for over kmer_to_occ(string)"
+    assert got[len(want):] == want, "std::thread slices through kmer_to_occ(vector<string>)"
 
 
 FACADE_EXE = os.path.join(ROOT, "oracle", "_ref", "kmcEx_facade")
