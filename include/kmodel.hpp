@@ -166,6 +166,32 @@ public:
 		return occ;
 	}
 
+	// Every overlapping k-mer of a read or contig at once (what error correction, repeat detection and assembly ask for):
+	// answer p = kmer_to_occ(seq.substr(p, k)), p = 0 .. len - k; none for a sequence shorter than k.  The bases go to the
+	// device as they are and the windows are cut there (kmx_query_seqs), instead of len - k + 1 strings built here.
+	std::vector<int> seq_to_occ(const std::string &seq)
+	{
+		const uint64_t off[2] = {0, (uint64_t)seq.size()};
+		std::vector<int> occ(seq.size());
+		if (!seq.empty()) check(kmx_query_seqs(h_, seq.data(), off, 1, (int32_t *)occ.data()));
+		occ.resize(windows(seq.size(), model_k()));
+		return occ;
+	}
+	std::vector<std::vector<int> > seq_to_occ(const std::vector<std::string> &seqs)
+	{
+		std::vector<uint64_t> off(seqs.size() + 1, 0);
+		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		std::vector<int32_t> occ((size_t)off.back());
+		if (!occ.empty()) check(kmx_query_seqs(h_, flat.data(), off.data(), seqs.size(), occ.data()));
+		std::vector<std::vector<int> > out(seqs.size());
+		const size_t k = model_k();
+		for (size_t i = 0; i < seqs.size(); i++) out[i].assign(occ.begin() + (size_t)off[i], occ.begin() + (size_t)off[i] + windows(seqs[i].size(), k));
+		return out;
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 
@@ -211,6 +237,13 @@ public:
 	kmx_model *handle() { return h_; }
 
 private:
+	size_t model_k()
+	{
+		kmx_stats st;
+		check(kmx_get_stats(h_, &st));
+		return st.k > 0 ? (size_t)st.k : 0;
+	}
+	static size_t windows(size_t len, size_t k) { return k && len >= k ? len - k + 1 : 0; }
 	static void die(const char *msg)
 	{
 		std::cout << msg << std::endl;

@@ -197,7 +197,7 @@ int kmx_dev_view(kmx_model *m, int which, int index, void **ptr, uint64_t *bytes
 int kmx_or_words_dev(kmx_model *m, void *d_dst, const void *d_src, uint64_t n_words);
 
 /* vector<int> KModel::kmer_to_occ(vector<string>, t_num)                   kmodel.hpp:90-98
- * Threads: the four query functions below may be called on one handle from any number of host threads at once (the
+ * Threads: the query functions below may be called on one handle from any number of host threads at once (the
  * reference calls kmer_to_occ from an OpenMP loop); the library serialises them per handle, one query at a time.
  * A build, load, save or destroy of a handle must not overlap anything else on that handle.                              */
 int kmx_query_packed(kmx_model *m, const uint64_t *kmers, uint64_t n, int32_t *out);
@@ -208,6 +208,23 @@ int kmx_query_ascii(kmx_model *m, const char *strs, int len, int stride, uint64_
 /* the same for n separate strings of `len` characters each (strs[i] need not be NUL-terminated): what a
  * vector<string> holds, without concatenating it first */
 int kmx_query_strings(kmx_model *m, const char *const *strs, int len, uint64_t n, int32_t *out);
+/* kmer_to_occ (kmodel.hpp:100-116) of every k-mer window of n_seqs sequences stored back to back: sequence i is
+ * seq[offsets[i] .. offsets[i+1]), offsets[0] = 0, n_bases = offsets[n_seqs]; out[n_bases] is aligned to the bases.
+ *   out[offsets[i] + p] = kmer_to_occ(s_i.substr(p, k)) for 0 <= p <= len_i - k: bit for bit what kmx_query_ascii gives that
+ *                         window (uppercase ACGT windows take the packed path, any other byte -- N, lowercase, IUPAC -- is
+ *                         hashed as it is, never uppercased);
+ *   out[offsets[i] + p] = -1 for the last k - 1 positions of each sequence and every position of one shorter than k.
+ *                         kmer_to_occ never returns -1: its answers are rest-table counts (>= ci >= 1), OccuBin means
+ *                         (occubin_tables / bin_to_mean, occu_bin.hpp:27-83: all >= 0) or 0.
+ * Indices are 64-bit throughout (one sequence may be a whole genome).  KMX_E_ARG when offsets[0] != 0 or the offsets
+ * decrease (checked before anything runs); n_seqs == 0 or n_bases == 0: KMX_OK, nothing written.  The bases travel as
+ * they are (one byte per window) and the windows are built on the device; the answers are timed as kernel class 6 (query)
+ * under kmx_set_profile(m, 1), and kmx_set_profile(m, 2)'s accounting (query_neighbour_calls) does not cover them.    */
+int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out);
+/* the same on DEVICE buffers: d_seq[n_bases], d_offsets[n_seqs + 1], d_out[n_bases]; enqueued on the model's stream, returns
+ * without waiting.  The offsets are not validated on the host: the kernels clamp every offset into [0, n_bases] and treat
+ * a decreasing pair as an empty sequence, so bad offsets give wrong answers, never an access outside d_seq / d_out.   */
+int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

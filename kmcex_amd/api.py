@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "kmx_ring_stale_dup_dev", "kmx_shard_local", "kmx_shard_complete", "kmx_dev_view", "kmx_or_words_dev",
     "kmx_debug_pack_strings", "kmx_kernel_classes", "kmx_abi_version", "kmx_get_stats_n",
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
+    "kmx_query_seqs", "kmx_query_seqs_dev",
 ]
 
 
@@ -148,6 +149,8 @@ def load_library():
     _sig(L, "kmx_kernel_classes", [])
     _sig(L, "kmx_abi_version", [])
     _sig(L, "kmx_get_stats_n", [vp, vp, u64])
+    _sig(L, "kmx_query_seqs", [vp, vp, vp, u64, vp])
+    _sig(L, "kmx_query_seqs_dev", [vp, vp, vp, u64, u64, vp])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -443,6 +446,40 @@ class KModel:
 
     def kmer_to_occ_dev(self, d_kmers_ptr: int, n: int, d_out_ptr: int) -> None:
         _chk(self.L.kmx_query_packed_dev(self.h, d_kmers_ptr, n, d_out_ptr))
+
+    def seq_to_occ_flat(self, buf: np.ndarray, offsets: np.ndarray) -> np.ndarray:
+        """kmx_query_seqs: uint8 bases of sequences stored back to back, uint64 offsets[n_seqs + 1] -> int32[n_bases], aligned
+        to the bases; -1 where no k-mer starts (the last k - 1 positions of each sequence)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        n_bases = int(offsets[-1])
+        if n_bases > buf.size:
+            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        out = np.empty(n_bases, dtype=np.int32)
+        _chk(self.L.kmx_query_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, out.ctypes.data))
+        return out
+
+    def seq_to_occ(self, seqs):
+        """kmer_to_occ of every overlapping k-mer of each sequence (str or bytes; one sequence or a list): one int32 array of
+        max(len - k + 1, 0) answers per sequence (a list of them for a list)."""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        k = self.stats().k
+        if k == 0:
+            raise KmxError(-4, "query before the model is built or loaded")
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        flat = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        occ = self.seq_to_occ_flat(flat, offsets) if raw else np.zeros(0, np.int32)
+        res = [occ[int(offsets[i]):int(offsets[i]) + max(len(r) - k + 1, 0)] for i, r in enumerate(raw)]
+        return res[0] if single else res
+
+    def seq_to_occ_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, d_out_ptr: int) -> None:
+        """kmx_query_seqs_dev: device buffers, enqueued on the model's stream (no wait)"""
+        _chk(self.L.kmx_query_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, d_out_ptr))
 
     # ---- persistence
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173

@@ -2118,20 +2118,27 @@ template <int W> __device__ __forceinline__ int neighbour_bins(const ModelDev &m
 // KModel::kmer_to_occ (kmodel.hpp:100-116) on packed k-mers
 // ACCT (never the timed kernel: kmx_set_profile(m, 2)): counts the queries that enter the neighbour disambiguation
 // (get_neighbor_kmer_bin, kmodel.hpp:344-359: up to 8 nested lookups in one lane) in acct[0]
+// the answer for one loaded packed k-mer v[W] -> *dst (k_query's lane body; k_query_seq answers its clean windows through it
+// too).  The answer is stored at each of the two exits, as the kernel always did: one common store changes its registers.
+template <int W, bool ACCT> __device__ __forceinline__ void query_packed_one(const ModelDev &md, u64 *v, u64 *acct, int *dst)
+{
+	if (md.k & 31) v[0] &= (1ULL << (2 * (md.k & 31))) - 1;          // bits above 2k are not part of a packed k-mer (a caller's stray bits would index past the tables)
+	min_kmer<W>(v, md.k);
+	int occ = rest_check<W>(md, v);
+	if (occ != 0) { *dst = occ; return; }
+	Aligned<W> al = left_align<W>(v, md.k);
+	Premixed<W> pf = premix_string<W>(al, md.gfull);
+	Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
+	*dst = occ_from_filters<W>(md, md.gfull, md.gback, pf, pb, [&](int *cand) { if (ACCT) atomicAdd(acct, 1ULL); return neighbour_bins<W>(md, v, cand); });
+}
+
 template <int W, bool ACCT> __global__ __launch_bounds__(256) void k_query(ModelDev md, const u64 *kmers, u64 n, int *out, u64 *acct)
 {
 	const u64 q = (u64)blockIdx.x * 256 + threadIdx.x;
 	if (q >= n) return;
 	u64 v[W];
 	load_kmer<W>(kmers, q, v);
-	if (md.k & 31) v[0] &= (1ULL << (2 * (md.k & 31))) - 1;          // bits above 2k are not part of a packed k-mer (a caller's stray bits would index past the tables)
-	min_kmer<W>(v, md.k);
-	int occ = rest_check<W>(md, v);
-	if (occ != 0) { out[q] = occ; return; }
-	Aligned<W> al = left_align<W>(v, md.k);
-	Premixed<W> pf = premix_string<W>(al, md.gfull);
-	Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
-	out[q] = occ_from_filters<W>(md, md.gfull, md.gback, pf, pb, [&](int *cand) { if (ACCT) atomicAdd(acct, 1ULL); return neighbour_bins<W>(md, v, cand); });
+	query_packed_one<W, ACCT>(md, v, acct, out + q);
 }
 
 // ------------------------------------------------------------------------------------------ query on raw strings
@@ -2241,26 +2248,15 @@ template <int W> __device__ __forceinline__ int astr_candidate(const ModelDev &m
 	return candidate_from_filters<2>(md, gf, gb, pf, pb);
 }
 
-template <int W> __global__ __launch_bounds__(256) void k_query_ascii(ModelDev md, StrGeom gf, StrGeom gb, int L, const unsigned char *strs, int stride, u64 n, int *out)
+// the answer for one byte string of L characters in a filled AStr -> *dst (k_query_ascii's lane body; k_query_ascii_at's too)
+template <int W> __device__ __forceinline__ void astr_query_one(const ModelDev &md, const StrGeom gf, const StrGeom gb, int L, AStr s, int *dst)
 {
-	const u64 q = (u64)blockIdx.x * 256 + threadIdx.x;
-	if (q >= n) return;
-	AStr s;
-	const unsigned char *p = strs + q * (u64)stride;
-#pragma unroll
-	for (int w = 0; w < 8; w++) {
-		u64 word = 0;
-#pragma unroll
-		for (int j = 0; j < 8; j++)
-			if (8 * w + j < L) word |= (u64)p[8 * w + j] << (8 * j);
-		s.b[w] = word;
-	}
 	astr_min_kmer(s, L);
 	const int occ = astr_rest_check<W>(md, s, L);
-	if (occ != 0) { out[q] = occ; return; }
+	if (occ != 0) { *dst = occ; return; }
 	Premixed<2> pf = astr_premix(s, gf);
 	Premixed<2> pb = astr_premix(astr_drop_first(s), gb);
-	out[q] = occ_from_filters<2>(md, gf, gb, pf, pb, [&](int *cand) {
+	*dst = occ_from_filters<2>(md, gf, gb, pf, pb, [&](int *cand) {
 		int nc = 0;
 		const AStr t1 = astr_drop_first(s);                      // kmer.substr(1): still holds s[L-1] at byte L-2
 		for (int x = 0; x < 8; x++) {
@@ -2273,6 +2269,126 @@ template <int W> __global__ __launch_bounds__(256) void k_query_ascii(ModelDev m
 		}
 		return nc;
 	});
+}
+
+// the L bytes at p -> an AStr (string byte i in b[i >> 3], bits 8*(i & 7); bytes from L on are 0)
+__device__ __forceinline__ AStr astr_load(const unsigned char *p, int L)
+{
+	AStr s;
+#pragma unroll
+	for (int w = 0; w < 8; w++) {
+		u64 word = 0;
+#pragma unroll
+		for (int j = 0; j < 8; j++)
+			if (8 * w + j < L) word |= (u64)p[8 * w + j] << (8 * j);
+		s.b[w] = word;
+	}
+	return s;
+}
+
+template <int W> __global__ __launch_bounds__(256) void k_query_ascii(ModelDev md, StrGeom gf, StrGeom gb, int L, const unsigned char *strs, int stride, u64 n, int *out)
+{
+	const u64 q = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (q >= n) return;
+	astr_query_one<W>(md, gf, gb, L, astr_load(strs + q * (u64)stride, L), out + q);
+}
+
+// ------------------------------------------------------------------------------------------ query along sequences
+// kmx_query_seqs: the k-mer window at every base of n_seqs sequences stored back to back in seq[0, n_bases), sequence i
+// = [offs[i], offs[i+1]).  k_query_seq answers the windows of uppercase ACGT through the packed body and lists the others
+// (any other byte: N, lowercase, IUPAC) by position; k_query_ascii_at answers the listed ones through the byte-string body.
+// Two kernels because an AStr is 8 x u64 per lane: folded into k_query_seq it would cost the gather-bound clean path its
+// occupancy.  Every offset is clamped into [0, n_bases] where it is read, and a window is answered only when it lies
+// inside [offs[i], offs[i+1]) -- so a decreasing pair is an empty sequence, and no offsets a caller passes can move a
+// read or a write outside seq[0, n_bases) / out[0, n_bases).
+static constexpr int SEQ_BT = 256;
+static constexpr int SEQ_TILE = SEQ_BT + 64;                      // a tile's windows + the k - 1 <= 63 bases of the last one
+static constexpr unsigned SEQ_DIRTY_WGS = 1024;                   // k_query_ascii_at's fixed grid
+
+__device__ __forceinline__ u64 seq_off(const u64 *offs, u64 i, u64 n_bases) { const u64 o = offs[i]; return o < n_bases ? o : n_bases; }
+// first i in [lo, hi) with seq_off(i) > p, or hi (std::upper_bound); reads only offs[lo, hi) whatever the entries hold
+__device__ __forceinline__ u64 seq_upper(const u64 *offs, u64 lo, u64 hi, u64 p, u64 n_bases)
+{
+	while (lo < hi) {
+		const u64 mid = lo + (hi - lo) / 2;
+		if (seq_off(offs, mid, n_bases) <= p) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+__device__ __forceinline__ u32 seq_code(u32 c) { return c == 'A' ? 0u : (c == 'C' ? 1u : (c == 'G' ? 2u : (c == 'T' ? 3u : 4u))); }
+
+// windows [p0, p0 + n_win) (all < n_bases): out[p] = the answer, or -1 when the window leaves its sequence; a window with a
+// byte outside uppercase ACGT is not answered here but appended (as p - p0) to dlist through dcnt, one atomic per wave.
+template <int W> __global__ __launch_bounds__(SEQ_BT) void k_query_seq(ModelDev md, const unsigned char *seq, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, int *out, u32 *dlist, u32 cap, u32 *dcnt)
+{
+	__shared__ unsigned char s_code[SEQ_TILE];                     // 2-bit code of each base of the tile, 4 = not uppercase ACGT
+	__shared__ u64 s_u[2];
+	const int k = md.k, tid = threadIdx.x;
+	const u64 t0 = p0 + (u64)blockIdx.x * SEQ_BT, p_end = p0 + n_win, p = t0 + tid;
+	const u64 t_last = (t0 + SEQ_BT < p_end ? t0 + SEQ_BT : p_end) - 1;
+	const u64 b_end = t0 + SEQ_BT + k - 1 < n_bases ? t0 + SEQ_BT + k - 1 : n_bases;   // the bases this tile reads: [t0, b_end)
+	// the boundaries around the tile, found once: every window of the tile has its upper bound in [u0, u1]
+	if (tid == 0) s_u[0] = seq_upper(offs, 0, n_seqs + 1, t0, n_bases);
+	if (tid == 64) s_u[1] = seq_upper(offs, 0, n_seqs + 1, t_last, n_bases);
+	// stage the tile's bases: dword loads where the tile is 4-byte aligned, bytes for the rest
+	const unsigned char *src = seq + t0;
+	const int nb = (int)(b_end - t0);
+	if (((uintptr_t)src & 3) == 0) {
+		if (4 * tid < nb) {
+			if (4 * tid + 4 <= nb) {
+				const u32 w = *(const u32 *)(src + 4 * tid);
+#pragma unroll
+				for (int j = 0; j < 4; j++) s_code[4 * tid + j] = (unsigned char)seq_code((w >> (8 * j)) & 0xFFu);
+			} else
+				for (int j = 4 * tid; j < nb; j++) s_code[j] = (unsigned char)seq_code(src[j]);
+		}
+	} else
+		for (int j = tid; j < nb; j += SEQ_BT) s_code[j] = (unsigned char)seq_code(src[j]);
+	__syncthreads();
+	bool valid = false, bad = false;
+	u64 v[W];
+	if (p < p_end) {
+		const u64 u0 = s_u[0], u1 = s_u[1];
+		const u64 u = seq_upper(offs, u0, u1 > u0 ? u1 : u0, p, n_bases);      // sequence u - 1 holds p
+		if (u >= 1 && u <= n_seqs) {
+			const u64 start = seq_off(offs, u - 1, n_bases), end = seq_off(offs, u, n_bases);
+			valid = start <= p && p + (u64)k <= end;
+		}
+		if (valid) {
+			u64 hi = 0, lo = 0;
+			u32 any = 0;
+			for (int j = 0; j < k; j++) {
+				const u32 c = s_code[tid + j];
+				any |= c;
+				if (W == 2) hi = (hi << 2) | (lo >> 62);
+				lo = (lo << 2) | (c & 3u);
+			}
+			bad = (any & 4u) != 0;
+			v[W - 1] = lo;
+			if (W == 2) v[0] = hi;
+		}
+	}
+	const bool dirty = valid && bad;
+	const u32 slot = wave_append_slot<u32>(dcnt, dirty);          // (every lane of the wave takes part)
+	if (dirty && slot < cap) dlist[slot] = (u32)(p - p0);
+	if (p >= p_end || dirty) return;
+	if (!valid) { out[p] = -1; return; }
+	query_packed_one<W, false>(md, v, nullptr, out + p);
+}
+
+// the windows k_query_seq listed: dcnt is read on the device (the host never waits for it), a fixed grid strides over
+// the list.  dcnt_next (the next piece's counter; that piece's k_query_seq runs after this launch on the same stream) is
+// zeroed here.
+template <int W> __global__ __launch_bounds__(256) void k_query_ascii_at(ModelDev md, StrGeom gf, StrGeom gb, const unsigned char *seq, u64 n_bases, u64 p0, const u32 *dlist, u32 cap, const u32 *dcnt, u32 *dcnt_next, int *out)
+{
+	if (blockIdx.x == 0 && threadIdx.x == 0) *dcnt_next = 0;
+	const u32 c = *dcnt, n = c < cap ? c : cap;
+	const int L = md.k;
+	for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+		const u64 p = p0 + dlist[i];
+		if (p + (u64)L > n_bases) continue;                          // (never for a listed window)
+		astr_query_one<W>(md, gf, gb, L, astr_load(seq + p, L), out + p);
+	}
 }
 
 // ------------------------------------------------------------------------------------------ KMC listing on the device
@@ -2724,6 +2840,18 @@ void query_ascii(const ModelDev &md, int L, const unsigned char *strs, int strid
 	if (!n) return;
 	const StrGeom gf = make_geom(L), gb = make_geom(L >= 2 ? L - 2 : 0);
 	DISPATCH_W(words(md), hipLaunchKernelGGL(k_query_ascii<W>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, md, gf, gb, L, strs, stride, n, out));
+}
+
+// windows [p0, p0 + n_win) of the sequences (k_query_seq) + the ones it listed (k_query_ascii_at): two launches, no host wait.
+// dlist holds cap >= n_win entries; dcnt must be 0 on entry, dcnt_next is zeroed for the next piece.
+void query_seq(const ModelDev &md, const unsigned char *seq, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, int *out, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+{
+	if (!n_win) return;
+	KPROF_BEGIN(prof, KC_QUERY, st);
+	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_query_seq<W>, dim3((unsigned)((n_win + SEQ_BT - 1) / SEQ_BT)), dim3(SEQ_BT), 0, st, md, seq, n_bases, offs, n_seqs, p0, n_win, out, dlist, cap, dcnt));
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_query_ascii_at<W>, dim3(SEQ_DIRTY_WGS), dim3(256), 0, st, md, gf, gb, seq, n_bases, p0, (const u32 *)dlist, cap, (const u32 *)dcnt, dcnt_next, out));
+	KPROF_END(prof, st);
 }
 
 void cells_from_disk(const unsigned char *val, const unsigned char *tag, u64 nbytes, cell_t *cells, u64 ncells, hipStream_t st)

@@ -18,10 +18,12 @@
 #include <cstring>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -52,6 +54,7 @@ void range_resolve(const ModelDev &, const BlockDev &, const RangeDev &, const R
 void range_commit_apply(const ModelDev &, const RangeIn &, int, hipStream_t);
 void query(const ModelDev &, const u64 *, u64, int *, hipStream_t, KernelProf *, u64 *acct = nullptr);
 void query_ascii(const ModelDev &, int, const unsigned char *, int, u64, int *, hipStream_t);
+void query_seq(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
 void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
 void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
 void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);
@@ -263,6 +266,10 @@ struct kmx_model {
 		size_t in_cap = 0, out_cap = 0;                            // bytes per slot / answers per slot
 		hipStream_t to_dev = nullptr, to_host = nullptr;
 		hipEvent_t ev_in[S] = {nullptr, nullptr, nullptr}, ev_k[S] = {nullptr, nullptr, nullptr}, ev_out[S] = {nullptr, nullptr, nullptr};
+		// kmx_query_seqs*: the positions of one piece's windows that are not uppercase ACGT + two counters (one per piece
+		// parity); seq_cap entries, at most one piece of windows, whatever the length of the input
+		u32 *d_seq_list = nullptr, *d_seq_cnt = nullptr;
+		u64 seq_cap = 0;
 	} qfeed;
 	// position-range partition over several GPUs (kmx_range_*): this rank's exchange buffers, its resolver tables, and the
 	// owner-side view of the block working set (overflow flags + padded bin counters for the detect kernel on received claims)
@@ -528,6 +535,9 @@ static void free_query_feed(kmx_model *m)
 		for (hipEvent_t *e : {&f.ev_in[s], &f.ev_k[s], &f.ev_out[s]}) { if (*e) hipEventDestroy(*e); *e = nullptr; }
 	}
 	f.in_cap = f.out_cap = 0;
+	hipFree(f.d_seq_list); hipFree(f.d_seq_cnt);
+	f.d_seq_list = f.d_seq_cnt = nullptr;
+	f.seq_cap = 0;
 }
 
 static int kmx_destroy_impl(kmx_model *m)
@@ -2002,25 +2012,36 @@ static int ensure_query_feed(kmx_model *m, size_t in_bytes, size_t answers)
 	return KMX_OK;
 }
 
+// A caller whose slots hold more than the items (kmx_query_seqs: a halo of bases and the chunk's sequence boundaries) fixes
+// the chunk, the slot size and the bytes copied in per chunk; in_bytes(c) is asked only after chunk c is staged.
+struct SlotShape {
+	u64 chunk;
+	size_t slot_bytes;
+	std::function<size_t(u64)> in_bytes;
+};
+
 // n items of item_bytes each through the pipeline.  stage(worker, lo, hi, dst): items [lo, hi) -> dst (their place in the
-// slot); launch(slot, count): the kernel from d_in[slot] to d_out[slot] on the model's stream; answers -> out[0 .. n).
+// slot); launch(slot, count) or launch(slot, count, chunk): the kernel from d_in[slot] to d_out[slot] on the model's
+// stream, chunk by chunk in order; answers -> out[0 .. n).
 // The caller holds m->query_mu.
 template <typename STAGE, typename LAUNCH>
-static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE stage, LAUNCH launch, int32_t *out)
+static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE stage, LAUNCH launch, int32_t *out, const SlotShape *shape = nullptr)
 {
 	auto &F = m->qfeed;
 	u64 C = std::max<u64>(kQuerySub, (kQuerySlotBytes / item_bytes) & ~(kQuerySub - 1));
 	C = std::min<u64>(C, (n + kQuerySub - 1) & ~(kQuerySub - 1));
+	if (shape) C = shape->chunk;
 	const u64 nc = (n + C - 1) / C;
-	TRY(ensure_query_feed(m, (size_t)C * item_bytes, (size_t)C));
+	TRY(ensure_query_feed(m, shape ? shape->slot_bytes : (size_t)C * item_bytes, (size_t)C));
 	auto count_of = [&](u64 c) { return std::min<u64>(C, n - c * C); };
 	auto subs_of = [&](u64 c) { return (count_of(c) + kQuerySub - 1) / kQuerySub; };
 	auto enqueue = [&](u64 c) -> bool {
 		const int s = (int)(c % F.S);
 		const u64 cn = count_of(c);
-		if (hipMemcpyAsync(F.d_in[s], F.h_in[s], cn * item_bytes, hipMemcpyHostToDevice, F.to_dev) != hipSuccess || hipEventRecord(F.ev_in[s], F.to_dev) != hipSuccess ||
+		if (hipMemcpyAsync(F.d_in[s], F.h_in[s], shape ? shape->in_bytes(c) : cn * item_bytes, hipMemcpyHostToDevice, F.to_dev) != hipSuccess || hipEventRecord(F.ev_in[s], F.to_dev) != hipSuccess ||
 		    hipStreamWaitEvent(m->stream, F.ev_in[s], 0) != hipSuccess) return false;
-		launch(s, cn);
+		if constexpr (std::is_invocable_v<LAUNCH, int, u64, u64>) launch(s, cn, c);
+		else launch(s, cn);
 		return hipEventRecord(F.ev_k[s], m->stream) == hipSuccess && hipStreamWaitEvent(F.to_host, F.ev_k[s], 0) == hipSuccess &&
 		       hipMemcpyAsync(F.h_out[s], F.d_out[s], cn * 4, hipMemcpyDeviceToHost, F.to_host) == hipSuccess && hipEventRecord(F.ev_out[s], F.to_host) == hipSuccess;
 	};
@@ -2144,6 +2165,111 @@ static int kmx_query_strings_impl(kmx_model *m, const char *const *strs, int len
 {
 	if (n && (!strs || !out)) return fail(KMX_E_ARG, "null argument");
 	return query_text(m, KmxStrBatch{strs, nullptr, len, len}, n, out);
+}
+
+// ------------------------------------------------------------------------------------------ query along sequences
+// kmx_query_seqs: the window at every base of n_seqs sequences stored back to back.  The bases travel as they are (1 byte
+// per window); k_query_seq builds the windows on the device and answers the clean ones, k_query_ascii_at the ones it
+// listed (kernels.hip).  The device list of those positions holds one piece of at most kSeqPiece windows: a longer input
+// runs in pieces, two launches each on the model's stream, with no host wait between them.
+static const u64 kSeqPiece = u64(1) << 24;                     // windows per piece (the dirty list: 64 MB of u32)
+static const u64 kSeqChunk = u64(1) << 22;                     // bases per pinned slot of the host variant
+
+// KMX_SEQ_CHUNK_BASES (test hook): pieces and host chunks of this many windows, so a test crosses many of their boundaries.
+// Read at every call (a test sets it after the library is loaded).
+static u64 seq_chunk_hook()
+{
+	const char *e = hook_env("KMX_SEQ_CHUNK_BASES");
+	const long long x = e ? atoll(e) : 0;
+	return x > 0 ? std::min<u64>((u64)x, kSeqPiece) : 0;
+}
+
+// (caller holds m->query_mu) the dirty list for pieces of `piece` windows + its two counters, both zeroed on the model's stream
+static int ensure_seq_scratch(kmx_model *m, u64 piece)
+{
+	auto &F = m->qfeed;
+	if (piece > F.seq_cap) {
+		HIPCHK(hipStreamSynchronize(m->stream));               // an earlier _dev call may still be using the old list
+		hipFree(F.d_seq_list);
+		F.d_seq_list = nullptr;
+		F.seq_cap = 0;
+		HIPCHK(timed_malloc((void **)&F.d_seq_list, piece * 4));
+		F.seq_cap = piece;
+	}
+	if (!F.d_seq_cnt) HIPCHK(timed_malloc((void **)&F.d_seq_cnt, 2 * sizeof(u32)));
+	HIPCHK(hipMemsetAsync(F.d_seq_cnt, 0, 2 * sizeof(u32), m->stream));
+	return KMX_OK;
+}
+
+static int kmx_query_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	if (!n_seqs || !n_bases) return KMX_OK;
+	if (!d_seq || !d_offsets || !d_out) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece;
+	TRY(ensure_seq_scratch(m, piece));
+	auto &F = m->qfeed;
+	int par = 0;
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1)
+		kmxk::query_seq(m->md, (const unsigned char *)d_seq, n_bases, (const u64 *)d_offsets, n_seqs, p0, std::min<u64>(piece, n_bases - p0), d_out,
+		                F.d_seq_list, (u32)F.seq_cap, F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+// The host variant streams the bases through the slots of m->qfeed (query_pipeline): chunk c answers windows
+// [c * C, c * C + cn) and carries the bases [c * C, c * C + nbytes), nbytes = min(cn + k - 1, n_bases - c * C), then, at
+// byte off_at, the sequence boundaries that fall inside those bytes, rebased to the chunk and deduplicated, between 0
+// and nbytes.  A sequence cut by the chunk's edges ends at nbytes there, which changes no answer: a window of the chunk
+// that fits in its sequence also fits in the chunk's bytes.
+static int kmx_query_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	if (!n_seqs) return KMX_OK;
+	if (!offsets) return fail(KMX_E_ARG, "null argument");
+	if (offsets[0] != 0) return fail(KMX_E_ARG, "offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
+	for (u64 i = 0; i < n_seqs; i++)
+		if (offsets[i + 1] < offsets[i]) return fail(KMX_E_ARG, "offsets decrease at sequence %llu", (unsigned long long)i);
+	const u64 n_bases = offsets[n_seqs];
+	if (!n_bases) return KMX_OK;
+	if (!seq || !out) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 k = (u64)m->k, hook = seq_chunk_hook();
+	const u64 C = std::min<u64>(hook ? hook : kSeqChunk, n_bases);
+	const size_t off_at = (size_t)((C + 64 + 7) & ~u64(7));
+	TRY(ensure_seq_scratch(m, C));
+	const u64 nc = (n_bases + C - 1) / C;
+	std::vector<u64> n_bnd(nc, 0);                                 // boundaries chunk c carries (written by the worker that stages its end)
+	auto nbytes_of = [&](u64 c) { const u64 c0 = c * C, cn = std::min<u64>(C, n_bases - c0); return std::min<u64>(cn + k - 1, n_bases - c0); };
+	SlotShape shape{C, off_at + 8 * (size_t)(C + 64), [&](u64 c) { return off_at + 8 * (size_t)n_bnd[c]; }};
+	const int T = (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1));
+	int par = 0;
+	auto &F = m->qfeed;
+	return query_pipeline(m, n_bases, 1, T,
+		[&](int, u64 lo, u64 hi, unsigned char *dst) {
+			memcpy(dst, seq + lo, hi - lo);
+			const u64 c = lo / C, c0 = c * C;
+			if (hi != c0 + std::min<u64>(C, n_bases - c0)) return;
+			unsigned char *slot = dst - (lo - c0);                // the task holding the chunk's last window adds its halo and boundaries
+			const u64 nbytes = nbytes_of(c), cn = hi - c0;
+			memcpy(slot + cn, seq + hi, nbytes - cn);
+			u64 *bnd = (u64 *)(slot + off_at), nb = 0;
+			bnd[nb++] = 0;
+			for (u64 i = (u64)(std::upper_bound(offsets, offsets + n_seqs + 1, c0) - offsets); i <= n_seqs && offsets[i] < c0 + nbytes; i++)
+				if (offsets[i] - c0 != bnd[nb - 1]) bnd[nb++] = offsets[i] - c0;
+			bnd[nb++] = nbytes;
+			n_bnd[c] = nb;
+		},
+		[&](int s, u64 cn, u64 c) {
+			kmxk::query_seq(m->md, F.d_in[s], nbytes_of(c), (const u64 *)(F.d_in[s] + off_at), n_bnd[c] - 1, 0, cn, F.d_out[s],
+			                F.d_seq_list, (u32)F.seq_cap, F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+			par ^= 1;
+		}, out, &shape);
 }
 
 // ------------------------------------------------------------------------------------------ persistence
@@ -2635,6 +2761,8 @@ extern "C" int kmx_query_packed_dev(kmx_model *m, const uint64_t *d_kmers, uint6
 extern "C" int kmx_query_packed(kmx_model *m, const uint64_t *kmers, uint64_t n, int32_t *out) { return guarded([&] { return kmx_query_packed_impl(m, kmers, n, out); }); }
 extern "C" int kmx_query_ascii(kmx_model *m, const char *strs, int len, int stride, uint64_t n, int32_t *out) { return guarded([&] { return kmx_query_ascii_impl(m, strs, len, stride, n, out); }); }
 extern "C" int kmx_query_strings(kmx_model *m, const char *const *strs, int len, uint64_t n, int32_t *out) { return guarded([&] { return kmx_query_strings_impl(m, strs, len, n, out); }); }
+extern "C" int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out) { return guarded([&] { return kmx_query_seqs_impl(m, seq, offsets, n_seqs, out); }); }
+extern "C" int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out) { return guarded([&] { return kmx_query_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_out); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }
 extern "C" int kmx_load(const char *dir, kmx_model **out) { return guarded([&] { return kmx_load_impl(dir, out); }); }

@@ -165,14 +165,19 @@ def from_strings(strs, k: int) -> np.ndarray:
     return out[:, 0] if W == 1 else out
 
 
+def genome_bases(n_bases: int, seed: int = 11) -> np.ndarray:
+    """The random sequence genome_stream draws its k-mers from: uint64 base codes (A=0 C=1 G=2 T=3), first base first."""
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, 4, size=n_bases, dtype=np.uint64)
+
+
 def genome_stream(n_bases: int, k: int, ci: int, cs: int, seed: int = 11, seed_c: int = 2):
     """Genome-like stream: all overlapping k-mers of a random sequence, canonicalised, distinct, in listing order.
 
     Unlike independent draws these k-mers have their de Bruijn neighbours in the set, which is what the query's
     neighbour-based disambiguation (kmodel.hpp:286-359) feeds on."""
     assert k <= 32
-    rng = np.random.default_rng(seed)
-    bases = rng.integers(0, 4, size=n_bases, dtype=np.uint64)
+    bases = genome_bases(n_bases, seed)
     n = n_bases - k + 1
     v = np.zeros(n, dtype=np.uint64)
     for j in range(k):
