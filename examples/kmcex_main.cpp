@@ -2,6 +2,7 @@
 //
 //   kmcEx [options] <input_file_name> <output_file_name> <working_directory>
 //     -k<len> -t<threads> -ci<min> -cs<max> -nh<hashes> -nb<arrays>         (main.cpp:46-51)
+//     -g   count the input's k-mers on the GPU (KModel::init_reads) instead of running KMC; no KMC database is written
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -16,6 +17,7 @@
 
 struct Params {
 	int k = 31, num_hash = 7, num_bit = 5, ci = 1, cs = 1023, t = 4;
+	bool gpu_count = false;
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -31,6 +33,7 @@ static bool parse(int argc, char **argv, Params &p)
 		else if (!strncmp(a, "-cs", 3)) p.cs = atoi(a + 3);
 		else if (!strncmp(a, "-t", 2)) p.t = atoi(a + 2);
 		else if (!strncmp(a, "-k", 2)) p.k = atoi(a + 2);
+		else if (!strcmp(a, "-g")) p.gpu_count = true;
 	}
 	if (argc - i < 3) return false;
 	p.input = argv[argc - 3];
@@ -45,12 +48,15 @@ int main(int argc, char **argv)
 	if (!parse(argc, argv, p)) {
 		std::cout << "kmcEx (MI355X): counted k-mer encoding & decoding\n"
 		             "USAGE  kmcEx [options] <input_file_name|@list> <output_file_name> <working_directory>\n"
-		             "       -k<len> (31) -t<threads> (4) -ci<min count> (1) -cs<max count> (1023) -nh<hashes> (7) -nb<arrays> (5)\n";
+		             "       -k<len> (31) -t<threads> (4) -ci<min count> (1) -cs<max count> (1023) -nh<hashes> (7) -nb<arrays> (5)\n"
+		             "       -g  count the k-mers of the FASTQ / FASTA input on the GPU instead of running KMC\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
 	std::string kmc = env ? env : "./kmc_api/kmc";
-	if (access(kmc.c_str(), X_OK) == 0) {
+	if (p.gpu_count) {
+		std::cout << "counting the k-mers of " << p.input << " on the GPU" << std::endl;
+	} else if (access(kmc.c_str(), X_OK) == 0) {
 		char cmd[4096];
 		snprintf(cmd, sizeof cmd, "%s -k%d -t%d -ci%d -cs%d %s %s %s", kmc.c_str(), p.k, p.t, p.ci, p.cs, p.input.c_str(), p.output.c_str(), p.workdir.c_str());
 		std::cout << cmd << std::endl;
@@ -59,7 +65,8 @@ int main(int argc, char **argv)
 		std::cout << "no KMC binary (" << kmc << "): using the existing database " << p.output << std::endl;
 	}
 	KModel *km = get_model(p.ci, p.cs, p.num_hash, p.num_bit);
-	km->init(p.output);
+	if (p.gpu_count) km->init_reads(p.input, p.k);
+	else km->init(p.output);
 	km->show_header_info();
 	km->show_kmodel_info();
 	const size_t slash = p.output.find_last_of('/');

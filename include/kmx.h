@@ -226,6 +226,44 @@ int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint6
  * a decreasing pair as an empty sequence, so bad offsets give wrong answers, never an access outside d_seq / d_out.   */
 int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out);
 
+/* ---- k-mer counting on the device: KMC's step of the pipeline, then KModel::init on what it lists
+ * (main.cpp:137-146 runs KMC on the reads, then init on its database; kmodel.hpp:57-86).
+ * The counting rule:
+ *   - bases are A C G T and a c g t, coded A=0 C=1 G=2 T=3 (KMC's CKmerAPI::num_codes, kmc_api/kmer_api.h:264-275); every
+ *     other byte (N, IUPAC letters, anything else) is not a base.  Lowercase counts as bases HERE, while kmx_query_seqs /
+ *     kmer_to_occ hash a lowercase window byte for byte, as the reference does: that asymmetry is the reference pipeline's;
+ *   - a window is counted when it lies wholly inside one sequence and holds k bases: k-mers never span two sequences;
+ *   - its key is the canonical k-mer: the numeric minimum of the 2k-bit forward word and its reverse complement, for every k
+ *     in [3, 64] (the model's own hashing keeps the reference's k > 32 quirk; it is not part of the count);
+ *   - c = the windows with that key, saturating at 2^32 - 1.  A k-mer is listed iff ci <= c <= 10^9 (10^9 is KMC's default
+ *     -cx, which the reference's driver keeps; no input of the tests reaches it), with the count min(c, cs); ci, cs are the
+ *     handle's (kmx_create);
+ *   - the listing is ascending by the 2k-bit integer (word 0 most significant): the order of a KMC1-layout database.
+ * The model kmx_count_finish builds is kmx_build_dev on that listing, so it is bit-identical to KModel::init on a KMC1-layout
+ * database holding those k-mers and counts.  A KMC 3 database (KMC2 layout) lists the same k-mers bin-major, in an order set
+ * by KMC's signature binning; the reference's model of it has the same k-mers and counts, but its arrays may differ.
+ * Counting calls are build-class calls (see the threading note of kmx_query_packed).  A failure inside a session
+ * (KMX_E_NOMEM, KMX_E_IO, KMX_E_NODEVICE) ends it and leaves the previous model as it was.                                */
+/* start a session for k in [3, 64]; the model is untouched until finish; drops the listing of an earlier finish           */
+int kmx_count_begin(kmx_model *m, int k);
+/* count the windows of n_seqs sequences on HOST buffers, in the layout of kmx_query_seqs (offsets[0] = 0, non-decreasing,
+ * 64-bit, checked before anything runs: KMX_E_ARG); n_seqs == 0 or no bases: KMX_OK.  Outside a session: KMX_E_STATE      */
+int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], enqueued on the model's stream; the offsets are clamped
+ * by the kernel as in kmx_query_seqs_dev (bad offsets miscount, never read outside the buffers)                          */
+int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases);
+/* filter and cap, then the build (= kmx_build_dev on the listing): the handle is READY; *n_listed (may be NULL) = n_total.
+ * Nothing listed: what kmx_build_dev with n = 0 returns.  Outside a session: KMX_E_STATE                                  */
+int kmx_count_finish(kmx_model *m, uint64_t *n_listed);
+/* the listing the last finish built from (kept on the device until the next kmx_count_begin, build, or destroy): *n
+ * entries; kmers[n * W] (packed, W = ceil(k/32)) and counts[n] (may be NULL) when kmers != NULL and capacity >= *n      */
+int kmx_count_listing(kmx_model *m, uint64_t *kmers, uint32_t *counts, uint64_t capacity, uint64_t *n);
+/* begin + count + finish on reads from files: a FASTQ or FASTA path (plain or gzip, detected from the content) or "@list",
+ * a file of paths, one per line.  FASTQ records have their sequence on one line; FASTA records join their lines; a '\r'
+ * at a line end is dropped.  A malformed or truncated record: KMX_E_IO naming the file and the record.  gzip needs
+ * libz.so.1 at run time (opened with dlopen; plain input does not).                                                       */
+int kmx_build_from_reads(kmx_model *m, int k, const char *input);
+
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);
 /* get_model(save_dir) = header parse + KModel::load                        kmodel.hpp:680-696, :209-235 */

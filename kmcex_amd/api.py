@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "kmx_debug_pack_strings", "kmx_kernel_classes", "kmx_abi_version", "kmx_get_stats_n",
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
     "kmx_query_seqs", "kmx_query_seqs_dev",
+    "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
 
 
@@ -151,6 +152,12 @@ def load_library():
     _sig(L, "kmx_get_stats_n", [vp, vp, u64])
     _sig(L, "kmx_query_seqs", [vp, vp, vp, u64, vp])
     _sig(L, "kmx_query_seqs_dev", [vp, vp, vp, u64, u64, vp])
+    _sig(L, "kmx_count_begin", [vp, i32])
+    _sig(L, "kmx_count_seqs", [vp, vp, vp, u64])
+    _sig(L, "kmx_count_seqs_dev", [vp, vp, vp, u64, u64])
+    _sig(L, "kmx_count_finish", [vp, C.POINTER(u64)])
+    _sig(L, "kmx_count_listing", [vp, vp, vp, u64, C.POINTER(u64)])
+    _sig(L, "kmx_build_from_reads", [vp, i32, C.c_char_p])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -480,6 +487,53 @@ class KModel:
     def seq_to_occ_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, d_out_ptr: int) -> None:
         """kmx_query_seqs_dev: device buffers, enqueued on the model's stream (no wait)"""
         _chk(self.L.kmx_query_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, d_out_ptr))
+
+    # ---- k-mer counting on the device (KMC's step, then init on its listing: main.cpp:137-146)
+    def init_reads(self, path: str, k: int) -> None:
+        """kmx_build_from_reads: count the k-mers of a FASTQ / FASTA file (plain or gzip) or "@list" and build the model"""
+        _chk(self.L.kmx_build_from_reads(self.h, k, path.encode()))
+        self._count_k = k
+
+    def count_begin(self, k: int) -> None:
+        _chk(self.L.kmx_count_begin(self.h, k))
+        self._count_k = k
+
+    def count_seqs(self, seqs, offsets=None) -> None:
+        """kmx_count_seqs: a str / bytes sequence or a list of them, or (uint8 buf, uint64 offsets[n_seqs + 1])"""
+        if offsets is None:
+            items = [seqs] if isinstance(seqs, (str, bytes)) else list(seqs)
+            raw = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in items]
+            offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+            offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+            buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        else:
+            buf = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        if int(offsets[-1]) > buf.size:
+            raise KmxError(-1, f"offsets end at {int(offsets[-1])}, past the {buf.size} bases given")
+        _chk(self.L.kmx_count_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1))
+
+    def count_seqs_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int) -> None:
+        """kmx_count_seqs_dev: device buffers, enqueued on the model's stream"""
+        _chk(self.L.kmx_count_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases))
+
+    def count_finish(self) -> int:
+        """filter + cap, then the build; returns the number of k-mers listed"""
+        n = C.c_uint64()
+        _chk(self.L.kmx_count_finish(self.h, C.byref(n)))
+        return n.value
+
+    def count_listing(self):
+        """(kmers uint64[n, W] squeezed to [n] when W = 1, counts uint32[n]) the last count_finish built from"""
+        n = C.c_uint64()
+        _chk(self.L.kmx_count_listing(self.h, None, None, 0, C.byref(n)))
+        W = ((getattr(self, "_count_k", 0) or self.stats().k) + 31) // 32
+        kmers = np.zeros((n.value, W), dtype=np.uint64)
+        counts = np.zeros(n.value, dtype=np.uint32)
+        _chk(self.L.kmx_count_listing(self.h, kmers.ctypes.data, counts.ctypes.data, n.value, C.byref(n)))
+        return (kmers[:, 0].copy() if W == 1 else kmers), counts
 
     # ---- persistence
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173

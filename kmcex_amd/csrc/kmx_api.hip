@@ -6,6 +6,7 @@
 #include "../../include/kmx.h"
 #include "kmc_reader.h"
 #include "kmx_types.h"
+#include "reads_reader.h"
 #include "strpack.h"
 
 #include <algorithm>
@@ -66,6 +67,11 @@ hipError_t rest_index(const u64 *, u64, int, int, int, int *, int *, u64 *, int 
 void rest_expand(const int *, const int *, const u64 *, int, int, int, int, u64 *, hipStream_t);
 void rest_accel(const u64 *, u64, int, int, int, const int *, const int *, const u64 *, int, u32 *, u64 *, hipStream_t);
 void rest_suffix_bytes(const u64 *, u64, int, int, unsigned char *, hipStream_t);
+void count_windows(int, const unsigned char *, u64, const u64 *, u64, u64, u64, u64 *, u64 *, u64, unsigned long long *, hipStream_t);
+hipError_t count_piece(int, int, u64 *, u64 *, u64, u64, u32 *, unsigned long long *, void **, size_t *, hipStream_t);
+hipError_t count_merge(int, const u64 *, const u32 *, u64, const u64 *, const u32 *, u64, u64 *, u32 *, void **, size_t *, hipStream_t);
+hipError_t count_reduce(int, const u64 *, const u32 *, u64, u64 *, u32 *, unsigned long long *, void **, size_t *, hipStream_t);
+hipError_t count_filter(int, const u64 *, const u32 *, u64, u32, u32, u32, u64 *, u32 *, unsigned char *, unsigned long long *, void **, size_t *, hipStream_t);
 }   // namespace kmxk
 
 // ------------------------------------------------------------------------------------------ errors
@@ -327,6 +333,26 @@ struct kmx_model {
 	// queries on one handle may come from several host threads (the reference's kmer_to_occ is called from an OpenMP loop):
 	// one query at a time holds this for its whole length -- qfeed, prof's vectors and h_stats[ST_QUERY_*] are shared
 	std::mutex query_mu;
+	// a counting session (kmx_count_*, count_host.h): one piece of window keys, the running listing (sorted, unique, saturating
+	// counts) in two buffers, and after finish the listing the model was built from
+	struct CountState {
+		bool on = false;                                           // between kmx_count_begin and the end of kmx_count_finish
+		bool building = false;                                     // kmx_count_finish is building from the listing (kmx_begin keeps it)
+		int k = 0, W = 1;
+		u64 piece = 0, fill = 0;                                   // window slots per piece / windows launched into the current one
+		u64 *d_pa = nullptr, *d_pb = nullptr;                      // [W piece] each: the piece's keys, then its distinct keys; sort scratch
+		u32 *d_pc = nullptr;                                       // [piece] the distinct keys' counts
+		unsigned long long *d_n = nullptr;                         // [4] windows in the piece, distinct in the piece, listed, spare
+		u64 *d_run[2] = {nullptr, nullptr};                        // keys (W words each) of the running listing / of the merge
+		u32 *d_runc[2] = {nullptr, nullptr};
+		u64 run_cap[2] = {0, 0};                                   // entries the two buffers hold
+		u64 D = 0;                                                 // entries of the running listing (in d_run[0])
+		u64 windows = 0;                                           // windows counted so far
+		void *d_tmp = nullptr;                                     // rocPRIM scratch
+		size_t tmp_cap = 0;
+		bool listed = false;                                       // d_run[1] holds the listing of the last finish
+		u64 n_list = 0;
+	} cnt;
 };
 
 static void prof_begin(KernelProf *p, int cls, hipStream_t st)
@@ -540,6 +566,24 @@ static void free_query_feed(kmx_model *m)
 	f.seq_cap = 0;
 }
 
+// the buffers of a counting session; with `listing`, the listing of the last kmx_count_finish as well
+static void free_count(kmx_model *m, bool listing)
+{
+	auto &C = m->cnt;
+	if (C.d_pa || C.d_pc || C.d_n || C.d_tmp || C.d_run[0] || C.d_run[1]) hipStreamSynchronize(m->stream);
+	hipFree(C.d_pa); hipFree(C.d_pb); hipFree(C.d_pc); hipFree(C.d_n); hipFree(C.d_tmp); hipFree(C.d_run[0]); hipFree(C.d_runc[0]);
+	C.d_pa = C.d_pb = nullptr; C.d_pc = nullptr; C.d_n = nullptr; C.d_tmp = nullptr; C.tmp_cap = 0;
+	C.d_run[0] = nullptr; C.d_runc[0] = nullptr; C.run_cap[0] = 0;
+	C.on = false;
+	C.piece = C.fill = C.D = C.windows = 0;
+	if (listing || !C.listed) {
+		hipFree(C.d_run[1]); hipFree(C.d_runc[1]);
+		C.d_run[1] = nullptr; C.d_runc[1] = nullptr; C.run_cap[1] = 0;
+		C.listed = false;
+		C.n_list = 0;
+	}
+}
+
 static int kmx_destroy_impl(kmx_model *m)
 {
 	if (!m) return KMX_OK;
@@ -557,6 +601,7 @@ static int kmx_destroy_impl(kmx_model *m)
 	free_feed(m);
 	free_query_feed(m);
 	free_range(m);
+	free_count(m, true);
 	if (m->probe.side) { hipStreamSynchronize(m->probe.side); hipStreamDestroy(m->probe.side); hipEventDestroy(m->probe.fork); hipEventDestroy(m->probe.done); hipFree(m->probe.sink); }
 	for (hipEvent_t e : m->prof_events) hipEventDestroy(e);
 	delete m;
@@ -817,6 +862,7 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 	if (!m) return fail(KMX_E_ARG, "null model");
 	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
 	HIPCHK(hipSetDevice(m->device));
+	if (!m->cnt.building) free_count(m, true);                   // a build from other data ends a counting session and drops its listing
 	u64 s = 0;
 	for (int i = 0; i < m->bf_num; i++) s += n_bf[i];
 	if (s > n_total) return fail(KMX_E_ARG, "n_bf exceeds n_total");
@@ -2022,7 +2068,8 @@ struct SlotShape {
 
 // n items of item_bytes each through the pipeline.  stage(worker, lo, hi, dst): items [lo, hi) -> dst (their place in the
 // slot); launch(slot, count) or launch(slot, count, chunk): the kernel from d_in[slot] to d_out[slot] on the model's
-// stream, chunk by chunk in order; answers -> out[0 .. n).
+// stream, chunk by chunk in order; answers -> out[0 .. n).  out == nullptr: the kernels answer nothing (kmx_count_seqs),
+// and a slot is free again once its kernel has run.
 // The caller holds m->query_mu.
 template <typename STAGE, typename LAUNCH>
 static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE stage, LAUNCH launch, int32_t *out, const SlotShape *shape = nullptr)
@@ -2032,7 +2079,7 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 	C = std::min<u64>(C, (n + kQuerySub - 1) & ~(kQuerySub - 1));
 	if (shape) C = shape->chunk;
 	const u64 nc = (n + C - 1) / C;
-	TRY(ensure_query_feed(m, shape ? shape->slot_bytes : (size_t)C * item_bytes, (size_t)C));
+	TRY(ensure_query_feed(m, shape ? shape->slot_bytes : (size_t)C * item_bytes, out ? (size_t)C : 0));
 	auto count_of = [&](u64 c) { return std::min<u64>(C, n - c * C); };
 	auto subs_of = [&](u64 c) { return (count_of(c) + kQuerySub - 1) / kQuerySub; };
 	auto enqueue = [&](u64 c) -> bool {
@@ -2043,12 +2090,12 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 		if constexpr (std::is_invocable_v<LAUNCH, int, u64, u64>) launch(s, cn, c);
 		else launch(s, cn);
 		return hipEventRecord(F.ev_k[s], m->stream) == hipSuccess && hipStreamWaitEvent(F.to_host, F.ev_k[s], 0) == hipSuccess &&
-		       hipMemcpyAsync(F.h_out[s], F.d_out[s], cn * 4, hipMemcpyDeviceToHost, F.to_host) == hipSuccess && hipEventRecord(F.ev_out[s], F.to_host) == hipSuccess;
+		       (!out || hipMemcpyAsync(F.h_out[s], F.d_out[s], cn * 4, hipMemcpyDeviceToHost, F.to_host) == hipSuccess) && hipEventRecord(F.ev_out[s], F.to_host) == hipSuccess;
 	};
 	if (nc == 1 && T == 1) {                                      // a handful of strings: no threads
 		stage(0, 0, n, F.h_in[0]);
 		if (!enqueue(0) || hipEventSynchronize(F.ev_out[0]) != hipSuccess) return fail(KMX_E_NODEVICE, "query failed");
-		memcpy(out, F.h_out[0], n * 4);
+		if (out) memcpy(out, F.h_out[0], n * 4);
 		return KMX_OK;
 	}
 	// phase p = the pack tasks of chunk p, then the copy-out tasks of chunk p - 2
@@ -2087,7 +2134,7 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 				const u64 c = p - lag;
 				if (!wait_for([&] { return ready[c].load(std::memory_order_acquire) != 0; })) return;
 				const u64 lo = c * C + s * kQuerySub, hi = std::min<u64>(lo + kQuerySub, c * C + count_of(c));
-				memcpy(out + lo, F.h_out[c % F.S] + (lo - c * C), (hi - lo) * 4);
+				if (out) memcpy(out + lo, F.h_out[c % F.S] + (lo - c * C), (hi - lo) * 4);
 				copied[c].fetch_add(1, std::memory_order_release);
 			}
 		}
@@ -2220,57 +2267,81 @@ static int kmx_query_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64
 	return KMX_OK;
 }
 
-// The host variant streams the bases through the slots of m->qfeed (query_pipeline): chunk c answers windows
-// [c * C, c * C + cn) and carries the bases [c * C, c * C + nbytes), nbytes = min(cn + k - 1, n_bases - c * C), then, at
-// byte off_at, the sequence boundaries that fall inside those bytes, rebased to the chunk and deduplicated, between 0
-// and nbytes.  A sequence cut by the chunk's edges ends at nbytes there, which changes no answer: a window of the chunk
-// that fits in its sequence also fits in the chunk's bytes.
+// The host variants (kmx_query_seqs, kmx_count_seqs) stream the bases through the slots of m->qfeed (query_pipeline):
+// chunk c takes the windows [c * C, c * C + cn) and carries the bases [c * C, c * C + nbytes), nbytes = min(cn + k - 1,
+// n_bases - c * C), then, at byte off_at, the sequence boundaries that fall inside those bytes, rebased to the chunk and
+// deduplicated, between 0 and nbytes.  A sequence cut by the chunk's edges ends at nbytes there, which changes no
+// window: a window of the chunk that fits in its sequence also fits in the chunk's bytes.
+struct SeqChunks {
+	const char *seq;
+	const uint64_t *offsets;
+	u64 n_seqs, n_bases, k, C, nc;
+	size_t off_at;
+	std::vector<u64> n_bnd;                                        // boundaries chunk c carries (written by the worker that stages its end)
+	SeqChunks(const char *seq_, const uint64_t *offsets_, u64 n_seqs_, u64 k_, u64 chunk)
+		: seq(seq_), offsets(offsets_), n_seqs(n_seqs_), n_bases(offsets_[n_seqs_]), k(k_), C(std::min<u64>(chunk, n_bases)),
+		  nc((n_bases + C - 1) / C), off_at((size_t)((C + 64 + 7) & ~u64(7))), n_bnd(nc, 0) {}
+	u64 nbytes_of(u64 c) const { const u64 c0 = c * C, cn = std::min<u64>(C, n_bases - c0); return std::min<u64>(cn + k - 1, n_bases - c0); }
+	SlotShape shape() { return SlotShape{C, off_at + 8 * (size_t)(C + 64), [this](u64 c) { return off_at + 8 * (size_t)n_bnd[c]; }}; }
+	int workers() const { return (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1)); }
+	// the pipeline's stage: bases [lo, hi) of one chunk -> dst; the task holding the chunk's last window adds its halo and boundaries
+	void stage(u64 lo, u64 hi, unsigned char *dst)
+	{
+		memcpy(dst, seq + lo, hi - lo);
+		const u64 c = lo / C, c0 = c * C;
+		if (hi != c0 + std::min<u64>(C, n_bases - c0)) return;
+		unsigned char *slot = dst - (lo - c0);
+		const u64 nbytes = nbytes_of(c), cn = hi - c0;
+		memcpy(slot + cn, seq + hi, nbytes - cn);
+		u64 *bnd = (u64 *)(slot + off_at), nb = 0;
+		bnd[nb++] = 0;
+		for (u64 i = (u64)(std::upper_bound(offsets, offsets + n_seqs + 1, c0) - offsets); i <= n_seqs && offsets[i] < c0 + nbytes; i++)
+			if (offsets[i] - c0 != bnd[nb - 1]) bnd[nb++] = offsets[i] - c0;
+		bnd[nb++] = nbytes;
+		n_bnd[c] = nb;
+	}
+	// chunk c in device slot d_slot: its bases, its boundaries (n_seqs_of(c) sequences)
+	const u64 *bounds(const unsigned char *d_slot) const { return (const u64 *)(d_slot + off_at); }
+	u64 seqs_of(u64 c) const { return n_bnd[c] - 1; }
+};
+
+// KMX_E_ARG when offsets[0] != 0 or the offsets decrease (before anything runs)
+static int check_offsets(const uint64_t *offsets, uint64_t n_seqs)
+{
+	if (!offsets) return fail(KMX_E_ARG, "null argument");
+	if (offsets[0] != 0) return fail(KMX_E_ARG, "offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
+	for (u64 i = 0; i < n_seqs; i++)
+		if (offsets[i + 1] < offsets[i]) return fail(KMX_E_ARG, "offsets decrease at sequence %llu", (unsigned long long)i);
+	return KMX_OK;
+}
+
 static int kmx_query_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
 	std::lock_guard<std::mutex> lk(m->query_mu);
 	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	if (!n_seqs) return KMX_OK;
-	if (!offsets) return fail(KMX_E_ARG, "null argument");
-	if (offsets[0] != 0) return fail(KMX_E_ARG, "offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
-	for (u64 i = 0; i < n_seqs; i++)
-		if (offsets[i + 1] < offsets[i]) return fail(KMX_E_ARG, "offsets decrease at sequence %llu", (unsigned long long)i);
+	TRY(check_offsets(offsets, n_seqs));
 	const u64 n_bases = offsets[n_seqs];
 	if (!n_bases) return KMX_OK;
 	if (!seq || !out) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 k = (u64)m->k, hook = seq_chunk_hook();
-	const u64 C = std::min<u64>(hook ? hook : kSeqChunk, n_bases);
-	const size_t off_at = (size_t)((C + 64 + 7) & ~u64(7));
-	TRY(ensure_seq_scratch(m, C));
-	const u64 nc = (n_bases + C - 1) / C;
-	std::vector<u64> n_bnd(nc, 0);                                 // boundaries chunk c carries (written by the worker that stages its end)
-	auto nbytes_of = [&](u64 c) { const u64 c0 = c * C, cn = std::min<u64>(C, n_bases - c0); return std::min<u64>(cn + k - 1, n_bases - c0); };
-	SlotShape shape{C, off_at + 8 * (size_t)(C + 64), [&](u64 c) { return off_at + 8 * (size_t)n_bnd[c]; }};
-	const int T = (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1));
+	const u64 hook = seq_chunk_hook();
+	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, hook ? hook : kSeqChunk);
+	TRY(ensure_seq_scratch(m, sc.C));
+	const SlotShape shape = sc.shape();
 	int par = 0;
 	auto &F = m->qfeed;
-	return query_pipeline(m, n_bases, 1, T,
-		[&](int, u64 lo, u64 hi, unsigned char *dst) {
-			memcpy(dst, seq + lo, hi - lo);
-			const u64 c = lo / C, c0 = c * C;
-			if (hi != c0 + std::min<u64>(C, n_bases - c0)) return;
-			unsigned char *slot = dst - (lo - c0);                // the task holding the chunk's last window adds its halo and boundaries
-			const u64 nbytes = nbytes_of(c), cn = hi - c0;
-			memcpy(slot + cn, seq + hi, nbytes - cn);
-			u64 *bnd = (u64 *)(slot + off_at), nb = 0;
-			bnd[nb++] = 0;
-			for (u64 i = (u64)(std::upper_bound(offsets, offsets + n_seqs + 1, c0) - offsets); i <= n_seqs && offsets[i] < c0 + nbytes; i++)
-				if (offsets[i] - c0 != bnd[nb - 1]) bnd[nb++] = offsets[i] - c0;
-			bnd[nb++] = nbytes;
-			n_bnd[c] = nb;
-		},
+	return query_pipeline(m, n_bases, 1, sc.workers(),
+		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
-			kmxk::query_seq(m->md, F.d_in[s], nbytes_of(c), (const u64 *)(F.d_in[s] + off_at), n_bnd[c] - 1, 0, cn, F.d_out[s],
+			kmxk::query_seq(m->md, F.d_in[s], sc.nbytes_of(c), sc.bounds(F.d_in[s]), sc.seqs_of(c), 0, cn, F.d_out[s],
 			                F.d_seq_list, (u32)F.seq_cap, F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
 			par ^= 1;
 		}, out, &shape);
 }
+
+#include "count_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -2763,6 +2834,12 @@ extern "C" int kmx_query_ascii(kmx_model *m, const char *strs, int len, int stri
 extern "C" int kmx_query_strings(kmx_model *m, const char *const *strs, int len, uint64_t n, int32_t *out) { return guarded([&] { return kmx_query_strings_impl(m, strs, len, n, out); }); }
 extern "C" int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out) { return guarded([&] { return kmx_query_seqs_impl(m, seq, offsets, n_seqs, out); }); }
 extern "C" int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out) { return guarded([&] { return kmx_query_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_out); }); }
+extern "C" int kmx_count_begin(kmx_model *m, int k) { return guarded([&] { return kmx_count_begin_impl(m, k); }); }
+extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }
+extern "C" int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases) { return guarded([&] { return kmx_count_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases); }); }
+extern "C" int kmx_count_finish(kmx_model *m, uint64_t *n_listed) { return guarded([&] { return kmx_count_finish_impl(m, n_listed); }); }
+extern "C" int kmx_count_listing(kmx_model *m, uint64_t *kmers, uint32_t *counts, uint64_t capacity, uint64_t *n) { return guarded([&] { return kmx_count_listing_impl(m, kmers, counts, capacity, n); }); }
+extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }
 extern "C" int kmx_load(const char *dir, kmx_model **out) { return guarded([&] { return kmx_load_impl(dir, out); }); }
