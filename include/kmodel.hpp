@@ -119,7 +119,8 @@ public:
 	}
 	void init_KModel(std::string db_file) { init(db_file); }                 // README.md:76
 	// KMC's counting step and init together (main.cpp:137-146): the k-mers of a FASTQ / FASTA file (plain or gzip) or "@list"
-	// counted on the GPU, the model built from their listing (kmx_build_from_reads).  Errors as init: a message, then exit(1).
+	// counted on the GPU, the model built from their listing (kmx_build_from_reads), k in [4, 64] like every model here (the
+	// reference's rest table is undefined at k = 3).  Errors as init: a message, then exit(1).
 	void init_reads(const std::string &input, int k) { check(kmx_build_from_reads(h_, k, input.c_str())); }
 
 	// kmodel.hpp:90 -- t_num is accepted for source compatibility; the batch runs on the GPU

@@ -14,7 +14,11 @@
  *   - packed k-mers: W = ceil(k/32) uint64 words per k-mer, word 0 most significant, holding the
  *     2k-bit integer right-aligned, A=0 C=1 G=2 T=3, first base most significant (tools.hpp:63-76);
  *   - "_dev" variants take DEVICE pointers valid on the model's device and enqueue on the model's
- *     stream (kmx_set_stream); they synchronise that stream only where a count has to reach the host.
+ *     stream (kmx_set_stream); they synchronise that stream only where a count has to reach the host;
+ *   - the k of a model or of a counting session is in [4, 64]: every entry point that builds, counts or
+ *     loads one refuses k = 3 with KMX_E_ARG before anything runs, and leaves the handle as it was.  The
+ *     reference's rest table is undefined there (rest.hpp:78-83 gives k = 3 a prefix of 7 bases), so it
+ *     cannot build that model either.  The kmx_debug_* entry points take k in [3, 64].
  */
 #ifndef KMX_H
 #define KMX_H
@@ -234,17 +238,17 @@ int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offset
  *     kmer_to_occ hash a lowercase window byte for byte, as the reference does: that asymmetry is the reference pipeline's;
  *   - a window is counted when it lies wholly inside one sequence and holds k bases: k-mers never span two sequences;
  *   - its key is the canonical k-mer: the numeric minimum of the 2k-bit forward word and its reverse complement, for every k
- *     in [3, 64] (the model's own hashing keeps the reference's k > 32 quirk; it is not part of the count);
+ *     in [4, 64] (the model's own hashing keeps the reference's k > 32 quirk; it is not part of the count);
  *   - c = the windows with that key, saturating at 2^32 - 1.  A k-mer is listed iff ci <= c <= 10^9 (10^9 is KMC's default
- *     -cx, which the reference's driver keeps; no input of the tests reaches it), with the count min(c, cs); ci, cs are the
- *     handle's (kmx_create);
+ *     -cx, which the reference's driver keeps; tests/test_gpu_count_edges.py reaches 10^9, 10^9 + 1 and 2^32 + 5), with
+ *     the count min(c, cs); ci, cs are the handle's (kmx_create);
  *   - the listing is ascending by the 2k-bit integer (word 0 most significant): the order of a KMC1-layout database.
  * The model kmx_count_finish builds is kmx_build_dev on that listing, so it is bit-identical to KModel::init on a KMC1-layout
  * database holding those k-mers and counts.  A KMC 3 database (KMC2 layout) lists the same k-mers bin-major, in an order set
  * by KMC's signature binning; the reference's model of it has the same k-mers and counts, but its arrays may differ.
  * Counting calls are build-class calls (see the threading note of kmx_query_packed).  A failure inside a session
  * (KMX_E_NOMEM, KMX_E_IO, KMX_E_NODEVICE) ends it and leaves the previous model as it was.                                */
-/* start a session for k in [3, 64]; the model is untouched until finish; drops the listing of an earlier finish           */
+/* start a session for k in [4, 64]; the model is untouched until finish; drops the listing of an earlier finish           */
 int kmx_count_begin(kmx_model *m, int k);
 /* count the windows of n_seqs sequences on HOST buffers, in the layout of kmx_query_seqs (offsets[0] = 0, non-decreasing,
  * 64-bit, checked before anything runs: KMX_E_ARG); n_seqs == 0 or no bases: KMX_OK.  Outside a session: KMX_E_STATE      */
@@ -266,7 +270,8 @@ int kmx_build_from_reads(kmx_model *m, int k, const char *input);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);
-/* get_model(save_dir) = header parse + KModel::load                        kmodel.hpp:680-696, :209-235 */
+/* get_model(save_dir) = header parse + KModel::load                        kmodel.hpp:680-696, :209-235
+ * rest.bin with k = 3: KMX_E_ARG; with a prefix longer than k (or not k minus whole groups of 4 bases): KMX_E_IO */
 int kmx_load(const char *dir, kmx_model **out);
 
 int kmx_get_stats(kmx_model *m, kmx_stats *st);

@@ -115,7 +115,7 @@ static int count_launch(kmx_model *m, const unsigned char *d_seq, u64 n_bases, c
 static int kmx_count_begin_impl(kmx_model *m, int k)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
+	TRY(check_model_k(k));
 	HIPCHK(hipSetDevice(m->device));
 	free_count(m, true);
 	auto &C = m->cnt;
@@ -220,7 +220,7 @@ static int kmx_count_listing_impl(kmx_model *m, uint64_t *kmers, uint32_t *count
 static int kmx_build_from_reads_impl(kmx_model *m, int k, const char *input)
 {
 	if (!m || !input) return fail(KMX_E_ARG, "null argument");
-	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
+	TRY(check_model_k(k));
 	std::vector<std::string> files;
 	std::string err;
 	if (!kmx::reads_inputs(input, files, err)) return fail(KMX_E_IO, "%s", err.c_str());

@@ -46,6 +46,7 @@ template <typename T> T rd(const unsigned char *p)
 bool KmcListing::open(const std::string &prefix, bool load_lut)
 {
 	close();
+	k_ = 0;                                                         // kmer_length() after a failed open: the header's k, or 0 if it was not read
 	const int pfd = ::open((prefix + ".kmc_pre").c_str(), O_RDONLY);
 	struct stat psb;
 	auto pread_all = [&](void *dst, size_t bytes, uint64_t off) { return pread_fully(pfd, dst, bytes, off); };

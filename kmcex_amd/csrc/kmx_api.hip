@@ -188,6 +188,13 @@ struct RestTable {
 	u64 *d_q = nullptr;
 };
 static int rest_prefix_len(int k) { for (int i = 7; i >= 3; i--) if ((k - i) % 4 == 0) return i; return 3; }   // rest.hpp:78-83
+// k of a model or of a counting session.  rest.hpp:78-83 gives k = 3 a prefix of 7 bases (-4 % 4 == 0 in C): a suffix of
+// -1 groups and a -8-bit suffix field, so the reference cannot build that model; like any input it cannot handle, it is refused.
+static int check_model_k(int k)
+{
+	if (k < 4 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [4,64]%s", k, k == 3 ? ": the reference's rest table is undefined at k = 3 (prefix of 7 bases, rest.hpp:78-83)" : "");
+	return KMX_OK;
+}
 
 struct RestEnt { u64 w[2]; int c; };
 
@@ -860,7 +867,7 @@ static int kmback_job_flush(kmx_model *m)
 static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t n_total)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
+	TRY(check_model_k(k));
 	HIPCHK(hipSetDevice(m->device));
 	if (!m->cnt.building) free_count(m, true);                   // a build from other data ends a counting session and drops its listing
 	u64 s = 0;
@@ -1440,14 +1447,14 @@ static int build_common(kmx_model *m, int k, const u64 *d_kmers, const u32 *d_co
 static int kmx_build_dev_impl(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
+	TRY(check_model_k(k));
 	return build_common(m, k, (const u64 *)d_kmers, (const u32 *)d_counts, n, n);
 }
 
 static int kmx_build_host_impl(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (k < 3 || k > 64) return fail(KMX_E_ARG, "k=%d out of range [3,64]", k);
+	TRY(check_model_k(k));
 	if (n && (!kmers || !counts)) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
 	HIPCHK(hipEventRecord(m->ev0, m->stream));
@@ -1542,6 +1549,14 @@ static bool feed_alloc(kmx_model *m, size_t B, size_t rb, int W, const kmx::KmcL
 	return good;
 }
 
+// a database that cannot be opened is KMX_E_IO, unless its header was read and gives a k no model takes (a KMC database of
+// k = 3 is refused as kmx_build_dev refuses k = 3)
+static int kmc_open_failed(const kmx::KmcListing &db, const char *db_prefix)
+{
+	if (db.kmer_length() >= 1 && db.kmer_length() < 4) return check_model_k((int)db.kmer_length());
+	return fail(KMX_E_IO, "can't open the kmer_data_base %s: %s", db_prefix, db.error().c_str());
+}
+
 static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 {
 	if (!m || !db_prefix) return fail(KMX_E_ARG, "null argument");
@@ -1550,7 +1565,7 @@ static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 	const auto t_start = std::chrono::steady_clock::now();
 	auto lap = [&](const char *what) { if (trace) fprintf(stderr, "[kmx] init(db) %-28s at %7.2f ms\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count() * 1e3); };
 	kmx::KmcListing db;
-	if (!db.open(db_prefix, false)) return fail(KMX_E_IO, "can't open the kmer_data_base %s: %s", db_prefix, db.error().c_str());
+	if (!db.open(db_prefix, false)) return kmc_open_failed(db, db_prefix);
 	unsigned hw = std::thread::hardware_concurrency();
 	const int T = hw > 32 ? 16 : (hw > 1 ? (int)hw / 2 : 1);          // per activity: pass 1 and the producer run side by side
 	db.set_threads(T);
@@ -2531,7 +2546,10 @@ static int kmx_load_impl(const char *dir, kmx_model **out)
 	bool ok = fread(h, 4, 4, f) == 4 && fread(&r.suff_bin_size, 8, 1, f) == 1 && fread(&r.entries, 8, 1, f) == 1;
 	if (ok) {
 		r.k = h[0]; r.pre_len = h[1]; r.map_size = h[2]; r.pre_buffer_size = h[3];
-		ok = r.k >= 3 && r.k <= 64 && r.pre_len >= 1 && r.pre_len <= 12 && r.map_size == (1 << (2 * r.pre_len)) && r.pre_buffer_size >= 1;
+		if (r.k >= 1 && r.k < 4) { fclose(f); return bail(check_model_k(r.k)); }
+		// the lookup takes the suffix as 2 (k - pre_len) bits in whole groups of 4 bases (rest.hpp:143-145)
+		ok = r.k >= 4 && r.k <= 64 && r.pre_len >= 1 && r.pre_len <= 12 && r.pre_len <= r.k && (r.k - r.pre_len) % 4 == 0 &&
+		     r.map_size == (1 << (2 * r.pre_len)) && r.pre_buffer_size >= 1;
 	}
 	if (ok) {
 		r.suff_group = (r.k - r.pre_len) / 4;

@@ -130,7 +130,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 	}
 	if (P == 1 && !by_range) return kmx_build_from_kmc_impl(hs[0], db_prefix);      // (one handle, by range: the partition's kernels alone, every word "sent" to itself)
 	kmx::KmcListing db;
-	if (!db.open(db_prefix, false)) return fail(KMX_E_IO, "can't open the kmer_data_base %s: %s", db_prefix, db.error().c_str());
+	if (!db.open(db_prefix, false)) return kmc_open_failed(db, db_prefix);
 	const int k = (int)db.kmer_length(), W = db.words(), nb = hs[0]->nb;
 	const u64 N = db.records();
 	const size_t rb = db.record_bytes();

@@ -394,7 +394,7 @@ int kmo_build_declared(kmo_model *m, int k, const uint64_t *kmers, const uint32_
 }
 static int build_impl(kmo_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint64_t total_kmers, const uint64_t *declared_n_bf)
 {
-	if (!m || k < 3 || k > 64) return -1;
+	if (!m || k < 4 || k > 64) return -1;                    /* k = 3: the reference's rest table is undefined (rest.hpp:78-83) */
 	int W = (k + 31) / 32, nb = m->nb;
 	m->k = k;
 	/* pass 1 (:423-434) */
@@ -453,7 +453,7 @@ static int build_impl(kmo_model *m, int k, const uint64_t *kmers, const uint32_t
  * Test infrastructure like everything else in this file. ---- */
 int kmo_shard_begin(kmo_model *m, int k, const uint64_t n_bf[3], uint64_t total_kmers)
 {
-	if (!m || k < 3 || k > 64) return -1;
+	if (!m || k < 4 || k > 64) return -1;                    /* k = 3: the reference's rest table is undefined (rest.hpp:78-83) */
 	m->k = k;
 	for (int i = 0; i < 3; i++) m->n_bf[i] = i < m->bf_num ? n_bf[i] : 0;
 	m->total = total_kmers;

@@ -46,13 +46,13 @@ def assert_same_model(m1, m2, nb):
         assert np.array_equal(x, y)
 
 
-@pytest.mark.parametrize("k", [16, 21, 27, 31, 32, 33, 55, 64])
+@pytest.mark.parametrize("k", [16, 21, 27, 31, 32, 33, 55, 64, 4, 5, 7, 8, 11, 15])
 @pytest.mark.parametrize("ci", [1, 2, 3])
 def test_listing_matches_restatement(k, ci):
     cs = 20
     buf, off = R.flatten(reads_for(k))
     km, cnt = CR.count(buf, off, k, ci, cs)
-    assert (cnt == cs).any() and len(km) > 1000
+    assert (cnt == cs).any() and len(km) > min(1000, 4 ** k // 4)      # (136 canonical 4-mers, 512 5-mers)
     m = KModel(ci, cs, NH, NB)
     m.count_begin(k)
     m.count_seqs(buf, off)
@@ -139,7 +139,7 @@ def test_batches_pieces_and_device_input(k, monkeypatch):
         assert_same_model(ref, m, NB)
 
 
-def test_cap_state_and_arguments():
+def test_cap_state_and_arguments(tmp_path):
     k = 21
     m = KModel(1, 20, NH, NB)
     L = m.L
@@ -160,6 +160,68 @@ def test_cap_state_and_arguments():
     assert km.tolist() == [0] and cnt.tolist() == [20]
     assert L.kmx_count_finish(m.h, None) == -4                  # the session ended with finish
     assert L.kmx_count_begin(m.h, 2) == -1 and L.kmx_count_begin(m.h, 65) == -1
+    _k3_refused_everywhere(m, tmp_path)
+    km, cnt = m.count_listing()                                  # the listing of the last finish is still there
+    assert km.tolist() == [0] and cnt.tolist() == [20]
+
+
+def _k3_refused_everywhere(m, tmp_path):
+    """k = 3 (the reference's rest table is undefined there) is KMX_E_ARG at every entry point that builds, counts or loads a
+    model, before anything is launched, and the model built before answers the same; k = 4 is taken"""
+    from kmcex_amd import kmcdb
+    import small_k as SK
+    L = m.L
+    q = np.array([0, 1, 5, 2 ** 42 - 1], dtype=np.uint64)
+    before = m.kmer_to_occ_packed(q)
+    st0 = m.stats()
+    km3 = np.arange(10, dtype=np.uint64)
+    cnt3 = np.ones(10, dtype=np.uint32)
+    nbf = [10, 0, 0]
+    CR.write_fastq(str(tmp_path / "r.fq"), [b"ACGTACGTAC"] * 3)
+    # a KMC1 database whose header says k = 3 (write one of k = 4, then set the header's k)
+    km4, cnt4 = SK.listing("k4_full")
+    db = str(tmp_path / "db3")
+    kmcdb.write_kmc1(db, km4, cnt4, 4, 1, 255)
+    with open(db + ".kmc_pre", "r+b") as f:
+        f.seek(-(8 + 64), os.SEEK_END)
+        f.write((3).to_bytes(4, "little"))
+    calls = {"begin": lambda: m.begin(3, nbf, 10),
+             "build_dev": lambda: m.build_dev(3, 0, 0, 0),
+             "build_host": lambda: m.build_packed(3, km3, cnt3),
+             "count_begin": lambda: m.count_begin(3),
+             "build_from_reads": lambda: m.init_reads(str(tmp_path / "r.fq"), 3),
+             "build_from_kmc": lambda: m.init(db),
+             "shard_begin (ring)": lambda: m.shard_begin(3, nbf, 10, 0, 1),
+             "range_begin": lambda: m.range_begin(3, nbf, 10, 0, 1)}
+    for what, call in calls.items():
+        with pytest.raises(KmxError) as e:
+            call()
+        assert e.value.code == -1 and "k=3" in str(e.value) and "rest table" in str(e.value), what
+        assert np.array_equal(m.kmer_to_occ_packed(q), before), what
+        st = m.stats()
+        assert (st.k, st.n_total, st.rest_entries, st.km_byte_size) == (st0.k, st0.n_total, st0.rest_entries, st0.km_byte_size), what
+    # kmx_load: a saved model whose rest.bin says k = 3, and one whose prefix is longer than k
+    m4 = KModel(1, 255, 3, 1)
+    m4.build_packed(4, km4, cnt4)
+    (tmp_path / "m4").mkdir()
+    m4.save(str(tmp_path / "m4"))
+    m7 = KModel(1, 255, 3, 1)
+    km7, cnt7 = SK.listing("k7_part")
+    m7.build_packed(7, km7, np.minimum(cnt7, 255))
+    (tmp_path / "m7").mkdir()
+    m7.save(str(tmp_path / "m7"))
+    for name, k_field, code in (("m4", 3, -1), ("m7", 6, -3)):
+        with open(str(tmp_path / name / "rest.bin"), "r+b") as f:
+            f.write(k_field.to_bytes(4, "little"))
+        with pytest.raises(KmxError) as e:
+            KModel.load(str(tmp_path / name))
+        assert e.value.code == code, name
+    # k = 4 is the smallest k a model or a session takes
+    m4b = KModel(1, 20, NH, NB)
+    m4b.count_begin(4)
+    m4b.count_seqs([b"ACGTTT" * 5])
+    assert m4b.count_finish() > 0
+    assert KModel(1, 20, NH, NB).begin(4, [1, 0, 0], 1) is None
 
 
 def test_nothing_listed_is_build_dev_of_nothing():

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("k", [31, 55, 21, 32, 33, 64, 16])
+@pytest.mark.parametrize("k", [31, 55, 21, 32, 33, 64, 16] + list(range(3, 16)))
 def test_device_hash_matches_oracle(k):
     """MurmurHash64A over the rebuilt ASCII string, k-mer and (k-2)-mer (tools.hpp:16-50)."""
     km = synth.random_kmers(2000, k, seed_k=5)
@@ -42,7 +42,7 @@ def test_device_hash_known_answers():
         assert int(api.debug_hash(31, km, seed0, False)[0, 0]) == h_back
 
 
-@pytest.mark.parametrize("k", [31, 55, 21, 32, 40, 64])
+@pytest.mark.parametrize("k", [31, 55, 21, 32, 40, 64] + list(range(4, 16)))
 def test_device_min_kmer_matches_oracle(k):
     """get_min_kmer incl. the k>32 overflow (tools.hpp:160-167, quirk Q4)."""
     km = synth.random_kmers(3000, k, seed_k=11)
