@@ -10,7 +10,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libkmx.so")
 SOURCES = ["kernels.hip", "rest_device.hip", "count_device.hip", "kmx_api.hip", "kmc_reader.cpp", "reads_reader.cpp", "strpack.cpp"]
-HEADERS = ["device_common.h", "kmx_types.h", "kmc_reader.h", "strpack.h", "range_kernels.h", "multi_build.h", "range_host.h", "count_kernels.h", "count_host.h", "reads_reader.h", os.path.join("..", "..", "include", "kmx.h")]
+HEADERS = ["device_common.h", "kmx_types.h", "hip_owned.h", "launchers.h", "kmc_reader.h", "strpack.h", "range_kernels.h", "multi_build.h", "range_host.h", "count_kernels.h", "count_host.h", "reads_reader.h", os.path.join("..", "..", "include", "kmx.h")]
 
 
 def hipcc() -> str:
@@ -46,7 +46,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
     failed = [c for c, p in zip(cmds, procs) if p.wait() != 0]
     if failed:
         raise subprocess.CalledProcessError(1, failed[0])
-    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-ldl"]
+    cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined", "-o", LIB] + objs + ["-ldl"]   # a launcher whose parameter list drifted from launchers.h fails here, not at load
     if verbose:
         print(" ".join(cmd), flush=True)
     subprocess.check_call(cmd)

@@ -5,7 +5,8 @@
 // unique, and equal keys are then reduced with a saturating sum.  The listing's keys are in the packed layout of
 // include/kmx.h (W words per key, word 0 most significant), so the build takes them as they are.  rocPRIM is the vendor
 // primitive for these whole-array passes, as for the rest table (rest_device.hip); its scratch is small beside the arrays.
-#include "kmx_types.h"
+#include "hip_owned.h"
+#include "launchers.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -40,57 +41,37 @@ __global__ __launch_bounds__(256) void k_cap(u32 *c, const unsigned long long *n
 
 inline unsigned nblk(u64 n) { return (unsigned)((n + 255) / 256); }
 
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
-// the caller's scratch, grown (after the stream has drained) when a pass asks for more
-struct Scratch {
-	void **p;
-	size_t *cap;
-	hipStream_t st;
-	hipError_t need(size_t bytes)
-	{
-		if (bytes <= *cap && *p) return hipSuccess;
-		RCHK(hipStreamSynchronize(st));
-		hipFree(*p);
-		*p = nullptr;
-		*cap = 0;
-		RCHK(hipMalloc(p, bytes ? bytes : 16));
-		*cap = bytes;
-		return hipSuccess;
-	}
-};
-
 template <typename KT, typename LESS>
-hipError_t merge_t(const KT *a, const u32 *ac, u64 na, const KT *b, const u32 *bc, u64 nb, KT *m, u32 *mc, Scratch s)
+hipError_t merge_t(const KT *a, const u32 *ac, u64 na, const KT *b, const u32 *bc, u64 nb, KT *m, u32 *mc, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
 	size_t bytes = 0;
-	RCHK(rocprim::merge(nullptr, bytes, a, b, m, ac, bc, mc, (size_t)na, (size_t)nb, LESS(), s.st));
-	RCHK(s.need(bytes));
-	return rocprim::merge(*s.p, bytes, a, b, m, ac, bc, mc, (size_t)na, (size_t)nb, LESS(), s.st);
+	RCHK(rocprim::merge(nullptr, bytes, a, b, m, ac, bc, mc, (size_t)na, (size_t)nb, LESS(), st));
+	RCHK(tmp.ensure(bytes, st));
+	return rocprim::merge(tmp.get(), bytes, a, b, m, ac, bc, mc, (size_t)na, (size_t)nb, LESS(), st);
 }
 
 template <typename KT>
-hipError_t reduce_t(const KT *m, const u32 *mc, u64 n, KT *out, u32 *oc, unsigned long long *d_nout, Scratch s)
+hipError_t reduce_t(const KT *m, const u32 *mc, u64 n, KT *out, u32 *oc, unsigned long long *d_nout, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
 	size_t bytes = 0;
-	RCHK(rocprim::reduce_by_key(nullptr, bytes, m, mc, (size_t)n, out, oc, d_nout, SatAdd(), rocprim::equal_to<KT>(), s.st));
-	RCHK(s.need(bytes));
-	return rocprim::reduce_by_key(*s.p, bytes, m, mc, (size_t)n, out, oc, d_nout, SatAdd(), rocprim::equal_to<KT>(), s.st);
+	RCHK(rocprim::reduce_by_key(nullptr, bytes, m, mc, (size_t)n, out, oc, d_nout, SatAdd(), rocprim::equal_to<KT>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	return rocprim::reduce_by_key(tmp.get(), bytes, m, mc, (size_t)n, out, oc, d_nout, SatAdd(), rocprim::equal_to<KT>(), st);
 }
 
 template <typename KT>
-hipError_t filter_t(const KT *in, const u32 *ic, u64 n, u32 ci, u32 cs, u32 cx, KT *out, u32 *oc, unsigned char *keep, unsigned long long *d_nout, Scratch s)
+hipError_t filter_t(const KT *in, const u32 *ic, u64 n, u32 ci, u32 cs, u32 cx, KT *out, u32 *oc, unsigned char *keep, unsigned long long *d_nout, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_keep, dim3(nblk(n)), dim3(256), 0, s.st, ic, n, ci, cx, keep);
+	hipLaunchKernelGGL(k_keep, dim3(nblk(n)), dim3(256), 0, st, ic, n, ci, cx, keep);
 	size_t b1 = 0, b2 = 0;
-	RCHK(rocprim::select(nullptr, b1, in, keep, out, d_nout, (size_t)n, s.st));
-	RCHK(rocprim::select(nullptr, b2, ic, keep, oc, d_nout, (size_t)n, s.st));
-	RCHK(s.need(b1 > b2 ? b1 : b2));
-	size_t bytes = *s.cap;
-	RCHK(rocprim::select(*s.p, bytes, in, keep, out, d_nout, (size_t)n, s.st));
-	bytes = *s.cap;
-	RCHK(rocprim::select(*s.p, bytes, ic, keep, oc, d_nout, (size_t)n, s.st));
-	hipLaunchKernelGGL(k_cap, dim3(nblk(n)), dim3(256), 0, s.st, oc, (const unsigned long long *)d_nout, cs);
+	RCHK(rocprim::select(nullptr, b1, in, keep, out, d_nout, (size_t)n, st));
+	RCHK(rocprim::select(nullptr, b2, ic, keep, oc, d_nout, (size_t)n, st));
+	RCHK(tmp.ensure(b1 > b2 ? b1 : b2, st));
+	size_t bytes = tmp.cap();
+	RCHK(rocprim::select(tmp.get(), bytes, in, keep, out, d_nout, (size_t)n, st));
+	bytes = tmp.cap();
+	RCHK(rocprim::select(tmp.get(), bytes, ic, keep, oc, d_nout, (size_t)n, st));
+	hipLaunchKernelGGL(k_cap, dim3(nblk(n)), dim3(256), 0, st, oc, (const unsigned long long *)d_nout, cs);
 	return hipGetLastError();
 }
 
@@ -100,60 +81,56 @@ namespace kmxk {
 
 // One piece of n window keys (W = 1: lo[n]; W = 2: hi[n], lo[n]; pa = lo, with hi at pa + cap) -> its distinct keys in the
 // packed layout at pa, their counts in pc, how many at *d_nu.  pb (2 cap words) is scratch.
-hipError_t count_piece(int W, int k, u64 *pa, u64 *pb, u64 cap, u64 n, u32 *pc, unsigned long long *d_nu, void **tmp, size_t *tmp_cap, hipStream_t st)
+hipError_t count_piece(int W, int k, u64 *pa, u64 *pb, u64 cap, u64 n, u32 *pc, unsigned long long *d_nu, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
-	Scratch s{tmp, tmp_cap, st};
 	size_t bytes = 0;
 	if (W == 1) {
 		RCHK(rocprim::radix_sort_keys(nullptr, bytes, pa, pb, (size_t)n, 0, 2 * k, st));
-		RCHK(s.need(bytes));
-		RCHK(rocprim::radix_sort_keys(*tmp, bytes, pa, pb, (size_t)n, 0, 2 * k, st));
+		RCHK(tmp.ensure(bytes, st));
+		RCHK(rocprim::radix_sort_keys(tmp.get(), bytes, pa, pb, (size_t)n, 0, 2 * k, st));
 		bytes = 0;
 		RCHK(rocprim::run_length_encode(nullptr, bytes, pb, (size_t)n, pa, pc, d_nu, st));
-		RCHK(s.need(bytes));
-		return rocprim::run_length_encode(*tmp, bytes, pb, (size_t)n, pa, pc, d_nu, st);
+		RCHK(tmp.ensure(bytes, st));
+		return rocprim::run_length_encode(tmp.get(), bytes, pb, (size_t)n, pa, pc, d_nu, st);
 	}
 	u64 *lo = pa, *hi = pa + cap, *lo2 = pb, *hi2 = pb + cap;
 	size_t b1 = 0, b2 = 0;
 	RCHK(rocprim::radix_sort_pairs(nullptr, b1, lo, lo2, hi, hi2, (size_t)n, 0, 64, st));
 	RCHK(rocprim::radix_sort_pairs(nullptr, b2, hi2, hi, lo2, lo, (size_t)n, 0, 2 * k - 64, st));
-	RCHK(s.need(b1 > b2 ? b1 : b2));
-	bytes = *tmp_cap;
-	RCHK(rocprim::radix_sort_pairs(*tmp, bytes, lo, lo2, hi, hi2, (size_t)n, 0, 64, st));          // by the low word
-	bytes = *tmp_cap;
-	RCHK(rocprim::radix_sort_pairs(*tmp, bytes, hi2, hi, lo2, lo, (size_t)n, 0, 2 * k - 64, st));  // stably by the high word
+	RCHK(tmp.ensure(b1 > b2 ? b1 : b2, st));
+	bytes = tmp.cap();
+	RCHK(rocprim::radix_sort_pairs(tmp.get(), bytes, lo, lo2, hi, hi2, (size_t)n, 0, 64, st));          // by the low word
+	bytes = tmp.cap();
+	RCHK(rocprim::radix_sort_pairs(tmp.get(), bytes, hi2, hi, lo2, lo, (size_t)n, 0, 2 * k - 64, st));  // stably by the high word
 	K2 *z = (K2 *)pb;
 	hipLaunchKernelGGL(k_zip2, dim3(nblk(n)), dim3(256), 0, st, (const u64 *)hi, (const u64 *)lo, n, z);
 	bytes = 0;
 	RCHK(rocprim::run_length_encode(nullptr, bytes, (const K2 *)z, (size_t)n, (K2 *)pa, pc, d_nu, st));
-	RCHK(s.need(bytes));
-	return rocprim::run_length_encode(*tmp, bytes, (const K2 *)z, (size_t)n, (K2 *)pa, pc, d_nu, st);
+	RCHK(tmp.ensure(bytes, st));
+	return rocprim::run_length_encode(tmp.get(), bytes, (const K2 *)z, (size_t)n, (K2 *)pa, pc, d_nu, st);
 }
 
 // the running listing a[na] + a piece's b[nb] (both sorted, unique) -> m[na + nb], merged; keys in the packed layout
-hipError_t count_merge(int W, const u64 *a, const u32 *ac, u64 na, const u64 *b, const u32 *bc, u64 nb, u64 *m, u32 *mc, void **tmp, size_t *tmp_cap, hipStream_t st)
+hipError_t count_merge(int W, const u64 *a, const u32 *ac, u64 na, const u64 *b, const u32 *bc, u64 nb, u64 *m, u32 *mc, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
-	Scratch s{tmp, tmp_cap, st};
-	if (W == 1) return merge_t<u64, rocprim::less<u64>>(a, ac, na, b, bc, nb, m, mc, s);
-	return merge_t<K2, K2Less>((const K2 *)a, ac, na, (const K2 *)b, bc, nb, (K2 *)m, mc, s);
+	if (W == 1) return merge_t<u64, rocprim::less<u64>>(a, ac, na, b, bc, nb, m, mc, tmp, st);
+	return merge_t<K2, K2Less>((const K2 *)a, ac, na, (const K2 *)b, bc, nb, (K2 *)m, mc, tmp, st);
 }
 
 // merged m[n] -> out: equal (adjacent) keys once, their counts summed with saturation; how many at *d_nout
-hipError_t count_reduce(int W, const u64 *m, const u32 *mc, u64 n, u64 *out, u32 *oc, unsigned long long *d_nout, void **tmp, size_t *tmp_cap, hipStream_t st)
+hipError_t count_reduce(int W, const u64 *m, const u32 *mc, u64 n, u64 *out, u32 *oc, unsigned long long *d_nout, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
-	Scratch s{tmp, tmp_cap, st};
-	if (W == 1) return reduce_t<u64>(m, mc, n, out, oc, d_nout, s);
-	return reduce_t<K2>((const K2 *)m, mc, n, (K2 *)out, oc, d_nout, s);
+	if (W == 1) return reduce_t<u64>(m, mc, n, out, oc, d_nout, tmp, st);
+	return reduce_t<K2>((const K2 *)m, mc, n, (K2 *)out, oc, d_nout, tmp, st);
 }
 
 // the listing's keys with ci <= count <= cx -> out (counts capped to cs), how many at *d_nout; keep[n] is scratch
-hipError_t count_filter(int W, const u64 *in, const u32 *ic, u64 n, u32 ci, u32 cs, u32 cx, u64 *out, u32 *oc, unsigned char *keep, unsigned long long *d_nout, void **tmp, size_t *tmp_cap, hipStream_t st)
+hipError_t count_filter(int W, const u64 *in, const u32 *ic, u64 n, u32 ci, u32 cs, u32 cx, u64 *out, u32 *oc, unsigned char *keep, unsigned long long *d_nout, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
-	Scratch s{tmp, tmp_cap, st};
 	RCHK(hipMemsetAsync(d_nout, 0, sizeof(unsigned long long), st));
 	if (!n) return hipSuccess;
-	if (W == 1) return filter_t<u64>(in, ic, n, ci, cs, cx, out, oc, keep, d_nout, s);
-	return filter_t<K2>((const K2 *)in, ic, n, ci, cs, cx, (K2 *)out, oc, keep, d_nout, s);
+	if (W == 1) return filter_t<u64>(in, ic, n, ci, cs, cx, out, oc, keep, d_nout, tmp, st);
+	return filter_t<K2>((const K2 *)in, ic, n, ci, cs, cx, (K2 *)out, oc, keep, d_nout, tmp, st);
 }
 
 }   // namespace kmxk

@@ -38,18 +38,13 @@ static int count_abort(kmx_model *m, int rc)
 static int count_grow(kmx_model *m, int b, u64 need)
 {
 	auto &C = m->cnt;
-	if (C.d_run[b] && C.run_cap[b] >= need) return KMX_OK;
+	if (C.d_run[b] && C.d_runc[b].cap() >= need) return KMX_OK;
 	HIPCHK(hipStreamSynchronize(m->stream));
-	hipFree(C.d_run[b]); hipFree(C.d_runc[b]);
-	C.d_run[b] = nullptr; C.d_runc[b] = nullptr; C.run_cap[b] = 0;
+	C.d_run[b].reset(); C.d_runc[b].reset();
 	for (u64 want : {need + need / 2, need}) {
 		want = std::max<u64>(want, 1);
-		if (hipMalloc((void **)&C.d_run[b], want * C.W * 8) == hipSuccess && hipMalloc((void **)&C.d_runc[b], want * 4) == hipSuccess) {
-			C.run_cap[b] = want;
-			return KMX_OK;
-		}
-		hipFree(C.d_run[b]); hipFree(C.d_runc[b]);
-		C.d_run[b] = nullptr; C.d_runc[b] = nullptr;
+		if (C.d_run[b].alloc(want * C.W) == hipSuccess && C.d_runc[b].alloc(want) == hipSuccess) return KMX_OK;
+		C.d_run[b].reset(); C.d_runc[b].reset();
 		hipGetLastError();
 	}
 	return fail(KMX_E_NOMEM, "counting: out of device memory for %llu listing entries, after %llu distinct k-mers", (unsigned long long)need, (unsigned long long)C.D);
@@ -76,7 +71,7 @@ static int count_flush(kmx_model *m)
 	np = std::min<u64>(np, C.piece);
 	if (!np) return KMX_OK;
 	C.windows += np;
-	hipError_t e = kmxk::count_piece(C.W, C.k, C.d_pa, C.d_pb, C.piece, np, C.d_pc, C.d_n + 1, &C.d_tmp, &C.tmp_cap, m->stream);
+	hipError_t e = kmxk::count_piece(C.W, C.k, C.d_pa, C.d_pb, C.piece, np, C.d_pc, C.d_n + 1, C.d_tmp, m->stream);
 	if (e != hipSuccess) return count_dev_fail(e, "the sort of a piece", C.D);
 	TRY(count_read(m, 1, &nu));
 	if (!C.D) {                                                    // the first piece is the listing
@@ -88,10 +83,10 @@ static int count_flush(kmx_model *m)
 	}
 	const u64 nm = C.D + nu;
 	TRY(count_grow(m, 1, nm));
-	e = kmxk::count_merge(C.W, C.d_run[0], C.d_runc[0], C.D, C.d_pa, C.d_pc, nu, C.d_run[1], C.d_runc[1], &C.d_tmp, &C.tmp_cap, m->stream);
+	e = kmxk::count_merge(C.W, C.d_run[0], C.d_runc[0], C.D, C.d_pa, C.d_pc, nu, C.d_run[1], C.d_runc[1], C.d_tmp, m->stream);
 	if (e != hipSuccess) return count_dev_fail(e, "the merge", C.D);
 	TRY(count_grow(m, 0, nm));                                     // (the merge has read d_run[0]: count_grow waits for it)
-	e = kmxk::count_reduce(C.W, C.d_run[1], C.d_runc[1], nm, C.d_run[0], C.d_runc[0], C.d_n + 2, &C.d_tmp, &C.tmp_cap, m->stream);
+	e = kmxk::count_reduce(C.W, C.d_run[1], C.d_runc[1], nm, C.d_run[0], C.d_runc[0], C.d_n + 2, C.d_tmp, m->stream);
 	if (e != hipSuccess) return count_dev_fail(e, "the merge", C.D);
 	return count_read(m, 2, &C.D);
 }
@@ -123,10 +118,10 @@ static int kmx_count_begin_impl(kmx_model *m, int k)
 	C.W = (k + 31) / 32;
 	const u64 hook = count_piece_hook();
 	C.piece = hook ? hook : kCountPiece;
-	hipError_t e = hipMalloc((void **)&C.d_pa, C.piece * C.W * 8);
-	if (e == hipSuccess) e = hipMalloc((void **)&C.d_pb, C.piece * C.W * 8);
-	if (e == hipSuccess) e = hipMalloc((void **)&C.d_pc, C.piece * 4);
-	if (e == hipSuccess) e = hipMalloc((void **)&C.d_n, 4 * sizeof(unsigned long long));
+	hipError_t e = C.d_pa.alloc(C.piece * C.W);
+	if (e == hipSuccess) e = C.d_pb.alloc(C.piece * C.W);
+	if (e == hipSuccess) e = C.d_pc.alloc(C.piece);
+	if (e == hipSuccess) e = C.d_n.alloc(4);
 	if (e == hipSuccess) e = hipMemsetAsync(C.d_n, 0, 4 * sizeof(unsigned long long), m->stream);
 	if (e != hipSuccess) return count_abort(m, count_dev_fail(e, "kmx_count_begin", 0));
 	C.on = true;
@@ -178,13 +173,12 @@ static int kmx_count_finish_impl(kmx_model *m, uint64_t *n_listed)
 	int rc = count_flush(m);
 	if (rc) return count_abort(m, rc);
 	HIPCHK(hipStreamSynchronize(m->stream));
-	hipFree(C.d_pa); hipFree(C.d_pb); hipFree(C.d_pc);
-	C.d_pa = C.d_pb = nullptr; C.d_pc = nullptr;
+	C.d_pa.reset(); C.d_pb.reset(); C.d_pc.reset();
 	// ci <= c <= 10^9, capped at cs: d_run[0] -> d_run[1]
 	if ((rc = count_grow(m, 1, C.D))) return count_abort(m, rc);
-	DevMem keep;
+	DevBuf<unsigned char> keep;
 	hipError_t e = keep.alloc(C.D);
-	if (e == hipSuccess) e = kmxk::count_filter(C.W, C.d_run[0], C.d_runc[0], C.D, (u32)m->ci, (u32)m->cs, kCountMax, C.d_run[1], C.d_runc[1], keep.as<unsigned char>(), C.d_n + 2, &C.d_tmp, &C.tmp_cap, m->stream);
+	if (e == hipSuccess) e = kmxk::count_filter(C.W, C.d_run[0], C.d_runc[0], C.D, (u32)m->ci, (u32)m->cs, kCountMax, C.d_run[1], C.d_runc[1], keep, C.d_n + 2, C.d_tmp, m->stream);
 	if (e != hipSuccess) return count_abort(m, count_dev_fail(e, "the filter", C.D));
 	u64 n = 0;
 	if ((rc = count_read(m, 2, &n))) return count_abort(m, rc);

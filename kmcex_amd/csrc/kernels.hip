@@ -26,7 +26,7 @@
 //   Fused launches: in rounds 0 and 1 one group of lists commits beside the check of the next (k_round_commit_check:
 //   memory-side atomics and gathers side by side); the finisher launches of those rounds (one workgroup per list) carry
 //   the km_back emission of the previous block as extra workgroups.
-#include "kmx_types.h"
+#include "launchers.h"
 #include <cstdlib>
 
 __constant__ u32 c_seeds[128] = {   // tools.hpp:9 -- 128 consecutive primes (data)

@@ -4,8 +4,9 @@
 // There is no CPU compute path in this file: every insert/query runs in the gfx950 kernels of
 // kernels.hip; the host only sizes, streams, sorts the (small) rest table and does file I/O.
 #include "../../include/kmx.h"
+#include "hip_owned.h"
 #include "kmc_reader.h"
-#include "kmx_types.h"
+#include "launchers.h"
 #include "reads_reader.h"
 #include "strpack.h"
 
@@ -33,47 +34,6 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-namespace kmxk {
-void histogram(const u32 *, u64, int, int, int, u64 *, u64 *, hipStream_t);
-int classify_tiles(u64 n);
-void classify_count(const ModelDev &, const u64 *, const u32 *, u64, u64, int *, int *, int *, u64 *, const BitScatter &, int, hipStream_t, KernelProf *);
-void classify_scatter(const ModelDev &, const u64 *, const u32 *, u64, const int *, u64 *, u32 *, u64, hipStream_t);
-void block_init(const BlockDev &, int, int, int, hipStream_t);
-void round(const ModelDev &, const BlockDev &, int, int, int, u64 *, int, hipStream_t, KernelProf *, const KmbackJob *, const BitScatter *, const RoundProbe *probe = nullptr);
-void commit_flush(const ModelDev &, const BlockDev &, int, int, hipStream_t, KernelProf *);
-void rest_append(const ModelDev &, const BlockDev &, int, int, int, u64 *, int *, unsigned long long *, u64 *, int *, u64 *, hipStream_t, int istride = 1);
-void kmback_emit(const ModelDev &, const BlockDev &, const u64 *, const unsigned char *, int, int, int, int, int, const BitScatter &, hipStream_t, int istride = 1);
-void bs_apply(const BitScatter &, hipStream_t);
-void ring_import(const ModelDev &, const BlockDev &, int, const RingLists &, u64 *, u32 *, hipStream_t);
-void ring_export(const ModelDev &, const BlockDev &, int, const RingLists &, u64 *, hipStream_t);
-void or_words(u32 *, const u32 *, u64, hipStream_t);
-void range_emit(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
-void range_seal(const RangeDev &, const RangePlan &, hipStream_t);
-void range_verdict(const ModelDev &, const BlockDev &, int *, int, const RangeIn &, unsigned char *, int, bool, hipStream_t);
-void range_apply(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
-void range_resolve(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
-void range_commit_apply(const ModelDev &, const RangeIn &, int, hipStream_t);
-void query(const ModelDev &, const u64 *, u64, int *, hipStream_t, KernelProf *, u64 *acct = nullptr);
-void query_ascii(const ModelDev &, int, const unsigned char *, int, u64, int *, hipStream_t);
-void query_seq(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
-void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
-void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
-void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);
-void debug_min_kmer(int, const u64 *, u64, u64 *, hipStream_t);
-void debug_mod(const u64 *, u64, u64, u64 *, hipStream_t);
-void micro(int, u64 *, u64, u64, u64, u64 *, hipStream_t);
-hipError_t rest_sort(const u64 *, const int *, u64, int, int, u64 *, int *, hipStream_t);
-hipError_t rest_index(const u64 *, u64, int, int, int, int *, int *, u64 *, int *, hipStream_t);
-void rest_expand(const int *, const int *, const u64 *, int, int, int, int, u64 *, hipStream_t);
-void rest_accel(const u64 *, u64, int, int, int, const int *, const int *, const u64 *, int, u32 *, u64 *, hipStream_t);
-void rest_suffix_bytes(const u64 *, u64, int, int, unsigned char *, hipStream_t);
-void count_windows(int, const unsigned char *, u64, const u64 *, u64, u64, u64, u64 *, u64 *, u64, unsigned long long *, hipStream_t);
-hipError_t count_piece(int, int, u64 *, u64 *, u64, u64, u32 *, unsigned long long *, void **, size_t *, hipStream_t);
-hipError_t count_merge(int, const u64 *, const u32 *, u64, const u64 *, const u32 *, u64, u64 *, u32 *, void **, size_t *, hipStream_t);
-hipError_t count_reduce(int, const u64 *, const u32 *, u64, u64 *, u32 *, unsigned long long *, void **, size_t *, hipStream_t);
-hipError_t count_filter(int, const u64 *, const u32 *, u64, u32, u32, u32, u64 *, u32 *, unsigned char *, unsigned long long *, void **, size_t *, hipStream_t);
-}   // namespace kmxk
-
 // ------------------------------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
 
@@ -100,24 +60,6 @@ static int fail(int code, const char *fmt, ...)
 	} while (0)
 
 extern "C" const char *kmx_last_error(void) { return g_err; }
-
-// temporaries of one call: freed on every way out
-struct DevMem {
-	void *p = nullptr;
-	DevMem() = default;
-	DevMem(const DevMem &) = delete;
-	DevMem &operator=(const DevMem &) = delete;
-	~DevMem() { if (p) hipFree(p); }
-	hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16); }
-	template <typename T> T *as() const { return (T *)p; }
-	void *release() { void *q = p; p = nullptr; return q; }
-};
-template <typename F> struct ScopeExit {
-	F f;
-	explicit ScopeExit(F g) : f(g) {}
-	~ScopeExit() { f(); }
-};
-template <typename F> static ScopeExit<F> scope_exit(F f) { return ScopeExit<F>(f); }
 
 static int kmx_device_count_impl(void)
 {
@@ -180,12 +122,13 @@ struct RestTable {
 	std::vector<unsigned char> suffix_bin;
 	bool host_valid = false;       // the four on-disk arrays above are materialised (load, or lazily at save)
 	// device
-	int *d_h2i = nullptr, *d_pre = nullptr, *d_cnt = nullptr;     // d_cnt: counts in sorted order
-	u64 *d_suf = nullptr;
-	u64 *d_sorted = nullptr;       // sorted k-mers [entries][W] (kept for save after a device build)
+	DevBuf<int> d_h2i, d_pre, d_cnt;   // d_cnt: counts in sorted order
+	DevBuf<u64> d_suf;
+	DevBuf<u64> d_sorted;          // sorted k-mers [entries][W] (kept for save after a device build)
 	int fbits = 0;                 // lookup accelerators (see ModelDev)
-	u32 *d_fine = nullptr;
-	u64 *d_q = nullptr;
+	DevBuf<u32> d_fine;
+	DevBuf<u64> d_q;
+	void reset_dev() { d_h2i.reset(); d_pre.reset(); d_cnt.reset(); d_suf.reset(); d_sorted.reset(); d_fine.reset(); d_q.reset(); }
 };
 static int rest_prefix_len(int k) { for (int i = 7; i >= 3; i--) if ((k - i) % 4 == 0) return i; return 3; }   // rest.hpp:78-83
 // k of a model or of a counting session.  rest.hpp:78-83 gives k = 3 a prefix of 7 bases (-4 % 4 == 0 in C): a suffix of
@@ -201,88 +144,93 @@ struct RestEnt { u64 w[2]; int c; };
 // ------------------------------------------------------------------------------------------ the model
 enum { ST_EMPTY = 0, ST_BUILDING = 1, ST_READY = 2 };
 
+// Ownership: every device / pinned buffer, stream and event below is a member that releases itself (hip_owned.h), so
+// kmx_destroy is `delete` once the caller's stream has drained.  Members go in reverse order of declaration, and a Stream
+// drains before it is destroyed: inside KmcFeed, QueryFeed and the probe the streams are declared AFTER the events and the
+// buffers their copies touch, so a stream has drained before those go.  `stream` is the caller's (kmx_set_stream), never
+// destroyed here; kmx_destroy synchronises it first.  Pointers into a slab (d_bf, d_bf_back, d_surv) and the device alias
+// d_feedback own nothing; the by-value kernel argument blocks (md, bd, blm, kmb, range.rd, probe) are views filled from the owners.
 struct kmx_model {
 	int ci = 1, cs = 1023, nh = 7, nb = 5, k = 0, bf_num = 1, W = 1;
 	int device = 0, state = ST_EMPTY;
 	hipStream_t stream = nullptr;
 	std::vector<u32> h_bin_of_occ, h_mean_of_bin;
-	u32 *d_bin_of_occ = nullptr, *d_mean_of_bin = nullptr;
+	DevBuf<u32> d_bin_of_occ, d_mean_of_bin;
 	u64 n_total = 0, n_km = 0, n_bf[3] = {0, 0, 0};
 	u64 byte_bf[3] = {0, 0, 0}, byte_bf_back[3] = {0, 0, 0}, km_byte_size = 0, byte_km_back = 0, ncells = 0;
-	u32 *d_bloom = nullptr;                                    // ONE slab for bf[i] / bf_back[i], back to back (d_bf / d_bf_back point into it)
-	u64 cap_bloom = 0, bloom_words = 0, bf_woff[3] = {0, 0, 0}, bf_back_woff[3] = {0, 0, 0};
-	u32 *d_bf[3] = {nullptr, nullptr, nullptr}, *d_bf_back[3] = {nullptr, nullptr, nullptr}, *d_km_back = nullptr;
-	cell_t *d_cells[KMX_MAX_NB] = {nullptr};
-	u64 cap_km_back = 0, cap_cells[KMX_MAX_NB] = {0};          // bytes allocated
+	DevBuf<u32> d_bloom;                                       // ONE slab for bf[i] / bf_back[i], back to back (d_bf / d_bf_back point into it)
+	u64 bloom_words = 0, bf_woff[3] = {0, 0, 0}, bf_back_woff[3] = {0, 0, 0};
+	u32 *d_bf[3] = {nullptr, nullptr, nullptr}, *d_bf_back[3] = {nullptr, nullptr, nullptr};
+	DevBuf<u32> d_km_back;
+	DevBuf<cell_t> d_cells[KMX_MAX_NB];
 	RestTable rest;
 	ModelDev md;
 	// ---- build-time state
-	u64 *d_stg_kmers = nullptr;
-	u32 *d_stg_counts = nullptr;
-	u64 stg_n = 0, stg_cap = 0;
+	DevBuf<u64> d_stg_kmers;
+	DevBuf<u32> d_stg_counts;                                  // (its capacity is the staging stream's: one front-end chunk + one block)
+	u64 stg_n = 0;
 	BlockDev bd;
-	void *d_block_scratch = nullptr;
-	u64 scratch_bytes = 0;
+	DevBuf<unsigned char> d_block_scratch;
 	int scratch_nb = 0, scratch_W = 0;
-	u64 *d_rest_kmers = nullptr;
-	int *d_rest_counts = nullptr;
-	unsigned long long *d_rest_n = nullptr;
-	u64 rest_cap = 0, rest_upper = 0;
-	u64 *d_stale_kmers = nullptr;
-	int *d_stale_counts = nullptr;
-	u64 *d_stats = nullptr, *d_nbf = nullptr;
-	int *d_tile_cnt = nullptr, *d_tile_off = nullptr, *d_total = nullptr;
-	u64 tile_cap = 0;                                          // tiles the two arrays above can hold
-	int *d_totals = nullptr, *h_totals = nullptr;              // per-chunk totals of one insert_batch call (h_: pinned)
-	u64 totals_cap = 0;
-	int *h_total = nullptr;                                    // pinned
-	u64 *h_feedback = nullptr;                                 // pinned: ST_MAX_U0 as of some earlier block (heuristic input)
+	DevBuf<u64> d_rest_kmers;
+	DevBuf<int> d_rest_counts;                                 // (its capacity is the rest accumulators')
+	DevBuf<unsigned long long> d_rest_n;
+	u64 rest_upper = 0;
+	DevBuf<u64> d_stale_kmers;
+	DevBuf<int> d_stale_counts;
+	DevBuf<u64> d_stats, d_nbf;
+	DevBuf<int> d_tile_cnt, d_tile_off, d_total;
+	DevBuf<int> d_totals;                                      // per-chunk totals of one insert_batch call
+	PinBuf<int> h_totals, h_total;
+	PinBuf<u64> h_feedback{hipHostMallocMapped};               // ST_MAX_U0 as of some earlier block (heuristic input)
 	u64 *d_feedback = nullptr;                                 // the same words as the device sees them (k_rest_append writes them)
 	u64 epoch = 1, blocks = 0, rounds = 0;
 	// Bloom-class k-mers of the front end as a partitioned bit-set over the slab (k_classify_count emits, k_bs_apply sweeps)
 	BitScatter blm;
-	u32 *d_blm_tup = nullptr;
-	u64 blm_tup_cap = 0;
-	int *d_blm_cnt = nullptr;
+	DevBuf<u32> d_blm_tup;
+	DevBuf<int> d_blm_cnt;
 	bool blm_deferred = false;
 	int blm_sweep_every = 1;                                   // chunks of the front end per sweep of the slab
 	// km_back insert as a partitioned bit-set (k_kmback_emit per round, k_bs_apply every few blocks)
 	BitScatter kmb;
-	u32 *d_kmb_tup = nullptr;
-	int *d_kmb_cnt = nullptr;
-	u64 kmb_tup_cap = 0;                                       // tuples allocated
+	DevBuf<u32> d_kmb_tup;
+	DevBuf<int> d_kmb_cnt;
 	u64 kmb_pending = 0, kmb_budget = 0;                       // upper bound of tuples emitted since the last apply / what the bins take
 	bool kmb_deferred = false;
 	bool dbg_kmb_direct = false;                               // KMX_KMB_DIRECT=1: the atomic path at every size (test hook)
 	unsigned char *d_surv[2] = {nullptr, nullptr};             // survivor flags of the current and of the previous block (inside the scratch slab)
 	KmbackJob kmb_job = {nullptr, nullptr, 0, 0, 0};            // km_back emission the last block still owes (hosted by the next block's finisher launches)
 	bool dbg_kmb_host = true;                                  // KMX_KMB_HOST=0: every block emits in a launch of its own (test hook)
-	u32 *d_bs2_tup = nullptr;                                  // second level of the two bit-sets (big filters), shared: [bins * tiles][cap2]
-	int *d_bs2_cnt = nullptr;
-	u64 bs2_tup_cap = 0, bs2_cnt_cap = 0;
+	DevBuf<u32> d_bs2_tup;                                     // second level of the two bit-sets (big filters), shared: [bins * tiles][cap2]
+	DevBuf<int> d_bs2_cnt;
 	// feed of KModel::init(db): pinned slots, device buffers, copy stream -- kept across calls on the handle (allocating and
 	// freeing ~300 MB of pinned + device memory costs ~30 ms per call on this stack)
 	struct KmcFeed {
-		unsigned char *raw[2] = {nullptr, nullptr}, *draw[2] = {nullptr, nullptr};
-		u64 *km[2] = {nullptr, nullptr}, *dk[2] = {nullptr, nullptr}, *d_lut = nullptr, *h_lut = nullptr;   // h_lut: pinned
-		u32 *cnt[2] = {nullptr, nullptr}, *dc[2] = {nullptr, nullptr};
-		size_t raw_cap = 0, km_cap = 0, dk_cap = 0, lut_cap = 0;   // bytes / bytes / k-mer words / entries
-		hipStream_t copy = nullptr;
-		hipEvent_t ev_copied[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr};
+		PinBuf<unsigned char> raw[2];                              // B raw records ...
+		DevBuf<unsigned char> draw[2];                             // ... and their device twins
+		PinBuf<u64> km[2];                                         // host-decoded (or the caller's) k-mers / counts
+		PinBuf<u32> cnt[2];
+		DevBuf<u64> dk[2], d_lut;                                  // k-mers / counts of a batch on the device; the prefix LUT
+		DevBuf<u32> dc[2];
+		PinBuf<u64> h_lut;
+		Event ev_copied[2], ev_free[2];
+		Stream copy;
+		enum { RAW = 1, HOST = 2, DEV = 4, LUT = 8 };
+		hipError_t ensure(int parts, size_t B, size_t rb, int W, size_t n_lut);
 	} feed;
 	// feed of kmer_to_occ(vector<string>): three slots of pinned + device buffers (strings in, answers out), a copy stream
 	// each way -- kept on the handle like the KMC feed
 	struct QueryFeed {
 		static const int S = 3;
-		unsigned char *h_in[S] = {nullptr, nullptr, nullptr}, *d_in[S] = {nullptr, nullptr, nullptr};
-		int32_t *h_out[S] = {nullptr, nullptr, nullptr}, *d_out[S] = {nullptr, nullptr, nullptr};
-		size_t in_cap = 0, out_cap = 0;                            // bytes per slot / answers per slot
-		hipStream_t to_dev = nullptr, to_host = nullptr;
-		hipEvent_t ev_in[S] = {nullptr, nullptr, nullptr}, ev_k[S] = {nullptr, nullptr, nullptr}, ev_out[S] = {nullptr, nullptr, nullptr};
+		PinBuf<unsigned char> h_in[S];
+		DevBuf<unsigned char> d_in[S];
+		PinBuf<int32_t> h_out[S];
+		DevBuf<int32_t> d_out[S];
 		// kmx_query_seqs*: the positions of one piece's windows that are not uppercase ACGT + two counters (one per piece
-		// parity); seq_cap entries, at most one piece of windows, whatever the length of the input
-		u32 *d_seq_list = nullptr, *d_seq_cnt = nullptr;
-		u64 seq_cap = 0;
+		// parity); at most one piece of windows, whatever the length of the input
+		DevBuf<u32> d_seq_list, d_seq_cnt;
+		Event ev_in[S], ev_k[S], ev_out[S];
+		Stream to_dev, to_host;
 	} qfeed;
 	// position-range partition over several GPUs (kmx_range_*): this rank's exchange buffers, its resolver tables, and the
 	// owner-side view of the block working set (overflow flags + padded bin counters for the detect kernel on received claims)
@@ -290,28 +238,35 @@ struct kmx_model {
 		bool on = false;
 		bool pending = false;                                      // a round was resolved since the last seal: its winners' commits sit in front of the regions
 		bool mailbox = false;                                      // the regions live in the owners' inboxes (kmx_build_from_kmc_multi_ex), not in d_send
-		RangeDev rd = {};
+		RangeDev rd = {};                                          // (a view: range_begin_common fills it from the owners below)
+		DevBuf<int> d_ccnt, d_tcnt, d_n_contended;
+		DevBuf<u32> d_tidx, d_contended, d_rt_resv, d_rt_mark, d_rt_eidx, d_rt_um;
+		DevBuf<u64> d_rt_key;
 		RangePlan plan = {};
 		RangeIn in = {};                                           // mailbox transport: this rank's inbox as its owner-side kernels see it
 		BlockDev obd = {};
-		int *d_oovf = nullptr;
-		int *d_opcnt = nullptr;                                    // the owner's claim-bin counters, one per 128-byte line (k_range_verdict)
-		unsigned char *d_lver = nullptr;                           // one verdict byte per triple received in a round (detect answers there, k_range_ship sends it on)
+		DevBuf<int> d_oovf;
+		DevBuf<int> d_opcnt;                                       // the owner's claim-bin counters, one per 128-byte line (k_range_verdict)
+		DevBuf<unsigned char> d_lver;                              // one verdict byte per triple received in a round (detect answers there, k_range_ship sends it on)
 		// caller-moved transport (kmx_range_*_dev): the regions and their headers in this rank's memory
-		u64 *d_send = nullptr;
-		u32 *d_hdr = nullptr, *h_hdr = nullptr;                    // [KMX_MAX_RANKS][2]; h_: pinned copy
+		DevBuf<u64> d_send;
+		DevBuf<u32> d_hdr;                                         // [KMX_MAX_RANKS][2]
+		PinBuf<u32> h_hdr;                                         // its pinned copy
 		u64 sent_tot[KMX_MAX_RANKS] = {};                          // words per destination of the last emit (where each region's verdicts start in what comes back)
 		bool inband = false;                                       // the regions travel as fixed-size messages [header | capx words] (kmx_range_inband)
 		u64 capx = 0, cap_full = 0;                                // words per region shipped / the worst case of a round
-		int *d_ovf = nullptr;                                      // raised by a launch that had to drop a word (fixed-size messages only)
+		DevBuf<int> d_ovf;                                         // raised by a launch that had to drop a word (fixed-size messages only)
 		// mailbox transport: what the other ranks write into (through peer mappings when they sit on other devices)
-		u64 *d_inbox = nullptr;                                    // [world][cap] region of sender s
-		u32 *d_in_hdr = nullptr;                                   // [world][2]
-		unsigned char *d_vbox = nullptr;                           // [world][cap] verdict bytes of the words this rank sent to owner q
+		DevBuf<u64> d_inbox;                                       // [world][cap] region of sender s
+		DevBuf<u32> d_in_hdr;                                      // [world][2]
+		DevBuf<unsigned char> d_vbox;                              // [world][cap] verdict bytes of the words this rank sent to owner q
 		u64 alloc_key = 0;                                         // nb, nh, world, transport the buffers were sized for
 		int n0[KMX_MAX_NB] = {};                                   // entries of the held lists when the block came in (km_back is emitted once per block)
 	} range;
 	RoundProbe probe = {false, nullptr, nullptr, nullptr, nullptr};   // KMX_PREGATHER_PROBE=1 (test hook): kernels.hip k_probe_pregather
+	DevBuf<u32> probe_sink;                                    // ... and what it points at
+	Event probe_fork, probe_done;
+	Stream probe_side;
 	bool ring = false;                                         // built by several GPUs (kmx_shard_begin): this handle holds ONE rank's share
 	int ring_rank = 0, ring_world = 1;
 	int nsub = 1;                                              // grid-wide ordered passes in round 0 (see process_block)
@@ -329,10 +284,10 @@ struct kmx_model {
 	bool dbg_ctrl = false;
 	u64 h_stats[ST_N] = {0};
 	double t_insert_kernels = 0, t_total = 0;
-	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	Event ev0, ev1;
 	// per-kernel-class timing (kmx_set_profile)
 	KernelProf prof;
-	std::vector<hipEvent_t> prof_events;
+	std::vector<Event> prof_events;
 	std::vector<int> prof_spans;
 	size_t prof_used = 0;
 	double kc_seconds[KC_N] = {0};
@@ -347,16 +302,14 @@ struct kmx_model {
 		bool building = false;                                     // kmx_count_finish is building from the listing (kmx_begin keeps it)
 		int k = 0, W = 1;
 		u64 piece = 0, fill = 0;                                   // window slots per piece / windows launched into the current one
-		u64 *d_pa = nullptr, *d_pb = nullptr;                      // [W piece] each: the piece's keys, then its distinct keys; sort scratch
-		u32 *d_pc = nullptr;                                       // [piece] the distinct keys' counts
-		unsigned long long *d_n = nullptr;                         // [4] windows in the piece, distinct in the piece, listed, spare
-		u64 *d_run[2] = {nullptr, nullptr};                        // keys (W words each) of the running listing / of the merge
-		u32 *d_runc[2] = {nullptr, nullptr};
-		u64 run_cap[2] = {0, 0};                                   // entries the two buffers hold
+		DevBuf<u64> d_pa, d_pb;                                    // [W piece] each: the piece's keys, then its distinct keys; sort scratch
+		DevBuf<u32> d_pc;                                          // [piece] the distinct keys' counts
+		DevBuf<unsigned long long> d_n;                            // [4] windows in the piece, distinct in the piece, listed, spare
+		DevBuf<u64> d_run[2];                                      // keys (W words each) of the running listing / of the merge
+		DevBuf<u32> d_runc[2];                                     // ... their counts (the capacity of d_runc[b] is the entries the pair holds)
 		u64 D = 0;                                                 // entries of the running listing (in d_run[0])
 		u64 windows = 0;                                           // windows counted so far
-		void *d_tmp = nullptr;                                     // rocPRIM scratch
-		size_t tmp_cap = 0;
+		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
 		bool listed = false;                                       // d_run[1] holds the listing of the last finish
 		u64 n_list = 0;
 	} cnt;
@@ -364,16 +317,16 @@ struct kmx_model {
 
 static void prof_begin(KernelProf *p, int cls, hipStream_t st)
 {
-	auto *ev = (std::vector<hipEvent_t> *)p->events;
+	auto *ev = (std::vector<Event> *)p->events;
 	auto *sp = (std::vector<int> *)p->spans;
 	const size_t need = 2 * sp->size() + 2;
-	while (ev->size() < need) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; ev->push_back(e); }
+	while (ev->size() < need) { Event e; if (e.ensure(hipEventDefault) != hipSuccess) return; ev->push_back(std::move(e)); }
 	sp->push_back(cls);
 	hipEventRecord((*ev)[2 * sp->size() - 2], st);
 }
 static void prof_end(KernelProf *p, hipStream_t st)
 {
-	auto *ev = (std::vector<hipEvent_t> *)p->events;
+	auto *ev = (std::vector<Event> *)p->events;
 	auto *sp = (std::vector<int> *)p->spans;
 	if (sp->empty() || ev->size() < 2 * sp->size()) return;
 	hipEventRecord((*ev)[2 * sp->size() - 1], st);
@@ -393,81 +346,37 @@ static void prof_collect(kmx_model *m)
 
 static const u64 kChunk = u64(1) << 23;                       // k-mers classified per pass of the front end
 
-static std::atomic<unsigned long long> g_malloc_ns{0};       // time inside hipMalloc (KMX_CTRL_DEBUG=1 prints it per build)
-static hipError_t timed_malloc(void **p, u64 bytes)
-{
-	const auto t0 = std::chrono::steady_clock::now();
-	const hipError_t e = hipMalloc(p, bytes);
-	g_malloc_ns += (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-	return e;
-}
+// the malloc-time counter and the KMX_FAIL_ALLOC countdown of hip_owned.h (three translation units allocate through it)
+std::atomic<unsigned long long> kmx_malloc_ns{0};
+std::atomic<long long> kmx_fail_alloc{0};
 
-template <typename T> static int dalloc(T **p, u64 n_elems, bool zero, hipStream_t st)
-{
-	*p = nullptr;
-	u64 bytes = n_elems * sizeof(T);
-	if (!bytes) bytes = 16;
-	HIPCHK(timed_malloc((void **)p, bytes));
-	if (zero) HIPCHK(hipMemsetAsync(*p, 0, bytes, st));
-	return KMX_OK;
-}
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
 
-// grow-only device buffer: reallocated only when `need` exceeds what is there (bench loops rebuild the same sizes)
-template <typename T> static int ensure(T **p, u64 *cap_bytes, u64 need_bytes, bool zero, hipStream_t st)
+// n elements, fresh (what the buffer held goes) / grown only when n exceeds what is there; `zero`: cleared on the stream
+template <typename T> static int dalloc(DevBuf<T> &b, u64 n, bool zero, hipStream_t st)
 {
-	if (!need_bytes) need_bytes = 16;
-	if (!*p || *cap_bytes < need_bytes) {
-		if (*p) { HIPCHK(hipStreamSynchronize(st)); hipFree(*p); *p = nullptr; }
-		HIPCHK(timed_malloc((void **)p, need_bytes));
-		*cap_bytes = need_bytes;
-	}
-	if (zero) HIPCHK(hipMemsetAsync(*p, 0, need_bytes, st));
+	HIPCHK(b.alloc(n));
+	if (zero) HIPCHK(hipMemsetAsync(b.get(), 0, n ? n * sizeof(T) : 16, st));
+	return KMX_OK;
+}
+template <typename T> static int ensure(DevBuf<T> &b, u64 n, bool zero, hipStream_t st)
+{
+	HIPCHK(b.ensure(n, st));
+	if (zero) HIPCHK(hipMemsetAsync(b.get(), 0, n ? n * sizeof(T) : 16, st));
 	return KMX_OK;
 }
 
+// everything kmx_begin sizes by (nb, W): dropped when the shape changes
 static void free_build_state(kmx_model *m)
 {
-	hipFree(m->d_stg_kmers); m->d_stg_kmers = nullptr;
-	hipFree(m->d_stg_counts); m->d_stg_counts = nullptr;
-	hipFree(m->d_block_scratch); m->d_block_scratch = nullptr;
-	hipFree(m->d_rest_kmers); m->d_rest_kmers = nullptr;
-	hipFree(m->d_rest_counts); m->d_rest_counts = nullptr;
-	hipFree(m->d_rest_n); m->d_rest_n = nullptr;
-	hipFree(m->d_stale_kmers); m->d_stale_kmers = nullptr;
-	hipFree(m->d_stale_counts); m->d_stale_counts = nullptr;
-	hipFree(m->d_tile_cnt); m->d_tile_cnt = nullptr;
-	hipFree(m->d_tile_off); m->d_tile_off = nullptr;
-	m->tile_cap = 0;
-	hipFree(m->d_total); m->d_total = nullptr;
-	hipFree(m->d_blm_tup); m->d_blm_tup = nullptr;
-	hipFree(m->d_blm_cnt); m->d_blm_cnt = nullptr;
-	m->blm_tup_cap = 0;
-	hipFree(m->d_kmb_tup); m->d_kmb_tup = nullptr;
-	hipFree(m->d_kmb_cnt); m->d_kmb_cnt = nullptr;
-	m->kmb_tup_cap = 0;
-	hipFree(m->d_bs2_tup); m->d_bs2_tup = nullptr;
-	hipFree(m->d_bs2_cnt); m->d_bs2_cnt = nullptr;
-	m->bs2_tup_cap = m->bs2_cnt_cap = 0;
-	m->stg_n = m->stg_cap = 0;
-}
-
-static void free_rest_dev(RestTable &r)
-{
-	hipFree(r.d_h2i); hipFree(r.d_pre); hipFree(r.d_cnt); hipFree(r.d_suf); hipFree(r.d_sorted); hipFree(r.d_fine); hipFree(r.d_q);
-	r.d_h2i = r.d_pre = r.d_cnt = nullptr;
-	r.d_suf = r.d_sorted = r.d_q = nullptr;
-	r.d_fine = nullptr;
-}
-
-static void free_arrays(kmx_model *m)
-{
-	hipFree(m->d_bloom); m->d_bloom = nullptr; m->cap_bloom = 0;
-	for (int i = 0; i < 3; i++) m->d_bf[i] = m->d_bf_back[i] = nullptr;
-	hipFree(m->d_km_back); m->d_km_back = nullptr;
-	for (int a = 0; a < KMX_MAX_NB; a++) { hipFree(m->d_cells[a]); m->d_cells[a] = nullptr; m->cap_cells[a] = 0; }
-	m->cap_km_back = 0;
-	free_rest_dev(m->rest);
+	m->d_stg_kmers.reset(); m->d_stg_counts.reset(); m->d_block_scratch.reset();
+	m->d_rest_kmers.reset(); m->d_rest_counts.reset(); m->d_rest_n.reset();
+	m->d_stale_kmers.reset(); m->d_stale_counts.reset();
+	m->d_tile_cnt.reset(); m->d_tile_off.reset(); m->d_total.reset();
+	m->d_blm_tup.reset(); m->d_blm_cnt.reset();
+	m->d_kmb_tup.reset(); m->d_kmb_cnt.reset();
+	m->d_bs2_tup.reset(); m->d_bs2_cnt.reset();
+	m->stg_n = 0;
 }
 
 static int create_device_side(kmx_model *m);
@@ -494,15 +403,15 @@ static int kmx_create_impl(int ci, int cs, int nh, int nb, kmx_model **out)
 static int create_device_side(kmx_model *m)
 {
 	HIPCHK(hipGetDevice(&m->device));
-	HIPCHK(hipMalloc((void **)&m->d_bin_of_occ, m->h_bin_of_occ.size() * 4));
-	HIPCHK(hipMalloc((void **)&m->d_mean_of_bin, m->h_mean_of_bin.size() * 4));
+	HIPCHK(m->d_bin_of_occ.alloc(m->h_bin_of_occ.size()));
+	HIPCHK(m->d_mean_of_bin.alloc(m->h_mean_of_bin.size()));
 	HIPCHK(hipMemcpy(m->d_bin_of_occ, m->h_bin_of_occ.data(), m->h_bin_of_occ.size() * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(m->d_mean_of_bin, m->h_mean_of_bin.data(), m->h_mean_of_bin.size() * 4, hipMemcpyHostToDevice));
-	HIPCHK(hipMalloc((void **)&m->d_stats, ST_N * 8));
-	HIPCHK(hipMalloc((void **)&m->d_nbf, 3 * 8));
+	HIPCHK(m->d_stats.alloc(ST_N));
+	HIPCHK(m->d_nbf.alloc(3));
 	HIPCHK(hipMemset(m->d_stats, 0, ST_N * 8));
-	HIPCHK(hipHostMalloc((void **)&m->h_total, 64));
-	HIPCHK(hipHostMalloc((void **)&m->h_feedback, 64, hipHostMallocMapped));
+	HIPCHK(m->h_total.alloc(16));
+	HIPCHK(m->h_feedback.alloc(8));
 	HIPCHK(hipHostGetDevicePointer((void **)&m->d_feedback, m->h_feedback, 0));
 	// [2]: the fullest claim bin of a late round (t >= 2), which picks the form of their k_round_detect: until the device reports
 	// one, a guess -- a quarter of a list still alive, every survivor a candidate on all its positions -- so that wide
@@ -519,58 +428,10 @@ static int create_device_side(kmx_model *m)
 		m->dbg_kmb_direct = env_int("KMX_KMB_DIRECT", 0) != 0;
 		m->dbg_kmb_host = env_int("KMX_KMB_HOST", 1) != 0;
 	}
-	HIPCHK(hipEventCreate(&m->ev0));
-	HIPCHK(hipEventCreate(&m->ev1));
+	HIPCHK(m->ev0.ensure(hipEventDefault));
+	HIPCHK(m->ev1.ensure(hipEventDefault));
 	m->prof.events = &m->prof_events; m->prof.spans = &m->prof_spans; m->prof.begin = prof_begin; m->prof.end = prof_end;
 	return KMX_OK;
-}
-
-static void free_feed(kmx_model *m)
-{
-	auto &f = m->feed;
-	if (f.copy) { hipStreamSynchronize(f.copy); hipStreamDestroy(f.copy); f.copy = nullptr; }
-	for (int s = 0; s < 2; s++) {
-		if (f.raw[s]) hipHostFree(f.raw[s]);
-		if (f.km[s]) hipHostFree(f.km[s]);
-		if (f.cnt[s]) hipHostFree(f.cnt[s]);
-		hipFree(f.draw[s]); hipFree(f.dk[s]); hipFree(f.dc[s]);
-		if (f.ev_copied[s]) hipEventDestroy(f.ev_copied[s]);
-		if (f.ev_free[s]) hipEventDestroy(f.ev_free[s]);
-		f.raw[s] = f.draw[s] = nullptr; f.km[s] = f.dk[s] = nullptr; f.cnt[s] = f.dc[s] = nullptr;
-		f.ev_copied[s] = f.ev_free[s] = nullptr;
-	}
-	hipFree(f.d_lut); f.d_lut = nullptr;
-	if (f.h_lut) hipHostFree(f.h_lut);
-	f.h_lut = nullptr;
-	f.raw_cap = f.km_cap = f.dk_cap = f.lut_cap = 0;
-}
-
-static void free_range(kmx_model *m)
-{
-	auto &R = m->range;
-	hipFree(R.d_send); hipFree(R.d_hdr); hipFree(R.rd.ccnt); hipFree(R.rd.tcnt); hipFree(R.rd.tidx); hipFree(R.rd.contended); hipFree(R.rd.n_contended);
-	hipFree(R.rd.rt_key); hipFree(R.rd.rt_resv); hipFree(R.rd.rt_mark); hipFree(R.rd.rt_eidx); hipFree(R.rd.rt_um);
-	hipFree(R.d_oovf); hipFree(R.d_opcnt); hipFree(R.d_lver); hipFree(R.d_inbox); hipFree(R.d_in_hdr); hipFree(R.d_vbox); hipFree(R.d_ovf);
-	if (R.h_hdr) hipHostFree(R.h_hdr);
-	R = kmx_model::RangeState();
-}
-
-static void free_query_feed(kmx_model *m)
-{
-	auto &f = m->qfeed;
-	if (f.to_dev) { hipStreamSynchronize(f.to_dev); hipStreamDestroy(f.to_dev); f.to_dev = nullptr; }
-	if (f.to_host) { hipStreamSynchronize(f.to_host); hipStreamDestroy(f.to_host); f.to_host = nullptr; }
-	for (int s = 0; s < f.S; s++) {
-		if (f.h_in[s]) hipHostFree(f.h_in[s]);
-		if (f.h_out[s]) hipHostFree(f.h_out[s]);
-		hipFree(f.d_in[s]); hipFree(f.d_out[s]);
-		f.h_in[s] = f.d_in[s] = nullptr; f.h_out[s] = f.d_out[s] = nullptr;
-		for (hipEvent_t *e : {&f.ev_in[s], &f.ev_k[s], &f.ev_out[s]}) { if (*e) hipEventDestroy(*e); *e = nullptr; }
-	}
-	f.in_cap = f.out_cap = 0;
-	hipFree(f.d_seq_list); hipFree(f.d_seq_cnt);
-	f.d_seq_list = f.d_seq_cnt = nullptr;
-	f.seq_cap = 0;
 }
 
 // the buffers of a counting session; with `listing`, the listing of the last kmx_count_finish as well
@@ -578,14 +439,11 @@ static void free_count(kmx_model *m, bool listing)
 {
 	auto &C = m->cnt;
 	if (C.d_pa || C.d_pc || C.d_n || C.d_tmp || C.d_run[0] || C.d_run[1]) hipStreamSynchronize(m->stream);
-	hipFree(C.d_pa); hipFree(C.d_pb); hipFree(C.d_pc); hipFree(C.d_n); hipFree(C.d_tmp); hipFree(C.d_run[0]); hipFree(C.d_runc[0]);
-	C.d_pa = C.d_pb = nullptr; C.d_pc = nullptr; C.d_n = nullptr; C.d_tmp = nullptr; C.tmp_cap = 0;
-	C.d_run[0] = nullptr; C.d_runc[0] = nullptr; C.run_cap[0] = 0;
+	C.d_pa.reset(); C.d_pb.reset(); C.d_pc.reset(); C.d_n.reset(); C.d_tmp.reset(); C.d_run[0].reset(); C.d_runc[0].reset();
 	C.on = false;
 	C.piece = C.fill = C.D = C.windows = 0;
 	if (listing || !C.listed) {
-		hipFree(C.d_run[1]); hipFree(C.d_runc[1]);
-		C.d_run[1] = nullptr; C.d_runc[1] = nullptr; C.run_cap[1] = 0;
+		C.d_run[1].reset(); C.d_runc[1].reset();
 		C.listed = false;
 		C.n_list = 0;
 	}
@@ -596,22 +454,7 @@ static int kmx_destroy_impl(kmx_model *m)
 	if (!m) return KMX_OK;
 	hipSetDevice(m->device);
 	hipStreamSynchronize(m->stream);
-	free_build_state(m);
-	free_arrays(m);
-	hipFree(m->d_bin_of_occ); hipFree(m->d_mean_of_bin); hipFree(m->d_stats); hipFree(m->d_nbf);
-	if (m->h_total) hipHostFree(m->h_total);
-	if (m->h_feedback) hipHostFree(m->h_feedback);
-	if (m->ev0) hipEventDestroy(m->ev0);
-	if (m->ev1) hipEventDestroy(m->ev1);
-	hipFree(m->d_totals);
-	if (m->h_totals) hipHostFree(m->h_totals);
-	free_feed(m);
-	free_query_feed(m);
-	free_range(m);
-	free_count(m, true);
-	if (m->probe.side) { hipStreamSynchronize(m->probe.side); hipStreamDestroy(m->probe.side); hipEventDestroy(m->probe.fork); hipEventDestroy(m->probe.done); hipFree(m->probe.sink); }
-	for (hipEvent_t e : m->prof_events) hipEventDestroy(e);
-	delete m;
+	delete m;                                                  // (the order its members go in: see the comment at the struct)
 	return KMX_OK;
 }
 
@@ -670,7 +513,7 @@ static void fill_model_dev(kmx_model *m)
 
 static int alloc_arrays(kmx_model *m)
 {
-	free_rest_dev(m->rest);
+	m->rest.reset_dev();
 	{   // the Bloom filters and their back filters live back to back in one slab (the BitScatter of the front end sweeps it)
 		u64 off = 0;
 		for (int i = 0; i < 3; i++) {
@@ -678,17 +521,16 @@ static int alloc_arrays(kmx_model *m)
 			m->bf_back_woff[i] = off; off += i < m->bf_num ? (m->byte_bf_back[i] + 3) / 4 + 1 : 0;
 		}
 		m->bloom_words = off;
-		TRY(ensure(&m->d_bloom, &m->cap_bloom, (off + 1) * 4, true, m->stream));
+		TRY(ensure(m->d_bloom, off + 1, true, m->stream));
 		for (int i = 0; i < 3; i++) {
 			m->d_bf[i] = i < m->bf_num ? m->d_bloom + m->bf_woff[i] : nullptr;
 			m->d_bf_back[i] = i < m->bf_num ? m->d_bloom + m->bf_back_woff[i] : nullptr;
 		}
 	}
-	TRY(ensure(&m->d_km_back, &m->cap_km_back, ((m->byte_km_back + 3) / 4 + 1) * 4, true, m->stream));
+	TRY(ensure(m->d_km_back, (m->byte_km_back + 3) / 4 + 1, true, m->stream));
 	// (hipMalloc of fresh device memory costs ~90 ms per GB on this stack, also from several threads at once:
 	// a cold build of 2.5e9 k-mers spends 2.3 s here, a rebuild on the same handle nothing)
-	const u64 need = (m->ncells + 1) * sizeof(cell_t);
-	for (int a = 0; a < m->nb; a++) TRY(ensure(&m->d_cells[a], &m->cap_cells[a], need, true, m->stream));
+	for (int a = 0; a < m->nb; a++) TRY(ensure(m->d_cells[a], m->ncells + 1, true, m->stream));
 	return KMX_OK;
 }
 
@@ -730,13 +572,11 @@ static int bs_geometry(kmx_model *m, BitScatter &bs, u64 nwords, u64 cap, bool *
 		// practice (and a full tile only costs atomics)
 		const u64 cap2 = bs_cap_hook() ? std::max<u64>(bs_cap_hook() / 4, 8) : (cap / tiles + cap / (4 * tiles) + 256);
 		const u64 need = (u64)BS_BINS * tiles * cap2, ncnt = (u64)BS_BINS * tiles;
-		if (m->bs2_tup_cap < need || m->bs2_cnt_cap < ncnt) {
+		if (m->d_bs2_tup.cap() < need || m->d_bs2_cnt.cap() < ncnt) {
 			HIPCHK(hipStreamSynchronize(m->stream));
-			hipFree(m->d_bs2_tup); hipFree(m->d_bs2_cnt);
-			m->d_bs2_tup = nullptr; m->d_bs2_cnt = nullptr; m->bs2_tup_cap = m->bs2_cnt_cap = 0;
-			TRY(dalloc(&m->d_bs2_tup, need, false, m->stream));
-			TRY(dalloc(&m->d_bs2_cnt, ncnt, true, m->stream));
-			m->bs2_tup_cap = need; m->bs2_cnt_cap = ncnt;
+			m->d_bs2_tup.reset(); m->d_bs2_cnt.reset();
+			TRY(dalloc(m->d_bs2_tup, need, false, m->stream));
+			TRY(dalloc(m->d_bs2_cnt, ncnt, true, m->stream));
 		}
 		bs.cap2 = (u32)cap2;
 	}
@@ -765,13 +605,11 @@ static int setup_kmback_scatter(kmx_model *m)
 	TRY(bs_geometry(m, m->kmb, nwords, cap, &ok));
 	if (!ok) return KMX_OK;                                        // too big: direct atomics
 	const u64 bins_used = (nwords * 32 + (1ULL << m->kmb.wshift) - 1) >> m->kmb.wshift;
-	if (!m->d_kmb_tup || m->kmb_tup_cap < (u64)BS_BINS * cap) {
+	if (m->d_kmb_tup.cap() < (u64)BS_BINS * cap || !m->d_kmb_cnt) {
 		HIPCHK(hipStreamSynchronize(m->stream));
-		hipFree(m->d_kmb_tup); hipFree(m->d_kmb_cnt);
-		m->d_kmb_tup = nullptr; m->d_kmb_cnt = nullptr; m->kmb_tup_cap = 0;
-		TRY(dalloc(&m->d_kmb_tup, (u64)BS_BINS * cap, false, m->stream));
-		TRY(dalloc(&m->d_kmb_cnt, (u64)BS_BINS, true, m->stream));
-		m->kmb_tup_cap = (u64)BS_BINS * cap;
+		m->d_kmb_tup.reset(); m->d_kmb_cnt.reset();
+		TRY(dalloc(m->d_kmb_tup, (u64)BS_BINS * cap, false, m->stream));
+		TRY(dalloc(m->d_kmb_cnt, (u64)BS_BINS, true, m->stream));
 	}
 	m->kmb.words = m->d_km_back;
 	m->kmb.tup = m->d_kmb_tup; m->kmb.cnt = m->d_kmb_cnt;
@@ -794,13 +632,11 @@ static int setup_bloom_scatter(kmx_model *m)
 	bool ok;
 	TRY(bs_geometry(m, m->blm, m->bloom_words, cap, &ok));
 	if (!ok) return KMX_OK;
-	if (!m->d_blm_tup || m->blm_tup_cap < (u64)BS_BINS * cap) {
+	if (m->d_blm_tup.cap() < (u64)BS_BINS * cap || !m->d_blm_cnt) {
 		HIPCHK(hipStreamSynchronize(m->stream));
-		hipFree(m->d_blm_tup); hipFree(m->d_blm_cnt);
-		m->d_blm_tup = nullptr; m->d_blm_cnt = nullptr; m->blm_tup_cap = 0;
-		TRY(dalloc(&m->d_blm_tup, (u64)BS_BINS * cap, false, m->stream));
-		TRY(dalloc(&m->d_blm_cnt, (u64)BS_BINS, true, m->stream));
-		m->blm_tup_cap = (u64)BS_BINS * cap;
+		m->d_blm_tup.reset(); m->d_blm_cnt.reset();
+		TRY(dalloc(m->d_blm_tup, (u64)BS_BINS * cap, false, m->stream));
+		TRY(dalloc(m->d_blm_cnt, (u64)BS_BINS, true, m->stream));
 	}
 	{
 		// chunks per sweep from the EXPECTED number of tuples of a chunk (the share of Bloom-class k-mers is known from pass 1):
@@ -863,6 +699,60 @@ static int kmback_job_flush(kmx_model *m)
 	return KMX_OK;
 }
 
+// the build-time buffers of one shape (nb, W): staging stream, the block working set in one slab, the small counters
+static int alloc_build_state(kmx_model *m)
+{
+	const int nb = m->nb;
+	const u64 blk = (u64)nb * KMX_BUCKET;
+	// staging stream for coupled-array k-mers: one front-end chunk plus one block of carry-over
+	TRY(dalloc(m->d_stg_kmers, (kChunk + blk) * m->W, false, m->stream));
+	TRY(dalloc(m->d_stg_counts, kChunk + blk, false, m->stream));
+	// one slab for the block working set
+	u64 off = 0;
+	auto carve = [&](u64 bytes) { u64 o = off; off += (bytes + 255) & ~u64(255); return o; };
+	u64 o_list0 = carve(blk * 4), o_list1 = carve(blk * 4), o_mv0 = carve(blk * 4), o_mv1 = carve(blk * 4);
+	u64 o_n0 = carve(nb * 4), o_n1 = carve(nb * 4), o_status0 = carve(blk), o_status1 = carve(blk), o_dfail = carve(blk);
+	u64 o_U[KMX_NSLOW];
+	for (int s2 = 0; s2 < KMX_NSLOW; s2++) o_U[s2] = carve(blk * 8 * (1 + m->W));
+	u64 o_Un = carve((u64)KMX_NSLOW * nb * KMX_CTR_STRIDE * 4), o_R = carve((u64)nb * KMX_RSIZE * 8);
+	u64 o_tc0 = carve((u64)nb * KMX_NTILES * 4), o_tc1 = carve((u64)nb * KMX_NTILES * 4);
+	const u64 cl_bins = m->nh <= 8 ? KMX_CL_BINS(8) : KMX_CL_BINS(16);
+	u64 o_surv = carve(blk), o_surv1 = carve(blk);
+	const u64 cl_bytes = (u64)nb * cl_bins * (u64)(m->nh <= 8 ? KMX_CL_CAP_OF(8) : KMX_CL_CAP_OF(16)) * 8;
+	u64 o_uw[2], o_crec[2], o_cl_tup[2], o_cl_cnt[2];
+	const u64 rec_words = (u64)((m->nh + (m->nh <= 8 ? 1 : 2) + 3) & ~3);      // kernels.hip crec_words
+	for (int q = 0; q < 2; q++) {
+		o_uw[q] = carve(blk * 4); o_crec[q] = carve(blk * 4 * rec_words);
+		o_cl_tup[q] = carve(cl_bytes); o_cl_cnt[q] = carve((u64)nb * KMX_CL_MAXBINS * 4);
+	}
+	u64 o_cl_ovf = carve((u64)nb * 4);
+	TRY(dalloc(m->d_block_scratch, off, true, m->stream));             // R starts at epoch 0; epochs only grow
+	m->scratch_nb = nb; m->scratch_W = m->W;
+	char *base = (char *)m->d_block_scratch.get();
+	BlockDev &bd = m->bd;
+	bd.kmers = nullptr; bd.counts = nullptr;
+	bd.list[0] = (u32 *)(base + o_list0); bd.list[1] = (u32 *)(base + o_list1);
+	bd.mover[0] = (u32 *)(base + o_mv0); bd.mover[1] = (u32 *)(base + o_mv1);
+	bd.n[0] = (int *)(base + o_n0); bd.n[1] = (int *)(base + o_n1);
+	bd.status[0] = (unsigned char *)(base + o_status0); bd.status[1] = (unsigned char *)(base + o_status1); bd.dfail = (unsigned char *)(base + o_dfail);
+	for (int s2 = 0; s2 < KMX_NSLOW; s2++) bd.Urec[s2] = (u64 *)(base + o_U[s2]);
+	bd.Un = (int *)(base + o_Un); bd.R = (u64 *)(base + o_R);
+	bd.tile_cnt[0] = (int *)(base + o_tc0); bd.tile_cnt[1] = (int *)(base + o_tc1);
+	bd.surv = (unsigned char *)(base + o_surv);
+	m->d_surv[0] = bd.surv; m->d_surv[1] = (unsigned char *)(base + o_surv1);   // block b flags into d_surv[b & 1]
+	for (int q = 0; q < 2; q++) {
+		bd.uw[q] = (u32 *)(base + o_uw[q]); bd.crec[q] = (u32 *)(base + o_crec[q]);
+		bd.cl_tup[q] = (u64 *)(base + o_cl_tup[q]); bd.cl_cnt[q] = (int *)(base + o_cl_cnt[q]);
+	}
+	bd.cl_ovf = (int *)(base + o_cl_ovf);                        // zeroed with the slab; the kernels keep it zero between rounds
+	bd.stats = m->d_stats;
+	TRY(dalloc(m->d_rest_n, 1, false, m->stream));
+	TRY(dalloc(m->d_stale_kmers, (u64)nb * 2, false, m->stream));
+	TRY(dalloc(m->d_stale_counts, (u64)nb, false, m->stream));
+	TRY(dalloc(m->d_total, 4, true, m->stream));
+	return KMX_OK;
+}
+
 // ------------------------------------------------------------------------------------------ streamed build
 static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t n_total)
 {
@@ -877,6 +767,9 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 	m->n_total = n_total;
 	for (int i = 0; i < 3; i++) m->n_bf[i] = i < m->bf_num ? n_bf[i] : 0;
 	compute_sizes(m);
+	// Build-time buffers are kept across builds of the same shape (nb, W): only the counters are re-zeroed.  (Dropped here,
+	// before the bit-sets below are pointed at their tuple buffers, which go with them.)
+	if (m->d_block_scratch && (m->scratch_nb != m->nb || m->scratch_W != m->W)) free_build_state(m);
 	TRY(alloc_arrays(m));
 	m->rest = RestTable();
 	TRY(setup_kmback_scatter(m));
@@ -885,58 +778,9 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 	fill_model_dev(m);
 	const int nb = m->nb;
 	const u64 B = KMX_BUCKET, blk = (u64)nb * B;
-	// Build-time buffers are kept across builds of the same shape (nb, W): only the counters are re-zeroed.
-	if (m->d_block_scratch && (m->scratch_nb != nb || m->scratch_W != m->W)) free_build_state(m);
 	if (!m->d_block_scratch) {
-		// staging stream for coupled-array k-mers: one front-end chunk plus one block of carry-over
-		m->stg_cap = kChunk + blk;
-		TRY(dalloc(&m->d_stg_kmers, m->stg_cap * m->W, false, m->stream));
-		TRY(dalloc(&m->d_stg_counts, m->stg_cap, false, m->stream));
-		// one slab for the block working set
-		u64 off = 0;
-		auto carve = [&](u64 bytes) { u64 o = off; off += (bytes + 255) & ~u64(255); return o; };
-		u64 o_list0 = carve(blk * 4), o_list1 = carve(blk * 4), o_mv0 = carve(blk * 4), o_mv1 = carve(blk * 4);
-		u64 o_n0 = carve(nb * 4), o_n1 = carve(nb * 4), o_status0 = carve(blk), o_status1 = carve(blk), o_dfail = carve(blk);
-		u64 o_U[KMX_NSLOW];
-		for (int s2 = 0; s2 < KMX_NSLOW; s2++) o_U[s2] = carve(blk * 8 * (1 + m->W));
-		u64 o_Un = carve((u64)KMX_NSLOW * nb * KMX_CTR_STRIDE * 4), o_R = carve((u64)nb * KMX_RSIZE * 8);
-		u64 o_tc0 = carve((u64)nb * KMX_NTILES * 4), o_tc1 = carve((u64)nb * KMX_NTILES * 4);
-		const u64 cl_bins = m->nh <= 8 ? KMX_CL_BINS(8) : KMX_CL_BINS(16);
-		u64 o_surv = carve(blk), o_surv1 = carve(blk);
-		const u64 cl_bytes = (u64)nb * cl_bins * (u64)(m->nh <= 8 ? KMX_CL_CAP_OF(8) : KMX_CL_CAP_OF(16)) * 8;
-		u64 o_uw[2], o_crec[2], o_cl_tup[2], o_cl_cnt[2];
-		const u64 rec_words = (u64)((m->nh + (m->nh <= 8 ? 1 : 2) + 3) & ~3);      // kernels.hip crec_words
-		for (int q = 0; q < 2; q++) {
-			o_uw[q] = carve(blk * 4); o_crec[q] = carve(blk * 4 * rec_words);
-			o_cl_tup[q] = carve(cl_bytes); o_cl_cnt[q] = carve((u64)nb * KMX_CL_MAXBINS * 4);
-		}
-		u64 o_cl_ovf = carve((u64)nb * 4);
-		HIPCHK(hipMalloc(&m->d_block_scratch, off));
-		HIPCHK(hipMemsetAsync(m->d_block_scratch, 0, off, m->stream));     // R starts at epoch 0; epochs only grow
-		m->scratch_bytes = off; m->scratch_nb = nb; m->scratch_W = m->W;
-		char *base = (char *)m->d_block_scratch;
-		BlockDev &bd = m->bd;
-		bd.kmers = nullptr; bd.counts = nullptr;
-		bd.list[0] = (u32 *)(base + o_list0); bd.list[1] = (u32 *)(base + o_list1);
-		bd.mover[0] = (u32 *)(base + o_mv0); bd.mover[1] = (u32 *)(base + o_mv1);
-		bd.n[0] = (int *)(base + o_n0); bd.n[1] = (int *)(base + o_n1);
-		bd.status[0] = (unsigned char *)(base + o_status0); bd.status[1] = (unsigned char *)(base + o_status1); bd.dfail = (unsigned char *)(base + o_dfail);
-		for (int s2 = 0; s2 < KMX_NSLOW; s2++) bd.Urec[s2] = (u64 *)(base + o_U[s2]);
-		bd.Un = (int *)(base + o_Un); bd.R = (u64 *)(base + o_R);
-		bd.tile_cnt[0] = (int *)(base + o_tc0); bd.tile_cnt[1] = (int *)(base + o_tc1);
-		bd.surv = (unsigned char *)(base + o_surv);
-		m->d_surv[0] = bd.surv; m->d_surv[1] = (unsigned char *)(base + o_surv1);   // block b flags into d_surv[b & 1]
-		for (int q = 0; q < 2; q++) {
-			bd.uw[q] = (u32 *)(base + o_uw[q]); bd.crec[q] = (u32 *)(base + o_crec[q]);
-			bd.cl_tup[q] = (u64 *)(base + o_cl_tup[q]); bd.cl_cnt[q] = (int *)(base + o_cl_cnt[q]);
-		}
-		bd.cl_ovf = (int *)(base + o_cl_ovf);                        // zeroed with the slab; the kernels keep it zero between rounds
-		bd.stats = m->d_stats;
-		TRY(dalloc(&m->d_rest_n, 1, false, m->stream));
-		TRY(dalloc(&m->d_stale_kmers, (u64)nb * 2, false, m->stream));
-		TRY(dalloc(&m->d_stale_counts, (u64)nb, false, m->stream));
-		TRY(dalloc(&m->d_total, 4, true, m->stream));
-		m->rest_cap = 0;
+		const int rc = alloc_build_state(m);
+		if (rc) { m->d_block_scratch.reset(); return rc; }        // (the slab stands for all of it at the next kmx_begin)
 	}
 	m->stg_n = 0;
 	// a build that ended on an error may have left claim counters or dfail marks behind
@@ -947,12 +791,10 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 	m->defer = !m->dbg_no_defer && m->km_byte_size * 8 <= (1ULL << KMX_CL_MIX_BITS);      // position identity inside a detect table is exact up to 2^36
 	// rest accumulators: grown on demand (see ensure_rest_capacity)
 	const u64 want_rest = std::max<u64>(m->n_km / 8, 2 * blk) + blk;
-	if (m->rest_cap < want_rest) {
-		hipFree(m->d_rest_kmers); hipFree(m->d_rest_counts);
-		m->d_rest_kmers = nullptr; m->d_rest_counts = nullptr;
-		TRY(dalloc(&m->d_rest_kmers, want_rest * m->W, false, m->stream));
-		TRY(dalloc(&m->d_rest_counts, want_rest, false, m->stream));
-		m->rest_cap = want_rest;
+	if (m->d_rest_counts.cap() < want_rest || !m->d_rest_kmers) {
+		m->d_rest_kmers.reset(); m->d_rest_counts.reset();
+		TRY(dalloc(m->d_rest_kmers, want_rest * m->W, false, m->stream));
+		TRY(dalloc(m->d_rest_counts, want_rest, false, m->stream));
 	}
 	m->rest_upper = 0;
 	HIPCHK(hipMemsetAsync(m->d_rest_n, 0, 8, m->stream));
@@ -980,10 +822,11 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 		const char *pe = hook_env("KMX_PREGATHER_PROBE");
 		const bool want = pe && pe[0] == '1';
 		if (want && !m->probe.side) {
-			HIPCHK(hipStreamCreateWithFlags(&m->probe.side, hipStreamNonBlocking));
-			HIPCHK(hipEventCreateWithFlags(&m->probe.fork, hipEventDisableTiming));
-			HIPCHK(hipEventCreateWithFlags(&m->probe.done, hipEventDisableTiming));
-			HIPCHK(hipMalloc((void **)&m->probe.sink, 256));
+			HIPCHK(m->probe_side.ensure());
+			HIPCHK(m->probe_fork.ensure());
+			HIPCHK(m->probe_done.ensure());
+			HIPCHK(m->probe_sink.alloc(64));
+			m->probe = {false, m->probe_side, m->probe_fork, m->probe_done, m->probe_sink};
 		}
 		if (want) HIPCHK(hipEventRecord(m->probe.done, m->probe.side));
 		m->probe.on = want;
@@ -995,21 +838,21 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 
 static int ensure_rest_capacity(kmx_model *m, u64 add)
 {
-	if (m->rest_upper + add <= m->rest_cap) { m->rest_upper += add; return KMX_OK; }
+	if (m->rest_upper + add <= m->d_rest_counts.cap()) { m->rest_upper += add; return KMX_OK; }
 	unsigned long long actual = 0;
 	HIPCHK(hipMemcpyAsync(&actual, m->d_rest_n, 8, hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	m->rest_upper = actual;
-	if (m->rest_upper + add > m->rest_cap) {
-		u64 ncap = std::max<u64>(m->rest_cap * 2, m->rest_upper + add);
-		DevMem nk, nc;
-		HIPCHK(nk.alloc(ncap * m->W * 8));
-		HIPCHK(nc.alloc(ncap * 4));
-		HIPCHK(hipMemcpyAsync(nk.p, m->d_rest_kmers, actual * m->W * 8, hipMemcpyDeviceToDevice, m->stream));
-		HIPCHK(hipMemcpyAsync(nc.p, m->d_rest_counts, actual * 4, hipMemcpyDeviceToDevice, m->stream));
+	if (m->rest_upper + add > m->d_rest_counts.cap()) {
+		u64 ncap = std::max<u64>(m->d_rest_counts.cap() * 2, m->rest_upper + add);
+		DevBuf<u64> nk;
+		DevBuf<int> nc;
+		HIPCHK(nk.alloc(ncap * m->W));
+		HIPCHK(nc.alloc(ncap));
+		HIPCHK(hipMemcpyAsync(nk, m->d_rest_kmers, actual * m->W * 8, hipMemcpyDeviceToDevice, m->stream));
+		HIPCHK(hipMemcpyAsync(nc, m->d_rest_counts, actual * 4, hipMemcpyDeviceToDevice, m->stream));
 		HIPCHK(hipStreamSynchronize(m->stream));
-		hipFree(m->d_rest_kmers); hipFree(m->d_rest_counts);
-		m->d_rest_kmers = (u64 *)nk.release(); m->d_rest_counts = (int *)nc.release(); m->rest_cap = ncap;
+		m->d_rest_kmers = std::move(nk); m->d_rest_counts = std::move(nc);
 	}
 	m->rest_upper += add;
 	return KMX_OK;
@@ -1113,7 +956,7 @@ static int process_block(kmx_model *m, u64 head, u64 n_in_block, bool final_part
 		int row = (int)((n_in_block - 1) / KMX_BUCKET);
 		if (row + 1 < nb && m->blocks > 0)
 			hipLaunchKernelGGL(k_stale_dup, dim3(1), dim3(64), 0, m->stream, row + 1, nb, m->W, (const u64 *)m->d_stale_kmers,
-			                   (const int *)m->d_stale_counts, m->d_rest_kmers, m->d_rest_counts, m->d_rest_n, m->d_stats);
+			                   (const int *)m->d_stale_counts, m->d_rest_kmers.get(), m->d_rest_counts.get(), m->d_rest_n.get(), m->d_stats.get());
 	}
 	kmxk::rest_append(m->md, m->bd, pp, 0, nb, m->d_rest_kmers, m->d_rest_counts, m->d_rest_n, m->d_stale_kmers, m->d_stale_counts, m->d_feedback, m->stream);
 	// km_back insert of everything the block inserted (kmodel.hpp:548-550): handed to the next block's finisher launches,
@@ -1130,25 +973,10 @@ static int process_block(kmx_model *m, u64 head, u64 n_in_block, bool final_part
 static int ensure_front_end(kmx_model *m, u64 n)
 {
 	const u64 n_chunks = (n + kChunk - 1) / kChunk, tiles = (u64)kmxk::classify_tiles(n);
-	if (tiles > m->tile_cap) {
-		HIPCHK(hipStreamSynchronize(m->stream));
-		hipFree(m->d_tile_cnt); hipFree(m->d_tile_off);
-		m->d_tile_cnt = m->d_tile_off = nullptr;
-		m->tile_cap = 0;
-		TRY(dalloc(&m->d_tile_cnt, tiles, false, m->stream));
-		TRY(dalloc(&m->d_tile_off, tiles, false, m->stream));
-		m->tile_cap = tiles;
-	}
-	if (n_chunks > m->totals_cap) {
-		HIPCHK(hipStreamSynchronize(m->stream));
-		hipFree(m->d_totals);
-		if (m->h_totals) hipHostFree(m->h_totals);
-		m->d_totals = nullptr; m->h_totals = nullptr;
-		m->totals_cap = 0;
-		TRY(dalloc(&m->d_totals, n_chunks, false, m->stream));
-		HIPCHK(hipHostMalloc((void **)&m->h_totals, n_chunks * 4));
-		m->totals_cap = n_chunks;
-	}
+	HIPCHK(m->d_tile_cnt.ensure(tiles, m->stream));
+	HIPCHK(m->d_tile_off.ensure(tiles, m->stream));
+	HIPCHK(m->d_totals.ensure(n_chunks, m->stream));
+	HIPCHK(m->h_totals.ensure(n_chunks, m->stream));
 	return KMX_OK;
 }
 
@@ -1179,7 +1007,7 @@ static int kmx_insert_batch_dev_impl(kmx_model *m, const uint64_t *d_kmers, cons
 		const u64 add = (u64)m->h_totals[ci];
 		done += c;
 		if (m->km_byte_size == 0 && add) continue;               // divergence D2: no arrays to insert into
-		if (m->stg_n + add > m->stg_cap) return fail(KMX_E_STATE, "staging overflow");
+		if (m->stg_n + add > m->d_stg_counts.cap()) return fail(KMX_E_STATE, "staging overflow");
 		kmxk::classify_scatter(m->md, km, ct, c, m->d_tile_off + ci * (kChunk / KMX_CLS_TILE), m->d_stg_kmers, m->d_stg_counts, m->stg_n, m->stream);
 		m->stg_n += add;
 		u64 head = 0;
@@ -1201,31 +1029,22 @@ static int kmx_insert_batch_dev_impl(kmx_model *m, const uint64_t *d_kmers, cons
 	return KMX_OK;
 }
 
-// Host buffers reach the device the way the KMC feed does: two pinned slots filled by a parallel memcpy, a copy stream
-// that moves slot b+1 (hipMemcpyAsync) while the model's stream inserts batch b.  The buffers live on the handle.
-static int ensure_host_feed(kmx_model *m, size_t B, int W)
+// The slots of the KMC feed for batches of B records of rb bytes / k-mers of W words, the copy stream and its events: the
+// `parts` asked for are grown to that size (never shrunk), whatever else the handle holds stays.  Host buffers reach the
+// device the same way (kmx_insert_batch: HOST | DEV): two pinned slots filled by a parallel memcpy, a copy stream that
+// moves slot b+1 (hipMemcpyAsync) while the model's stream inserts batch b.
+hipError_t kmx_model::KmcFeed::ensure(int parts, size_t B, size_t rb, int W, size_t n_lut)
 {
-	auto &F = m->feed;
-	if (!F.copy) HIPCHK(hipStreamCreateWithFlags(&F.copy, hipStreamNonBlocking));
+	RCHK(copy.ensure());
 	for (int s = 0; s < 2; s++) {
-		if (!F.ev_copied[s]) { HIPCHK(hipEventCreateWithFlags(&F.ev_copied[s], hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&F.ev_free[s], hipEventDisableTiming)); }
-		if (F.km_cap < B * (size_t)W) {
-			if (F.km[s]) hipHostFree(F.km[s]);
-			if (F.cnt[s]) hipHostFree(F.cnt[s]);
-			F.km[s] = nullptr; F.cnt[s] = nullptr;
-			HIPCHK(hipHostMalloc((void **)&F.km[s], B * W * 8));
-			HIPCHK(hipHostMalloc((void **)&F.cnt[s], B * 4));
-		}
-		if (F.dk_cap < B * (size_t)W) {
-			hipFree(F.dk[s]); hipFree(F.dc[s]);
-			F.dk[s] = nullptr; F.dc[s] = nullptr;
-			HIPCHK(hipMalloc((void **)&F.dk[s], B * W * 8));
-			HIPCHK(hipMalloc((void **)&F.dc[s], B * 4));
-		}
+		RCHK(ev_copied[s].ensure());
+		RCHK(ev_free[s].ensure());
+		if (parts & RAW) { RCHK(raw[s].ensure(B * rb + 16, copy)); RCHK(draw[s].ensure(B * rb + 16, copy)); }
+		if (parts & HOST) { RCHK(km[s].ensure(B * W, copy)); RCHK(cnt[s].ensure(B, copy)); }
+		if (parts & DEV) { RCHK(dk[s].ensure(B * W, copy)); RCHK(dc[s].ensure(B, copy)); }
 	}
-	F.km_cap = std::max(F.km_cap, B * (size_t)W);
-	F.dk_cap = std::max(F.dk_cap, B * (size_t)W);
-	return KMX_OK;
+	if (parts & LUT) { RCHK(d_lut.ensure(n_lut, copy)); RCHK(h_lut.ensure(n_lut, copy)); }
+	return hipSuccess;
 }
 
 static void parallel_copy(void *dst, const void *src, size_t bytes)
@@ -1252,8 +1071,8 @@ static int kmx_insert_batch_impl(kmx_model *m, const uint64_t *kmers, const uint
 	HIPCHK(hipSetDevice(m->device));
 	const size_t B = size_t(1) << 23;
 	const int W = m->W;
-	TRY(ensure_host_feed(m, B, W));
 	auto &F = m->feed;
+	HIPCHK(F.ensure(F.HOST | F.DEV, B, 0, W, 0));
 	auto drain = scope_exit([&] { hipStreamSynchronize(F.copy); hipStreamSynchronize(m->stream); });   // the caller's buffers and the slots are free on return
 	HIPCHK(hipEventRecord(F.ev_free[0], m->stream));
 	HIPCHK(hipEventRecord(F.ev_free[1], m->stream));
@@ -1273,7 +1092,7 @@ static int kmx_insert_batch_impl(kmx_model *m, const uint64_t *kmers, const uint
 		const uint64_t c = std::min<uint64_t>(B, n - done), next = done + c;
 		if (next < n) TRY(stage(s ^ 1, next, std::min<uint64_t>(B, n - next)));      // copied under this batch's rounds
 		HIPCHK(hipStreamWaitEvent(m->stream, F.ev_copied[s], 0));
-		TRY(kmx_insert_batch_dev(m, (const uint64_t *)F.dk[s], F.dc[s], c));
+		TRY(kmx_insert_batch_dev(m, (const uint64_t *)F.dk[s].get(), F.dc[s], c));
 		HIPCHK(hipEventRecord(F.ev_free[s], m->stream));
 		done = next;
 	}
@@ -1288,7 +1107,7 @@ static int rest_build_accel(kmx_model *m);
 static int build_rest(kmx_model *m, u64 n)
 {
 	RestTable &r = m->rest;
-	free_rest_dev(r);
+	r.reset_dev();
 	const int W = m->W, k = m->k;
 	r.k = k;
 	r.pre_len = rest_prefix_len(k);
@@ -1297,11 +1116,11 @@ static int build_rest(kmx_model *m, u64 n)
 	r.entries = n;
 	r.suff_bin_size = n * (u64)r.suff_group;
 	r.host_valid = false;
-	HIPCHK(hipMalloc((void **)&r.d_sorted, n * W * 8 + 16));
-	HIPCHK(hipMalloc((void **)&r.d_cnt, n * 4 + 16));
-	HIPCHK(hipMalloc((void **)&r.d_suf, n * W * 8 + 16));
-	HIPCHK(hipMalloc((void **)&r.d_h2i, (u64)r.map_size * 4));
-	HIPCHK(hipMalloc((void **)&r.d_pre, ((u64)r.map_size + 2) * 4));
+	HIPCHK(r.d_sorted.alloc(n * W + 2));
+	HIPCHK(r.d_cnt.alloc(n + 4));
+	HIPCHK(r.d_suf.alloc(n * W + 2));
+	HIPCHK(r.d_h2i.alloc((u64)r.map_size));
+	HIPCHK(r.d_pre.alloc((u64)r.map_size + 2));
 	HIPCHK(hipMemsetAsync(r.d_h2i, 0xFF, (u64)r.map_size * 4, m->stream));
 	KPROF_BEGIN(&m->prof, KC_REST, m->stream);                        // class 5: the rest table -- radix sort + index kernels (the accelerators follow)
 	HIPCHK(kmxk::rest_sort(m->d_rest_kmers, m->d_rest_counts, n, W, k, r.d_sorted, r.d_cnt, m->stream));
@@ -1322,8 +1141,8 @@ static int rest_build_accel(kmx_model *m)
 	F = std::max(F, 2 * r.pre_len);
 	F = std::min(F, 2 * r.k);
 	r.fbits = F;
-	HIPCHK(hipMalloc((void **)&r.d_fine, ((1ULL << F) + 2) * 4));
-	HIPCHK(hipMalloc((void **)&r.d_q, (u64)r.map_size * m->W * 8));
+	HIPCHK(r.d_fine.alloc((1ULL << F) + 2));
+	HIPCHK(r.d_q.alloc((u64)r.map_size * m->W));
 	kmxk::rest_accel(r.d_sorted, r.entries, m->W, r.k, F, r.d_h2i, r.d_pre, r.d_suf, r.map_size, r.d_fine, r.d_q, m->stream);
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -1340,13 +1159,12 @@ static int rest_materialize_host(kmx_model *m)
 	HIPCHK(hipMemcpy(r.hash2index.data(), r.d_h2i, (u64)r.map_size * 4, hipMemcpyDeviceToHost));
 	HIPCHK(hipMemcpy(r.pre_buffer.data(), r.d_pre, (u64)r.pre_buffer_size * 4, hipMemcpyDeviceToHost));
 	if (n) {
-		unsigned char *d_bytes = nullptr;                           // the byte rows are cut on the device
-		HIPCHK(hipMalloc((void **)&d_bytes, r.suff_bin_size));
+		DevBuf<unsigned char> d_bytes;                              // the byte rows are cut on the device
+		HIPCHK(d_bytes.alloc(r.suff_bin_size));
 		kmxk::rest_suffix_bytes(r.d_sorted, n, m->W, r.suff_group, d_bytes, m->stream);
 		hipError_t e = hipMemcpyAsync(r.suffix_bin.data(), d_bytes, r.suff_bin_size, hipMemcpyDeviceToHost, m->stream);
 		if (e == hipSuccess) e = hipMemcpyAsync(r.count_bin.data(), r.d_cnt, n * 4, hipMemcpyDeviceToHost, m->stream);
 		if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-		hipFree(d_bytes);
 		if (e != hipSuccess) return fail(KMX_E_NODEVICE, "rest table download failed");
 	}
 	r.host_valid = true;
@@ -1366,15 +1184,15 @@ static int rest_to_device(kmx_model *m)
 		if (W == 1) suf[e] = (u64)val;
 		else { suf[2 * e] = (u64)(val >> 64); suf[2 * e + 1] = (u64)val; }
 	}
-	HIPCHK(hipMalloc((void **)&r.d_h2i, (u64)r.map_size * 4));
-	HIPCHK(hipMalloc((void **)&r.d_pre, (u64)r.pre_buffer_size * 4 + 4));
-	HIPCHK(hipMalloc((void **)&r.d_cnt, n * 4 + 4));
-	HIPCHK(hipMalloc((void **)&r.d_suf, suf.size() * 8));
+	HIPCHK(r.d_h2i.alloc((u64)r.map_size));
+	HIPCHK(r.d_pre.alloc((u64)r.pre_buffer_size + 1));
+	HIPCHK(r.d_cnt.alloc(n + 1));
+	HIPCHK(r.d_suf.alloc(suf.size()));
 	HIPCHK(hipMemcpy(r.d_h2i, r.hash2index.data(), (u64)r.map_size * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(r.d_pre, r.pre_buffer.data(), (u64)r.pre_buffer_size * 4, hipMemcpyHostToDevice));
 	if (n) HIPCHK(hipMemcpy(r.d_cnt, r.count_bin.data(), n * 4, hipMemcpyHostToDevice));
 	HIPCHK(hipMemcpy(r.d_suf, suf.data(), suf.size() * 8, hipMemcpyHostToDevice));
-	HIPCHK(hipMalloc((void **)&r.d_sorted, n * W * 8 + 16));
+	HIPCHK(r.d_sorted.alloc(n * W + 2));
 	kmxk::rest_expand(r.d_h2i, r.d_pre, r.d_suf, r.map_size, W, r.k, r.pre_len, r.d_sorted, m->stream);
 	r.host_valid = true;
 	return rest_build_accel(m);
@@ -1434,7 +1252,7 @@ static int build_common(kmx_model *m, int k, const u64 *d_kmers, const u32 *d_co
 	TRY(kmx_finish(m));
 	if (m->dbg_ctrl) {
 		auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count() * 1e3; };
-		fprintf(stderr, "[kmx] build: begin (allocate + clear) %.1f ms of which hipMalloc %.1f ms, insert %.1f ms, finish (last block + rest table) %.1f ms\n", ms(t0, t1), (double)g_malloc_ns.exchange(0) * 1e-6, ms(t1, t2), ms(t2, std::chrono::steady_clock::now()));
+		fprintf(stderr, "[kmx] build: begin (allocate + clear) %.1f ms of which hipMalloc %.1f ms, insert %.1f ms, finish (last block + rest table) %.1f ms\n", ms(t0, t1), (double)kmx_malloc_ns.exchange(0) * 1e-6, ms(t1, t2), ms(t2, std::chrono::steady_clock::now()));
 	}
 	HIPCHK(hipEventRecord(m->ev1, m->stream));
 	HIPCHK(hipEventSynchronize(m->ev1));
@@ -1501,7 +1319,6 @@ static int kmx_build_host_impl(kmx_model *m, int k, const uint64_t *kmers, const
 // packing) and inserted.  ONE decode of the database, none of it on the host.  Databases that hold records outside the
 // header's [min_count, max_count] (ReadNextKmer skips those; KMC itself never writes them) take the host decoder
 // instead, and so does KMX_KMC_HOST_DECODE=1 (test hook).
-namespace kmxk { void kmc_decode(const KmcDecode &, int, u64, u64, u64 *, u32 *, hipStream_t); }
 namespace {
 struct FeedSlot {
 	unsigned char *raw = nullptr;     // GPU decode: record bytes
@@ -1513,40 +1330,14 @@ struct FeedSlot {
 };
 }   // namespace
 
-// the feed of KModel::init(db) on the handle: two pinned slots of B raw records + their device twins, decoded k-mers / counts
-// of a batch, a copy stream, events, the prefix LUT on the device -- kept across calls (kmx_model::KmcFeed)
+// the feed of KModel::init(db) on the handle (kmx_model::KmcFeed) for this database, its prefix LUT(s) on the device: file ->
+// the handle's pinned buffer (parallel preads into memory that is resident already) -> device
 static bool feed_alloc(kmx_model *m, size_t B, size_t rb, int W, const kmx::KmcListing &db)
 {
 	auto &F = m->feed;
-	if (hipSetDevice(m->device) != hipSuccess) return false;
-	bool good = F.copy || hipStreamCreateWithFlags(&F.copy, hipStreamNonBlocking) == hipSuccess;
-	for (int s = 0; s < 2 && good; s++) {
-		if (!F.ev_copied[s]) good = hipEventCreateWithFlags(&F.ev_copied[s], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&F.ev_free[s], hipEventDisableTiming) == hipSuccess;
-		if (good && F.raw_cap < B * rb + 16) {
-			if (F.raw[s]) hipHostFree(F.raw[s]);
-			hipFree(F.draw[s]);
-			F.raw[s] = nullptr; F.draw[s] = nullptr;
-			good = hipHostMalloc((void **)&F.raw[s], B * rb + 16) == hipSuccess && hipMalloc((void **)&F.draw[s], B * rb + 16) == hipSuccess;
-		}
-		if (good && F.dk_cap < B * (size_t)W) {
-			hipFree(F.dk[s]); hipFree(F.dc[s]);
-			F.dk[s] = nullptr; F.dc[s] = nullptr;
-			good = hipMalloc((void **)&F.dk[s], B * W * 8) == hipSuccess && hipMalloc((void **)&F.dc[s], B * 4) == hipSuccess;
-		}
-	}
-	if (good) { F.raw_cap = std::max(F.raw_cap, B * rb + 16); F.dk_cap = std::max(F.dk_cap, B * (size_t)W); }
-	// the prefix LUT(s): file -> the handle's pinned buffer (parallel preads into memory that is resident already) -> device
 	const size_t n_lut = db.lut_entries();
-	if (good && F.lut_cap < n_lut) {
-		hipFree(F.d_lut); F.d_lut = nullptr;
-		if (F.h_lut) hipHostFree(F.h_lut);
-		F.h_lut = nullptr;
-		good = hipMalloc((void **)&F.d_lut, n_lut * 8) == hipSuccess && hipHostMalloc((void **)&F.h_lut, n_lut * 8) == hipSuccess;
-		F.lut_cap = good ? n_lut : 0;
-	}
-	if (good) good = n_lut && db.read_lut((uint64_t *)F.h_lut) && hipMemcpy(F.d_lut, F.h_lut, n_lut * 8, hipMemcpyHostToDevice) == hipSuccess;
-	if (!good) F.raw_cap = F.dk_cap = 0;                         // whatever is half there is replaced next time
-	return good;
+	return hipSetDevice(m->device) == hipSuccess && F.ensure(F.RAW | F.DEV | F.LUT, B, rb, W, n_lut) == hipSuccess &&
+	       n_lut && db.read_lut((uint64_t *)F.h_lut.get()) && hipMemcpy(F.d_lut, F.h_lut, n_lut * 8, hipMemcpyHostToDevice) == hipSuccess;
 }
 
 // a database that cannot be opened is KMX_E_IO, unless its header was read and gives a k no model takes (a KMC database of
@@ -1583,9 +1374,10 @@ static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 	if (const char *op = hook_env("KMX_ONE_PASS")) if (op[0] == '1') {
 		const u64 N = db.records();
 		if (!feed_alloc(m, B, rb, W, db)) return fail(KMX_E_NOMEM, "pinned / device buffers for the listing feed could not be allocated");
-		DevMem all_k, all_c;
-		HIPCHK(all_k.alloc(std::max<u64>(N, 1) * W * 8));
-		HIPCHK(all_c.alloc(std::max<u64>(N, 1) * 4));
+		DevBuf<u64> all_k;
+		DevBuf<u32> all_c;
+		HIPCHK(all_k.alloc(std::max<u64>(N, 1) * W));
+		HIPCHK(all_c.alloc(std::max<u64>(N, 1)));
 		auto &F = m->feed;
 		hipStream_t st = m->stream;
 		KmcDecode kd;
@@ -1603,12 +1395,12 @@ static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 			HIPCHK(hipEventRecord(F.ev_copied[s2], F.copy));
 			HIPCHK(hipStreamWaitEvent(st, F.ev_copied[s2], 0));
 			kd.recs = F.draw[s2];
-			kmxk::kmc_decode(kd, W, done, c, (u64 *)all_k.p + done * W, (u32 *)all_c.p + done, st);
+			kmxk::kmc_decode(kd, W, done, c, all_k + done * W, all_c + done, st);
 			HIPCHK(hipEventRecord(F.ev_free[s2], st));
 		}
 		if (db.io_failed()) return fail(KMX_E_IO, "reading %s.kmc_suf failed", db_prefix);
 		lap("listing enqueued (one pass)");
-		const int rc1 = build_common(m, k, (const u64 *)all_k.p, (const u32 *)all_c.p, N, db.kmer_count());
+		const int rc1 = build_common(m, k, all_k, all_c, N, db.kmer_count());
 		lap("finish returned");
 		hipStreamSynchronize(st);
 		return rc1;
@@ -1690,15 +1482,8 @@ static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 		{ std::lock_guard<std::mutex> lk(mu); stop = false; for (auto &sl : slot) sl = FeedSlot(); }
 		gpu_decode = false;
 	}
-	if (!gpu_decode && F.km_cap < B * (size_t)W) {                   // host decoder: pinned k-mer / count slots
-		for (int s = 0; s < 2 && !rc; s++) {
-			if (F.km[s]) hipHostFree(F.km[s]);
-			if (F.cnt[s]) hipHostFree(F.cnt[s]);
-			F.km[s] = nullptr; F.cnt[s] = nullptr;
-			if (hipHostMalloc((void **)&F.km[s], B * W * 8) != hipSuccess || hipHostMalloc((void **)&F.cnt[s], B * 4) != hipSuccess) rc = fail(KMX_E_NOMEM, "pinned buffers for the listing feed could not be allocated");
-		}
-		F.km_cap = rc ? 0 : B * (size_t)W;
-	}
+	if (!gpu_decode && F.ensure(F.HOST, B, rb, W, 0) != hipSuccess)  // host decoder: pinned k-mer / count slots
+		rc = fail(KMX_E_NOMEM, "pinned buffers for the listing feed could not be allocated");
 	if (!rc && !gpu_decode) start_producer(false);
 	if (!rc && db.io_failed()) rc = fail(KMX_E_IO, "reading %s.kmc_suf failed during pass 1", db_prefix);
 	if (!rc && bad) rc = fail(KMX_E_RANGE, "%llu k-mers with a count outside [ci=%d, cs=%d]", (unsigned long long)bad, m->ci, m->cs);
@@ -1744,7 +1529,7 @@ static int kmx_build_from_kmc_impl(kmx_model *m, const char *db_prefix)
 				if (hipStreamWaitEvent(m->stream, F.ev_copied[s], 0) != hipSuccess) rc = fail(KMX_E_NODEVICE, "stream wait failed");
 				else {
 					if (gpu_decode) { kd.recs = F.draw[s]; kmxk::kmc_decode(kd, W, slot[s].rec0, n, F.dk[s], F.dc[s], m->stream); }
-					rc = kmx_insert_batch_dev(m, (const uint64_t *)F.dk[s], F.dc[s], n);
+					rc = kmx_insert_batch_dev(m, (const uint64_t *)F.dk[s].get(), F.dc[s], n);
 				}
 				hipEventRecord(F.ev_free[s], m->stream);                       // everything that reads the device buffers of s is enqueued by now
 			}
@@ -1884,7 +1669,7 @@ static int kmx_ring_stale_dup_dev_impl(kmx_model *m, int first_unused_row)
 	HIPCHK(hipSetDevice(m->device));
 	TRY(ensure_rest_capacity(m, (u64)m->nb));
 	hipLaunchKernelGGL(k_stale_dup, dim3(1), dim3(64), 0, m->stream, first_unused_row, m->nb, m->W, (const u64 *)m->d_stale_kmers,
-	                   (const int *)m->d_stale_counts, m->d_rest_kmers, m->d_rest_counts, m->d_rest_n, m->d_stats);
+	                   (const int *)m->d_stale_counts, m->d_rest_kmers.get(), m->d_rest_counts.get(), m->d_rest_n.get(), m->d_stats.get());
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
 }
@@ -1925,14 +1710,8 @@ static int kmx_shard_complete_impl(kmx_model *m, const uint64_t *d_rest_kmers, c
 	if (n_rest && (!d_rest_kmers || !d_rest_counts)) return fail(KMX_E_ARG, "null rest list");
 	HIPCHK(hipSetDevice(m->device));
 	if (n_rest && (const u64 *)d_rest_kmers != m->d_rest_kmers) {
-		if (n_rest > m->rest_cap) {
-			HIPCHK(hipStreamSynchronize(m->stream));
-			hipFree(m->d_rest_kmers); hipFree(m->d_rest_counts);
-			m->d_rest_kmers = nullptr; m->d_rest_counts = nullptr; m->rest_cap = 0;
-			TRY(dalloc(&m->d_rest_kmers, n_rest * m->W, false, m->stream));
-			TRY(dalloc(&m->d_rest_counts, n_rest, false, m->stream));
-			m->rest_cap = n_rest;
-		}
+		HIPCHK(m->d_rest_kmers.ensure(n_rest * m->W, m->stream));
+		HIPCHK(m->d_rest_counts.ensure(n_rest, m->stream));
 		HIPCHK(hipMemcpyAsync(m->d_rest_kmers, d_rest_kmers, n_rest * m->W * 8, hipMemcpyDeviceToDevice, m->stream));
 		HIPCHK(hipMemcpyAsync(m->d_rest_counts, d_rest_counts, n_rest * 4, hipMemcpyDeviceToDevice, m->stream));
 	}
@@ -2011,12 +1790,13 @@ static int kmx_query_packed_impl(kmx_model *m, const uint64_t *kmers, uint64_t n
 	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	if (!n) return KMX_OK;
 	HIPCHK(hipSetDevice(m->device));
-	DevMem dk, dout;
-	HIPCHK(dk.alloc(n * m->W * 8));
-	HIPCHK(dout.alloc(n * 4));
-	int rc = hipMemcpyAsync(dk.p, kmers, n * m->W * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess ? KMX_OK : fail(KMX_E_NODEVICE, "H2D copy failed");
-	if (!rc) rc = query_packed_dev_locked(m, dk.as<uint64_t>(), n, dout.as<int32_t>());
-	if (!rc && hipMemcpyAsync(out, dout.p, n * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) rc = fail(KMX_E_NODEVICE, "D2H copy failed");
+	DevBuf<uint64_t> dk;
+	DevBuf<int32_t> dout;
+	HIPCHK(dk.alloc(n * m->W));
+	HIPCHK(dout.alloc(n));
+	int rc = hipMemcpyAsync(dk, kmers, n * m->W * 8, hipMemcpyHostToDevice, m->stream) == hipSuccess ? KMX_OK : fail(KMX_E_NODEVICE, "H2D copy failed");
+	if (!rc) rc = query_packed_dev_locked(m, dk, n, dout);
+	if (!rc && hipMemcpyAsync(out, dout, n * 4, hipMemcpyDeviceToHost, m->stream) != hipSuccess) rc = fail(KMX_E_NODEVICE, "D2H copy failed");
 	if (hipStreamSynchronize(m->stream) != hipSuccess && !rc) rc = fail(KMX_E_NODEVICE, "query failed");
 	return rc;
 }
@@ -2037,38 +1817,17 @@ static const size_t kQuerySlotBytes = size_t(32) << 20;        // input bytes pe
 static int ensure_query_feed(kmx_model *m, size_t in_bytes, size_t answers)
 {
 	auto &F = m->qfeed;
-	if (!F.to_dev) HIPCHK(hipStreamCreateWithFlags(&F.to_dev, hipStreamNonBlocking));
-	if (!F.to_host) HIPCHK(hipStreamCreateWithFlags(&F.to_host, hipStreamNonBlocking));
-	for (int s = 0; s < F.S; s++)
-		for (hipEvent_t *e : {&F.ev_in[s], &F.ev_k[s], &F.ev_out[s]})
-			if (!*e) HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-	if (in_bytes > F.in_cap) {
-		HIPCHK(hipStreamSynchronize(m->stream));
-		for (int s = 0; s < F.S; s++) {
-			if (F.h_in[s]) hipHostFree(F.h_in[s]);
-			hipFree(F.d_in[s]);
-			F.h_in[s] = F.d_in[s] = nullptr;
-		}
-		F.in_cap = 0;
-		for (int s = 0; s < F.S; s++) {
-			HIPCHK(hipHostMalloc((void **)&F.h_in[s], in_bytes));
-			HIPCHK(timed_malloc((void **)&F.d_in[s], in_bytes));
-		}
-		F.in_cap = in_bytes;
-	}
-	if (answers > F.out_cap) {
-		HIPCHK(hipStreamSynchronize(m->stream));
-		for (int s = 0; s < F.S; s++) {
-			if (F.h_out[s]) hipHostFree(F.h_out[s]);
-			hipFree(F.d_out[s]);
-			F.h_out[s] = F.d_out[s] = nullptr;
-		}
-		F.out_cap = 0;
-		for (int s = 0; s < F.S; s++) {
-			HIPCHK(hipHostMalloc((void **)&F.h_out[s], answers * 4));
-			HIPCHK(timed_malloc((void **)&F.d_out[s], answers * 4));
-		}
-		F.out_cap = answers;
+	HIPCHK(F.to_dev.ensure());
+	HIPCHK(F.to_host.ensure());
+	for (int s = 0; s < F.S; s++) {
+		HIPCHK(F.ev_in[s].ensure());
+		HIPCHK(F.ev_k[s].ensure());
+		HIPCHK(F.ev_out[s].ensure());
+		HIPCHK(F.h_in[s].ensure(in_bytes, m->stream));
+		HIPCHK(F.d_in[s].ensure(in_bytes, m->stream));
+		if (!answers) continue;                                    // (kmx_count_seqs: the kernels answer nothing)
+		HIPCHK(F.h_out[s].ensure(answers, m->stream));
+		HIPCHK(F.d_out[s].ensure(answers, m->stream));
 	}
 	return KMX_OK;
 }
@@ -2205,7 +1964,7 @@ static int query_text(kmx_model *m, const KmxStrBatch &sb, uint64_t n, int32_t *
 	std::vector<std::vector<uint64_t>> dirty((size_t)T);
 	TRY(query_pipeline(m, n, (size_t)W * 8, T,
 	                   [&](int t, u64 lo, u64 hi, unsigned char *d) { kmx_pack_strings(sb, W, lo, hi, (uint64_t *)d, &dirty[(size_t)t]); },
-	                   [&](int s, u64 cn) { kmxk::query(m->md, (const u64 *)m->qfeed.d_in[s], cn, m->qfeed.d_out[s], m->stream, &m->prof); }, out));
+	                   [&](int s, u64 cn) { kmxk::query(m->md, (const u64 *)m->qfeed.d_in[s].get(), cn, m->qfeed.d_out[s], m->stream, &m->prof); }, out));
 	std::vector<const char *> dptr;
 	std::vector<uint64_t> didx;
 	for (auto &v : dirty) for (uint64_t i : v) { didx.push_back(i); dptr.push_back(sb.ptrs ? sb.ptrs[i] : sb.flat + i * (uint64_t)sb.stride); }
@@ -2250,16 +2009,8 @@ static u64 seq_chunk_hook()
 static int ensure_seq_scratch(kmx_model *m, u64 piece)
 {
 	auto &F = m->qfeed;
-	if (piece > F.seq_cap) {
-		HIPCHK(hipStreamSynchronize(m->stream));               // an earlier _dev call may still be using the old list
-		hipFree(F.d_seq_list);
-		F.d_seq_list = nullptr;
-		F.seq_cap = 0;
-		HIPCHK(timed_malloc((void **)&F.d_seq_list, piece * 4));
-		F.seq_cap = piece;
-	}
-	if (!F.d_seq_cnt) HIPCHK(timed_malloc((void **)&F.d_seq_cnt, 2 * sizeof(u32)));
-	HIPCHK(hipMemsetAsync(F.d_seq_cnt, 0, 2 * sizeof(u32), m->stream));
+	HIPCHK(F.d_seq_list.ensure(piece, m->stream));             // (waits first: an earlier _dev call may still be using the old list)
+	TRY(ensure(F.d_seq_cnt, 2, true, m->stream));
 	return KMX_OK;
 }
 
@@ -2277,7 +2028,7 @@ static int kmx_query_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64
 	int par = 0;
 	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1)
 		kmxk::query_seq(m->md, (const unsigned char *)d_seq, n_bases, (const u64 *)d_offsets, n_seqs, p0, std::min<u64>(piece, n_bases - p0), d_out,
-		                F.d_seq_list, (u32)F.seq_cap, F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+		                F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
 }
@@ -2351,7 +2102,7 @@ static int kmx_query_seqs_impl(kmx_model *m, const char *seq, const uint64_t *of
 		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
 			kmxk::query_seq(m->md, F.d_in[s], sc.nbytes_of(c), sc.bounds(F.d_in[s]), sc.seqs_of(c), 0, cn, F.d_out[s],
-			                F.d_seq_list, (u32)F.seq_cap, F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+			                F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
 			par ^= 1;
 		}, out, &shape);
 }
@@ -2374,10 +2125,10 @@ static int download_array(kmx_model *m, int which, int index, std::vector<unsign
 	const u64 nbytes = m->km_byte_size;
 	out.resize(nbytes);
 	if (!nbytes) return KMX_OK;
-	DevMem tmp;
+	DevBuf<unsigned char> tmp;
 	HIPCHK(tmp.alloc(m->ncells * 2));
-	kmxk::cells_to_disk(m->d_cells[index], m->ncells, nbytes, which - 3, tmp.as<unsigned char>(), m->stream);
-	hipError_t e = hipMemcpyAsync(out.data(), tmp.p, nbytes, hipMemcpyDeviceToHost, m->stream);
+	kmxk::cells_to_disk(m->d_cells[index], m->ncells, nbytes, which - 3, tmp, m->stream);
+	hipError_t e = hipMemcpyAsync(out.data(), tmp, nbytes, hipMemcpyDeviceToHost, m->stream);
 	if (hipStreamSynchronize(m->stream) != hipSuccess || e != hipSuccess) return fail(KMX_E_NODEVICE, "D2H copy failed");
 	return KMX_OK;
 }
@@ -2402,8 +2153,8 @@ static int kmx_download_impl(kmx_model *m, int which, int index, uint8_t *dst, u
 // writes and the next array's kernel overlap.
 namespace {
 struct SaveChunk {
-	unsigned char *buf = nullptr;
-	hipEvent_t ready = nullptr;
+	PinBuf<unsigned char> buf;
+	Event ready;
 	u64 len = 0, off = 0;
 	int state = 0;                                              // 0 free, 1 filled (copy enqueued), 2 being written
 };
@@ -2420,11 +2171,11 @@ static int save_km_bin(kmx_model *m, const std::string &path)
 	constexpr int R = 6, T = 4;
 	constexpr u64 CH = 16ull << 20;
 	SaveChunk ring[R];
-	unsigned char *tmp = nullptr;
+	DevBuf<unsigned char> tmp;
 	int rc = KMX_OK;
 	for (auto &c : ring)
-		if (hipHostMalloc((void **)&c.buf, CH) != hipSuccess || hipEventCreateWithFlags(&c.ready, hipEventDisableTiming) != hipSuccess) rc = fail(KMX_E_NOMEM, "pinned buffers for save could not be allocated");
-	if (!rc && m->km_byte_size && hipMalloc((void **)&tmp, m->ncells * 2) != hipSuccess) rc = fail(KMX_E_NOMEM, "device buffer for save could not be allocated");
+		if (c.buf.alloc(CH) != hipSuccess || c.ready.ensure() != hipSuccess) rc = fail(KMX_E_NOMEM, "pinned buffers for save could not be allocated");
+	if (!rc && m->km_byte_size && tmp.alloc(m->ncells * 2) != hipSuccess) rc = fail(KMX_E_NOMEM, "device buffer for save could not be allocated");
 	std::mutex mu;
 	std::condition_variable cv;
 	bool done = false;
@@ -2470,7 +2221,7 @@ static int save_km_bin(kmx_model *m, const std::string &path)
 	};
 	if (!rc) {
 		for (int i = 0; i < m->bf_num; i++) { emit((const unsigned char *)m->d_bf[i], m->byte_bf[i]); emit((const unsigned char *)m->d_bf_back[i], m->byte_bf_back[i]); }
-		emit((const unsigned char *)m->d_km_back, m->byte_km_back);
+		emit((const unsigned char *)m->d_km_back.get(), m->byte_km_back);
 		for (int a = 0; a < m->nb && !rc && m->km_byte_size; a++)
 			for (int which = 0; which < 2; which++) {                          // bit_array_1 (value), bit_array_2 (tag)
 				kmxk::cells_to_disk(m->d_cells[a], m->ncells, m->km_byte_size, which, tmp, m->stream);   // waits, in stream order, for the copies out of tmp
@@ -2481,9 +2232,7 @@ static int save_km_bin(kmx_model *m, const std::string &path)
 	cv.notify_all();
 	// the writers drain what is filled before they see `done` with nothing left
 	for (auto &w : writers) w.join();
-	hipStreamSynchronize(m->stream);
-	for (auto &c : ring) { if (c.buf) hipHostFree(c.buf); if (c.ready) hipEventDestroy(c.ready); }
-	hipFree(tmp);
+	hipStreamSynchronize(m->stream);                             // (before the ring and tmp go out of scope)
 	if (close(fd) != 0) io_ok = false;
 	if (!rc && !io_ok) rc = fail(KMX_E_IO, "short write to %s", path.c_str());
 	return rc;
@@ -2607,15 +2356,14 @@ static int kmx_load_impl(const char *dir, kmx_model **out)
 	};
 	for (int i = 0; i < m->bf_num && ok; i++) ok = upload(m->d_bf[i], m->byte_bf[i]) && upload(m->d_bf_back[i], m->byte_bf_back[i]);
 	ok = ok && upload(m->d_km_back, m->byte_km_back);
-	unsigned char *dv = nullptr, *dt = nullptr;
 	if (ok && m->km_byte_size) {
-		ok = hipMalloc((void **)&dv, m->ncells * 2) == hipSuccess && hipMalloc((void **)&dt, m->ncells * 2) == hipSuccess;
+		DevBuf<unsigned char> dv, dt;
+		ok = dv.alloc(m->ncells * 2) == hipSuccess && dt.alloc(m->ncells * 2) == hipSuccess;
 		for (int a = 0; a < m->nb && ok; a++) {
 			ok = upload(dv, m->km_byte_size) && upload(dt, m->km_byte_size);
 			if (ok) kmxk::cells_from_disk(dv, dt, m->km_byte_size, m->d_cells[a], m->ncells, m->stream);
 		}
 		ok = ok && hipStreamSynchronize(m->stream) == hipSuccess;
-		hipFree(dv); hipFree(dt);
 	}
 	ok = ok && hipStreamSynchronize(m->stream) == hipSuccess;
 	unmap();
@@ -2670,14 +2418,15 @@ static int kmx_debug_hash_impl(int k, const uint64_t *kmers, uint64_t n, const u
 {
 	if (k < 3 || k > 64 || n_seeds < 1) return fail(KMX_E_ARG, "bad arguments");
 	const int W = (k + 31) / 32;
-	DevMem dk, dh, ds;
-	HIPCHK(dk.alloc(n * W * 8 + 8));
-	HIPCHK(dh.alloc(n * n_seeds * 8 + 8));
-	HIPCHK(ds.alloc(n_seeds * 4));
-	HIPCHK(hipMemcpy(dk.p, kmers, n * W * 8, hipMemcpyHostToDevice));
-	HIPCHK(hipMemcpy(ds.p, seeds, n_seeds * 4, hipMemcpyHostToDevice));
-	kmxk::debug_hash(k, dk.as<u64>(), n, ds.as<u32>(), n_seeds, whole, dh.as<u64>(), nullptr);
-	HIPCHK(hipMemcpy(hashes, dh.p, n * n_seeds * 8, hipMemcpyDeviceToHost));
+	DevBuf<u64> dk, dh;
+	DevBuf<u32> ds;
+	HIPCHK(dk.alloc(n * W + 1));
+	HIPCHK(dh.alloc(n * n_seeds + 1));
+	HIPCHK(ds.alloc(n_seeds));
+	HIPCHK(hipMemcpy(dk, kmers, n * W * 8, hipMemcpyHostToDevice));
+	HIPCHK(hipMemcpy(ds, seeds, n_seeds * 4, hipMemcpyHostToDevice));
+	kmxk::debug_hash(k, dk, n, ds, n_seeds, whole, dh, nullptr);
+	HIPCHK(hipMemcpy(hashes, dh, n * n_seeds * 8, hipMemcpyDeviceToHost));
 	return KMX_OK;
 }
 
@@ -2685,24 +2434,24 @@ static int kmx_debug_min_kmer_impl(int k, const uint64_t *kmers, uint64_t n, uin
 {
 	if (k < 3 || k > 64) return fail(KMX_E_ARG, "bad arguments");
 	const int W = (k + 31) / 32;
-	DevMem dk, dout;
-	HIPCHK(dk.alloc(n * W * 8 + 8));
-	HIPCHK(dout.alloc(n * W * 8 + 8));
-	HIPCHK(hipMemcpy(dk.p, kmers, n * W * 8, hipMemcpyHostToDevice));
-	kmxk::debug_min_kmer(k, dk.as<u64>(), n, dout.as<u64>(), nullptr);
-	HIPCHK(hipMemcpy(out, dout.p, n * W * 8, hipMemcpyDeviceToHost));
+	DevBuf<u64> dk, dout;
+	HIPCHK(dk.alloc(n * W + 1));
+	HIPCHK(dout.alloc(n * W + 1));
+	HIPCHK(hipMemcpy(dk, kmers, n * W * 8, hipMemcpyHostToDevice));
+	kmxk::debug_min_kmer(k, dk, n, dout, nullptr);
+	HIPCHK(hipMemcpy(out, dout, n * W * 8, hipMemcpyDeviceToHost));
 	return KMX_OK;
 }
 
 static int kmx_debug_mod_impl(const uint64_t *h, uint64_t n, uint64_t d, uint64_t *out)
 {
 	if (!d || !n) return fail(KMX_E_ARG, "bad arguments");
-	DevMem dh, dout;
-	HIPCHK(dh.alloc(n * 8));
-	HIPCHK(dout.alloc(n * 8));
-	HIPCHK(hipMemcpy(dh.p, h, n * 8, hipMemcpyHostToDevice));
-	kmxk::debug_mod(dh.as<u64>(), n, d, dout.as<u64>(), nullptr);
-	HIPCHK(hipMemcpy(out, dout.p, n * 8, hipMemcpyDeviceToHost));
+	DevBuf<u64> dh, dout;
+	HIPCHK(dh.alloc(n));
+	HIPCHK(dout.alloc(n));
+	HIPCHK(hipMemcpy(dh, h, n * 8, hipMemcpyHostToDevice));
+	kmxk::debug_mod(dh, n, d, dout, nullptr);
+	HIPCHK(hipMemcpy(out, dout, n * 8, hipMemcpyDeviceToHost));
 	return KMX_OK;
 }
 
@@ -2711,35 +2460,28 @@ static int kmx_debug_mod_impl(const uint64_t *h, uint64_t n, uint64_t d, uint64_
 // gather-bound and the atomic-bound kernels of a round could hide behind each other.
 static int microbench_pair(uint64_t bytes, uint64_t touches, int iters, double *seconds)
 {
-	DevMem b0, b1, sinkm;
+	DevBuf<u64> b0, b1, sinkm;
 	const u64 ncell = bytes / 8, lanes = touches / 8;
-	HIPCHK(b0.alloc(ncell * 8));
-	HIPCHK(b1.alloc(ncell * 8));
-	HIPCHK(sinkm.alloc(8));
-	HIPCHK(hipMemset(b0.as<u64>(), 0, ncell * 8));
-	HIPCHK(hipMemset(b1.as<u64>(), 0, ncell * 8));
-	hipStream_t s0 = nullptr, s1 = nullptr;
-	hipEvent_t e0 = nullptr, e1 = nullptr, j = nullptr;
-	auto guard = scope_exit([&] {
-		if (e0) hipEventDestroy(e0);
-		if (e1) hipEventDestroy(e1);
-		if (j) hipEventDestroy(j);
-		if (s0) hipStreamDestroy(s0);
-		if (s1) hipStreamDestroy(s1);
-	});
-	HIPCHK(hipStreamCreateWithFlags(&s0, hipStreamNonBlocking));
-	HIPCHK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
-	HIPCHK(hipEventCreate(&e0));
-	HIPCHK(hipEventCreate(&e1));
-	HIPCHK(hipEventCreateWithFlags(&j, hipEventDisableTiming));
-	kmxk::micro(8, b0.as<u64>(), ncell, lanes, 12345, sinkm.as<u64>(), s0);
-	kmxk::micro(5, b1.as<u64>(), ncell, lanes, 12345, sinkm.as<u64>(), s1);
+	HIPCHK(b0.alloc(ncell));
+	HIPCHK(b1.alloc(ncell));
+	HIPCHK(sinkm.alloc(1));
+	HIPCHK(hipMemset(b0, 0, ncell * 8));
+	HIPCHK(hipMemset(b1, 0, ncell * 8));
+	Stream s0, s1;
+	Event e0, e1, j;
+	HIPCHK(s0.ensure());
+	HIPCHK(s1.ensure());
+	HIPCHK(e0.ensure(hipEventDefault));
+	HIPCHK(e1.ensure(hipEventDefault));
+	HIPCHK(j.ensure());
+	kmxk::micro(8, b0, ncell, lanes, 12345, sinkm, s0);
+	kmxk::micro(5, b1, ncell, lanes, 12345, sinkm, s1);
 	HIPCHK(hipDeviceSynchronize());
 	HIPCHK(hipEventRecord(e0, s0));
 	HIPCHK(hipStreamWaitEvent(s1, e0, 0));
 	for (int it = 0; it < iters; it++) {
-		kmxk::micro(8, b0.as<u64>(), ncell, lanes, 1000003ULL * (it + 1), sinkm.as<u64>(), s0);
-		kmxk::micro(5, b1.as<u64>(), ncell, lanes, 1000003ULL * (it + 1), sinkm.as<u64>(), s1);
+		kmxk::micro(8, b0, ncell, lanes, 1000003ULL * (it + 1), sinkm, s0);
+		kmxk::micro(5, b1, ncell, lanes, 1000003ULL * (it + 1), sinkm, s1);
 	}
 	HIPCHK(hipEventRecord(j, s1));
 	HIPCHK(hipStreamWaitEvent(s0, j, 0));
@@ -2755,16 +2497,15 @@ static int kmx_microbench_impl(int mode, uint64_t bytes, uint64_t touches, int i
 {
 	if (bytes < 4096 || touches < 8 || iters < 1 || !seconds) return fail(KMX_E_ARG, "bad arguments");
 	if (mode == 20) return microbench_pair(bytes, touches, iters, seconds);
-	DevMem bufm, sinkm;
+	DevBuf<u64> bufm, sinkm;
 	const u64 ncell = bytes / 8, lanes = touches / 8;
-	HIPCHK(bufm.alloc(ncell * 8));
-	HIPCHK(sinkm.alloc(8));
-	u64 *buf = bufm.as<u64>(), *sink = sinkm.as<u64>();
+	HIPCHK(bufm.alloc(ncell));
+	HIPCHK(sinkm.alloc(1));
+	u64 *buf = bufm, *sink = sinkm;
 	HIPCHK(hipMemset(buf, 0, ncell * 8));
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	auto ev_guard = scope_exit([&] { if (e0) hipEventDestroy(e0); if (e1) hipEventDestroy(e1); });
-	HIPCHK(hipEventCreate(&e0));
-	HIPCHK(hipEventCreate(&e1));
+	Event e0, e1;
+	HIPCHK(e0.ensure(hipEventDefault));
+	HIPCHK(e1.ensure(hipEventDefault));
 	kmxk::micro(mode, buf, ncell, lanes, 12345, sink, nullptr);            // warm-up
 	HIPCHK(hipEventRecord(e0, nullptr));
 	for (int it = 0; it < iters; it++) kmxk::micro(mode, buf, ncell, lanes, 1000003ULL * (it + 1), sink, nullptr);
@@ -2801,8 +2542,13 @@ static int kmx_get_kernel_times_impl(kmx_model *m, double *seconds, uint64_t *la
 
 // ------------------------------------------------------------------------------------------ exception firewall
 // Nothing may unwind through the C ABI: every entry point runs its implementation inside this guard.
+// (KMX_FAIL_ALLOC, test hook: the outermost entry point of a thread -- they call each other, kmx_build_host -> kmx_begin --
+// arms the countdown of hip_owned.h for its own length)
+static thread_local int g_entry_depth = 0;
 template <typename F> static int guarded(F f)
 {
+	if (g_entry_depth++ == 0) if (const char *e = hook_env("KMX_FAIL_ALLOC")) kmx_fail_alloc = atoll(e);
+	auto leave = scope_exit([] { if (--g_entry_depth == 0 && kmx_fail_alloc.load(std::memory_order_relaxed)) kmx_fail_alloc = 0; });
 	try { return f(); }
 	catch (const std::bad_alloc &) { return fail(KMX_E_NOMEM, "out of host memory"); }
 	catch (const std::exception &e) { return fail(KMX_E_ARG, "internal error: %s", e.what()); }

@@ -1,0 +1,50 @@
+// launchers.h -- every kmxk:: launcher of kernels.hip (with range_kernels.h, count_kernels.h), rest_device.hip and
+// count_device.hip, declared once: the defining files include it too, so a changed return type or default argument no longer
+// compiles (a changed parameter list is an unresolved symbol when libkmx.so is linked).
+#pragma once
+#include "kmx_types.h"
+
+template <typename T> struct DevBuf;                               // hip_owned.h
+
+namespace kmxk {
+void histogram(const u32 *, u64, int, int, int, u64 *, u64 *, hipStream_t);
+int classify_tiles(u64 n);
+void classify_count(const ModelDev &, const u64 *, const u32 *, u64, u64, int *, int *, int *, u64 *, const BitScatter &, int, hipStream_t, KernelProf *);
+void classify_scatter(const ModelDev &, const u64 *, const u32 *, u64, const int *, u64 *, u32 *, u64, hipStream_t);
+void block_init(const BlockDev &, int, int, int, hipStream_t);
+void round(const ModelDev &, const BlockDev &, int, int, int, u64 *, int, hipStream_t, KernelProf *, const KmbackJob *, const BitScatter *, const RoundProbe *probe = nullptr);
+void commit_flush(const ModelDev &, const BlockDev &, int, int, hipStream_t, KernelProf *);
+void rest_append(const ModelDev &, const BlockDev &, int, int, int, u64 *, int *, unsigned long long *, u64 *, int *, u64 *, hipStream_t, int istride = 1);
+void kmback_emit(const ModelDev &, const BlockDev &, const u64 *, const unsigned char *, int, int, int, int, int, const BitScatter &, hipStream_t, int istride = 1);
+void bs_apply(const BitScatter &, hipStream_t);
+void ring_import(const ModelDev &, const BlockDev &, int, const RingLists &, u64 *, u32 *, hipStream_t);
+void ring_export(const ModelDev &, const BlockDev &, int, const RingLists &, u64 *, hipStream_t);
+void or_words(u32 *, const u32 *, u64, hipStream_t);
+void range_emit(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
+void range_seal(const RangeDev &, const RangePlan &, hipStream_t);
+void range_verdict(const ModelDev &, const BlockDev &, int *, int, const RangeIn &, unsigned char *, int, bool, hipStream_t);
+void range_apply(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
+void range_resolve(const ModelDev &, const BlockDev &, const RangeDev &, const RangePlan &, int, int, bool, hipStream_t);
+void range_commit_apply(const ModelDev &, const RangeIn &, int, hipStream_t);
+void query(const ModelDev &, const u64 *, u64, int *, hipStream_t, KernelProf *, u64 *acct = nullptr);
+void query_ascii(const ModelDev &, int, const unsigned char *, int, u64, int *, hipStream_t);
+void query_seq(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
+void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
+void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);
+void debug_min_kmer(int, const u64 *, u64, u64 *, hipStream_t);
+void debug_mod(const u64 *, u64, u64, u64 *, hipStream_t);
+void micro(int, u64 *, u64, u64, u64, u64 *, hipStream_t);
+hipError_t rest_sort(const u64 *, const int *, u64, int, int, u64 *, int *, hipStream_t);
+hipError_t rest_index(const u64 *, u64, int, int, int, int *, int *, u64 *, int *, hipStream_t);
+void rest_expand(const int *, const int *, const u64 *, int, int, int, int, u64 *, hipStream_t);
+void rest_accel(const u64 *, u64, int, int, int, const int *, const int *, const u64 *, int, u32 *, u64 *, hipStream_t);
+void rest_suffix_bytes(const u64 *, u64, int, int, unsigned char *, hipStream_t);
+void count_windows(int, const unsigned char *, u64, const u64 *, u64, u64, u64, u64 *, u64 *, u64, unsigned long long *, hipStream_t);
+void kmc_decode(const KmcDecode &, int, u64, u64, u64 *, u32 *, hipStream_t);
+// count_device.hip: `tmp` is rocPRIM's scratch, grown (after the stream has drained) when a pass asks for more
+hipError_t count_piece(int, int, u64 *, u64 *, u64, u64, u32 *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t count_merge(int, const u64 *, const u32 *, u64, const u64 *, const u32 *, u64, u64 *, u32 *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t count_reduce(int, const u64 *, const u32 *, u64, u64 *, u32 *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t count_filter(int, const u64 *, const u32 *, u64, u32, u32, u32, u64 *, u32 *, unsigned char *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+}   // namespace kmxk

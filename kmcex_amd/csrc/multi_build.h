@@ -145,17 +145,17 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 		if (not_listed) return fail(KMX_E_ARG, "the database holds records outside its header's count range: build it on one device");
 		db.set_threads(std::max(1, (int)std::min(hw ? hw : 1u, 32u) / P));     // every handle's thread reads its slice with this many preads side by side
 	}
-	struct Rank {
-		u64 *d_km = nullptr, *d_ck = nullptr, *d_rk = nullptr, *d_allk = nullptr;
-		u32 *d_cnt = nullptr, *d_cc = nullptr, *d_rc = nullptr;
-		int *d_allc = nullptr;
-		u32 *d_tmp = nullptr;
+	struct Rank {                                                 // (its buffers free themselves: at the end of the rank's body, see there)
+		DevBuf<u64> d_km, d_ck, d_rk, d_allk;
+		DevBuf<u32> d_cnt, d_cc, d_rc;
+		DevBuf<int> d_allc;
+		DevBuf<u32> d_tmp;
 		u64 n = 0, n_c = 0, n_r = 0, rec_lo = 0;
-		std::vector<u64 *> msg;                                    // [nb * 2] list i, parity
-		hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // ring: round r is enqueued (r & 1); range: the regions are sealed / the verdicts shipped / the bulk of the commits is out / ... is applied
-		hipStream_t side = nullptr;                               // range: the owner's stream for the bulk of the commits
-		u64 *x_recv = nullptr;                                    // RCCL transport: what the senders' regions arrive in, the verdict bytes
-		unsigned char *x_ver = nullptr, *x_back = nullptr;        // this rank answers with / gets back
+		std::vector<DevBuf<u64>> msg;                              // [nb * 2] list i, parity
+		Event ev[4];                                              // ring: round r is enqueued (r & 1); range: the regions are sealed / the verdicts shipped / the bulk of the commits is out / ... is applied
+		Stream side;                                              // range: the owner's stream for the bulk of the commits
+		DevBuf<u64> x_recv;                                       // RCCL transport: what the senders' regions arrive in, the verdict bytes
+		DevBuf<unsigned char> x_ver, x_back;                      // this rank answers with / gets back
 		u64 x_stride = 0, x_capx = 0;
 		kmx_stats st;
 		void *rest_k = nullptr, *rest_c = nullptr;
@@ -193,12 +193,11 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 		if (!err) {
 			const u64 B = u64(1) << 23;
 			auto &F = m->feed;
-			bool ok = hip_ok(hipEventCreateWithFlags(&r.ev[0], hipEventDisableTiming), "event") && hip_ok(hipEventCreateWithFlags(&r.ev[1], hipEventDisableTiming), "event") &&
-			          hip_ok(hipEventCreateWithFlags(&r.ev[2], hipEventDisableTiming), "event") && hip_ok(hipEventCreateWithFlags(&r.ev[3], hipEventDisableTiming), "event") &&
-			          (!by_range || hip_ok(hipStreamCreateWithFlags(&r.side, hipStreamNonBlocking), "stream"));
+			bool ok = hip_ok(r.ev[0].ensure(), "event") && hip_ok(r.ev[1].ensure(), "event") && hip_ok(r.ev[2].ensure(), "event") && hip_ok(r.ev[3].ensure(), "event") &&
+			          (!by_range || hip_ok(r.side.ensure(), "stream"));
 			if (ok && !feed_alloc(m, (size_t)B, rb, W, db)) { fail(KMX_E_NOMEM, "pinned / device buffers for the listing feed could not be allocated"); note(KMX_E_NOMEM); ok = false; }
-			if (ok) ok = hip_ok(hipMalloc((void **)&r.d_km, std::max<u64>(r.n, 1) * W * 8), "hipMalloc") && hip_ok(hipMalloc((void **)&r.d_cnt, std::max<u64>(r.n, 1) * 4), "hipMalloc") &&
-			             hip_ok(hipMalloc((void **)&r.d_ck, std::max<u64>(r.n, 1) * W * 8), "hipMalloc") && hip_ok(hipMalloc((void **)&r.d_cc, std::max<u64>(r.n, 1) * 4), "hipMalloc");
+			if (ok) ok = hip_ok(r.d_km.alloc(std::max<u64>(r.n, 1) * W), "hipMalloc") && hip_ok(r.d_cnt.alloc(std::max<u64>(r.n, 1)), "hipMalloc") &&
+			             hip_ok(r.d_ck.alloc(std::max<u64>(r.n, 1) * W), "hipMalloc") && hip_ok(r.d_cc.alloc(std::max<u64>(r.n, 1)), "hipMalloc");
 			mark(d, "  buffers");
 			KmcDecode kd;
 			kd.lut = F.d_lut; kd.n_lut = db.lut_entries() - 1; kd.prefix_mask = db.prefix_mask();
@@ -228,10 +227,10 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 			uint64_t stride = 0, capx = 0;
 			if (!note(kmx_range_inband_impl(m, nullptr, &stride, &capx))) {
 				r.x_stride = stride; r.x_capx = capx;
-				hip_ok(hipMalloc((void **)&r.x_recv, (u64)P * stride * 8), "hipMalloc") && hip_ok(hipMalloc((void **)&r.x_ver, (u64)P * capx), "hipMalloc") && hip_ok(hipMalloc((void **)&r.x_back, (u64)P * capx), "hipMalloc");
+				hip_ok(r.x_recv.alloc((u64)P * stride), "hipMalloc") && hip_ok(r.x_ver.alloc((u64)P * capx), "hipMalloc") && hip_ok(r.x_back.alloc((u64)P * capx), "hipMalloc");
 			}
 		}
-		if (!err) { uint64_t nc = 0; if (!note(kmx_shard_classify_dev_impl(m, (const uint64_t *)r.d_km, r.d_cnt, r.n, (uint64_t *)r.d_ck, r.d_cc, &nc))) r.n_c = nc; }
+		if (!err) { uint64_t nc = 0; if (!note(kmx_shard_classify_dev_impl(m, (const uint64_t *)r.d_km.get(), r.d_cnt, r.n, (uint64_t *)r.d_ck.get(), r.d_cc, &nc))) r.n_c = nc; }
 		if (!err) hip_ok(hipStreamSynchronize(st), "classify");
 		mark(d, "  begin + classify");
 		bar.wait();
@@ -244,7 +243,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 		// ---- routing: every buffer of the stream to the owner of the array it meets first, in block order (dist.plan_routing)
 		if (!err) {
 			for (u64 b = 0; b < n_blocks; b++) for (int i = 0; i < nb; i++) if (own[(size_t)i] == d) r.n_r += (u64)list_len(b, i);
-			bool ok = hip_ok(hipMalloc((void **)&r.d_rk, std::max<u64>(r.n_r, 1) * W * 8), "hipMalloc") && hip_ok(hipMalloc((void **)&r.d_rc, std::max<u64>(r.n_r, 1) * 4), "hipMalloc");
+			bool ok = hip_ok(r.d_rk.alloc(std::max<u64>(r.n_r, 1) * W), "hipMalloc") && hip_ok(r.d_rc.alloc(std::max<u64>(r.n_r, 1)), "hipMalloc");
 			u64 at = 0;
 			for (u64 b = 0; ok && b < n_blocks; b++)
 				for (int i = 0; ok && i < nb; i++) {
@@ -262,9 +261,9 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 			if (by_range && !over_rccl) { if (ok) note(range_link(hs, P, d)); }          // (every handle allocated its inbox in range_begin, two barriers ago)
 			else if (by_range) { /* RCCL: the regions stay local, ncclSend / ncclRecv move them */ }
 			else {
-				try { r.msg.assign((size_t)nb * 2, nullptr); } catch (...) { fail(KMX_E_NOMEM, "out of memory"); note(KMX_E_NOMEM); ok = false; }
+				try { r.msg.resize((size_t)nb * 2); } catch (...) { fail(KMX_E_NOMEM, "out of memory"); note(KMX_E_NOMEM); ok = false; }
 				for (int q = 0; ok && q < P; q++) if (note(peer_access(m->device, hs[q]->device))) ok = false;      // k_ring_export stores into the next owner's buffer
-				for (auto &p : r.msg) if (ok) { ok = hip_ok(hipMalloc((void **)&p, msg_words * 8), "hipMalloc") && hip_ok(hipMemsetAsync(p, 0, msg_words * 8, st), "memset"); }
+				for (auto &p : r.msg) if (ok) { ok = hip_ok(p.alloc(msg_words), "hipMalloc") && hip_ok(hipMemsetAsync(p, 0, msg_words * 8, st), "memset"); }
 			}
 			if (ok) hip_ok(hipStreamSynchronize(st), "routing");
 		}
@@ -314,7 +313,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 					if (!err) note(range_list_emit(m, t, lists, n_lists));                          // 1. [header | commits of the round before + this round's triples] per owner
 					exchange(m->range.d_send, r.x_recv, stride, ncclUint64, 8);
 					RangeIn in;
-					if (!err && !note(range_in_inband(m, (const uint64_t *)r.x_recv, P, r.x_ver, in))) note(range_owner_round(m, t, in, RANGE_ALL));   // 2. commits applied, one verdict byte per word
+					if (!err && !note(range_in_inband(m, (const uint64_t *)r.x_recv.get(), P, r.x_ver, in))) note(range_owner_round(m, t, in, RANGE_ALL));   // 2. commits applied, one verdict byte per word
 					exchange(r.x_ver, r.x_back, capx, ncclUint8, 1);
 					if (!err) {                                                                     // 3. winners decided; their commits go to the front of the regions
 						for (int q = 0; q < P; q++) m->range.rd.vin[q] = r.x_back + (u64)q * capx;
@@ -327,7 +326,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 				if (!err) { kmxk::range_seal(m->range.rd, m->range.plan, st); m->range.pending = false; }
 				exchange(m->range.d_send, r.x_recv, stride, ncclUint64, 8);
 				RangeIn in;
-				if (!err && !note(range_in_inband(m, (const uint64_t *)r.x_recv, P, nullptr, in))) { kmxk::range_commit_apply(m->md, in, RANGE_ALL, st); hip_ok(hipGetLastError(), "commit"); }
+				if (!err && !note(range_in_inband(m, (const uint64_t *)r.x_recv.get(), P, nullptr, in))) { kmxk::range_commit_apply(m->md, in, RANGE_ALL, st); hip_ok(hipGetLastError(), "commit"); }
 			}
 		} else if (by_range) {
 			// A round's commits can be set by the owners on a SIDE stream, beside what the list ranks do next, instead of in front of
@@ -422,7 +421,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 					memset(&l, 0, sizeof l);
 					l.list = i;
 					const int next = own[(size_t)((a + 1) % nb)], prev = own[(size_t)((a + nb - 1) % nb)];
-					l.dst_msg = t + 1 < nb ? R[(size_t)next].msg[(size_t)i * 2 + ((t + 1) & 1)] : nullptr;      // the next owner's buffer (possibly this rank's own)
+					l.dst_msg = t + 1 < nb ? R[(size_t)next].msg[(size_t)i * 2 + ((t + 1) & 1)].get() : nullptr;      // the next owner's buffer (possibly this rank's own)
 					if (t + 1 < nb && next != d) peer[next] = true;
 					if (t == 0) { l.n_host = n_i; l.src_kmers = r.d_rk + pos * W; l.src_counts = r.d_rc + pos; pos += (u64)n_i; }
 					else { l.n_host = -1; l.src_msg = r.msg[(size_t)i * 2 + (t & 1)]; if (prev != d) peer[prev] = true; }
@@ -454,7 +453,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 		}
 		bar.wait();
 		if (!err) {
-			bool ok = hip_ok(hipMalloc((void **)&r.d_allk, std::max<u64>(n_rest_all, 1) * W * 8), "hipMalloc") && hip_ok(hipMalloc((void **)&r.d_allc, std::max<u64>(n_rest_all, 1) * 4), "hipMalloc");
+			bool ok = hip_ok(r.d_allk.alloc(std::max<u64>(n_rest_all, 1) * W), "hipMalloc") && hip_ok(r.d_allc.alloc(std::max<u64>(n_rest_all, 1)), "hipMalloc");
 			for (int q = 0; ok && q < P; q++) {
 				const u64 c = rest_off[(size_t)q + 1] - rest_off[(size_t)q];
 				if (!c) continue;
@@ -472,7 +471,7 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 		if (!err && d == 0) {                                              // rank 0 ORs everybody's partial filters ...
 			u64 wmax = 0;
 			for (int f = 0; f < 2 * m->bf_num + 1; f++) { u32 *p; u64 w; filter(m, f < m->bf_num ? 0 : (f < 2 * m->bf_num ? 1 : 2), f % m->bf_num, &p, &w); wmax = std::max(wmax, w); }
-			bool ok = hip_ok(hipMalloc((void **)&r.d_tmp, std::max<u64>(wmax, 1) * 4), "hipMalloc");
+			bool ok = hip_ok(r.d_tmp.alloc(std::max<u64>(wmax, 1)), "hipMalloc");
 			for (int f = 0; ok && f < 2 * m->bf_num + 1; f++) {
 				const int which = f < m->bf_num ? 0 : (f < 2 * m->bf_num ? 1 : 2), idx = which == 2 ? 0 : f % m->bf_num;
 				u32 *mine; u64 w;
@@ -508,15 +507,11 @@ static int kmx_build_from_kmc_multi_ex_impl(kmx_model **hs, int P, const char *d
 			hip_ok(hipStreamSynchronize(st), "merge");
 		}
 		bar.wait();
-		if (!err) note(kmx_shard_complete_impl(m, (const uint64_t *)r.d_allk, r.d_allc, n_rest_all, &totals));
+		if (!err) note(kmx_shard_complete_impl(m, (const uint64_t *)r.d_allk.get(), r.d_allc, n_rest_all, &totals));
 		hipStreamSynchronize(st);
 		bar.wait();                                                         // nobody frees what a peer may still be reading
 		mark(d, "merged and complete");
-		hipFree(r.d_km); hipFree(r.d_cnt); hipFree(r.d_ck); hipFree(r.d_cc); hipFree(r.d_rk); hipFree(r.d_rc); hipFree(r.d_allk); hipFree(r.d_allc);
-		hipFree(r.d_tmp); hipFree(r.x_recv); hipFree(r.x_ver); hipFree(r.x_back);
-		for (u64 *p : r.msg) hipFree(p);
-		for (hipEvent_t e : r.ev) if (e) hipEventDestroy(e);
-		if (r.side) { hipStreamSynchronize(r.side); hipStreamDestroy(r.side); }
+		r = Rank();                                                         // its buffers, events and side stream go here, with this rank's device current
 	};
 	// (a body must reach every barrier whatever happens to it: an exception -- bad_alloc in one of its vectors -- is noted like
 	// any other error and the walk goes on with empty steps; a thread that cannot be created leaves the build with an error

@@ -18,36 +18,38 @@ static int range_begin_common(kmx_model *m, int k, const uint64_t n_bf[3], uint6
 	const u64 key = ((u64)nb << 32) | ((u64)nh << 16) | ((u64)world << 1) | (mailbox ? 1u : 0u);
 	if (R.alloc_key != key) {
 		HIPCHK(hipStreamSynchronize(m->stream));
-		free_range(m);
+		R = kmx_model::RangeState();                                 // (what the last shape's buffers held goes)
 		const u64 held = (u64)((nb + world - 1) / world), slots = (u64)nb * KMX_BUCKET;
 		R.rd.cap = 2 * held * KMX_BUCKET * (u64)nh;                  // a round's triples behind the previous round's commits
 		R.rd.rt_bits = nh <= 8 ? 22 : 23;
 		if (mailbox) {
-			TRY(dalloc(&R.d_inbox, (u64)world * R.rd.cap, false, m->stream));
-			TRY(dalloc(&R.d_in_hdr, (u64)KMX_MAX_RANKS * KMX_RANGE_HDR, true, m->stream));
-			TRY(dalloc(&R.d_vbox, (u64)world * R.rd.cap, false, m->stream));
+			TRY(dalloc(R.d_inbox, (u64)world * R.rd.cap, false, m->stream));
+			TRY(dalloc(R.d_in_hdr, (u64)KMX_MAX_RANKS * KMX_RANGE_HDR, true, m->stream));
+			TRY(dalloc(R.d_vbox, (u64)world * R.rd.cap, false, m->stream));
 		} else {
-			TRY(dalloc(&R.d_send, (u64)world * R.rd.cap, false, m->stream));
-			TRY(dalloc(&R.d_hdr, (u64)KMX_MAX_RANKS * KMX_RANGE_HDR, true, m->stream));
-			HIPCHK(hipHostMalloc((void **)&R.h_hdr, sizeof(u32) * KMX_MAX_RANKS * KMX_RANGE_HDR));
+			TRY(dalloc(R.d_send, (u64)world * R.rd.cap, false, m->stream));
+			TRY(dalloc(R.d_hdr, (u64)KMX_MAX_RANKS * KMX_RANGE_HDR, true, m->stream));
+			HIPCHK(R.h_hdr.alloc(KMX_MAX_RANKS * KMX_RANGE_HDR));
 		}
-		TRY(dalloc(&R.rd.ccnt, (u64)KMX_MAX_RANKS * KMX_CTR_STRIDE, true, m->stream));
-		TRY(dalloc(&R.rd.tcnt, (u64)KMX_MAX_RANKS * KMX_CTR_STRIDE, true, m->stream));
-		TRY(dalloc(&R.rd.tidx, slots * nh, false, m->stream));
-		TRY(dalloc(&R.rd.contended, slots, false, m->stream));
-		TRY(dalloc(&R.rd.n_contended, (u64)KMX_MAX_NB * KMX_CTR_STRIDE, true, m->stream));
-		TRY(dalloc(&R.rd.rt_key, held << R.rd.rt_bits, false, m->stream));
-		TRY(dalloc(&R.rd.rt_resv, held << R.rd.rt_bits, false, m->stream));
-		TRY(dalloc(&R.rd.rt_mark, held << R.rd.rt_bits, false, m->stream));
-		TRY(dalloc(&R.rd.rt_eidx, slots * nh, false, m->stream));
-		TRY(dalloc(&R.rd.rt_um, slots, false, m->stream));
-		TRY(dalloc(&R.d_oovf, (u64)KMX_MAX_NB, true, m->stream));
-		TRY(dalloc(&R.d_opcnt, (u64)KMX_MAX_NB * KMX_CL_MAXBINS * KMX_CTR_STRIDE, true, m->stream));
-		TRY(dalloc(&R.d_lver, slots * nh, false, m->stream));        // every triple of a round may come to one owner
-		TRY(dalloc(&R.d_ovf, (u64)KMX_CTR_STRIDE, true, m->stream));
+		TRY(dalloc(R.d_ccnt, (u64)KMX_MAX_RANKS * KMX_CTR_STRIDE, true, m->stream));
+		TRY(dalloc(R.d_tcnt, (u64)KMX_MAX_RANKS * KMX_CTR_STRIDE, true, m->stream));
+		TRY(dalloc(R.d_tidx, slots * nh, false, m->stream));
+		TRY(dalloc(R.d_contended, slots, false, m->stream));
+		TRY(dalloc(R.d_n_contended, (u64)KMX_MAX_NB * KMX_CTR_STRIDE, true, m->stream));
+		TRY(dalloc(R.d_rt_key, held << R.rd.rt_bits, false, m->stream));
+		TRY(dalloc(R.d_rt_resv, held << R.rd.rt_bits, false, m->stream));
+		TRY(dalloc(R.d_rt_mark, held << R.rd.rt_bits, false, m->stream));
+		TRY(dalloc(R.d_rt_eidx, slots * nh, false, m->stream));
+		TRY(dalloc(R.d_rt_um, slots, false, m->stream));
+		TRY(dalloc(R.d_oovf, (u64)KMX_MAX_NB, true, m->stream));
+		TRY(dalloc(R.d_opcnt, (u64)KMX_MAX_NB * KMX_CL_MAXBINS * KMX_CTR_STRIDE, true, m->stream));
+		TRY(dalloc(R.d_lver, slots * nh, false, m->stream));         // every triple of a round may come to one owner
+		TRY(dalloc(R.d_ovf, (u64)KMX_CTR_STRIDE, true, m->stream));
 		R.cap_full = R.rd.cap;
 		R.alloc_key = key;
 	}
+	R.rd.ccnt = R.d_ccnt; R.rd.tcnt = R.d_tcnt; R.rd.tidx = R.d_tidx; R.rd.contended = R.d_contended; R.rd.n_contended = R.d_n_contended;
+	R.rd.rt_key = R.d_rt_key; R.rd.rt_resv = R.d_rt_resv; R.rd.rt_mark = R.d_rt_mark; R.rd.rt_eidx = R.d_rt_eidx; R.rd.rt_um = R.d_rt_um;
 	R.mailbox = mailbox;
 	R.inband = false;
 	R.rd.cap = R.cap_full;

@@ -5,7 +5,8 @@
 // 2*pre_len bits), so here: one device radix sort (rocPRIM, the vendor primitive for a plain key sort -- not a
 // hot-path kernel) + three small kernels that emit hash2index / pre_buffer / the suffix integers k_query
 // searches.  The on-disk byte arrays are materialised on the host only when save() is called.
-#include "kmx_types.h"
+#include "hip_owned.h"
+#include "launchers.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -131,44 +132,41 @@ __global__ __launch_bounds__(256) void k_rest_suffix_bytes(const u64 *km, u64 n,
 
 namespace kmxk {
 
-#define RCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return e_; } while (0)
-
 // Sort n (k-mer, count) pairs ascending by k-mer.  in/out buffers are distinct; scratch is allocated here
-// (rest tables are a few % of the input, and this runs once per build).
+// (rest tables are a few % of the input, and this runs once per build) and released on every way out
+// (an early return frees with work in flight: hipFree waits for the device).
 hipError_t rest_sort(const u64 *km_in, const int *cnt_in, u64 n, int W, int k, u64 *km_out, int *cnt_out, hipStream_t st)
 {
 	if (!n) return hipSuccess;
 	size_t tmp_bytes = 0;
-	void *tmp = nullptr;
+	DevBuf<unsigned char> tmp;
 	if (W == 1) {
 		RCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st));
-		RCHK(hipMalloc(&tmp, tmp_bytes));
-		hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st);
+		RCHK(tmp.alloc(tmp_bytes));
+		hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st);
 		hipStreamSynchronize(st);
-		hipFree(tmp);
 		return e;
 	}
 	// two-word keys: LSD -- stable sort by the low word, then by the high word, carrying a permutation
-	u64 *hi = nullptr, *lo = nullptr, *key2 = nullptr, *key3 = nullptr;
-	u32 *i0 = nullptr, *i1 = nullptr;
-	RCHK(hipMalloc((void **)&hi, n * 8)); RCHK(hipMalloc((void **)&lo, n * 8));
-	RCHK(hipMalloc((void **)&key2, n * 8)); RCHK(hipMalloc((void **)&key3, n * 8));
-	RCHK(hipMalloc((void **)&i0, n * 4)); RCHK(hipMalloc((void **)&i1, n * 4));
-	hipLaunchKernelGGL(k_split2, dim3(nblk(n)), dim3(256), 0, st, km_in, n, hi, lo);
-	hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(256), 0, st, i0, n);
+	DevBuf<u64> hi, lo, key2, key3;
+	DevBuf<u32> i0, i1;
+	RCHK(hi.alloc(n)); RCHK(lo.alloc(n));
+	RCHK(key2.alloc(n)); RCHK(key3.alloc(n));
+	RCHK(i0.alloc(n)); RCHK(i1.alloc(n));
+	hipLaunchKernelGGL(k_split2, dim3(nblk(n)), dim3(256), 0, st, km_in, n, hi.get(), lo.get());
+	hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(256), 0, st, i0.get(), n);
 	size_t t1 = 0, t2 = 0;
-	RCHK(rocprim::radix_sort_pairs(nullptr, t1, lo, key2, i0, i1, n, 0, 64, st));
-	RCHK(rocprim::radix_sort_pairs(nullptr, t2, key2, key3, i1, i0, n, 0, 2 * k - 64, st));
+	RCHK(rocprim::radix_sort_pairs(nullptr, t1, lo.get(), key2.get(), i0.get(), i1.get(), n, 0, 64, st));
+	RCHK(rocprim::radix_sort_pairs(nullptr, t2, key2.get(), key3.get(), i1.get(), i0.get(), n, 0, 2 * k - 64, st));
 	tmp_bytes = t1 > t2 ? t1 : t2;
-	RCHK(hipMalloc(&tmp, tmp_bytes));
-	hipError_t e = rocprim::radix_sort_pairs(tmp, tmp_bytes, lo, key2, i0, i1, n, 0, 64, st);            // by low word -> perm i1
+	RCHK(tmp.alloc(tmp_bytes));
+	hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, lo.get(), key2.get(), i0.get(), i1.get(), n, 0, 64, st);            // by low word -> perm i1
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n)), dim3(256), 0, st, (const u64 *)hi, (const u32 *)i1, n, key2);   // high words in that order
-		e = rocprim::radix_sort_pairs(tmp, tmp_bytes, key2, key3, i1, i0, n, 0, 2 * k - 64, st);          // stable by high word -> perm i0
+		hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n)), dim3(256), 0, st, (const u64 *)hi.get(), (const u32 *)i1.get(), n, key2.get());   // high words in that order
+		e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, key2.get(), key3.get(), i1.get(), i0.get(), n, 0, 2 * k - 64, st);          // stable by high word -> perm i0
 	}
-	if (e == hipSuccess) hipLaunchKernelGGL(k_gather_final2, dim3(nblk(n)), dim3(256), 0, st, km_in, cnt_in, (const u32 *)i0, n, km_out, cnt_out);
+	if (e == hipSuccess) hipLaunchKernelGGL(k_gather_final2, dim3(nblk(n)), dim3(256), 0, st, km_in, cnt_in, (const u32 *)i0.get(), n, km_out, cnt_out);
 	hipStreamSynchronize(st);
-	hipFree(tmp); hipFree(hi); hipFree(lo); hipFree(key2); hipFree(key3); hipFree(i0); hipFree(i1);
 	return e;
 }
 
@@ -179,18 +177,17 @@ hipError_t rest_index(const u64 *km_sorted, u64 n, int W, int k, int pre_len, in
 	RCHK(hipMemsetAsync(groups, 0, 4, st));
 	RCHK(hipMemsetAsync(pre, 0, 4, st));
 	if (!n) return hipSuccess;
-	int *flag = nullptr, *scan = nullptr;
-	void *tmp = nullptr;
+	DevBuf<int> flag, scan;
+	DevBuf<unsigned char> tmp;
 	size_t tmp_bytes = 0;
-	RCHK(hipMalloc((void **)&flag, n * 4));
-	RCHK(hipMalloc((void **)&scan, n * 4));
-	hipLaunchKernelGGL(k_rest_flags, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, flag, suf);
-	RCHK(rocprim::inclusive_scan(nullptr, tmp_bytes, flag, scan, n, rocprim::plus<int>(), st));
-	RCHK(hipMalloc(&tmp, tmp_bytes));
-	hipError_t e = rocprim::inclusive_scan(tmp, tmp_bytes, flag, scan, n, rocprim::plus<int>(), st);
-	if (e == hipSuccess) hipLaunchKernelGGL(k_rest_index, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, (const int *)flag, (const int *)scan, h2i, pre, groups);
+	RCHK(flag.alloc(n));
+	RCHK(scan.alloc(n));
+	hipLaunchKernelGGL(k_rest_flags, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, flag.get(), suf);
+	RCHK(rocprim::inclusive_scan(nullptr, tmp_bytes, flag.get(), scan.get(), n, rocprim::plus<int>(), st));
+	RCHK(tmp.alloc(tmp_bytes));
+	hipError_t e = rocprim::inclusive_scan(tmp.get(), tmp_bytes, flag.get(), scan.get(), n, rocprim::plus<int>(), st);
+	if (e == hipSuccess) hipLaunchKernelGGL(k_rest_index, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, (const int *)flag.get(), (const int *)scan.get(), h2i, pre, groups);
 	hipStreamSynchronize(st);
-	hipFree(tmp); hipFree(flag); hipFree(scan);
 	return e;
 }
 
