@@ -195,6 +195,26 @@ public:
 		for (size_t i = 0; i < seqs.size(); i++) out[i].assign(occ.begin() + (size_t)off[i], occ.begin() + (size_t)off[i] + windows(seqs[i].size(), k));
 		return out;
 	}
+	// seq_to_occ's vector reduced per sequence on the device (kmx_summarise_seqs): n_windows, sum, min, max, the windows at or
+	// above each of up to KMX_SEQ_THRESHOLDS thresholds, and the first / last window below thr[0]
+	kmx_seq_summary seq_summary(const std::string &seq, const std::vector<int> &thr = std::vector<int>())
+	{
+		const uint64_t off[2] = {0, (uint64_t)seq.size()};
+		kmx_seq_summary out;
+		check(kmx_summarise_seqs(h_, seq.data(), off, 1, (const int32_t *)thr.data(), (int)thr.size(), &out));
+		return out;
+	}
+	std::vector<kmx_seq_summary> seq_summary(const std::vector<std::string> &seqs, const std::vector<int> &thr = std::vector<int>())
+	{
+		std::vector<uint64_t> off(seqs.size() + 1, 0);
+		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		std::vector<kmx_seq_summary> out(seqs.size());
+		check(kmx_summarise_seqs(h_, flat.data(), off.data(), seqs.size(), (const int32_t *)thr.data(), (int)thr.size(), out.data()));
+		return out;
+	}
 
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78

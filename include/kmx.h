@@ -230,6 +230,43 @@ int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint6
  * a decreasing pair as an empty sequence, so bad offsets give wrong answers, never an access outside d_seq / d_out.   */
 int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out);
 
+/* The answers of kmx_query_seqs reduced per sequence on the device: what error correction, repeat detection and read
+ * filtering ask of a read (how many of its k-mers are solid, the lowest and highest count, the mean = sum / n_windows,
+ * whether the median reaches a coverage target: 2 * n_ge[j] > n_windows, where the first and last weak k-mer lie).  64 bytes
+ * per sequence come back instead of 4 per base, and the host reduces nothing.                                            */
+#define KMX_SEQ_THRESHOLDS 3
+typedef struct kmx_seq_summary {     /* one per sequence; 64 bytes, no padding */
+	uint64_t n_windows;              /* max(len - k + 1, 0)                                                         */
+	uint64_t sum;                    /* sum of the windows' answers (each is kmer_to_occ of that window, >= 0)       */
+	int32_t  min, max;               /* over the windows; -1, -1 when n_windows == 0                                 */
+	uint64_t n_ge[KMX_SEQ_THRESHOLDS]; /* windows with answer >= thr[j]; 0 for j >= n_thr                            */
+	uint64_t first_below;            /* smallest window index p (0-based, inside the sequence) with answer < thr[0]; */
+	uint64_t last_below;             /* largest such p.  Both = n_windows when there is none, or when n_thr == 0      */
+} kmx_seq_summary;
+/* Sequences in the layout of kmx_query_seqs (sequence i = seq[offsets[i] .. offsets[i+1]), offsets[0] = 0, 64-bit).
+ *   The windows and their answers are EXACTLY those of kmx_query_seqs: out[i] is what a caller computes from kmx_query_seqs'
+ *   out[offsets[i] .. offsets[i+1]) after dropping the -1 entries.  Windows with N, lowercase or IUPAC bytes are answered
+ *   byte for byte as there, and take part in the summary.
+ *   thr holds n_thr values, 0 <= n_thr <= KMX_SEQ_THRESHOLDS (KMX_E_ARG otherwise, and for n_thr > 0 with thr == NULL); any
+ *   int32 is a legal threshold and they need not ascend; thr[0] also defines first_below / last_below.
+ *   Every counter is 64-bit (one sequence may be a whole genome), and every field is an integer sum, count, minimum or
+ *   maximum: two runs, the host and the device variant, and any chunk size give identical bytes.
+ * KMX_E_ARG when offsets[0] != 0 or the offsets decrease, checked before anything runs; n_seqs == 0: KMX_OK, nothing written;
+ * no bases but n_seqs > 0: every record is the empty one (n_windows = 0, min = max = -1, first_below = last_below = 0) --
+ * unlike kmx_query_seqs there is something to write.  KMX_E_STATE before the model is built or loaded; KMX_E_NOMEM when the
+ * call's memory (72 bytes per sequence on the device: the records and the offsets; the handle's pinned slots and dirty list,
+ * shared with kmx_query_seqs) cannot be had, and the handle stays usable: the same call may be repeated.  The
+ * bases travel as in kmx_query_seqs and nothing per base comes back; the call returns when out is complete.  A query-class
+ * call (see the threading note of kmx_query_packed), timed as kernel class 6 under kmx_set_profile(m, 1).                */
+int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs,
+                       const int32_t *thr, int n_thr, kmx_seq_summary *out /* [n_seqs] */);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], d_out[n_seqs] (thr is read on the HOST, during the call);
+ * enqueued on the model's stream, returns without waiting.  d_out[0, n_seqs) is overwritten whatever it held.  The offsets
+ * are not validated on the host: as in kmx_query_seqs_dev each is clamped into [0, n_bases] where it is read and a decreasing
+ * pair is an empty sequence, so bad offsets give wrong records, never an access outside d_seq[0, n_bases) / d_out[0, n_seqs). */
+int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                           const int32_t *thr /* HOST, n_thr values */, int n_thr, kmx_seq_summary *d_out /* [n_seqs] */);
+
 /* ---- k-mer counting on the device: KMC's step of the pipeline, then KModel::init on what it lists
  * (main.cpp:137-146 runs KMC on the reads, then init on its database; kmodel.hpp:57-86).
  * The counting rule:

@@ -47,9 +47,21 @@ ABI_SYMBOLS = [
     "kmx_ring_stale_dup_dev", "kmx_shard_local", "kmx_shard_complete", "kmx_dev_view", "kmx_or_words_dev",
     "kmx_debug_pack_strings", "kmx_kernel_classes", "kmx_abi_version", "kmx_get_stats_n",
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
-    "kmx_query_seqs", "kmx_query_seqs_dev",
+    "kmx_query_seqs", "kmx_query_seqs_dev", "kmx_summarise_seqs", "kmx_summarise_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
+
+
+class SeqSummary(C.Structure):
+    """kmx_seq_summary of include/kmx.h: one per sequence, 64 bytes"""
+    _fields_ = [("n_windows", C.c_uint64), ("sum", C.c_uint64), ("min", C.c_int32), ("max", C.c_int32),
+                ("n_ge", C.c_uint64 * 3), ("first_below", C.c_uint64), ("last_below", C.c_uint64)]
+
+
+# the same record as a NumPy structured dtype (what KModel.seq_summary_flat returns)
+SEQ_SUMMARY_DTYPE = np.dtype([("n_windows", "<u8"), ("sum", "<u8"), ("min", "<i4"), ("max", "<i4"), ("n_ge", "<u8", (3,)),
+                              ("first_below", "<u8"), ("last_below", "<u8")])
+SEQ_THRESHOLDS = 3
 
 
 class RingList(C.Structure):
@@ -152,6 +164,8 @@ def load_library():
     _sig(L, "kmx_get_stats_n", [vp, vp, u64])
     _sig(L, "kmx_query_seqs", [vp, vp, vp, u64, vp])
     _sig(L, "kmx_query_seqs_dev", [vp, vp, vp, u64, u64, vp])
+    _sig(L, "kmx_summarise_seqs", [vp, vp, vp, u64, vp, i32, vp])
+    _sig(L, "kmx_summarise_seqs_dev", [vp, vp, vp, u64, u64, vp, i32, vp])
     _sig(L, "kmx_count_begin", [vp, i32])
     _sig(L, "kmx_count_seqs", [vp, vp, vp, u64])
     _sig(L, "kmx_count_seqs_dev", [vp, vp, vp, u64, u64])
@@ -487,6 +501,39 @@ class KModel:
     def seq_to_occ_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, d_out_ptr: int) -> None:
         """kmx_query_seqs_dev: device buffers, enqueued on the model's stream (no wait)"""
         _chk(self.L.kmx_query_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, d_out_ptr))
+
+    def seq_summary_flat(self, buf: np.ndarray, offsets: np.ndarray, thr=()) -> np.ndarray:
+        """kmx_summarise_seqs: the answers of seq_to_occ_flat reduced per sequence on the device -> a structured array of
+        n_seqs records (SEQ_SUMMARY_DTYPE: n_windows, sum, min, max, n_ge[3], first_below, last_below); thr: up to 3 int32
+        thresholds, thr[0] also defines first_below / last_below."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        n_bases = int(offsets[-1])
+        if n_bases > buf.size:
+            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        t = np.ascontiguousarray(thr, dtype=np.int32).reshape(-1)
+        out = np.zeros(offsets.size - 1, dtype=SEQ_SUMMARY_DTYPE)
+        _chk(self.L.kmx_summarise_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1,
+                                       t.ctypes.data if t.size else None, t.size, out.ctypes.data))
+        return out
+
+    def seq_summary(self, seqs, thr=()):
+        """seq_summary_flat for a str / bytes sequence (-> one record) or a list of them (-> a structured array)"""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        res = self.seq_summary_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr)
+        return res[0] if single else res
+
+    def seq_summary_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr, d_out_ptr: int) -> None:
+        """kmx_summarise_seqs_dev: device buffers (d_out: n_seqs records of 64 bytes), enqueued on the model's stream (no
+        wait); thr is a host sequence, read during the call"""
+        t = np.ascontiguousarray(thr, dtype=np.int32).reshape(-1)
+        _chk(self.L.kmx_summarise_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, t.ctypes.data if t.size else None, t.size, d_out_ptr))
 
     # ---- k-mer counting on the device (KMC's step, then init on its listing: main.cpp:137-146)
     def init_reads(self, path: str, k: int) -> None:

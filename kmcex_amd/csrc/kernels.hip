@@ -2317,21 +2317,24 @@ __device__ __forceinline__ u64 seq_upper(const u64 *offs, u64 lo, u64 hi, u64 p,
 }
 __device__ __forceinline__ u32 seq_code(u32 c) { return c == 'A' ? 0u : (c == 'C' ? 1u : (c == 'G' ? 2u : (c == 'T' ? 3u : 4u))); }
 
-// windows [p0, p0 + n_win) (all < n_bases): out[p] = the answer, or -1 when the window leaves its sequence; a window with a
-// byte outside uppercase ACGT is not answered here but appended (as p - p0) to dlist through dcnt, one atomic per wave.
-template <int W> __global__ __launch_bounds__(SEQ_BT) void k_query_seq(ModelDev md, const unsigned char *seq, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, int *out, u32 *dlist, u32 cap, u32 *dcnt)
+// What k_query_seq and k_summarise_seq share: the window of lane tid of the tile at t0.  Positions are those of the offsets;
+// the bases on hand are the positions [g0, n_bases), seq[0] being the base at g0 (g0 = 0 unless the caller holds one chunk
+// of a longer input), and the offsets are clamped to n_bases.  Stages the tile's bases in s_code, brackets the tile's
+// boundaries in s_u (both in LDS; holds a barrier: every lane of the workgroup calls it), then for p = t0 + tid < p_end:
+// u = the upper bound of p (sequence u - 1 holds p when 1 <= u <= n_seqs), start = that sequence's first position,
+// valid = the window lies inside it, and for a valid window v[W] = its packed k-mer, bad = it holds a byte outside ACGT.
+struct SeqLane { u64 u, start; bool valid, bad; };
+template <int W> __device__ __forceinline__ SeqLane seq_tile_window(int k, const unsigned char *seq, u64 g0, u64 n_bases, const u64 *offs, u64 n_seqs, u64 t0, u64 p_end, unsigned char *s_code, u64 *s_u, u64 *v)
 {
-	__shared__ unsigned char s_code[SEQ_TILE];                     // 2-bit code of each base of the tile, 4 = not uppercase ACGT
-	__shared__ u64 s_u[2];
-	const int k = md.k, tid = threadIdx.x;
-	const u64 t0 = p0 + (u64)blockIdx.x * SEQ_BT, p_end = p0 + n_win, p = t0 + tid;
+	const int tid = threadIdx.x;
+	const u64 p = t0 + tid;
 	const u64 t_last = (t0 + SEQ_BT < p_end ? t0 + SEQ_BT : p_end) - 1;
 	const u64 b_end = t0 + SEQ_BT + k - 1 < n_bases ? t0 + SEQ_BT + k - 1 : n_bases;   // the bases this tile reads: [t0, b_end)
 	// the boundaries around the tile, found once: every window of the tile has its upper bound in [u0, u1]
 	if (tid == 0) s_u[0] = seq_upper(offs, 0, n_seqs + 1, t0, n_bases);
 	if (tid == 64) s_u[1] = seq_upper(offs, 0, n_seqs + 1, t_last, n_bases);
 	// stage the tile's bases: dword loads where the tile is 4-byte aligned, bytes for the rest
-	const unsigned char *src = seq + t0;
+	const unsigned char *src = seq + (t0 - g0);
 	const int nb = (int)(b_end - t0);
 	if (((uintptr_t)src & 3) == 0) {
 		if (4 * tid < nb) {
@@ -2345,16 +2348,16 @@ template <int W> __global__ __launch_bounds__(SEQ_BT) void k_query_seq(ModelDev 
 	} else
 		for (int j = tid; j < nb; j += SEQ_BT) s_code[j] = (unsigned char)seq_code(src[j]);
 	__syncthreads();
-	bool valid = false, bad = false;
-	u64 v[W];
+	SeqLane w = {0, 0, false, false};
 	if (p < p_end) {
 		const u64 u0 = s_u[0], u1 = s_u[1];
-		const u64 u = seq_upper(offs, u0, u1 > u0 ? u1 : u0, p, n_bases);      // sequence u - 1 holds p
-		if (u >= 1 && u <= n_seqs) {
-			const u64 start = seq_off(offs, u - 1, n_bases), end = seq_off(offs, u, n_bases);
-			valid = start <= p && p + (u64)k <= end;
+		w.u = seq_upper(offs, u0, u1 > u0 ? u1 : u0, p, n_bases);      // sequence u - 1 holds p
+		if (w.u >= 1 && w.u <= n_seqs) {
+			const u64 end = seq_off(offs, w.u, n_bases);
+			w.start = seq_off(offs, w.u - 1, n_bases);
+			w.valid = w.start <= p && p + (u64)k <= end;
 		}
-		if (valid) {
+		if (w.valid) {
 			u64 hi = 0, lo = 0;
 			u32 any = 0;
 			for (int j = 0; j < k; j++) {
@@ -2363,16 +2366,28 @@ template <int W> __global__ __launch_bounds__(SEQ_BT) void k_query_seq(ModelDev 
 				if (W == 2) hi = (hi << 2) | (lo >> 62);
 				lo = (lo << 2) | (c & 3u);
 			}
-			bad = (any & 4u) != 0;
+			w.bad = (any & 4u) != 0;
 			v[W - 1] = lo;
 			if (W == 2) v[0] = hi;
 		}
 	}
-	const bool dirty = valid && bad;
+	return w;
+}
+
+// windows [p0, p0 + n_win) (all < n_bases): out[p] = the answer, or -1 when the window leaves its sequence; a window with a
+// byte outside uppercase ACGT is not answered here but appended (as p - p0) to dlist through dcnt, one atomic per wave.
+template <int W> __global__ __launch_bounds__(SEQ_BT) void k_query_seq(ModelDev md, const unsigned char *seq, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, int *out, u32 *dlist, u32 cap, u32 *dcnt)
+{
+	__shared__ unsigned char s_code[SEQ_TILE];                     // 2-bit code of each base of the tile, 4 = not uppercase ACGT
+	__shared__ u64 s_u[2];
+	const u64 t0 = p0 + (u64)blockIdx.x * SEQ_BT, p_end = p0 + n_win, p = t0 + threadIdx.x;
+	u64 v[W];
+	const SeqLane w = seq_tile_window<W>(md.k, seq, 0, n_bases, offs, n_seqs, t0, p_end, s_code, s_u, v);
+	const bool dirty = w.valid && w.bad;
 	const u32 slot = wave_append_slot<u32>(dcnt, dirty);          // (every lane of the wave takes part)
 	if (dirty && slot < cap) dlist[slot] = (u32)(p - p0);
 	if (p >= p_end || dirty) return;
-	if (!valid) { out[p] = -1; return; }
+	if (!w.valid) { out[p] = -1; return; }
 	query_packed_one<W, false>(md, v, nullptr, out + p);
 }
 
@@ -2388,6 +2403,122 @@ template <int W> __global__ __launch_bounds__(256) void k_query_ascii_at(ModelDe
 		const u64 p = p0 + dlist[i];
 		if (p + (u64)L > n_bases) continue;                          // (never for a listed window)
 		astr_query_one<W>(md, gf, gb, L, astr_load(seq + p, L), out + p);
+	}
+}
+
+// ------------------------------------------------------------------------------------------ summary along sequences
+// kmx_summarise_seqs: the windows and answers of kmx_query_seqs, folded into one SeqSummary per sequence instead of stored.
+// k_seq_summary_init, then per piece k_summarise_seq (clean windows) + k_summarise_ascii_at (the listed ones), then
+// k_seq_summary_finish.  Every field is an integer sum, count, minimum or maximum folded with atomics, so neither the
+// order of the windows nor the cut into pieces and chunks changes a byte of the records.
+__global__ __launch_bounds__(256) void k_seq_summary_init(SeqSummary *rec, u64 n_seqs)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_seqs) return;
+	rec[i] = SeqSummary{0, 0, INT_MAX, -1, {0, 0, 0}, ~0ULL, 0};
+}
+// n_windows from the clamped offsets (a decreasing pair is an empty sequence); the conventions of a record nothing was
+// folded into, and of one with no window below thr[0]
+__global__ __launch_bounds__(256) void k_seq_summary_finish(SeqSummary *rec, const u64 *offs, u64 n_seqs, u64 n_bases, int k)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n_seqs) return;
+	const u64 a = seq_off(offs, i, n_bases), b = seq_off(offs, i + 1, n_bases), len = b > a ? b - a : 0;
+	const u64 nw = len >= (u64)k ? len - (u64)k + 1 : 0;
+	SeqSummary *r = rec + i;
+	r->n_windows = nw;
+	if (r->mn == INT_MAX) r->mn = r->mx = -1;
+	if (r->first_below == ~0ULL) r->first_below = r->last_below = nw;
+}
+
+// one window (index idx inside its sequence) into its record: the listed windows, which are rare
+__device__ __forceinline__ void seq_fold_one(const SeqSumDev &sd, SeqSummary *r, int ans, u64 idx)
+{
+	atomicAdd(&r->sum, (u64)ans);
+	atomicMin(&r->mn, ans);
+	atomicMax(&r->mx, ans);
+	for (int j = 0; j < sd.n_thr; j++)
+		if (ans >= sd.thr[j]) atomicAdd(&r->n_ge[j], 1ULL);
+	if (sd.n_thr > 0 && ans < sd.thr[0]) { atomicMin(&r->first_below, idx); atomicMax(&r->last_below, idx); }
+}
+
+// The clean windows of a wave into their records.  key = the lane's sequence (u, or ~0 past the piece's end): it never
+// decreases along the lanes, so the lanes of one sequence are one segment [s, e] of the wave.  act: the lane holds an answer
+// (ans >= 0), the window idx of its sequence; idx grows by one per lane inside a segment, active or not.  Counts and the
+// first / last weak window come from ballots cut to the segment; sum, min and max from a segmented shuffle reduction (after
+// step d lane i holds lanes [i, min(i + 2d - 1, e)]).  The segment's first lane then issues ONE set of atomics, and none for
+// a segment without an active lane.  Every lane of the wave calls it.
+__device__ __forceinline__ void seq_fold_wave(const SeqSumDev &sd, u64 key, bool act, int ans, u64 idx)
+{
+	const int lane = threadIdx.x & 63;
+	const u64 prev = __shfl_up(key, 1, 64);
+	const u64 heads = __ballot(lane == 0 || key != prev), am = __ballot(act);
+	u64 gm[3];
+#pragma unroll
+	for (int j = 0; j < 3; j++) gm[j] = __ballot(act && j < sd.n_thr && ans >= sd.thr[j]);
+	const int s = 63 - __clzll((long long)(heads & (~0ULL >> (63 - lane))));
+	const u64 above = lane == 63 ? 0 : heads & (~0ULL << (lane + 1));
+	const int e = above ? __ffsll((long long)above) - 2 : 63;
+	const u64 seg = (~0ULL >> (63 - e)) & (~0ULL << s);
+	u64 sum = act ? (u64)ans : 0;
+	int mn = act ? ans : INT_MAX, mx = act ? ans : -1;
+#pragma unroll
+	for (int d = 1; d < 64; d <<= 1) {
+		const u64 s2 = __shfl_down(sum, d, 64);
+		const int a = __shfl_down(mn, d, 64), b = __shfl_down(mx, d, 64);
+		if (lane + d <= e) { sum += s2; mn = a < mn ? a : mn; mx = b > mx ? b : mx; }
+	}
+	if (lane != s || !(am & seg)) return;
+	SeqSummary *r = sd.rec + (key - 1);                           // (an active lane's key is in [1, n_seqs])
+	atomicAdd(&r->sum, sum);
+	atomicMin(&r->mn, mn);
+	atomicMax(&r->mx, mx);
+#pragma unroll
+	for (int j = 0; j < 3; j++)
+		if (gm[j] & seg) atomicAdd(&r->n_ge[j], (u64)__popcll(gm[j] & seg));
+	const u64 below = sd.n_thr > 0 ? am & ~gm[0] & seg : 0;
+	if (below) {
+		atomicMin(&r->first_below, idx + (u64)(__ffsll((long long)below) - 1 - s));
+		atomicMax(&r->last_below, idx + (u64)(63 - __clzll((long long)below) - s));
+	}
+}
+
+// k_query_seq with the answers folded into sd.rec instead of stored: same tile, same windows, same answers; the listed
+// windows go to k_summarise_ascii_at.  A window outside every sequence contributes nothing.
+template <int W> __global__ __launch_bounds__(SEQ_BT) void k_summarise_seq(ModelDev md, const unsigned char *seq, u64 g0, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, SeqSumDev sd, u32 *dlist, u32 cap, u32 *dcnt)
+{
+	__shared__ unsigned char s_code[SEQ_TILE];
+	__shared__ u64 s_u[2];
+	__shared__ u64 s_key[SEQ_BT], s_idx[SEQ_BT];
+	const u64 t0 = p0 + (u64)blockIdx.x * SEQ_BT, p_end = p0 + n_win, p = t0 + threadIdx.x;
+	u64 v[W];
+	const SeqLane w = seq_tile_window<W>(md.k, seq, g0, n_bases, offs, n_seqs, t0, p_end, s_code, s_u, v);
+	const bool dirty = w.valid && w.bad, act = w.valid && !w.bad;
+	const u32 slot = wave_append_slot<u32>(dcnt, dirty);
+	if (dirty && slot < cap) dlist[slot] = (u32)(p - p0);
+	// what the reduction needs of the lane waits in LDS (each lane reads back its own words: no barrier), so that the answer
+	// has k_query_seq's registers to itself and the reduction takes the ones it leaves
+	s_key[threadIdx.x] = p < p_end ? w.u : ~0ULL;
+	s_idx[threadIdx.x] = p - w.start;
+	int ans = 0;
+	if (act) query_packed_one<W, false>(md, v, nullptr, &ans);
+	seq_fold_wave(sd, s_key[threadIdx.x], act, ans, s_idx[threadIdx.x]);
+}
+
+// the windows k_summarise_seq listed (k_query_ascii_at's loop): the window's sequence is searched again, and every window
+// issues its own atomics
+template <int W> __global__ __launch_bounds__(256) void k_summarise_ascii_at(ModelDev md, StrGeom gf, StrGeom gb, const unsigned char *seq, u64 g0, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, const u32 *dlist, u32 cap, const u32 *dcnt, u32 *dcnt_next, SeqSumDev sd)
+{
+	if (blockIdx.x == 0 && threadIdx.x == 0) *dcnt_next = 0;
+	const u32 c = *dcnt, n = c < cap ? c : cap;
+	const int L = md.k;
+	for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
+		const u64 p = p0 + dlist[i];
+		const u64 u = seq_upper(offs, 0, n_seqs + 1, p, n_bases);
+		if (p < g0 || p + (u64)L > n_bases || u < 1 || u > n_seqs) continue;   // (never for a listed window)
+		int ans = 0;
+		astr_query_one<W>(md, gf, gb, L, astr_load(seq + (p - g0), L), &ans);
+		seq_fold_one(sd, sd.rec + (u - 1), ans, p - seq_off(offs, u - 1, n_bases));
 	}
 }
 
@@ -2851,6 +2982,33 @@ void query_seq(const ModelDev &md, const unsigned char *seq, u64 n_bases, const 
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);
 	DISPATCH_W(words(md), hipLaunchKernelGGL(k_query_seq<W>, dim3((unsigned)((n_win + SEQ_BT - 1) / SEQ_BT)), dim3(SEQ_BT), 0, st, md, seq, n_bases, offs, n_seqs, p0, n_win, out, dlist, cap, dcnt));
 	DISPATCH_W(words(md), hipLaunchKernelGGL(k_query_ascii_at<W>, dim3(SEQ_DIRTY_WGS), dim3(256), 0, st, md, gf, gb, seq, n_bases, p0, (const u32 *)dlist, cap, (const u32 *)dcnt, dcnt_next, out));
+	KPROF_END(prof, st);
+}
+
+// kmx_summarise_seqs: the records before the first piece and after the last one (n_bases: where the offsets are clamped) ...
+void seq_summary_init(SeqSummary *rec, u64 n_seqs, hipStream_t st, KernelProf *prof)
+{
+	if (!n_seqs) return;
+	KPROF_BEGIN(prof, KC_QUERY, st);
+	hipLaunchKernelGGL(k_seq_summary_init, dim3((unsigned)((n_seqs + 255) / 256)), dim3(256), 0, st, rec, n_seqs);
+	KPROF_END(prof, st);
+}
+void seq_summary_finish(SeqSummary *rec, const u64 *offs, u64 n_seqs, u64 n_bases, int k, hipStream_t st, KernelProf *prof)
+{
+	if (!n_seqs) return;
+	KPROF_BEGIN(prof, KC_QUERY, st);
+	hipLaunchKernelGGL(k_seq_summary_finish, dim3((unsigned)((n_seqs + 255) / 256)), dim3(256), 0, st, rec, offs, n_seqs, n_bases, k);
+	KPROF_END(prof, st);
+}
+// ... and one piece, query_seq's two launches with its dirty list: the windows [p0, p0 + n_win), of which seq holds the bases
+// [g0, n_bases) (positions of the offsets), into sd.rec
+void summarise_seq(const ModelDev &md, const unsigned char *seq, u64 g0, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, const SeqSumDev &sd, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+{
+	if (!n_win) return;
+	KPROF_BEGIN(prof, KC_QUERY, st);
+	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_summarise_seq<W>, dim3((unsigned)((n_win + SEQ_BT - 1) / SEQ_BT)), dim3(SEQ_BT), 0, st, md, seq, g0, n_bases, offs, n_seqs, p0, n_win, sd, dlist, cap, dcnt));
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_summarise_ascii_at<W>, dim3(SEQ_DIRTY_WGS), dim3(256), 0, st, md, gf, gb, seq, g0, n_bases, offs, n_seqs, p0, (const u32 *)dlist, cap, (const u32 *)dcnt, dcnt_next, sd));
 	KPROF_END(prof, st);
 }
 

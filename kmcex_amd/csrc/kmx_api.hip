@@ -2050,15 +2050,25 @@ struct SeqChunks {
 	u64 nbytes_of(u64 c) const { const u64 c0 = c * C, cn = std::min<u64>(C, n_bases - c0); return std::min<u64>(cn + k - 1, n_bases - c0); }
 	SlotShape shape() { return SlotShape{C, off_at + 8 * (size_t)(C + 64), [this](u64 c) { return off_at + 8 * (size_t)n_bnd[c]; }}; }
 	int workers() const { return (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1)); }
-	// the pipeline's stage: bases [lo, hi) of one chunk -> dst; the task holding the chunk's last window adds its halo and boundaries
-	void stage(u64 lo, u64 hi, unsigned char *dst)
+	// bases [lo, hi) of one chunk -> dst; the task holding the chunk's last window adds the chunk's halo and gets the slot back
+	unsigned char *stage_bases(u64 lo, u64 hi, unsigned char *dst) const
 	{
 		memcpy(dst, seq + lo, hi - lo);
 		const u64 c = lo / C, c0 = c * C;
-		if (hi != c0 + std::min<u64>(C, n_bases - c0)) return;
+		if (hi != c0 + std::min<u64>(C, n_bases - c0)) return nullptr;
 		unsigned char *slot = dst - (lo - c0);
-		const u64 nbytes = nbytes_of(c), cn = hi - c0;
-		memcpy(slot + cn, seq + hi, nbytes - cn);
+		const u64 cn = hi - c0;
+		memcpy(slot + cn, seq + hi, nbytes_of(c) - cn);
+		return slot;
+	}
+	// slots of bases and halo alone (kmx_summarise_seqs: its kernels search the caller's offsets, uploaded once)
+	SlotShape bases_shape() { return SlotShape{C, (size_t)(C + 64), [this](u64 c) { return (size_t)nbytes_of(c); }}; }
+	// the pipeline's stage: the bases, and with the chunk's last window its boundaries
+	void stage(u64 lo, u64 hi, unsigned char *dst)
+	{
+		unsigned char *slot = stage_bases(lo, hi, dst);
+		if (!slot) return;
+		const u64 c = lo / C, c0 = c * C, nbytes = nbytes_of(c);
 		u64 *bnd = (u64 *)(slot + off_at), nb = 0;
 		bnd[nb++] = 0;
 		for (u64 i = (u64)(std::upper_bound(offsets, offsets + n_seqs + 1, c0) - offsets); i <= n_seqs && offsets[i] < c0 + nbytes; i++)
@@ -2105,6 +2115,101 @@ static int kmx_query_seqs_impl(kmx_model *m, const char *seq, const uint64_t *of
 			                F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
 			par ^= 1;
 		}, out, &shape);
+}
+
+// kmx_summarise_seqs: kmx_query_seqs' windows and answers, folded per sequence on the device (kernels.hip: k_summarise_seq).
+static_assert(sizeof(kmx_seq_summary) == 64 && sizeof(SeqSummary) == 64 && KMX_SEQ_THRESHOLDS == 3, "kmx_seq_summary is 64 bytes");
+static_assert(offsetof(kmx_seq_summary, min) == offsetof(SeqSummary, mn) && offsetof(kmx_seq_summary, n_ge) == offsetof(SeqSummary, n_ge) &&
+              offsetof(kmx_seq_summary, first_below) == offsetof(SeqSummary, first_below), "SeqSummary (kmx_types.h) is the layout of kmx_seq_summary");
+
+static int seq_thresholds(const int32_t *thr, int n_thr, kmx_seq_summary *recs, SeqSumDev &sd)
+{
+	if (n_thr < 0 || n_thr > KMX_SEQ_THRESHOLDS) return fail(KMX_E_ARG, "n_thr = %d, not in [0, %d]", n_thr, KMX_SEQ_THRESHOLDS);
+	if (n_thr && !thr) return fail(KMX_E_ARG, "null thresholds");
+	sd = SeqSumDev{(SeqSummary *)recs, {0, 0, 0}, n_thr};
+	for (int j = 0; j < n_thr; j++) sd.thr[j] = thr[j];
+	return KMX_OK;
+}
+
+// the handle's shared buffers for pieces / chunks of `piece` windows (the dirty list; slot_bytes != 0: the pinned slots too).
+// They only ever fail to allocate, and for this call that is KMX_E_NOMEM like its own buffers.
+static int ensure_summary_buffers(kmx_model *m, u64 piece, size_t slot_bytes)
+{
+	if (ensure_seq_scratch(m, piece) == KMX_OK && (!slot_bytes || ensure_query_feed(m, slot_bytes, 0) == KMX_OK)) return KMX_OK;
+	const std::string why = g_err;
+	return fail(KMX_E_NOMEM, "the buffers of a sequence summary could not be allocated (%s)", why.c_str());
+}
+
+static int kmx_summarise_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	SeqSumDev sd;
+	TRY(seq_thresholds(thr, n_thr, d_out, sd));
+	if (!n_seqs) return KMX_OK;
+	if (!d_offsets || !d_out || (n_bases && !d_seq)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece;
+	TRY(ensure_summary_buffers(m, piece, 0));
+	auto &F = m->qfeed;
+	kmxk::seq_summary_init(sd.rec, n_seqs, m->stream, &m->prof);
+	int par = 0;
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1)
+		kmxk::summarise_seq(m->md, (const unsigned char *)d_seq, 0, n_bases, (const u64 *)d_offsets, n_seqs, p0, std::min<u64>(piece, n_bases - p0), sd,
+		                    F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	kmxk::seq_summary_finish(sd.rec, (const u64 *)d_offsets, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+// The host variant: the bases go through the pinned slots like kmx_query_seqs' and nothing per base comes back.  A slot holds
+// bases and halo only: SeqChunks' rebased, deduplicated boundaries would lose the empty sequences and the true start of a
+// sequence cut by a chunk's edge, so the caller's offsets are uploaded once and chunk c's kernels work in the positions of
+// the whole input, of which they hold the bases [c * C, c * C + nbytes).  The records stay on the device until the end.
+static int kmx_summarise_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, const int32_t *thr, int n_thr, kmx_seq_summary *out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	SeqSumDev sd;
+	TRY(seq_thresholds(thr, n_thr, nullptr, sd));
+	if (!n_seqs) return KMX_OK;
+	TRY(check_offsets(offsets, n_seqs));
+	if (!out) return fail(KMX_E_ARG, "null argument");
+	const u64 n_bases = offsets[n_seqs];
+	if (!n_bases) {
+		for (u64 i = 0; i < n_seqs; i++) out[i] = kmx_seq_summary{0, 0, -1, -1, {0, 0, 0}, 0, 0};
+		return KMX_OK;
+	}
+	if (!seq) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	DevBuf<u64> d_offs;
+	DevBuf<SeqSummary> d_rec;
+	if (d_offs.alloc(n_seqs + 1) != hipSuccess || d_rec.alloc(n_seqs) != hipSuccess)
+		return fail(KMX_E_NOMEM, "device memory for the records and offsets of %llu sequences could not be allocated", (unsigned long long)n_seqs);
+	sd.rec = d_rec;
+	const u64 hook = seq_chunk_hook();
+	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, hook ? hook : kSeqChunk);
+	const SlotShape shape = sc.bases_shape();
+	TRY(ensure_summary_buffers(m, sc.C, shape.slot_bytes));
+	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });   // (d_offs and d_rec go when this returns)
+	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	kmxk::seq_summary_init(sd.rec, n_seqs, m->stream, &m->prof);
+	int par = 0;
+	auto &F = m->qfeed;
+	TRY(query_pipeline(m, n_bases, 1, sc.workers(),
+		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage_bases(lo, hi, dst); },
+		[&](int s, u64 cn, u64 c) {
+			kmxk::summarise_seq(m->md, F.d_in[s], c * sc.C, c * sc.C + sc.nbytes_of(c), d_offs, n_seqs, c * sc.C, cn, sd,
+			                    F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+			par ^= 1;
+		}, (int32_t *)nullptr, &shape));
+	kmxk::seq_summary_finish(sd.rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	HIPCHK(hipMemcpyAsync(out, d_rec.get(), n_seqs * sizeof(kmx_seq_summary), hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
 }
 
 #include "count_host.h"
@@ -2599,6 +2704,8 @@ extern "C" int kmx_query_strings(kmx_model *m, const char *const *strs, int len,
 extern "C" int kmx_query_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out) { return guarded([&] { return kmx_query_seqs_impl(m, seq, offsets, n_seqs, out); }); }
 extern "C" int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out) { return guarded([&] { return kmx_query_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_out); }); }
 extern "C" int kmx_count_begin(kmx_model *m, int k) { return guarded([&] { return kmx_count_begin_impl(m, k); }); }
+extern "C" int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, const int32_t *thr, int n_thr, kmx_seq_summary *out) { return guarded([&] { return kmx_summarise_seqs_impl(m, seq, offsets, n_seqs, thr, n_thr, out); }); }
+extern "C" int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out) { return guarded([&] { return kmx_summarise_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, n_thr, d_out); }); }
 extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }
 extern "C" int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases) { return guarded([&] { return kmx_count_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases); }); }
 extern "C" int kmx_count_finish(kmx_model *m, uint64_t *n_listed) { return guarded([&] { return kmx_count_finish_impl(m, n_listed); }); }

@@ -215,6 +215,21 @@ struct RoundProbe {
 	u32 *sink;
 };
 
+// kmx_summarise_seqs: one record per sequence, the layout of kmx_seq_summary (include/kmx.h; kmx_api.hip asserts it) ...
+struct SeqSummary {
+	u64 n_windows, sum;
+	int mn, mx;
+	u64 n_ge[3];
+	u64 first_below, last_below;
+};
+// ... and what the kernels that fold windows into the records take by value.  Between k_seq_summary_init and
+// k_seq_summary_finish a record holds mn = INT_MAX, first_below = ~0 until a window is folded in (below thr[0]).
+struct SeqSumDev {
+	SeqSummary *rec;
+	int thr[3];
+	int n_thr;
+};
+
 enum { SLOT_UNDECIDED = 0, SLOT_FAILED = 1, SLOT_INSERTED = 2, SLOT_CONTENDED = 3 };
 
 // Optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg).

@@ -29,6 +29,9 @@ void range_commit_apply(const ModelDev &, const RangeIn &, int, hipStream_t);
 void query(const ModelDev &, const u64 *, u64, int *, hipStream_t, KernelProf *, u64 *acct = nullptr);
 void query_ascii(const ModelDev &, int, const unsigned char *, int, u64, int *, hipStream_t);
 void query_seq(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void seq_summary_init(SeqSummary *, u64, hipStream_t, KernelProf *);
+void seq_summary_finish(SeqSummary *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
+void summarise_seq(const ModelDev &, const unsigned char *, u64, u64, const u64 *, u64, u64, u64, const SeqSumDev &, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
 void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
 void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
 void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);
