@@ -216,6 +216,30 @@ public:
 		return out;
 	}
 
+	// Substitution errors corrected from the k-mer spectrum (kmx_correct_seqs; the rule is in kmx.h): a window is weak when its
+	// answer is below thr, a site is tried when at least min_support windows verify it.  Returns the corrected read(s); rec, if
+	// given, receives one record per read.
+	std::string seq_correct(const std::string &seq, int thr, int min_support = 1, kmx_seq_correction *rec = 0)
+	{
+		const uint64_t off[2] = {0, (uint64_t)seq.size()};
+		std::string out(seq.size(), '\0');
+		check(kmx_correct_seqs(h_, seq.data(), off, 1, thr, min_support, &out[0], rec));
+		return out;
+	}
+	std::vector<std::string> seq_correct(const std::vector<std::string> &seqs, int thr, int min_support = 1, std::vector<kmx_seq_correction> *rec = 0)
+	{
+		std::vector<uint64_t> off(seqs.size() + 1, 0);
+		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		if (rec) rec->assign(seqs.size(), kmx_seq_correction());
+		if (!flat.empty() || !seqs.empty()) check(kmx_correct_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, &flat[0], rec && !seqs.empty() ? &(*rec)[0] : 0));
+		std::vector<std::string> out(seqs.size());
+		for (size_t i = 0; i < seqs.size(); i++) out[i] = flat.substr((size_t)off[i], seqs[i].size());
+		return out;
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -267,6 +267,45 @@ int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, u
 int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                            const int32_t *thr /* HOST, n_thr values */, int n_thr, kmx_seq_summary *d_out /* [n_seqs] */);
 
+/* Substitution errors of reads corrected from the k-mer spectrum: what kmx_query_seqs' answers are for.  Everything is
+ * decided from the answers on the INPUT bases (bit for bit those of kmx_query_seqs, dirty windows hashed byte for byte as
+ * there); no decision depends on another correction, so the result does not depend on the order of evaluation, the cut into
+ * pieces and chunks, or the variant.  Per sequence of length L: nW = max(L - k + 1, 0) windows, window p covers the bases
+ * p .. p+k-1; thr is any int32, min_support in [1, 64].
+ *   1. weak(p) = answer(p) < thr; n_weak counts these.
+ *   2. Gap closing: a window 0 < p < nW-1 that is not weak while p-1 and p+1 are weak (judged on weak, not on closed flags)
+ *      counts as weak for run forming (the model answers about 0.7 % of erroneous k-mers with a positive count).
+ *   3. A run [s, e] is a maximal stretch of (closed) weak windows, len = e-s+1; n_runs counts them.  hasL = s > 0,
+ *      hasR = e < nW-1.  Its sites (base b, verification windows V = [v0, v1]):
+ *        neither hasL nor hasR: none;   hasR only: b = e, V = [max(s, e-k+1), e];   hasL only: b = s+k-1, V = [s, min(e, s+k-1)];
+ *        both, len < k: none;   both, len = k: b = e, V = [s, e];
+ *        both, len > k: two: b = s+k-1, V = [s, min(s+k-1, e-k)]  and  b = e, V = [max(e-k+1, s+k), e].
+ *      A site is tried iff v1-v0+1 >= min_support; n_sites counts the tried ones.
+ *   4. The candidates of a tried site are 'A', 'C', 'G', 'T' in that order without the input byte at b (an N, IUPAC or
+ *      lowercase byte has four).  A candidate passes iff every window of V, taken from the input with only base b replaced,
+ *      answers >= thr (the answer kmx_query_ascii gives those k bytes).  Exactly one passes: the output byte at b is that
+ *      candidate, n_corrected++; more than one: n_ambiguous++; none: n_unfixable++ (byte unchanged in both).
+ *   5. Every other output byte equals the input byte.
+ * Out of scope: insertions / deletions, more than the two outer errors of a long run per call (call again on the output),
+ * quality values.                                                                                                         */
+typedef struct kmx_seq_correction {      /* one per sequence; 64 bytes, no padding */
+	uint64_t n_windows, n_weak, n_runs, n_sites, n_corrected, n_ambiguous, n_unfixable, reserved /* 0 */;
+} kmx_seq_correction;
+/* Sequences in the layout of kmx_query_seqs.  seq_out[n_bases] receives the corrected bases (seq_out == seq corrects in
+ * place; any other overlap is KMX_E_ARG), rec[n_seqs] the records (may be NULL).  KMX_E_ARG when min_support is outside
+ * [1, 64], offsets[0] != 0 or the offsets decrease, all checked before anything runs; n_seqs == 0: KMX_OK, nothing written;
+ * no bases but n_seqs > 0: all-zero records.  KMX_E_STATE before the model is built or loaded; KMX_E_NOMEM leaves the handle
+ * usable.  The bases travel as in kmx_query_seqs; the corrections come back as a sparse (position, base) list, not one byte
+ * per base.  A query-class call, timed as kernel class 6 under kmx_set_profile(m, 1).                                      */
+int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs,
+                     int32_t thr, int min_support, char *seq_out /* [n_bases] */, kmx_seq_correction *rec /* [n_seqs] or NULL */);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], d_seq_out[n_bases], d_rec[n_seqs] (or NULL); enqueued on
+ * the model's stream, returns without waiting.  d_seq_out must not overlap d_seq (KMX_E_ARG).  The offsets are not validated
+ * on the host: each is clamped into [0, n_bases] where it is read, so bad offsets give wrong output, never an access outside
+ * d_seq[0, n_bases), d_seq_out[0, n_bases), d_rec[0, n_seqs).                                                              */
+int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                         int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec /* or NULL */);
+
 /* ---- k-mer counting on the device: KMC's step of the pipeline, then KModel::init on what it lists
  * (main.cpp:137-146 runs KMC on the reads, then init on its database; kmodel.hpp:57-86).
  * The counting rule:

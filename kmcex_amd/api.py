@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "kmx_debug_pack_strings", "kmx_kernel_classes", "kmx_abi_version", "kmx_get_stats_n",
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
     "kmx_query_seqs", "kmx_query_seqs_dev", "kmx_summarise_seqs", "kmx_summarise_seqs_dev",
+    "kmx_correct_seqs", "kmx_correct_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
 
@@ -62,6 +63,8 @@ class SeqSummary(C.Structure):
 SEQ_SUMMARY_DTYPE = np.dtype([("n_windows", "<u8"), ("sum", "<u8"), ("min", "<i4"), ("max", "<i4"), ("n_ge", "<u8", (3,)),
                               ("first_below", "<u8"), ("last_below", "<u8")])
 SEQ_THRESHOLDS = 3
+# kmx_seq_correction of include/kmx.h (what KModel.seq_correct_flat returns beside the corrected bases): 8 x uint64
+SEQ_CORRECTION_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_runs", "n_sites", "n_corrected", "n_ambiguous", "n_unfixable", "reserved")])
 
 
 class RingList(C.Structure):
@@ -166,6 +169,8 @@ def load_library():
     _sig(L, "kmx_query_seqs_dev", [vp, vp, vp, u64, u64, vp])
     _sig(L, "kmx_summarise_seqs", [vp, vp, vp, u64, vp, i32, vp])
     _sig(L, "kmx_summarise_seqs_dev", [vp, vp, vp, u64, u64, vp, i32, vp])
+    _sig(L, "kmx_correct_seqs", [vp, vp, vp, u64, i32, i32, vp, vp])
+    _sig(L, "kmx_correct_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, vp, vp])
     _sig(L, "kmx_count_begin", [vp, i32])
     _sig(L, "kmx_count_seqs", [vp, vp, vp, u64])
     _sig(L, "kmx_count_seqs_dev", [vp, vp, vp, u64, u64])
@@ -534,6 +539,41 @@ class KModel:
         wait); thr is a host sequence, read during the call"""
         t = np.ascontiguousarray(thr, dtype=np.int32).reshape(-1)
         _chk(self.L.kmx_summarise_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, t.ctypes.data if t.size else None, t.size, d_out_ptr))
+
+    def seq_correct_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, min_support: int = 1):
+        """kmx_correct_seqs: substitution errors corrected from the k-mer spectrum (the rule: include/kmx.h) -> (uint8 corrected
+        bases [n_bases], SEQ_CORRECTION_DTYPE records [n_seqs]); a window is weak when its answer is below thr, a site is tried
+        when at least min_support windows verify it."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        n_bases = int(offsets[-1])
+        if n_bases > buf.size:
+            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        out = np.empty(n_bases, dtype=np.uint8)
+        rec = np.zeros(offsets.size - 1, dtype=SEQ_CORRECTION_DTYPE)
+        _chk(self.L.kmx_correct_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, int(thr), int(min_support),
+                                     out.ctypes.data, rec.ctypes.data))
+        return out, rec
+
+    def seq_correct(self, seqs, thr: int, min_support: int = 1):
+        """seq_correct_flat for a str / bytes sequence (-> (bytes, record)) or a list of them (-> (list of bytes, records))"""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        out, rec = self.seq_correct_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr, min_support)
+        fixed = [out[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(raw))]
+        return (fixed[0], rec[0]) if single else (fixed, rec)
+
+    def seq_correct_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int,
+                        d_seq_out_ptr: int, d_rec_ptr: int = 0) -> None:
+        """kmx_correct_seqs_dev: device buffers (d_seq_out: n_bases bytes, not overlapping d_seq; d_rec: n_seqs records of 64
+        bytes, or 0), enqueued on the model's stream (no wait)"""
+        _chk(self.L.kmx_correct_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, int(thr), int(min_support),
+                                         d_seq_out_ptr, d_rec_ptr or None))
 
     # ---- k-mer counting on the device (KMC's step, then init on its listing: main.cpp:137-146)
     def init_reads(self, path: str, k: int) -> None:

@@ -229,6 +229,9 @@ struct kmx_model {
 		// kmx_query_seqs*: the positions of one piece's windows that are not uppercase ACGT + two counters (one per piece
 		// parity); at most one piece of windows, whatever the length of the input
 		DevBuf<u32> d_seq_list, d_seq_cnt;
+		// kmx_correct_seqs*: one bit per window of a piece and its halos, one byte per workgroup of the piece
+		DevBuf<u64> d_corr_bits;
+		DevBuf<unsigned char> d_corr_flags;
 		Event ev_in[S], ev_k[S], ev_out[S];
 		Stream to_dev, to_host;
 	} qfeed;
@@ -1838,6 +1841,12 @@ struct SlotShape {
 	u64 chunk;
 	size_t slot_bytes;
 	std::function<size_t(u64)> in_bytes;
+	// a caller whose kernels leave something else than one answer per item in d_out[slot] (kmx_correct_seqs: a sparse list):
+	// int32 words a slot's output takes, the bytes of it copied back with every chunk, and what the driving thread does with
+	// h_out[slot] once chunk c's copy has arrived (non-zero: the call fails with that code)
+	size_t answers = 0;
+	size_t out_bytes = 0;
+	std::function<int(u64, int)> consume;
 };
 
 // n items of item_bytes each through the pipeline.  stage(worker, lo, hi, dst): items [lo, hi) -> dst (their place in the
@@ -1853,7 +1862,7 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 	C = std::min<u64>(C, (n + kQuerySub - 1) & ~(kQuerySub - 1));
 	if (shape) C = shape->chunk;
 	const u64 nc = (n + C - 1) / C;
-	TRY(ensure_query_feed(m, shape ? shape->slot_bytes : (size_t)C * item_bytes, out ? (size_t)C : 0));
+	TRY(ensure_query_feed(m, shape ? shape->slot_bytes : (size_t)C * item_bytes, out ? (size_t)C : (shape ? shape->answers : 0)));
 	auto count_of = [&](u64 c) { return std::min<u64>(C, n - c * C); };
 	auto subs_of = [&](u64 c) { return (count_of(c) + kQuerySub - 1) / kQuerySub; };
 	auto enqueue = [&](u64 c) -> bool {
@@ -1864,12 +1873,14 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 		if constexpr (std::is_invocable_v<LAUNCH, int, u64, u64>) launch(s, cn, c);
 		else launch(s, cn);
 		return hipEventRecord(F.ev_k[s], m->stream) == hipSuccess && hipStreamWaitEvent(F.to_host, F.ev_k[s], 0) == hipSuccess &&
-		       (!out || hipMemcpyAsync(F.h_out[s], F.d_out[s], cn * 4, hipMemcpyDeviceToHost, F.to_host) == hipSuccess) && hipEventRecord(F.ev_out[s], F.to_host) == hipSuccess;
+		       (!out || hipMemcpyAsync(F.h_out[s], F.d_out[s], cn * 4, hipMemcpyDeviceToHost, F.to_host) == hipSuccess) &&
+		       (!(shape && shape->out_bytes) || hipMemcpyAsync(F.h_out[s], F.d_out[s], shape->out_bytes, hipMemcpyDeviceToHost, F.to_host) == hipSuccess) && hipEventRecord(F.ev_out[s], F.to_host) == hipSuccess;
 	};
 	if (nc == 1 && T == 1) {                                      // a handful of strings: no threads
 		stage(0, 0, n, F.h_in[0]);
 		if (!enqueue(0) || hipEventSynchronize(F.ev_out[0]) != hipSuccess) return fail(KMX_E_NODEVICE, "query failed");
 		if (out) memcpy(out, F.h_out[0], n * 4);
+		if (shape && shape->consume) TRY(shape->consume(0, 0));
 		return KMX_OK;
 	}
 	// phase p = the pack tasks of chunk p, then the copy-out tasks of chunk p - 2
@@ -1927,6 +1938,7 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 		hipError_t e;
 		while ((e = hipEventQuery(F.ev_out[c % F.S])) == hipErrorNotReady) std::this_thread::yield();
 		if (e != hipSuccess && !rc) rc = fail(KMX_E_NODEVICE, "query failed");
+		if (!rc && shape && shape->consume) rc = shape->consume(c, (int)(c % F.S));
 		if (rc) abort = true;
 		ready[c].store(1, std::memory_order_release);
 	};
@@ -2209,6 +2221,136 @@ static int kmx_summarise_seqs_impl(kmx_model *m, const char *seq, const uint64_t
 	HIPCHK(hipMemcpyAsync(out, d_rec.get(), n_seqs * sizeof(kmx_seq_summary), hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------ correction along sequences
+// kmx_correct_seqs: substitution errors corrected from the answers of kmx_query_seqs (the rule: include/kmx.h; the kernels:
+// correct_kernels.h).  A piece of windows needs the weak bits of KMX_CORR_HALO(k) windows beyond each end, so its kernels
+// answer [p0 - halo, p0 + n + halo) and decide the sites of [p0, p0 + n): every run edge belongs to exactly one piece, and
+// positions, run shapes and records are those of the whole input whatever the cut.
+static_assert(sizeof(kmx_seq_correction) == 64 && sizeof(SeqCorrection) == 64, "kmx_seq_correction is 64 bytes");
+static_assert(offsetof(kmx_seq_correction, n_weak) == offsetof(SeqCorrection, n_weak) && offsetof(kmx_seq_correction, n_unfixable) == offsetof(SeqCorrection, n_unfixable),
+              "SeqCorrection (kmx_types.h) is the layout of kmx_seq_correction");
+
+static bool ranges_overlap(const void *a, const void *b, u64 n)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return x < y + n && y < x + n;
+}
+
+// the handle's buffers for pieces / chunks of `piece` windows: dirty list and weak bits with both halos, a flag per
+// workgroup (slot_bytes != 0: the pinned slots too, `answers` int32 words of output each).  Failing is KMX_E_NOMEM.
+static int ensure_correct_buffers(kmx_model *m, u64 piece, size_t slot_bytes, size_t answers)
+{
+	auto &F = m->qfeed;
+	const u64 ext = piece + 2 * KMX_CORR_HALO(64);
+	if (ensure_seq_scratch(m, ext) == KMX_OK && F.d_corr_bits.ensure((size_t)((ext + 255) / 256 * 4), m->stream) == hipSuccess &&
+	    F.d_corr_flags.ensure((size_t)((piece + 255) / 256), m->stream) == hipSuccess && (!slot_bytes || ensure_query_feed(m, slot_bytes, answers) == KMX_OK)) return KMX_OK;
+	return fail(KMX_E_NOMEM, "the buffers of a sequence correction could not be allocated");
+}
+
+static int kmx_correct_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
+	if (!n_seqs) return KMX_OK;
+	if (!d_offsets || (n_bases && (!d_seq || !d_seq_out))) return fail(KMX_E_ARG, "null argument");
+	if (n_bases && ranges_overlap(d_seq, d_seq_out, n_bases)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece, H = KMX_CORR_HALO(m->k);
+	TRY(ensure_correct_buffers(m, piece, 0, 0));
+	auto &F = m->qfeed;
+	kmxk::seq_correction_init((SeqCorrection *)d_rec, (const u64 *)d_offsets, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	if (n_bases) HIPCHK(hipMemcpyAsync(d_seq_out, d_seq, n_bases, hipMemcpyDeviceToDevice, m->stream));
+	const CorrDev cd{(SeqCorrection *)d_rec, (unsigned char *)d_seq_out, nullptr, 0, thr, min_support};
+	int par = 0;
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1) {
+		const u64 cn = std::min<u64>(piece, n_bases - p0);
+		kmxk::correct_piece(m->md, (const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets, n_seqs, p0, cn, p0 > H ? p0 - H : 0, std::min<u64>(p0 + cn + H, n_bases),
+		                    F.d_corr_bits, cd, F.d_corr_flags, F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	}
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+// The host variant: the bases go through the pinned slots with a halo on BOTH sides (a slot = kCorrPad bytes, of which the
+// last min(halo, c0) hold the bases before the chunk, then the chunk and halo + k - 1 bases behind it); the caller's offsets
+// are uploaded once and the kernels work in the positions of the whole input (DESIGN.md 3.7's chunk trap).  What comes back
+// is sparse: chunk c's kernels append (position - c0) << 2 | code to a list in d_out[slot], sized for the worst case of a
+// chunk (a tried site needs a run edge, runs lie >= 2 windows apart and two sites need a run longer than k: fewer than one
+// site per 3 windows; the list takes cn / 2 + 8); the count and the first cn / 16 + 16 entries travel with every chunk, the
+// rare longer list is fetched when its count arrives.  The corrections are applied to seq_out after the last chunk, so an
+// in-place call never feeds a corrected base to a later chunk.
+static const size_t kCorrPad = 256;
+static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, char *seq_out, kmx_seq_correction *rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
+	if (!n_seqs) return KMX_OK;
+	TRY(check_offsets(offsets, n_seqs));
+	const u64 n_bases = offsets[n_seqs];
+	if (!n_bases) {
+		if (rec) memset(rec, 0, n_seqs * sizeof *rec);
+		return KMX_OK;
+	}
+	if (!seq || !seq_out) return fail(KMX_E_ARG, "null argument");
+	if (seq_out != seq && ranges_overlap(seq, seq_out, n_bases)) return fail(KMX_E_ARG, "seq_out overlaps seq (only seq_out == seq is allowed)");
+	HIPCHK(hipSetDevice(m->device));
+	DevBuf<u64> d_offs;
+	DevBuf<SeqCorrection> d_rec;
+	if (d_offs.alloc(n_seqs + 1) != hipSuccess || (rec && d_rec.alloc(n_seqs) != hipSuccess))
+		return fail(KMX_E_NOMEM, "device memory for the records and offsets of %llu sequences could not be allocated", (unsigned long long)n_seqs);
+	const u64 hook = seq_chunk_hook(), C = std::min<u64>(hook ? hook : kSeqChunk, n_bases), k = (u64)m->k, H = KMX_CORR_HALO(k);
+	const u32 fix_cap = (u32)(C / 2 + 8), eager = (u32)std::min<u64>(C / 16 + 16, fix_cap);
+	auto g1_of = [&](u64 c0, u64 cn) { return std::min<u64>(c0 + cn + H + k - 1, n_bases); };
+	SlotShape shape{C, kCorrPad + (size_t)(C + H + k + 8), [&](u64 c) { const u64 c0 = c * C; return kCorrPad + (size_t)(g1_of(c0, std::min<u64>(C, n_bases - c0)) - c0); }};
+	shape.answers = 2 + (size_t)fix_cap;
+	shape.out_bytes = (2 + (size_t)eager) * 4;
+	TRY(ensure_correct_buffers(m, C, shape.slot_bytes, shape.answers));
+	auto &F = m->qfeed;
+	std::vector<u64> fixes;                                        // position << 2 | code
+	shape.consume = [&](u64 c, int s) -> int {
+		u32 *h = (u32 *)F.h_out[s].get();
+		const u32 n = h[0];
+		if (n > fix_cap) return fail(KMX_E_STATE, "the correction list of a chunk overflowed (%u > %u)", n, fix_cap);
+		if (n > eager && (hipMemcpyAsync(h + 2 + eager, (u32 *)F.d_out[s].get() + 2 + eager, (size_t)(n - eager) * 4, hipMemcpyDeviceToHost, F.to_host) != hipSuccess ||
+		                  hipStreamSynchronize(F.to_host) != hipSuccess)) return fail(KMX_E_NODEVICE, "D2H copy failed");
+		try { for (u32 i = 0; i < n; i++) fixes.push_back(((c * C + (h[2 + i] >> 2)) << 2) | (h[2 + i] & 3)); }
+		catch (...) { return fail(KMX_E_NOMEM, "out of host memory"); }
+		return KMX_OK;
+	};
+	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });   // (d_offs and d_rec go when this returns)
+	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	kmxk::seq_correction_init(d_rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	CorrDev cd{d_rec, nullptr, nullptr, fix_cap, thr, min_support};
+	int par = 0;
+	const int T = (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1));
+	TRY(query_pipeline(m, n_bases, 1, T,
+		[&](int, u64 lo, u64 hi, unsigned char *dst) {
+			const u64 c0 = lo / C * C, cn = std::min<u64>(C, n_bases - c0);
+			unsigned char *slot = dst - (lo - c0);
+			memcpy(dst + kCorrPad, seq + lo, hi - lo);
+			if (seq_out != seq) memcpy(seq_out + lo, seq + lo, hi - lo);
+			if (lo == c0) { const u64 hl = std::min<u64>(H, c0); memcpy(slot + kCorrPad - hl, seq + c0 - hl, hl); }
+			if (hi == c0 + cn) memcpy(slot + kCorrPad + cn, seq + hi, g1_of(c0, cn) - hi);
+		},
+		[&](int s, u64 cn, u64 c) {
+			const u64 c0 = c * C, hl = std::min<u64>(H, c0);
+			(void)hipMemsetAsync(F.d_out[s], 0, 8, m->stream);
+			cd.fix = (u32 *)F.d_out[s].get();
+			kmxk::correct_piece(m->md, F.d_in[s] + (kCorrPad - hl), c0 - hl, g1_of(c0, cn), n_bases, d_offs, n_seqs, c0, cn, c0 - hl, std::min<u64>(c0 + cn + H, n_bases),
+			                    F.d_corr_bits, cd, F.d_corr_flags, F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+			par ^= 1;
+		}, (int32_t *)nullptr, &shape));
+	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	HIPCHK(hipGetLastError());
+	for (u64 f : fixes) seq_out[f >> 2] = "ACGT"[f & 3];
 	return KMX_OK;
 }
 
@@ -2706,6 +2848,8 @@ extern "C" int kmx_query_seqs_dev(kmx_model *m, const char *d_seq, const uint64_
 extern "C" int kmx_count_begin(kmx_model *m, int k) { return guarded([&] { return kmx_count_begin_impl(m, k); }); }
 extern "C" int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, const int32_t *thr, int n_thr, kmx_seq_summary *out) { return guarded([&] { return kmx_summarise_seqs_impl(m, seq, offsets, n_seqs, thr, n_thr, out); }); }
 extern "C" int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out) { return guarded([&] { return kmx_summarise_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, n_thr, d_out); }); }
+extern "C" int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, char *seq_out, kmx_seq_correction *rec) { return guarded([&] { return kmx_correct_seqs_impl(m, seq, offsets, n_seqs, thr, min_support, seq_out, rec); }); }
+extern "C" int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec) { return guarded([&] { return kmx_correct_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, d_seq_out, d_rec); }); }
 extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }
 extern "C" int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases) { return guarded([&] { return kmx_count_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases); }); }
 extern "C" int kmx_count_finish(kmx_model *m, uint64_t *n_listed) { return guarded([&] { return kmx_count_finish_impl(m, n_listed); }); }

@@ -230,6 +230,23 @@ struct SeqSumDev {
 	int n_thr;
 };
 
+// kmx_correct_seqs: one record per sequence, the layout of kmx_seq_correction (include/kmx.h; kmx_api.hip asserts it) ...
+struct SeqCorrection {
+	u64 n_windows, n_weak, n_runs, n_sites, n_corrected, n_ambiguous, n_unfixable, reserved;
+};
+// ... and where the kernels of one piece leave what they decide (correct_kernels.h).  A corrected byte goes to out[b]
+// (positions of the offsets; the device variant) or, as (b - p0) << 2 | code, to fix[2 + fix[0]++] (the host variant:
+// fix[0] is zero before the piece; the host sizes fix_cap for the worst case of a piece, checks the count it reads back and
+// fails the call if it ever exceeds fix_cap, so an entry the kernel had no room for is never lost silently).  rec may be null.
+struct CorrDev {
+	SeqCorrection *rec;
+	unsigned char *out;
+	u32 *fix;
+	u32 fix_cap;
+	int thr, min_support;
+};
+#define KMX_CORR_HALO(k) (2 * (k) + 2)         // windows of weak bits a piece needs beyond each of its ends
+
 enum { SLOT_UNDECIDED = 0, SLOT_FAILED = 1, SLOT_INSERTED = 2, SLOT_CONTENDED = 3 };
 
 // Optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg).
