@@ -240,6 +240,36 @@ public:
 		return out;
 	}
 
+	// Seeds extended to the right along the unique path of k-mers answered >= thr (kmx_extend_seqs; the rule is in kmx.h):
+	// at most max_ext bases each, ties broken by a lookahead of `depth` (0 ... 3).  Returns the appended bases; rec, if given,
+	// receives one record per seed (why the walk stopped, the counts along it).
+	std::string seq_extend(const std::string &seed, int thr, int max_ext, int depth = 2, kmx_seq_extension *rec = 0)
+	{
+		const uint64_t off[2] = {0, (uint64_t)seed.size()};
+		std::string ext(max_ext > 0 ? (size_t)max_ext : 1, '\0');
+		kmx_seq_extension r;
+		check(kmx_extend_seqs(h_, seed.data(), off, 1, thr, max_ext, depth, &ext[0], &r));
+		if (rec) *rec = r;
+		ext.resize(r.n_ext);
+		return ext;
+	}
+	std::vector<std::string> seq_extend(const std::vector<std::string> &seeds, int thr, int max_ext, int depth = 2, std::vector<kmx_seq_extension> *rec = 0)
+	{
+		std::vector<uint64_t> off(seeds.size() + 1, 0);
+		for (size_t i = 0; i < seeds.size(); i++) off[i + 1] = off[i] + seeds[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seeds.size(); i++) flat += seeds[i];
+		const size_t row = max_ext > 0 ? (size_t)max_ext : 1;
+		std::vector<char> ext(seeds.size() * row + 1);
+		std::vector<kmx_seq_extension> r(seeds.size());
+		if (!seeds.empty()) check(kmx_extend_seqs(h_, flat.data(), off.data(), seeds.size(), thr, max_ext, depth, &ext[0], &r[0]));
+		std::vector<std::string> out(seeds.size());
+		for (size_t i = 0; i < seeds.size(); i++) out[i].assign(&ext[i * row], r[i].n_ext);
+		if (rec) rec->swap(r);
+		return out;
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

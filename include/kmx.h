@@ -306,6 +306,61 @@ int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uin
 int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                          int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec /* or NULL */);
 
+/* Seeds extended to the right along unique k-mer paths: a walk through the de Bruijn graph the model implicitly holds (the
+ * primitive of unitig construction, gap filling, seed-and-extend).  occ(s) is the answer kmx_query_ascii gives the k bytes s;
+ * every string a walk asks about is uppercase ACGT, so it is also kmx_query_packed of its packed form.  The result is a
+ * function of those answers alone and independent per seed: it does not depend on the batch, the cut into chunks and
+ * launches, or the variant.  thr is any int32, max_ext in [1, KMX_EXT_MAX_EXT_LIMIT], depth in [0, KMX_EXT_MAX_DEPTH].
+ * The model answers some absent k-mers with a positive count; without a tie-break a walk meets such a neighbour within a
+ * dozen bases or so and stops.  The tie-break is a lookahead, defined as an existence statement so that no order of evaluation shows:
+ *   sup_f(x, 0) is true; sup_f(x, d) holds iff some c in ACGT has occ(x[1:] + c) >= thr and sup_f(x[1:] + c, d - 1);
+ *   sup_b(x, d) is its mirror image with c + x[:-1].
+ * Per seed i (sequences in the layout of kmx_query_seqs):
+ *   1. A seed shorter than k, or whose last k bytes hold anything but uppercase ACGT: stop = KMX_EXT_BAD_SEED, n_ext = 0,
+ *      seed_occ = -1.  Otherwise cur = first = the last k bytes and seed_occ = occ(first); the seed need not be solid.
+ *   2. Step: a_c = occ(cur[1:] + c) and b_d = occ(d + cur[1:]) for c, d in A, C, G, T (the successors of cur and the
+ *      predecessors of the k-mer the walk would move to).  S = {c : a_c >= thr}; if |S| > 1 and depth > 0,
+ *      S = {c in S : sup_f(cur[1:] + c, depth)}.  |S| == 0: stop = KMX_EXT_DEAD_END; |S| > 1: stop = KMX_EXT_BRANCH.
+ *      Otherwise P = {d != cur[0] : b_d >= thr}; if P is not empty and depth > 0, P = {d in P : sup_b(d + cur[1:], depth)}.
+ *      P not empty: stop = KMX_EXT_JOIN.  (DEAD_END and BRANCH come before JOIN.)
+ *   3. nxt = cur[1:] + c for the one c in S.  nxt == first: stop = KMX_EXT_CYCLE, nothing is appended.
+ *   4. Append c: n_ext++; sum_occ, min_occ, max_occ take a_c; n_lookahead++ if this step evaluated sup_f or sup_b;
+ *      cur = nxt; n_ext == max_ext: stop = KMX_EXT_MAX_EXT.  Otherwise step again.
+ * ext[i * max_ext .. i * max_ext + n_ext) holds the appended bases, the rest of the row is 0.
+ * Leftward extension is rightward extension of the reverse complement (the Python facade's left=True does that on the
+ * host); the ABI is rightward only.  For k > 32 the reference canonicalises through one 64-bit word, so the two strands of a
+ * k-mer need not get the same answer there and a leftward walk need not mirror the rightward one.
+ * Out of scope: marking k-mers as visited across seeds (the result would depend on the order), bubble popping, tip removal
+ * beyond the tie-break.                                                                                                    */
+#define KMX_EXT_DEAD_END 1
+#define KMX_EXT_BRANCH 2
+#define KMX_EXT_JOIN 3
+#define KMX_EXT_CYCLE 4
+#define KMX_EXT_MAX_EXT 5
+#define KMX_EXT_BAD_SEED 6
+#define KMX_EXT_MAX_EXT_LIMIT 65536
+#define KMX_EXT_MAX_DEPTH 3
+typedef struct kmx_seq_extension {       /* one per seed; 32 bytes, no padding */
+	uint32_t n_ext, stop;
+	int32_t  seed_occ, min_occ, max_occ;   /* min_occ = max_occ = -1 when n_ext == 0 */
+	uint32_t n_lookahead;
+	uint64_t sum_occ;
+} kmx_seq_extension;
+/* ext[n_seqs * max_ext] receives the rows, rec[n_seqs] the records (may be NULL).  KMX_E_ARG when max_ext or depth is out of
+ * range, offsets[0] != 0 or the offsets decrease, all checked before anything runs; n_seqs == 0: KMX_OK, nothing written.
+ * KMX_E_STATE before the model is built or loaded; KMX_E_NOMEM leaves the handle usable.  Only the last k bytes of every
+ * seed cross the link; the seeds run in chunks, so the device memory for ext stays bounded.  A query-class call, timed as
+ * kernel class 6 under kmx_set_profile(m, 1).  No kernel launch walks a seed more than a bounded number of steps; walks that
+ * have not stopped are compacted and launched again.                                                                       */
+int kmx_extend_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs,
+                    int32_t thr, int max_ext, int depth, char *ext /* [n_seqs * max_ext] */, kmx_seq_extension *rec /* [n_seqs] or NULL */);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], d_ext[n_seqs * max_ext], d_rec[n_seqs] (or NULL); enqueued
+ * on the model's stream, returns without waiting (the host reads nothing back between the launches).  The offsets are not
+ * validated on the host: each is clamped into [0, n_bases] where it is read, so bad offsets give wrong walks, never an
+ * access outside d_seq[0, n_bases), d_ext[0, n_seqs * max_ext), d_rec[0, n_seqs).                                           */
+int kmx_extend_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
+                        int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec /* or NULL */);
+
 /* ---- k-mer counting on the device: KMC's step of the pipeline, then KModel::init on what it lists
  * (main.cpp:137-146 runs KMC on the reads, then init on its database; kmodel.hpp:57-86).
  * The counting rule:

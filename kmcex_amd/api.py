@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
     "kmx_query_seqs", "kmx_query_seqs_dev", "kmx_summarise_seqs", "kmx_summarise_seqs_dev",
     "kmx_correct_seqs", "kmx_correct_seqs_dev",
+    "kmx_extend_seqs", "kmx_extend_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
 
@@ -65,6 +66,11 @@ SEQ_SUMMARY_DTYPE = np.dtype([("n_windows", "<u8"), ("sum", "<u8"), ("min", "<i4
 SEQ_THRESHOLDS = 3
 # kmx_seq_correction of include/kmx.h (what KModel.seq_correct_flat returns beside the corrected bases): 8 x uint64
 SEQ_CORRECTION_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_runs", "n_sites", "n_corrected", "n_ambiguous", "n_unfixable", "reserved")])
+# kmx_seq_extension of include/kmx.h (what KModel.seq_extend_flat returns beside the rows of appended bases): 32 bytes
+SEQ_EXTENSION_DTYPE = np.dtype([("n_ext", "<u4"), ("stop", "<u4"), ("seed_occ", "<i4"), ("min_occ", "<i4"), ("max_occ", "<i4"), ("n_lookahead", "<u4"), ("sum_occ", "<u8")])
+SEQ_EXTENSION_STOPS = {1: "DEAD_END", 2: "BRANCH", 3: "JOIN", 4: "CYCLE", 5: "MAX_EXT", 6: "BAD_SEED"}
+_REVCOMP = np.arange(256, dtype=np.uint8)
+_REVCOMP[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.frombuffer(b"TGCA", dtype=np.uint8)
 
 
 class RingList(C.Structure):
@@ -171,6 +177,8 @@ def load_library():
     _sig(L, "kmx_summarise_seqs_dev", [vp, vp, vp, u64, u64, vp, i32, vp])
     _sig(L, "kmx_correct_seqs", [vp, vp, vp, u64, i32, i32, vp, vp])
     _sig(L, "kmx_correct_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, vp, vp])
+    _sig(L, "kmx_extend_seqs", [vp, vp, vp, u64, i32, i32, i32, vp, vp])
+    _sig(L, "kmx_extend_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, vp, vp])
     _sig(L, "kmx_count_begin", [vp, i32])
     _sig(L, "kmx_count_seqs", [vp, vp, vp, u64])
     _sig(L, "kmx_count_seqs_dev", [vp, vp, vp, u64, u64])
@@ -574,6 +582,48 @@ class KModel:
         bytes, or 0), enqueued on the model's stream (no wait)"""
         _chk(self.L.kmx_correct_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, int(thr), int(min_support),
                                          d_seq_out_ptr, d_rec_ptr or None))
+
+    def seq_extend_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, max_ext: int, depth: int = 2):
+        """kmx_extend_seqs: every seed walked to the right along the unique path of k-mers answered >= thr (the rule:
+        include/kmx.h) -> (uint8 appended bases [n_seqs, max_ext], 0 behind the n_ext of a row; SEQ_EXTENSION_DTYPE records
+        [n_seqs]).  depth 0 ... 3 is the lookahead that breaks the ties the model's false positives cause."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        if int(offsets[-1]) > buf.size:
+            raise KmxError(-1, f"offsets end at {int(offsets[-1])}, past the {buf.size} bases given")
+        n_seqs = offsets.size - 1
+        rows = int(max_ext) if 1 <= int(max_ext) <= 65536 else 1               # (an invalid max_ext is the library's to refuse)
+        ext = np.empty((n_seqs, rows), dtype=np.uint8)
+        rec = np.zeros(n_seqs, dtype=SEQ_EXTENSION_DTYPE)
+        _chk(self.L.kmx_extend_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, n_seqs, int(thr), int(max_ext), int(depth),
+                                    ext.ctypes.data, rec.ctypes.data))
+        return ext, rec
+
+    def seq_extend(self, seqs, thr: int, max_ext: int, depth: int = 2, left: bool = False):
+        """seq_extend_flat for a str / bytes seed (-> (bytes, record)) or a list of them (-> (list of bytes, records)): the
+        appended bases of every seed.  left=True extends to the left instead: the walk of the seed's reverse complement,
+        returned reverse-complemented again, so the result reads in the seed's direction and ends where the seed begins
+        (for k > 32 the two strands of a k-mer need not get the same answer: include/kmx.h)."""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        if left:
+            raw = [_REVCOMP[np.frombuffer(r, dtype=np.uint8)[::-1]].tobytes() for r in raw]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        ext, rec = self.seq_extend_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr, max_ext, depth)
+        out = [ext[i, :int(rec["n_ext"][i])] for i in range(len(raw))]
+        out = [(_REVCOMP[e[::-1]] if left else e).tobytes() for e in out]
+        return (out[0], rec[0]) if single else (out, rec)
+
+    def seq_extend_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, max_ext: int, depth: int,
+                       d_ext_ptr: int, d_rec_ptr: int = 0) -> None:
+        """kmx_extend_seqs_dev: device buffers (d_ext: n_seqs * max_ext bytes; d_rec: n_seqs records of 32 bytes, or 0),
+        enqueued on the model's stream (no wait)"""
+        _chk(self.L.kmx_extend_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, int(thr), int(max_ext), int(depth),
+                                        d_ext_ptr, d_rec_ptr or None))
 
     # ---- k-mer counting on the device (KMC's step, then init on its listing: main.cpp:137-146)
     def init_reads(self, path: str, k: int) -> None:

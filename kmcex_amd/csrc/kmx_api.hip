@@ -232,6 +232,9 @@ struct kmx_model {
 		// kmx_correct_seqs*: one bit per window of a piece and its halos, one byte per workgroup of the piece
 		DevBuf<u64> d_corr_bits;
 		DevBuf<unsigned char> d_corr_flags;
+		// kmx_extend_seqs*: the walks of one chunk of seeds, the two lists of live walks and their three counters
+		DevBuf<ExtWalk> d_ext_walk;
+		DevBuf<u32> d_ext_lists, d_ext_cnt;
 		Event ev_in[S], ev_k[S], ev_out[S];
 		Stream to_dev, to_host;
 	} qfeed;
@@ -2354,6 +2357,123 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 	return KMX_OK;
 }
 
+// ------------------------------------------------------------------------------------------ extension along unique paths
+// kmx_extend_seqs: seeds walked to the right through the model's de Bruijn graph (the rule: include/kmx.h; the kernels:
+// extend_kernels.h).  The seeds run in chunks of at most kExtChunk: the walk states and live lists on the handle are one
+// chunk's.  A chunk is one k_extend_init and ceil(max_ext / steps) launches of k_extend_step, all enqueued at once: the host
+// does not read the live count, a launch whose list is empty ends at once.
+static_assert(sizeof(kmx_seq_extension) == 32 && sizeof(SeqExtension) == 32 && sizeof(ExtWalk) == 64, "kmx_seq_extension is 32 bytes");
+static_assert(offsetof(kmx_seq_extension, seed_occ) == offsetof(SeqExtension, seed_occ) && offsetof(kmx_seq_extension, n_lookahead) == offsetof(SeqExtension, n_lookahead) &&
+              offsetof(kmx_seq_extension, sum_occ) == offsetof(SeqExtension, sum_occ), "SeqExtension (kmx_types.h) is the layout of kmx_seq_extension");
+static_assert(EXT_DEAD_END == KMX_EXT_DEAD_END && EXT_BRANCH == KMX_EXT_BRANCH && EXT_JOIN == KMX_EXT_JOIN && EXT_CYCLE == KMX_EXT_CYCLE && EXT_MAX_EXT == KMX_EXT_MAX_EXT &&
+              EXT_BAD_SEED == KMX_EXT_BAD_SEED, "the stop codes of kmx_types.h are those of kmx.h");
+
+static const u64 kExtChunk = u64(1) << 20;                     // seeds per chunk (64 MB of walk states)
+static const u64 kExtRowBytes = u64(1) << 28;                  // device bytes of ext rows a chunk of the host variant may take
+static const int kExtSteps = 256;                              // steps of a walk per launch
+
+// KMX_EXTEND_STEPS: steps per launch, read at every call like KMX_SEQ_CHUNK_BASES; KMX_EXTEND_CHUNK_SEEDS (test hook): seeds
+// per chunk, so a test crosses many chunk boundaries
+static int extend_steps()
+{
+	const char *e = hook_env("KMX_EXTEND_STEPS");
+	const long long x = e ? atoll(e) : 0;
+	return x > 0 ? (int)std::min<long long>(x, KMX_EXT_MAX_EXT_LIMIT) : kExtSteps;
+}
+static u64 extend_chunk_hook()
+{
+	const char *e = hook_env("KMX_EXTEND_CHUNK_SEEDS");
+	const long long x = e ? atoll(e) : 0;
+	return x > 0 ? std::min<u64>((u64)x, kExtChunk) : 0;
+}
+
+static int extend_args(int max_ext, int depth)
+{
+	if (max_ext < 1 || max_ext > KMX_EXT_MAX_EXT_LIMIT) return fail(KMX_E_ARG, "max_ext = %d, not in [1, %d]", max_ext, KMX_EXT_MAX_EXT_LIMIT);
+	if (depth < 0 || depth > KMX_EXT_MAX_DEPTH) return fail(KMX_E_ARG, "depth = %d, not in [0, %d]", depth, KMX_EXT_MAX_DEPTH);
+	return KMX_OK;
+}
+
+// (caller holds m->query_mu) the handle's buffers for chunks of n seeds.  Failing is KMX_E_NOMEM.
+static int ensure_extend_buffers(kmx_model *m, u64 n)
+{
+	auto &F = m->qfeed;
+	if (F.d_ext_walk.ensure((size_t)n, m->stream) == hipSuccess && F.d_ext_lists.ensure((size_t)(2 * n), m->stream) == hipSuccess && F.d_ext_cnt.ensure(3, m->stream) == hipSuccess) return KMX_OK;
+	return fail(KMX_E_NOMEM, "the walk states of %llu seeds could not be allocated", (unsigned long long)n);
+}
+
+static int kmx_extend_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	TRY(extend_args(max_ext, depth));
+	if (!n_seqs) return KMX_OK;
+	if (!d_offsets || !d_ext || (n_bases && !d_seq)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 hook = extend_chunk_hook(), C = std::min<u64>(hook ? hook : kExtChunk, n_seqs);
+	TRY(ensure_extend_buffers(m, C));
+	auto &F = m->qfeed;
+	HIPCHK(hipMemsetAsync(d_ext, 0, (size_t)(n_seqs * (u64)max_ext), m->stream));
+	const int steps = extend_steps();
+	for (u64 s0 = 0; s0 < n_seqs; s0 += C) {
+		const u64 cn = std::min<u64>(C, n_seqs - s0);
+		const ExtDev xd{F.d_ext_walk, d_rec ? (SeqExtension *)d_rec + s0 : nullptr, (unsigned char *)d_ext + s0 * (u64)max_ext, thr, (u32)max_ext, depth};
+		kmxk::extend_walks(m->md, (const unsigned char *)d_seq, n_bases, (const u64 *)d_offsets + s0, (u32)cn, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
+	}
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+// The host variant: of every seed only its last min(length, k) bytes are staged (pinned) and sent, with offsets of their own,
+// so a seed shorter than k is still one on the device; a chunk's rows and records come back before the next chunk is staged.
+// A chunk holds as many seeds as keep its rows within kExtRowBytes.
+static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int max_ext, int depth, char *ext, kmx_seq_extension *rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	TRY(extend_args(max_ext, depth));
+	if (!n_seqs) return KMX_OK;
+	TRY(check_offsets(offsets, n_seqs));
+	if (!ext || (offsets[n_seqs] && !seq)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 k = (u64)m->k, hook = extend_chunk_hook();
+	const u64 C = std::min<u64>(hook ? hook : std::min<u64>(kExtChunk, std::max<u64>(1, kExtRowBytes / (u64)max_ext)), n_seqs);
+	TRY(ensure_extend_buffers(m, C));
+	auto &F = m->qfeed;
+	PinBuf<unsigned char> h_tail;
+	PinBuf<u64> h_offs;
+	DevBuf<unsigned char> d_tail, d_rows;
+	DevBuf<u64> d_offs;
+	DevBuf<SeqExtension> d_rec;
+	if (h_tail.alloc((size_t)(C * k)) != hipSuccess || h_offs.alloc((size_t)(C + 1)) != hipSuccess || d_tail.alloc((size_t)(C * k)) != hipSuccess || d_rows.alloc((size_t)(C * (u64)max_ext)) != hipSuccess ||
+	    d_offs.alloc((size_t)(C + 1)) != hipSuccess || (rec && d_rec.alloc((size_t)C) != hipSuccess))
+		return fail(KMX_E_NOMEM, "the buffers of a chunk of %llu seeds could not be allocated", (unsigned long long)C);
+	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });   // (the chunk's buffers go when this returns)
+	const int steps = extend_steps();
+	for (u64 s0 = 0; s0 < n_seqs; s0 += C) {
+		const u64 cn = std::min<u64>(C, n_seqs - s0);
+		u64 t = 0;
+		h_offs[0] = 0;
+		for (u64 i = 0; i < cn; i++) {
+			const u64 b = offsets[s0 + i + 1], take = std::min<u64>(b - offsets[s0 + i], k);
+			memcpy(h_tail + t, seq + (b - take), take);
+			h_offs[i + 1] = t += take;
+		}
+		if (t) HIPCHK(hipMemcpyAsync(d_tail, h_tail, t, hipMemcpyHostToDevice, m->stream));
+		HIPCHK(hipMemcpyAsync(d_offs, h_offs, (cn + 1) * 8, hipMemcpyHostToDevice, m->stream));
+		HIPCHK(hipMemsetAsync(d_rows, 0, (size_t)(cn * (u64)max_ext), m->stream));
+		const ExtDev xd{F.d_ext_walk, d_rec, d_rows, thr, (u32)max_ext, depth};
+		kmxk::extend_walks(m->md, d_tail, t, d_offs, (u32)cn, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
+		HIPCHK(hipGetLastError());
+		HIPCHK(hipMemcpyAsync(ext + s0 * (u64)max_ext, d_rows.get(), (size_t)(cn * (u64)max_ext), hipMemcpyDeviceToHost, m->stream));
+		if (rec) HIPCHK(hipMemcpyAsync(rec + s0, d_rec.get(), cn * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+		HIPCHK(hipStreamSynchronize(m->stream));
+	}
+	return KMX_OK;
+}
+
 #include "count_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
@@ -2850,6 +2970,8 @@ extern "C" int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t 
 extern "C" int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out) { return guarded([&] { return kmx_summarise_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, n_thr, d_out); }); }
 extern "C" int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, char *seq_out, kmx_seq_correction *rec) { return guarded([&] { return kmx_correct_seqs_impl(m, seq, offsets, n_seqs, thr, min_support, seq_out, rec); }); }
 extern "C" int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec) { return guarded([&] { return kmx_correct_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, d_seq_out, d_rec); }); }
+extern "C" int kmx_extend_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int max_ext, int depth, char *ext, kmx_seq_extension *rec) { return guarded([&] { return kmx_extend_seqs_impl(m, seq, offsets, n_seqs, thr, max_ext, depth, ext, rec); }); }
+extern "C" int kmx_extend_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec) { return guarded([&] { return kmx_extend_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, max_ext, depth, d_ext, d_rec); }); }
 extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }
 extern "C" int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases) { return guarded([&] { return kmx_count_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases); }); }
 extern "C" int kmx_count_finish(kmx_model *m, uint64_t *n_listed) { return guarded([&] { return kmx_count_finish_impl(m, n_listed); }); }

@@ -247,6 +247,31 @@ struct CorrDev {
 };
 #define KMX_CORR_HALO(k) (2 * (k) + 2)         // windows of weak bits a piece needs beyond each of its ends
 
+// kmx_extend_seqs: one record per seed, the layout of kmx_seq_extension (include/kmx.h; kmx_api.hip asserts it) ...
+struct SeqExtension {
+	u32 n_ext, stop;
+	int seed_occ, min_occ, max_occ;
+	u32 n_lookahead;
+	u64 sum_occ;
+};
+enum { EXT_DEAD_END = 1, EXT_BRANCH = 2, EXT_JOIN = 3, EXT_CYCLE = 4, EXT_MAX_EXT = 5, EXT_BAD_SEED = 6 };   // KMX_EXT_* of kmx.h
+// ... a walk between two launches (extend_kernels.h): the k-mer it stands on, the seed's k-mer, the record so far
+// (one word each for k <= 32) ...
+struct ExtWalk {
+	u64 cur[2], first[2];
+	SeqExtension r;
+};
+// ... and what the kernels of one chunk of seeds take by value: walk, rec (may be null) and ext (rows of max_ext bytes, zero
+// on entry) are the chunk's, indexed by the seed's place in it
+struct ExtDev {
+	ExtWalk *walk;
+	SeqExtension *rec;
+	unsigned char *ext;
+	int thr;
+	u32 max_ext;
+	int depth;
+};
+
 enum { SLOT_UNDECIDED = 0, SLOT_FAILED = 1, SLOT_INSERTED = 2, SLOT_CONTENDED = 3 };
 
 // Optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg).

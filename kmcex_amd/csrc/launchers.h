@@ -34,6 +34,7 @@ void seq_summary_finish(SeqSummary *, const u64 *, u64, u64, int, hipStream_t, K
 void summarise_seq(const ModelDev &, const unsigned char *, u64, u64, const u64 *, u64, u64, u64, const SeqSumDev &, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
 void seq_correction_init(SeqCorrection *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
 void correct_piece(const ModelDev &, const unsigned char *, u64, u64, u64, const u64 *, u64, u64, u64, u64, u64, u64 *, const CorrDev &, unsigned char *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void extend_walks(const ModelDev &, const unsigned char *, u64, const u64 *, u32, const ExtDev &, u32 *, u32 *, int, hipStream_t, KernelProf *);
 void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
 void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
 void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);

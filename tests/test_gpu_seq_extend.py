@@ -1,0 +1,329 @@
+"""kmx_extend_seqs / kmx_extend_seqs_dev: seeds walked along unique k-mer paths on the device.  Rows of appended bases and
+records must EQUAL, byte for byte, the reference rule (tests/seq_extend_ref.py) driven by the same model's kmer_to_occ_rows,
+and the digests of the oracle-made fixture: every field is an integer and a function of the model's answers, there is no
+tolerance."""
+import json
+import os
+import subprocess
+import sys
+import threading
+
+import numpy as np
+import pytest
+
+import count_reads as CR
+import seq_extend_ref as X
+import seq_reads as R
+import small_k as SK
+from common import CASE, GENOME_CASES
+from kmcex_amd import KModel, api, synth
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+GCASE = {c[0]: c for c in GENOME_CASES}
+REC = api.SEQ_EXTENSION_DTYPE
+MAX_EXT = 300
+
+
+def _genome_model(name):
+    _, k, ci, cs, nh, nb, n_bases = GCASE[name]
+    km, cnt = synth.genome_stream(n_bases, k, ci, cs)
+    m = KModel(ci, cs, nh, nb)
+    m.build_packed(k, km, cnt)
+    return m, k, ci, n_bases
+
+
+def _dev(m, buf, offsets, thr, max_ext, depth, n_bases=None, records=True):
+    """the device variant on fresh device copies; outputs pre-filled with 0xFF"""
+    import torch
+    n_seqs = len(offsets) - 1
+    d_seq = torch.from_numpy(np.ascontiguousarray(buf)).to("cuda") if len(buf) else torch.zeros(1, dtype=torch.uint8, device="cuda")
+    d_off = torch.from_numpy(np.ascontiguousarray(offsets, dtype=np.uint64).view(np.int64)).to("cuda")
+    d_ext = torch.full((max(n_seqs * max_ext, 1),), 0xFF, dtype=torch.uint8, device="cuda")
+    d_rec = torch.full((max(n_seqs, 1) * 32,), 0xFF, dtype=torch.uint8, device="cuda")
+    m.seq_extend_dev(d_seq.data_ptr(), d_off.data_ptr(), n_seqs, len(buf) if n_bases is None else n_bases, thr, max_ext, depth, d_ext.data_ptr(),
+                     d_rec.data_ptr() if records else 0)
+    torch.cuda.synchronize()
+    return d_ext.cpu().numpy()[:n_seqs * max_ext].reshape(n_seqs, max_ext), d_rec.cpu().numpy()[:n_seqs * 32].view(REC)
+
+
+def _gpu_rule(m, buf, offsets, k, thr, max_ext, depth):
+    """the reference rule over the GPU's own answers"""
+    return X.extend(buf, offsets, k, thr, max_ext, depth, lambda rows: m.kmer_to_occ_rows(rows, k, separate=False))[:2]
+
+
+def _same(got, want):
+    return got[0].shape == want[0].shape and np.array_equal(got[0], want[0]) and X.same(got[1], want[1])
+
+
+def _explain(got, want):
+    bad = np.nonzero([got[1][i].tobytes() != want[1][i].tobytes() or not np.array_equal(got[0][i], want[0][i]) for i in range(len(want[1]))])[0]
+    return f"{len(bad)} seeds differ, first {bad[:3].tolist()}: got {got[1][bad[:3]]} want {want[1][bad[:3]]}"
+
+
+def _check_both(m, buf, offsets, k, thr, max_ext, depth):
+    want = _gpu_rule(m, buf, offsets, k, thr, max_ext, depth)
+    got = m.seq_extend_flat(buf, offsets, thr, max_ext, depth)
+    assert got[0].dtype == np.uint8 and got[1].dtype == REC and got[1].shape == (len(offsets) - 1,)
+    assert _same(got, want), ("host", thr, depth, _explain(got, want))
+    got = _dev(m, buf, offsets, thr, max_ext, depth)
+    assert _same(got, want), ("device", thr, depth, _explain(got, want))
+    return want
+
+
+@pytest.mark.parametrize("name", [c[0] for c in GENOME_CASES])
+def test_genome_seeds_match_the_rule_and_the_golden(name):
+    import make_seq_extend_golden as G
+    m, k, ci, n_bases = _genome_model(name)
+    buf, offsets = G.seeds_of(GCASE[name])
+    with open(os.path.join(ROOT, "tests", "golden", "seq_extend_golden.json")) as f:
+        sg = json.load(f)
+    assert sg["recipe"] == G.RECIPE and sg["recipe"]["max_ext"] == MAX_EXT
+    e = sg["cases"][name]
+    for thr in (ci, 3):
+        for depth in (0, 1, 2, 3):
+            want = _check_both(m, buf, offsets, k, thr, MAX_EXT, depth)
+            t = X.tallies(want[1])
+            print(name, "thr", thr, "depth", depth, t)
+            if thr == e["thr"] and str(depth) in e["depth"]:           # the oracle-made fixture
+                d = e["depth"][str(depth)]
+                assert t == d["tallies"] and X.sha_ext(want[0]) == d["ext_sha256"] and X.sha_records(want[1]) == d["records_sha256"]
+    t2 = e["depth"]["2"]["tallies"]
+    assert t2["max_ext"] >= 500 and t2["bad_seed"] >= 100 and t2["n_lookahead"] >= 1000          # the data is not degenerate
+    # the list form, one seed, and to the left
+    seeds = [buf[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(0, len(offsets) - 1, 9)]
+    sb, so = R.flatten(seeds)
+    w_ext, w_rec = _gpu_rule(m, sb, so, k, ci, MAX_EXT, 2)
+    got, rec = m.seq_extend(seeds, ci, MAX_EXT, 2)
+    assert X.same(rec, w_rec) and got == [w_ext[i, :int(w_rec["n_ext"][i])].tobytes() for i in range(len(seeds))]
+    i = int(np.argmax(w_rec["n_ext"]))
+    one, r1 = m.seq_extend(seeds[i].decode("latin-1"), ci, MAX_EXT, 2)
+    assert one == got[i] and len(one) == MAX_EXT and r1.tobytes() == w_rec[i].tobytes()
+    l_ext, l_rec, _ = X.extend_left(sb, so, k, ci, MAX_EXT, 2, lambda rows: m.kmer_to_occ_rows(rows, k, separate=False))
+    got, rec = m.seq_extend(seeds, ci, MAX_EXT, 2, left=True)
+    assert X.same(rec, l_rec) and got == [X.revcomp(l_ext[i, :int(l_rec["n_ext"][i])].tobytes()) for i in range(len(seeds))]
+    assert int(l_rec["n_ext"].sum()) > 1000
+
+
+def test_dev_without_records_gives_the_same_rows():
+    m, k, ci, n_bases = _genome_model("genome_k27_ci2")
+    buf, offsets = R.flatten(R.make_reads(n_bases, k, n_reads=300, seed=5))
+    want = _gpu_rule(m, buf, offsets, k, ci, 100, 2)
+    assert np.array_equal(_dev(m, buf, offsets, ci, 100, 2, records=False)[0], want[0])
+    ext = np.full((len(offsets) - 1, 100), 0xFF, dtype=np.uint8)
+    assert m.L.kmx_extend_seqs(m.h, buf.ctypes.data, offsets.ctypes.data, len(offsets) - 1, ci, 100, 2, ext.ctypes.data, None) == 0    # rec == NULL
+    assert np.array_equal(ext, want[0])
+
+
+def test_two_words_and_small_k():
+    """k = 55 (two-word k-mers; the parameters of CASES' k55_nh9_nb6 over a genome) and small k, where the graph is dense and
+    most walks meet real branches: k = 4 asks about nodes whose every base is a lookahead digit"""
+    _, k, ci, cs, nh, nb, _ = CASE["k55_nh9_nb6"]
+    g = R.genome_ascii(30000, seed=55)
+    gb, go = R.flatten([g.tobytes()])
+    km, cnt = CR.count(gb, go, k, ci, cs)
+    m = KModel(ci, cs, nh, nb)
+    m.build_packed(k, km, cnt)
+    rng = np.random.default_rng(55)
+    seeds = [g[a:a + int(rng.integers(k - 2, 90))].tobytes() for a in rng.integers(0, 29000, size=600).tolist()]
+    seeds += [X.revcomp(s) for s in seeds[:200]] + [b"", b"N" * k]
+    buf, offsets = R.flatten(seeds)
+    for thr in (ci, 3):
+        for depth in (0, 1, 2, 3):
+            want = _check_both(m, buf, offsets, k, thr, 200, depth)
+            print("k55 thr", thr, "depth", depth, X.tallies(want[1]))
+    # (above k = 32 the reference canonicalises through one word, so most windows of a genome are not found again and the
+    # walks are short: the CPU oracle appends 284 bases to these seeds at thr = ci, depth 2)
+    assert X.tallies(_gpu_rule(m, buf, offsets, k, ci, 200, 2)[1])["n_ext"] >= 200
+    for name in ("k4_full", "k4_part", "k5_part", "k7_part", "k9", "k13"):
+        _, k, ci, cs, nh, nb, _, seed = SK.CASE[name]
+        km, cnt = SK.listing(name)
+        m = KModel(ci, cs, nh, nb)
+        m.build_packed(k, km, cnt)
+        rows = synth.to_ascii(np.concatenate([km[:400], synth.revcomp(km[:400], k), synth.random_kmers(200, k, seed_k=seed + 7)]), k)
+        buf, offsets = R.flatten([r.tobytes() for r in rows] + [rows[0].tobytes()[:k - 1], b"ACGTN"[:k]])
+        for thr in (ci, 3):
+            for depth in (0, 1, 2, 3):
+                want = _check_both(m, buf, offsets, k, thr, 64, depth)
+                print(name, "thr", thr, "depth", depth, X.tallies(want[1]))
+
+
+def test_short_launches_and_small_chunks_give_the_same_bytes(monkeypatch):
+    """KMX_EXTEND_STEPS: every long walk is launched again dozens of times; KMX_EXTEND_CHUNK_SEEDS (test hook): a few seeds per
+    chunk of both variants"""
+    m, k, ci, n_bases = _genome_model("genome_k31_ci1")
+    buf, offsets = R.flatten(R.make_reads(n_bases, k, n_reads=700, seed=41, long_read=900))
+    monkeypatch.delenv("KMX_EXTEND_STEPS", raising=False)
+    monkeypatch.delenv("KMX_EXTEND_CHUNK_SEEDS", raising=False)
+    plain = _check_both(m, buf, offsets, k, ci, 500, 2)
+    assert int((plain[1]["stop"] == X.MAX_EXT).sum()) >= 300
+    for steps, chunk in (("7", None), ("1", "64"), (None, "5"), ("13", "3"), ("100000", "700")):
+        for name, v in (("KMX_EXTEND_STEPS", steps), ("KMX_EXTEND_CHUNK_SEEDS", chunk)):
+            monkeypatch.setenv(name, v) if v else monkeypatch.delenv(name, raising=False)
+        assert _same(m.seq_extend_flat(buf, offsets, ci, 500, 2), plain), (steps, chunk)
+        assert _same(_dev(m, buf, offsets, ci, 500, 2), plain), (steps, chunk)
+
+
+def test_edges_and_errors():
+    import torch
+    k, ci, cs, nh, nb = 31, 1, 1023, 7, 5
+    m = KModel(ci, cs, nh, nb)
+    g = R.genome_ascii(20000)
+    buf = g[:160].copy()
+    off1 = np.array([0, 160], dtype=np.uint64)
+    ext = np.full(64, 0x5A, dtype=np.uint8)
+    rec = np.full(32, 0x5A, dtype=np.uint8).view(REC)
+    with pytest.raises(api.KmxError) as e:                                       # before the build
+        m.seq_extend_flat(buf, off1, 1, 10, 2)
+    assert e.value.code == -4
+    assert m.L.kmx_extend_seqs_dev(m.h, buf.ctypes.data, off1.ctypes.data, 1, 160, 1, 10, 2, ext.ctypes.data, None) == -4
+    km, cnt = synth.genome_stream(20000, k, ci, cs)
+    m.build_packed(k, km, cnt)
+    # n_seqs = 0: nothing written, whatever else is passed
+    assert m.L.kmx_extend_seqs(m.h, None, np.zeros(1, np.uint64).ctypes.data, 0, 1, 10, 2, None, None) == 0
+    assert m.L.kmx_extend_seqs_dev(m.h, None, None, 0, 0, 1, 10, 2, None, None) == 0
+    assert m.seq_extend([], 1, 10)[0] == []
+    m.set_profile(1)
+    m.kernel_times(reset=True)
+    for max_ext, depth in ((0, 2), (-1, 2), (65537, 2), (10, -1), (10, 4)):      # max_ext outside [1, 65536], depth outside [0, 3]
+        assert m.L.kmx_extend_seqs(m.h, buf.ctypes.data, off1.ctypes.data, 1, 1, max_ext, depth, ext.ctypes.data, rec.ctypes.data) == -1
+        assert m.L.kmx_extend_seqs_dev(m.h, buf.ctypes.data, off1.ctypes.data, 1, 160, 1, max_ext, depth, ext.ctypes.data, rec.ctypes.data) == -1
+    for bad in ([1, 160], [0, 100, 90, 160], [0, 0, 160, 159]):                  # bad offsets on the host
+        o = np.array(bad, dtype=np.uint64)
+        assert m.L.kmx_extend_seqs(m.h, buf.ctypes.data, o.ctypes.data, len(bad) - 1, 1, 10, 2, ext.ctypes.data, rec.ctypes.data) == -1, bad
+    assert m.L.kmx_extend_seqs(m.h, None, None, 1, 1, 10, 2, None, None) == -1
+    assert m.L.kmx_extend_seqs(m.h, buf.ctypes.data, off1.ctypes.data, 1, 1, 10, 2, None, None) == -1
+    assert (ext == 0x5A).all() and (rec.view(np.uint8) == 0x5A).all()
+    assert sum(v["launches"] for v in m.kernel_times(reset=True).values()) == 0     # rejected before anything was launched
+    # seeds without a base: every one a bad seed, rows of zeros
+    e0, r0 = m.seq_extend_flat(buf, np.zeros(4, dtype=np.uint64), 1, 10, 2)
+    want0 = np.zeros(3, REC)
+    want0["stop"], want0["seed_occ"], want0["min_occ"], want0["max_occ"] = X.BAD_SEED, -1, -1, -1
+    assert e0.shape == (3, 10) and not e0.any() and X.same(r0, want0)
+    d0 = _dev(m, buf[:0], np.zeros(4, dtype=np.uint64), 1, 10, 2)
+    assert not d0[0].any() and X.same(d0[1], want0)
+    # max_ext = 1 and the largest max_ext
+    for max_ext in (1, 65536):
+        want = _gpu_rule(m, buf, off1, k, 1, max_ext, 2)
+        assert _same(m.seq_extend_flat(buf, off1, 1, max_ext, 2), want) and _same(_dev(m, buf, off1, 1, max_ext, 2), want)
+    assert int(want[1]["n_ext"][0]) > 1000                                       # (it ran on to the genome's end)
+    times = m.kernel_times(reset=True)
+    assert [c for c, v in times.items() if v["launches"]] == [api.KModel.KERNEL_CLASSES[6]]
+    m.set_profile(0)
+    # the device variant with out-of-range, decreasing and huge offsets: wrong walks allowed, nothing outside its buffers
+    reads = R.make_reads(20000, k, n_reads=200, long_read=3000)
+    rbuf, roff = R.flatten(reads)
+    n_seqs, guard, max_ext = len(reads), 256, 50
+    d_seq = torch.full((len(rbuf) + 2 * guard,), 0xEE, dtype=torch.uint8, device="cuda")
+    d_seq[guard:-guard] = torch.from_numpy(rbuf).to("cuda")
+    for kind in ("past the end", "decreasing", "huge"):
+        bad = roff.copy()
+        if kind == "past the end":
+            bad[n_seqs // 2:] += np.uint64(len(rbuf))
+        elif kind == "decreasing":
+            bad[1:-1] = bad[1:-1][::-1]
+        else:
+            bad[3::7] = np.uint64(2**64 - 1)
+        d_off = torch.from_numpy(bad.view(np.int64)).to("cuda")
+        d_ext = torch.full((n_seqs * max_ext + 2 * guard,), 0xFF, dtype=torch.uint8, device="cuda")
+        d_rec = torch.full(((n_seqs + 2 * 16) * 32,), 0xFF, dtype=torch.uint8, device="cuda")
+        m.seq_extend_dev(d_seq.data_ptr() + guard, d_off.data_ptr(), n_seqs, len(rbuf), 1, max_ext, 2, d_ext.data_ptr() + guard, d_rec.data_ptr() + 16 * 32)
+        torch.cuda.synchronize()
+        h, hr = d_ext.cpu().numpy(), d_rec.cpu().numpy()
+        assert (h[:guard] == 0xFF).all() and (h[-guard:] == 0xFF).all(), kind
+        assert (hr[:16 * 32] == 0xFF).all() and (hr[-16 * 32:] == 0xFF).all(), kind
+        r = hr[16 * 32:-16 * 32].view(REC)
+        assert ((r["stop"] >= 1) & (r["stop"] <= 6)).all() and (r["n_ext"] <= max_ext).all(), kind                # every record was written
+        rows = h[guard:-guard].reshape(n_seqs, max_ext)
+        assert all(np.isin(rows[i, :r["n_ext"][i]], R.ACGT).all() and not rows[i, r["n_ext"][i]:].any() for i in range(n_seqs)), kind
+    assert _same(_dev(m, rbuf, roff, 1, max_ext, 2), _gpu_rule(m, rbuf, roff, k, 1, max_ext, 2))
+
+
+def test_concurrent_callers_and_a_side_stream():
+    import torch
+    m, k, ci, n_bases = _genome_model("genome_k31_ci1")
+    reads = R.make_reads(n_bases, k, n_reads=1500, seed=101)
+    buf, offsets = R.flatten(reads)
+    strs = [g.tobytes().decode() for g in synth.to_ascii(synth.genome_stream(n_bases, k, ci, 1023)[0][:20000], k)]
+    occ = m.kmer_to_occ(strs)
+    want = _gpu_rule(m, buf, offsets, k, ci, 200, 2)
+    alone = m.seq_extend(reads, ci, 200, 2)
+    errors = []
+
+    def run(t):
+        try:
+            for _ in range(5):
+                if t == 0:
+                    got = m.seq_extend(reads, ci, 200, 2)
+                    assert got[0] == alone[0] and X.same(got[1], alone[1]) and X.same(got[1], want[1])
+                else:
+                    assert m.kmer_to_occ(strs) == occ
+        except Exception as ex:  # noqa: BLE001
+            errors.append((t, repr(ex)))
+
+    th = [threading.Thread(target=run, args=(t,)) for t in range(2)]
+    for x in th:
+        x.start()
+    for x in th:
+        x.join()
+    assert not errors, errors
+    s = torch.cuda.Stream()
+    m.set_stream(s.cuda_stream)
+    with torch.cuda.stream(s):
+        d_seq = torch.from_numpy(buf).to("cuda")
+        d_off = torch.from_numpy(offsets.view(np.int64)).to("cuda")
+        d_ext = torch.full((len(reads) * 200,), 0xFF, dtype=torch.uint8, device="cuda")
+        d_rec = torch.full((len(reads) * 32,), 0xFF, dtype=torch.uint8, device="cuda")
+    s.synchronize()
+    for _ in range(2):
+        m.seq_extend_dev(d_seq.data_ptr(), d_off.data_ptr(), len(reads), len(buf), ci, 200, 2, d_ext.data_ptr(), d_rec.data_ptr())
+    s.synchronize()
+    assert _same((d_ext.cpu().numpy().reshape(len(reads), 200), d_rec.cpu().numpy().view(REC)), want)
+    assert _same(m.seq_extend_flat(buf, offsets, ci, 200, 2), want)
+
+
+@pytest.mark.parametrize("k", [31, 55])
+def test_allocation_failures(k, monkeypatch):
+    """tests/test_gpu_alloc_failure.py's walk over seq_extend_flat on a freshly built handle: KMX_E_NOMEM, then the handle works"""
+    import test_gpu_alloc_failure as A
+    from test_gpu_alloc_failure import walk
+    buf, off = R.flatten(R.make_reads(20000, k, n_reads=300, long_read=3000))
+    m0 = A.built(k)
+    want = _gpu_rule(m0, buf, off, k, 1, 100, 2)
+
+    def call(m):
+        try:
+            return m.seq_extend_flat(buf, off, 1, 100, 2)
+        except api.KmxError as e:
+            assert e.code == A.KMX_E_NOMEM, e
+            raise
+
+    walk(monkeypatch, lambda: A.built(k), call, lambda m, got: _same(got, want) or pytest.fail("result differs"))
+
+
+def test_facade_seq_extend(tmp_path):
+    """include/kmodel.hpp: seq_extend(seed) and seq_extend(vector) against the rule over the GPU's own answers"""
+    api.load_library()
+    exe = str(tmp_path / "facade_seq_extend")
+    subprocess.check_call(["g++", "-O3", "-m64", "-std=c++11", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "facade_seq_extend.cpp"),
+                           "-L" + os.path.join(ROOT, "kmcex_amd"), "-lkmx", "-Wl,-rpath," + os.path.join(ROOT, "kmcex_amd"), "-o", exe])
+    m, k, ci, n_bases = _genome_model("genome_k31_ci1")
+    d = str(tmp_path / "model")
+    os.makedirs(d)
+    m.save(d)
+    seeds = [r for r in R.make_reads(n_bases, k, n_reads=300, seed=77) if b"\n" not in r]
+    with open(str(tmp_path / "seeds.txt"), "wb") as f:
+        f.write(b"\n".join(r if r else b"-" for r in seeds) + b"\n")
+    p = subprocess.run([exe, d, str(tmp_path / "seeds.txt"), str(ci), "150", "2"], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-500:] + p.stderr[-500:]
+    lines = p.stdout.split("\n")
+    assert lines[len(seeds)] == "ok"
+    buf, offsets = R.flatten(seeds)
+    w_ext, w_rec = _gpu_rule(m, buf, offsets, k, ci, 150, 2)
+    assert int((w_rec["stop"] == X.MAX_EXT).sum()) > 100
+    for i in range(len(seeds)):
+        f = lines[i].split(" ")
+        assert f[0].encode("latin-1") == (w_ext[i, :int(w_rec["n_ext"][i])].tobytes() or b"-"), i
+        assert [int(x) for x in f[1:]] == [int(w_rec[i][n]) for n in X.FIELDS], i
