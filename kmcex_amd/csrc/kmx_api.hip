@@ -121,14 +121,23 @@ struct RestTable {
 	std::vector<int> hash2index, pre_buffer, count_bin;
 	std::vector<unsigned char> suffix_bin;
 	bool host_valid = false;       // the four on-disk arrays above are materialised (load, or lazily at save)
-	// device
+	// device: kept by capacity from build to build like the arrays (grow-only; a table is valid through `entries` and the
+	// sizes above, never through what the buffers can hold)
 	DevBuf<int> d_h2i, d_pre, d_cnt;   // d_cnt: counts in sorted order
 	DevBuf<u64> d_suf;
 	DevBuf<u64> d_sorted;          // sorted k-mers [entries][W] (kept for save after a device build)
 	int fbits = 0;                 // lookup accelerators (see ModelDev)
 	DevBuf<u32> d_fine;
 	DevBuf<u64> d_q;
-	void reset_dev() { d_h2i.reset(); d_pre.reset(); d_cnt.reset(); d_suf.reset(); d_sorted.reset(); d_fine.reset(); d_q.reset(); }
+	DevBuf<unsigned char> d_tmp;   // scratch of rest_sort / rest_index (rest_device.hip)
+	// an empty table again; the device buffers stay for the next one
+	void clear()
+	{
+		k = pre_len = map_size = pre_buffer_size = suff_group = fbits = 0;
+		suff_bin_size = entries = 0;
+		hash2index = {}; pre_buffer = {}; count_bin = {}; suffix_bin = {};
+		host_valid = false;
+	}
 };
 static int rest_prefix_len(int k) { for (int i = 7; i >= 3; i--) if ((k - i) % 4 == 0) return i; return 3; }   // rest.hpp:78-83
 // k of a model or of a counting session.  rest.hpp:78-83 gives k = 3 a prefix of 7 bases (-4 % 4 == 0 in C): a suffix of
@@ -182,6 +191,7 @@ struct kmx_model {
 	DevBuf<int> d_tile_cnt, d_tile_off, d_total;
 	DevBuf<int> d_totals;                                      // per-chunk totals of one insert_batch call
 	PinBuf<int> h_totals, h_total;
+	PinBuf<u64> h_words;                                       // what a build reads back between its steps: [ST_N] stats, then the HW_* words
 	PinBuf<u64> h_feedback{hipHostMallocMapped};               // ST_MAX_U0 as of some earlier block (heuristic input)
 	u64 *d_feedback = nullptr;                                 // the same words as the device sees them (k_rest_append writes them)
 	u64 epoch = 1, blocks = 0, rounds = 0;
@@ -350,6 +360,7 @@ static void prof_collect(kmx_model *m)
 	m->prof_spans.clear();
 }
 
+enum { HW_NREST = ST_N, HW_NBF, HW_BAD = HW_NBF + 3, HW_N };   // kmx_model::h_words
 static const u64 kChunk = u64(1) << 23;                       // k-mers classified per pass of the front end
 
 // the malloc-time counter and the KMX_FAIL_ALLOC countdown of hip_owned.h (three translation units allocate through it)
@@ -417,6 +428,7 @@ static int create_device_side(kmx_model *m)
 	HIPCHK(m->d_nbf.alloc(3));
 	HIPCHK(hipMemset(m->d_stats, 0, ST_N * 8));
 	HIPCHK(m->h_total.alloc(16));
+	HIPCHK(m->h_words.alloc(HW_N));
 	HIPCHK(m->h_feedback.alloc(8));
 	HIPCHK(hipHostGetDevicePointer((void **)&m->d_feedback, m->h_feedback, 0));
 	// [2]: the fullest claim bin of a late round (t >= 2), which picks the form of their k_round_detect: until the device reports
@@ -519,7 +531,6 @@ static void fill_model_dev(kmx_model *m)
 
 static int alloc_arrays(kmx_model *m)
 {
-	m->rest.reset_dev();
 	{   // the Bloom filters and their back filters live back to back in one slab (the BitScatter of the front end sweeps it)
 		u64 off = 0;
 		for (int i = 0; i < 3; i++) {
@@ -777,7 +788,7 @@ static int kmx_begin_impl(kmx_model *m, int k, const uint64_t n_bf[3], uint64_t 
 	// before the bit-sets below are pointed at their tuple buffers, which go with them.)
 	if (m->d_block_scratch && (m->scratch_nb != m->nb || m->scratch_W != m->W)) free_build_state(m);
 	TRY(alloc_arrays(m));
-	m->rest = RestTable();
+	m->rest.clear();
 	TRY(setup_kmback_scatter(m));
 	TRY(setup_bloom_scatter(m));
 	bs_attach_level2(m);
@@ -1113,7 +1124,6 @@ static int rest_build_accel(kmx_model *m);
 static int build_rest(kmx_model *m, u64 n)
 {
 	RestTable &r = m->rest;
-	r.reset_dev();
 	const int W = m->W, k = m->k;
 	r.k = k;
 	r.pre_len = rest_prefix_len(k);
@@ -1122,20 +1132,21 @@ static int build_rest(kmx_model *m, u64 n)
 	r.entries = n;
 	r.suff_bin_size = n * (u64)r.suff_group;
 	r.host_valid = false;
-	HIPCHK(r.d_sorted.alloc(n * W + 2));
-	HIPCHK(r.d_cnt.alloc(n + 4));
-	HIPCHK(r.d_suf.alloc(n * W + 2));
-	HIPCHK(r.d_h2i.alloc((u64)r.map_size));
-	HIPCHK(r.d_pre.alloc((u64)r.map_size + 2));
+	HIPCHK(r.d_sorted.ensure(n * W + 2, m->stream));
+	HIPCHK(r.d_cnt.ensure(n + 4, m->stream));
+	HIPCHK(r.d_suf.ensure(n * W + 2, m->stream));
+	HIPCHK(r.d_h2i.ensure((u64)r.map_size, m->stream));
+	HIPCHK(r.d_pre.ensure((u64)r.map_size + 2, m->stream));
 	HIPCHK(hipMemsetAsync(r.d_h2i, 0xFF, (u64)r.map_size * 4, m->stream));
 	KPROF_BEGIN(&m->prof, KC_REST, m->stream);                        // class 5: the rest table -- radix sort + index kernels (the accelerators follow)
-	HIPCHK(kmxk::rest_sort(m->d_rest_kmers, m->d_rest_counts, n, W, k, r.d_sorted, r.d_cnt, m->stream));
-	HIPCHK(kmxk::rest_index(r.d_sorted, n, W, k, r.pre_len, r.d_h2i, r.d_pre, r.d_suf, m->d_total, m->stream));
+	HIPCHK(kmxk::rest_sort(m->d_rest_kmers, m->d_rest_counts, n, W, k, r.d_sorted, r.d_cnt, r.d_tmp, m->stream));
+	HIPCHK(kmxk::rest_index(r.d_sorted, n, W, k, r.pre_len, r.d_h2i, r.d_pre, r.d_suf, m->d_total, r.d_tmp, m->stream));
 	KPROF_END(&m->prof, m->stream);
 	HIPCHK(hipMemcpyAsync(m->h_total, m->d_total, 4, hipMemcpyDeviceToHost, m->stream));
+	const int rc = rest_build_accel(m);                                // (needs no count of groups: enqueued before the one wait of this function)
 	HIPCHK(hipStreamSynchronize(m->stream));
 	r.pre_buffer_size = *m->h_total + 1;
-	return rest_build_accel(m);
+	return rc;
 }
 
 // bucket index + next-group table for k_query's lookup (device only)
@@ -1147,8 +1158,8 @@ static int rest_build_accel(kmx_model *m)
 	F = std::max(F, 2 * r.pre_len);
 	F = std::min(F, 2 * r.k);
 	r.fbits = F;
-	HIPCHK(r.d_fine.alloc((1ULL << F) + 2));
-	HIPCHK(r.d_q.alloc((u64)r.map_size * m->W));
+	HIPCHK(r.d_fine.ensure((1ULL << F) + 2, m->stream));
+	HIPCHK(r.d_q.ensure((u64)r.map_size * m->W, m->stream));
 	kmxk::rest_accel(r.d_sorted, r.entries, m->W, r.k, F, r.d_h2i, r.d_pre, r.d_suf, r.map_size, r.d_fine, r.d_q, m->stream);
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -1213,12 +1224,12 @@ static int kmx_finish_impl(kmx_model *m)
 	m->stg_n = 0;
 	TRY(flush_pending_commit(m));
 	TRY(kmback_flush(m));
-	unsigned long long n_rest = 0;
-	int range_ovf = 0;
-	HIPCHK(hipMemcpyAsync(m->h_stats, m->d_stats, ST_N * 8, hipMemcpyDeviceToHost, m->stream));
-	HIPCHK(hipMemcpyAsync(&n_rest, m->d_rest_n, 8, hipMemcpyDeviceToHost, m->stream));
-	if (m->range.on && m->range.d_ovf) HIPCHK(hipMemcpyAsync(&range_ovf, m->range.d_ovf, sizeof(int), hipMemcpyDeviceToHost, m->stream));
+	u64 *hw = m->h_words;                                            // pinned: the copies are enqueued, one wait for all of them
+	HIPCHK(hipMemcpyAsync(hw, m->d_stats, ST_N * 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipMemcpyAsync(hw + HW_NREST, m->d_rest_n, 8, hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
+	memcpy(m->h_stats, hw, ST_N * 8);
+	const unsigned long long n_rest = hw[HW_NREST];
 	if (m->h_stats[ST_BAD_COUNT]) {
 		m->state = ST_EMPTY;
 		return fail(KMX_E_RANGE, "%llu k-mers with a count outside [ci=%d, cs=%d]", (unsigned long long)m->h_stats[ST_BAD_COUNT], m->ci, m->cs);
@@ -1243,10 +1254,10 @@ static int build_common(kmx_model *m, int k, const u64 *d_kmers, const u32 *d_co
 	HIPCHK(hipMemsetAsync(m->d_nbf, 0, 24, m->stream));
 	HIPCHK(hipMemsetAsync(m->d_stats, 0, ST_N * 8, m->stream));
 	kmxk::histogram(d_counts, n, m->ci, m->cs, m->bf_num, m->d_nbf, m->d_stats, m->stream);    // pass 1
-	u64 nbf[3], bad = 0;
-	HIPCHK(hipMemcpyAsync(nbf, m->d_nbf, 24, hipMemcpyDeviceToHost, m->stream));
-	HIPCHK(hipMemcpyAsync(&bad, m->d_stats + ST_BAD_COUNT, 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipMemcpyAsync(m->h_words + HW_NBF, m->d_nbf, 24, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipMemcpyAsync(m->h_words + HW_BAD, m->d_stats + ST_BAD_COUNT, 8, hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
+	const u64 nbf[3] = {m->h_words[HW_NBF], m->h_words[HW_NBF + 1], m->h_words[HW_NBF + 2]}, bad = m->h_words[HW_BAD];
 	if (bad) return fail(KMX_E_RANGE, "%llu k-mers with a count outside [ci=%d, cs=%d]", (unsigned long long)bad, m->ci, m->cs);
 	const auto t0 = std::chrono::steady_clock::now();
 	TRY(kmx_begin(m, k, (const uint64_t *)nbf, n_total));

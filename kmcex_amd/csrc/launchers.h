@@ -41,8 +41,9 @@ void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t
 void debug_min_kmer(int, const u64 *, u64, u64 *, hipStream_t);
 void debug_mod(const u64 *, u64, u64, u64 *, hipStream_t);
 void micro(int, u64 *, u64, u64, u64, u64 *, hipStream_t);
-hipError_t rest_sort(const u64 *, const int *, u64, int, int, u64 *, int *, hipStream_t);
-hipError_t rest_index(const u64 *, u64, int, int, int, int *, int *, u64 *, int *, hipStream_t);
+// rest_device.hip: `tmp` is the scratch of both, grown (after the stream has drained) when a table asks for more
+hipError_t rest_sort(const u64 *, const int *, u64, int, int, u64 *, int *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t rest_index(const u64 *, u64, int, int, int, int *, int *, u64 *, int *, DevBuf<unsigned char> &tmp, hipStream_t);
 void rest_expand(const int *, const int *, const u64 *, int, int, int, int, u64 *, hipStream_t);
 void rest_accel(const u64 *, u64, int, int, int, const int *, const int *, const u64 *, int, u32 *, u64 *, hipStream_t);
 void rest_suffix_bytes(const u64 *, u64, int, int, unsigned char *, hipStream_t);

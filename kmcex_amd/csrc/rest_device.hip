@@ -132,62 +132,66 @@ __global__ __launch_bounds__(256) void k_rest_suffix_bytes(const u64 *km, u64 n,
 
 namespace kmxk {
 
-// Sort n (k-mer, count) pairs ascending by k-mer.  in/out buffers are distinct; scratch is allocated here
-// (rest tables are a few % of the input, and this runs once per build) and released on every way out
-// (an early return frees with work in flight: hipFree waits for the device).
-hipError_t rest_sort(const u64 *km_in, const int *cnt_in, u64 n, int W, int k, u64 *km_out, int *cnt_out, hipStream_t st)
+// Scratch of the two launchers below: pieces of `tmp`, the caller's grow-only buffer (kept on the handle, so a warm rebuild
+// allocates and frees nothing here and no call waits for the device; growing it drains the stream first).  Every piece
+// starts on a 256-byte boundary.
+struct Carve {
+	size_t off = 0;
+	size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
+};
+
+// Sort n (k-mer, count) pairs ascending by k-mer.  in/out buffers are distinct; the scratch is carved from `tmp`.  Nothing
+// here waits for the stream: the work is enqueued, `tmp` and the buffers must outlive it.
+hipError_t rest_sort(const u64 *km_in, const int *cnt_in, u64 n, int W, int k, u64 *km_out, int *cnt_out, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
 	if (!n) return hipSuccess;
 	size_t tmp_bytes = 0;
-	DevBuf<unsigned char> tmp;
 	if (W == 1) {
 		RCHK(rocprim::radix_sort_pairs(nullptr, tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st));
-		RCHK(tmp.alloc(tmp_bytes));
-		hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st);
-		hipStreamSynchronize(st);
-		return e;
+		RCHK(tmp.ensure(tmp_bytes, st));
+		return rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, km_in, km_out, cnt_in, cnt_out, n, 0, 2 * k, st);
 	}
 	// two-word keys: LSD -- stable sort by the low word, then by the high word, carrying a permutation
-	DevBuf<u64> hi, lo, key2, key3;
-	DevBuf<u32> i0, i1;
-	RCHK(hi.alloc(n)); RCHK(lo.alloc(n));
-	RCHK(key2.alloc(n)); RCHK(key3.alloc(n));
-	RCHK(i0.alloc(n)); RCHK(i1.alloc(n));
-	hipLaunchKernelGGL(k_split2, dim3(nblk(n)), dim3(256), 0, st, km_in, n, hi.get(), lo.get());
-	hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(256), 0, st, i0.get(), n);
 	size_t t1 = 0, t2 = 0;
-	RCHK(rocprim::radix_sort_pairs(nullptr, t1, lo.get(), key2.get(), i0.get(), i1.get(), n, 0, 64, st));
-	RCHK(rocprim::radix_sort_pairs(nullptr, t2, key2.get(), key3.get(), i1.get(), i0.get(), n, 0, 2 * k - 64, st));
+	RCHK(rocprim::radix_sort_pairs(nullptr, t1, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 64, st));
+	RCHK(rocprim::radix_sort_pairs(nullptr, t2, (const u64 *)nullptr, (u64 *)nullptr, (const u32 *)nullptr, (u32 *)nullptr, n, 0, 2 * k - 64, st));
 	tmp_bytes = t1 > t2 ? t1 : t2;
-	RCHK(tmp.alloc(tmp_bytes));
-	hipError_t e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, lo.get(), key2.get(), i0.get(), i1.get(), n, 0, 64, st);            // by low word -> perm i1
+	Carve c;
+	const size_t o_hi = c.take(n * 8), o_lo = c.take(n * 8), o_key2 = c.take(n * 8), o_key3 = c.take(n * 8);
+	const size_t o_i0 = c.take(n * 4), o_i1 = c.take(n * 4), o_tmp = c.take(tmp_bytes);
+	RCHK(tmp.ensure(c.off, st));
+	unsigned char *base = tmp.get();
+	u64 *hi = (u64 *)(base + o_hi), *lo = (u64 *)(base + o_lo), *key2 = (u64 *)(base + o_key2), *key3 = (u64 *)(base + o_key3);
+	u32 *i0 = (u32 *)(base + o_i0), *i1 = (u32 *)(base + o_i1);
+	hipLaunchKernelGGL(k_split2, dim3(nblk(n)), dim3(256), 0, st, km_in, n, hi, lo);
+	hipLaunchKernelGGL(k_iota, dim3(nblk(n)), dim3(256), 0, st, i0, n);
+	hipError_t e = rocprim::radix_sort_pairs(base + o_tmp, tmp_bytes, (const u64 *)lo, key2, (const u32 *)i0, i1, n, 0, 64, st);            // by low word -> perm i1
 	if (e == hipSuccess) {
-		hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n)), dim3(256), 0, st, (const u64 *)hi.get(), (const u32 *)i1.get(), n, key2.get());   // high words in that order
-		e = rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, key2.get(), key3.get(), i1.get(), i0.get(), n, 0, 2 * k - 64, st);          // stable by high word -> perm i0
+		hipLaunchKernelGGL(k_gather_u64, dim3(nblk(n)), dim3(256), 0, st, (const u64 *)hi, (const u32 *)i1, n, key2);   // high words in that order
+		e = rocprim::radix_sort_pairs(base + o_tmp, tmp_bytes, (const u64 *)key2, key3, (const u32 *)i1, i0, n, 0, 2 * k - 64, st);          // stable by high word -> perm i0
 	}
-	if (e == hipSuccess) hipLaunchKernelGGL(k_gather_final2, dim3(nblk(n)), dim3(256), 0, st, km_in, cnt_in, (const u32 *)i0.get(), n, km_out, cnt_out);
-	hipStreamSynchronize(st);
+	if (e == hipSuccess) hipLaunchKernelGGL(k_gather_final2, dim3(nblk(n)), dim3(256), 0, st, km_in, cnt_in, (const u32 *)i0, n, km_out, cnt_out);
 	return e;
 }
 
-// From the sorted table: h2i[map_size] (pre-set to -1 by the caller), pre[map_size+1], suf[n*W], *groups.
-hipError_t rest_index(const u64 *km_sorted, u64 n, int W, int k, int pre_len, int *h2i, int *pre, u64 *suf, int *groups, hipStream_t st)
+// From the sorted table: h2i[map_size] (pre-set to -1 by the caller), pre[map_size+1], suf[n*W], *groups.  Scratch from
+// `tmp` like rest_sort (what the sort left there is dead: the same stream), and no wait either.
+hipError_t rest_index(const u64 *km_sorted, u64 n, int W, int k, int pre_len, int *h2i, int *pre, u64 *suf, int *groups, DevBuf<unsigned char> &tmp, hipStream_t st)
 {
 	const int sbits = 2 * (k - pre_len);
 	RCHK(hipMemsetAsync(groups, 0, 4, st));
 	RCHK(hipMemsetAsync(pre, 0, 4, st));
 	if (!n) return hipSuccess;
-	DevBuf<int> flag, scan;
-	DevBuf<unsigned char> tmp;
 	size_t tmp_bytes = 0;
-	RCHK(flag.alloc(n));
-	RCHK(scan.alloc(n));
-	hipLaunchKernelGGL(k_rest_flags, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, flag.get(), suf);
-	RCHK(rocprim::inclusive_scan(nullptr, tmp_bytes, flag.get(), scan.get(), n, rocprim::plus<int>(), st));
-	RCHK(tmp.alloc(tmp_bytes));
-	hipError_t e = rocprim::inclusive_scan(tmp.get(), tmp_bytes, flag.get(), scan.get(), n, rocprim::plus<int>(), st);
-	if (e == hipSuccess) hipLaunchKernelGGL(k_rest_index, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, (const int *)flag.get(), (const int *)scan.get(), h2i, pre, groups);
-	hipStreamSynchronize(st);
+	RCHK(rocprim::inclusive_scan(nullptr, tmp_bytes, (int *)nullptr, (int *)nullptr, n, rocprim::plus<int>(), st));
+	Carve c;
+	const size_t o_flag = c.take(n * 4), o_scan = c.take(n * 4), o_tmp = c.take(tmp_bytes);
+	RCHK(tmp.ensure(c.off, st));
+	unsigned char *base = tmp.get();
+	int *flag = (int *)(base + o_flag), *scan = (int *)(base + o_scan);
+	hipLaunchKernelGGL(k_rest_flags, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, flag, suf);
+	const hipError_t e = rocprim::inclusive_scan(base + o_tmp, tmp_bytes, flag, scan, n, rocprim::plus<int>(), st);
+	if (e == hipSuccess) hipLaunchKernelGGL(k_rest_index, dim3(nblk(n)), dim3(256), 0, st, km_sorted, n, W, sbits, (const int *)flag, (const int *)scan, h2i, pre, groups);
 	return e;
 }
 
