@@ -240,6 +240,34 @@ public:
 		return out;
 	}
 
+	// Substitutions and single-base insertions / deletions found from the k-mer spectrum and applied (kmx_edit_seqs and
+	// kmx_apply_edits; the rule is in kmx.h): returns the edited reads, whose lengths may differ from the input's.  ops is a
+	// subset of KMX_EDIT_OPS_SUB | KMX_EDIT_OPS_DEL | KMX_EDIT_OPS_INS; rec, if given, receives one record per read.
+	std::string seq_edit(const std::string &seq, int thr, int min_support = 1, int ops = 7, kmx_seq_edits *rec = 0)
+	{
+		std::vector<kmx_seq_edits> r;
+		const std::string out = seq_edit(std::vector<std::string>(1, seq), thr, min_support, ops, &r)[0];
+		if (rec) *rec = r[0];
+		return out;
+	}
+	std::vector<std::string> seq_edit(const std::vector<std::string> &seqs, int thr, int min_support = 1, int ops = 7, std::vector<kmx_seq_edits> *rec = 0)
+	{
+		std::vector<uint64_t> off(seqs.size() + 1, 0), off_out(seqs.size() + 1, 0);
+		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		if (rec) rec->assign(seqs.size(), kmx_seq_edits());
+		std::vector<kmx_edit> edits((size_t)(off.back() / 3 + 1));
+		uint64_t n_edits = 0;
+		if (!seqs.empty()) check(kmx_edit_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, &edits[0], edits.size(), &n_edits, rec ? &(*rec)[0] : 0));
+		std::string fixed(flat.size() + (size_t)n_edits, '\0');
+		check(kmx_apply_edits(flat.data(), off.data(), seqs.size(), &edits[0], n_edits, &fixed[0], fixed.size(), &off_out[0]));
+		std::vector<std::string> out(seqs.size());
+		for (size_t i = 0; i < seqs.size(); i++) out[i] = fixed.substr((size_t)off_out[i], (size_t)(off_out[i + 1] - off_out[i]));
+		return out;
+	}
+
 	// Seeds extended to the right along the unique path of k-mers answered >= thr (kmx_extend_seqs; the rule is in kmx.h):
 	// at most max_ext bases each, ties broken by a lookahead of `depth` (0 ... 3).  Returns the appended bases; rec, if given,
 	// receives one record per seed (why the walk stopped, the counts along it).

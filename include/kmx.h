@@ -306,6 +306,87 @@ int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uin
 int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases,
                          int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec /* or NULL */);
 
+/* Substitutions and single-base insertions / deletions of reads found from the k-mer spectrum: kmx_correct_seqs with a wider
+ * shape table, verification windows built with one base skipped or inserted, and an output that may change a read's length.
+ * As there, every decision is taken from the answers on the INPUT bytes and none depends on another edit, so the result is a
+ * function of the input alone: it does not depend on the order of evaluation, the cut into pieces, or the variant.  An edit
+ * list in input coordinates is also a SNP / indel call list when a reference sequence is run against a sample's model.
+ * Steps 1 - 3 of kmx_correct_seqs hold word for word (weak windows, gap closing, runs [s, e], len, hasL, hasR).  x = the
+ * sequence's bytes, L its length, nW its window count; thr is any int32, min_support in [1, 64], ops a non-empty subset of
+ * KMX_EDIT_OPS_SUB | KMX_EDIT_OPS_DEL | KMX_EDIT_OPS_INS.
+ *   Candidates: an edited string t and verification windows V (start positions q in t, every window k bytes of t).
+ *     SUB at p, base c: x with x[p] replaced by c;  V = [v0, v1] of kmx_correct_seqs' table for that site.
+ *     DEL at p:         x without x[p] (the read has a base in excess);  V = the windows of t that hold both new neighbours,
+ *                       q in [max(0, p-k+1), min(p-1, L-1-k)].
+ *     INS at j, base c: x with c placed before x[j] (the read lost a base);  V = the windows of t that hold the new base,
+ *                       q in [max(0, j-k+1), min(j, L+1-k)].
+ *     c is one of A C G T.
+ *   Sites of a run, the candidates in this order, each kind only if its ops bit is set:
+ *     neither hasL nor hasR: none;
+ *     hasR only: anchor a = e, junction j = e+1: SUB at a for c != x[a] with V = [max(s, e-k+1), e]; DEL at a; INS at j for all four c;
+ *     hasL only: a = j = s+k-1: SUB at a with V = [s, min(e, s+k-1)]; DEL at a; INS at j for all four c;
+ *     both, len > k: the two SUB sites of kmx_correct_seqs' table and nothing else;
+ *     both, len <= k: one site; its core is the bytes common to all the run's windows, x[e .. s+k-1], h = k-len+1 of them:
+ *       len = k: SUB at e for c != x[e], V = [s, e];
+ *       DEL at e iff all h core bytes are equal (always so for h = 1; deleting any byte of a homopolymer gives the same
+ *       string, the leftmost is the canonical one);
+ *       h = 2: INS at e+1 for all four c;   h >= 3: the single INS at e+1 with c = x[e+1], provided x[e+1 .. s+k-2] are all
+ *       that byte and it is one of ACGT.
+ *     (A surplus base inside a homopolymer of h bytes makes exactly the windows holding the whole homopolymer plus a flank
+ *     weak: len = k-h+1.  A lost base whose homopolymer keeps m bytes makes the windows holding flank, A^m, flank weak:
+ *     len = k-1-m, the core those m+2 bytes.  At a read end only one edge of the run is visible, so all three kinds are tried.)
+ *   A candidate is tried iff |V| >= min_support, a site iff one of its candidates is; n_sites counts the tried sites.  A tried
+ *   candidate passes iff every window of V answers >= thr (the answer kmx_query_ascii gives those k bytes: bytes outside ACGT
+ *   are hashed as they are).  Exactly one passes: it becomes an edit and n_sub / n_del / n_ins is incremented; more than one:
+ *   n_ambiguous++; none: n_unfixable++.
+ *   With ops = KMX_EDIT_OPS_SUB the tried sites, counts and changed bytes are exactly those of kmx_correct_seqs.  Anchors of
+ *   distinct sites are distinct and junctions lie inside their sequence, so (pos, op) is unique: one position carries at most
+ *   one of SUB / DEL, possibly plus one INS.
+ * Out of scope: more than one base per edit; two errors within k of each other stay substitution-only (both, len > k); more
+ * than the two outer errors of a long run per call (call again on the output); quality values.                             */
+#define KMX_EDIT_OPS_SUB 1
+#define KMX_EDIT_OPS_DEL 2
+#define KMX_EDIT_OPS_INS 4
+#define KMX_EDIT_SUB 1
+#define KMX_EDIT_DEL 2
+#define KMX_EDIT_INS 3
+/* pos << 8 | op << 4 | code: pos = position in the whole input (flat), op = KMX_EDIT_SUB / KMX_EDIT_DEL / KMX_EDIT_INS (insert
+ * before the base at pos), code 0..3 = A C G T (0 for DEL)                                                                 */
+typedef uint64_t kmx_edit;
+typedef struct kmx_seq_edits {           /* one per sequence; 80 bytes, no padding; out_len = L + n_ins - n_del */
+	uint64_t n_windows, n_weak, n_runs, n_sites, n_sub, n_del, n_ins, n_ambiguous, n_unfixable, out_len;
+} kmx_seq_edits;
+/* Sequences in the layout of kmx_query_seqs.  edits[capacity] receives the list, sorted ascending as numbers (so it is
+ * byte-identical across runs, variants and piece sizes), *n_edits the number of edits found, rec[n_seqs] the records (may be
+ * NULL).  More edits than capacity: KMX_E_RANGE, *n_edits is the number needed, the records are complete, the list's content
+ * is unspecified; capacity >= n_bases / 3 + 1 always suffices (runs lie at least two windows apart after gap closing, and only
+ * a run longer than k has two sites).  KMX_E_ARG when ops is outside 1..7, min_support outside [1, 64], offsets[0] != 0 or the
+ * offsets decrease, all checked before anything runs; n_seqs == 0: KMX_OK, nothing written; no bases but n_seqs > 0: all-zero
+ * records, *n_edits = 0.  KMX_E_STATE before the model is built or loaded; KMX_E_NOMEM leaves the handle usable.  A run at an
+ * end of its sequence takes other candidates than one inside however long it is, so the weak bits of the whole input are kept
+ * (n_bases / 8 bytes) and the bases stay on the device for the call: the host variant uploads them whole (n_bases bytes of
+ * device memory).  A query-class call, timed as kernel class 6 under kmx_set_profile(m, 1).                                */
+int kmx_edit_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops,
+                  kmx_edit *edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *rec /* [n_seqs] or NULL */);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], d_edits[capacity], d_rec[n_seqs] (or NULL); n_edits is on
+ * the HOST.  Enqueued on the model's stream; it waits for the stream once, where the count reaches the host, and returns with
+ * the sort of the list enqueued.  The offsets are not validated on the host: each is clamped into [0, n_bases] where it is
+ * read, so bad offsets give wrong edits, never an access outside d_seq[0, n_bases), d_edits[0, capacity), d_rec[0, n_seqs).   */
+int kmx_edit_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops,
+                      kmx_edit *d_edits, uint64_t capacity, uint64_t *n_edits /* HOST */, kmx_seq_edits *d_rec /* or NULL */);
+/* A list applied to the input it was found on; needs no GPU.  Walk the input positions p of a sequence in order: emit the
+ * inserted base if an INS sits at p, then the input byte, or its SUB base, or nothing for a DEL.  seq_out[out_capacity]
+ * receives the bytes, offsets_out[n_seqs + 1] the running sum of the output lengths (the records' out_len).  KMX_E_ARG when the
+ * list is not strictly ascending, a pos >= n_bases, an unknown op or code, SUB and DEL at one pos, or bad offsets;
+ * KMX_E_RANGE when out_capacity is too small (n_bases + the insertions - the deletions are needed).                         */
+int kmx_apply_edits(const char *seq, const uint64_t *offsets, uint64_t n_seqs, const kmx_edit *edits, uint64_t n_edits,
+                    char *seq_out, uint64_t out_capacity, uint64_t *offsets_out /* [n_seqs + 1] */);
+/* the same on DEVICE buffers, enqueued on the model's stream; waits once, for the output's length (KMX_E_RANGE as above, after
+ * the bytes that fit were written).  The list is not validated on the device: one that is no sorted edit list of this input gives
+ * wrong bytes, never a write outside d_seq_out[0, out_capacity) and d_offsets_out[0, n_seqs].  Needs no built model.       */
+int kmx_apply_edits_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const kmx_edit *d_edits, uint64_t n_edits,
+                        char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out);
+
 /* Seeds extended to the right along unique k-mer paths: a walk through the de Bruijn graph the model implicitly holds (the
  * primitive of unitig construction, gap filling, seed-and-extend).  occ(s) is the answer kmx_query_ascii gives the k bytes s;
  * every string a walk asks about is uppercase ACGT, so it is also kmx_query_packed of its packed form.  The result is a

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
     "kmx_query_seqs", "kmx_query_seqs_dev", "kmx_summarise_seqs", "kmx_summarise_seqs_dev",
     "kmx_correct_seqs", "kmx_correct_seqs_dev",
+    "kmx_edit_seqs", "kmx_edit_seqs_dev", "kmx_apply_edits", "kmx_apply_edits_dev",
     "kmx_extend_seqs", "kmx_extend_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
@@ -66,6 +67,10 @@ SEQ_SUMMARY_DTYPE = np.dtype([("n_windows", "<u8"), ("sum", "<u8"), ("min", "<i4
 SEQ_THRESHOLDS = 3
 # kmx_seq_correction of include/kmx.h (what KModel.seq_correct_flat returns beside the corrected bases): 8 x uint64
 SEQ_CORRECTION_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_runs", "n_sites", "n_corrected", "n_ambiguous", "n_unfixable", "reserved")])
+# kmx_seq_edits of include/kmx.h (what KModel.seq_edit_flat returns beside the edit list): 10 x uint64
+SEQ_EDITS_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_runs", "n_sites", "n_sub", "n_del", "n_ins", "n_ambiguous", "n_unfixable", "out_len")])
+EDIT_OPS_SUB, EDIT_OPS_DEL, EDIT_OPS_INS = 1, 2, 4
+EDIT_SUB, EDIT_DEL, EDIT_INS = 1, 2, 3
 # kmx_seq_extension of include/kmx.h (what KModel.seq_extend_flat returns beside the rows of appended bases): 32 bytes
 SEQ_EXTENSION_DTYPE = np.dtype([("n_ext", "<u4"), ("stop", "<u4"), ("seed_occ", "<i4"), ("min_occ", "<i4"), ("max_occ", "<i4"), ("n_lookahead", "<u4"), ("sum_occ", "<u8")])
 SEQ_EXTENSION_STOPS = {1: "DEAD_END", 2: "BRANCH", 3: "JOIN", 4: "CYCLE", 5: "MAX_EXT", 6: "BAD_SEED"}
@@ -177,6 +182,10 @@ def load_library():
     _sig(L, "kmx_summarise_seqs_dev", [vp, vp, vp, u64, u64, vp, i32, vp])
     _sig(L, "kmx_correct_seqs", [vp, vp, vp, u64, i32, i32, vp, vp])
     _sig(L, "kmx_correct_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, vp, vp])
+    _sig(L, "kmx_edit_seqs", [vp, vp, vp, u64, i32, i32, i32, vp, u64, vp, vp])
+    _sig(L, "kmx_edit_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, vp, u64, vp, vp])
+    _sig(L, "kmx_apply_edits", [vp, vp, u64, vp, u64, vp, u64, vp])
+    _sig(L, "kmx_apply_edits_dev", [vp, vp, vp, u64, u64, vp, u64, vp, u64, vp])
     _sig(L, "kmx_extend_seqs", [vp, vp, vp, u64, i32, i32, i32, vp, vp])
     _sig(L, "kmx_extend_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, vp, vp])
     _sig(L, "kmx_count_begin", [vp, i32])
@@ -283,6 +292,21 @@ def microbench(mode: int, nbytes: int, touches: int, iters: int = 3) -> float:
     s = C.c_double(0)
     _chk(load_library().kmx_microbench(mode, nbytes, touches, iters, C.byref(s)))
     return s.value
+
+
+def apply_edits(buf: np.ndarray, offsets: np.ndarray, edits: np.ndarray):
+    """kmx_apply_edits (host only, needs no GPU): an edit list applied to the bases it was found on -> (uint8 edited bases,
+    uint64 offsets_out [n_seqs + 1])"""
+    L = load_library()
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    edits = np.ascontiguousarray(edits, dtype=np.uint64).reshape(-1)
+    if offsets.size == 0 or int(offsets[-1]) > buf.size:
+        raise KmxError(-1, "offsets must hold n_seqs + 1 entries and end inside the bases given")
+    out = np.empty(int(offsets[-1]) + edits.size, dtype=np.uint8)
+    off = np.zeros(offsets.size, dtype=np.uint64)
+    _chk(L.kmx_apply_edits(buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, edits.ctypes.data, edits.size, out.ctypes.data, out.size, off.ctypes.data))
+    return out[:int(off[-1])].copy(), off
 
 
 class KModel:
@@ -582,6 +606,58 @@ class KModel:
         bytes, or 0), enqueued on the model's stream (no wait)"""
         _chk(self.L.kmx_correct_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, int(thr), int(min_support),
                                          d_seq_out_ptr, d_rec_ptr or None))
+
+    def seq_edit_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, min_support: int = 1, ops: int = 7):
+        """kmx_edit_seqs: substitutions and single-base insertions / deletions found from the k-mer spectrum (the rule:
+        include/kmx.h) -> (uint64 edits, ascending: pos << 8 | op << 4 | code; SEQ_EDITS_DTYPE records [n_seqs]).  ops is a subset
+        of EDIT_OPS_SUB | EDIT_OPS_DEL | EDIT_OPS_INS; apply_edits turns the list into the edited bases."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        n_bases = int(offsets[-1])
+        if n_bases > buf.size:
+            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        rec = np.zeros(offsets.size - 1, dtype=SEQ_EDITS_DTYPE)
+        edits = np.empty(n_bases // 3 + 1, dtype=np.uint64)        # always enough (include/kmx.h)
+        n = C.c_uint64(0)
+        _chk(self.L.kmx_edit_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, int(thr), int(min_support), int(ops),
+                                  edits.ctypes.data, edits.size, C.addressof(n), rec.ctypes.data))
+        return edits[:n.value].copy(), rec
+
+    def seq_edit(self, seqs, thr: int, min_support: int = 1, ops: int = 7):
+        """seq_edit_flat and apply_edits for a str / bytes sequence (-> (edited bytes, record, edits)) or a list of them
+        (-> (list of edited bytes, records, edits)); the positions of the edits are those of the reads joined end to end"""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        edits, rec = self.seq_edit_flat(buf, offsets, thr, min_support, ops)
+        out, off = apply_edits(buf, offsets, edits)
+        fixed = [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(raw))]
+        return (fixed[0], rec[0], edits) if single else (fixed, rec, edits)
+
+    def seq_edit_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int, ops: int,
+                     d_edits_ptr: int, capacity: int, d_rec_ptr: int = 0) -> int:
+        """kmx_edit_seqs_dev: device buffers (d_edits: capacity uint64, d_rec: n_seqs records of 80 bytes, or 0) -> the number of
+        edits found; KmxError -5 (KMX_E_RANGE) with .needed = that number when it exceeds capacity.  Waits once, for the count."""
+        n = C.c_uint64(0)
+        rc = self.L.kmx_edit_seqs_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, int(thr), int(min_support), int(ops),
+                                      d_edits_ptr or None, capacity, C.addressof(n), d_rec_ptr or None)
+        try:
+            _chk(rc)
+        except KmxError as e:
+            e.needed = n.value
+            raise
+        return n.value
+
+    def apply_edits_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, d_edits_ptr: int, n_edits: int,
+                        d_seq_out_ptr: int, out_capacity: int, d_offsets_out_ptr: int) -> None:
+        """kmx_apply_edits_dev: the (sorted) device list applied to the device bases it was found on; d_offsets_out: n_seqs + 1"""
+        _chk(self.L.kmx_apply_edits_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, d_edits_ptr or None, n_edits,
+                                        d_seq_out_ptr or None, out_capacity, d_offsets_out_ptr))
 
     def seq_extend_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, max_ext: int, depth: int = 2):
         """kmx_extend_seqs: every seed walked to the right along the unique path of k-mers answered >= thr (the rule:

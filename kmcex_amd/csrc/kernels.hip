@@ -3059,4 +3059,5 @@ void micro(int mode, u64 *buf, u64 ncell, u64 n_lanes, u64 salt, u64 *sink, hipS
 #include "range_kernels.h"
 #include "count_kernels.h"
 #include "correct_kernels.h"
+#include "edit_kernels.h"
 #include "extend_kernels.h"

@@ -242,6 +242,11 @@ struct kmx_model {
 		// kmx_correct_seqs*: one bit per window of a piece and its halos, one byte per workgroup of the piece
 		DevBuf<u64> d_corr_bits;
 		DevBuf<unsigned char> d_corr_flags;
+		// kmx_edit_seqs* / kmx_apply_edits_dev: one weak bit per window of the WHOLE input, the edit counter (and the totals of
+		// an apply), room for the sort's second list and the scan of an apply, rocPRIM's scratch
+		DevBuf<u64> d_edit_bits, d_edit_alt;
+		DevBuf<unsigned long long> d_edit_cnt;
+		DevBuf<unsigned char> d_edit_tmp;
 		// kmx_extend_seqs*: the walks of one chunk of seeds, the two lists of live walks and their three counters
 		DevBuf<ExtWalk> d_ext_walk;
 		DevBuf<u32> d_ext_lists, d_ext_cnt;
@@ -2368,6 +2373,170 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 	return KMX_OK;
 }
 
+// ------------------------------------------------------------------------------------------ edits along sequences
+// kmx_edit_seqs: substitutions and single-base insertions / deletions from the answers of kmx_query_seqs (the rule:
+// include/kmx.h; the kernels: edit_kernels.h, edit_device.hip).  A run that touches an end of its sequence takes other
+// candidates than one inside, however long it is, so no halo of fixed width decides a site: the weak bits of the whole input
+// are written first (n_bases / 8 bytes on the handle), piece by piece, then the sites are decided piece by piece.  Both passes
+// need the bases on the device, so the host variant uploads them whole instead of streaming them through the pinned slots.
+static_assert(sizeof(kmx_seq_edits) == 80 && sizeof(SeqEdits) == 80 && sizeof(kmx_edit) == 8, "kmx_seq_edits is 80 bytes");
+static_assert(offsetof(kmx_seq_edits, n_sub) == offsetof(SeqEdits, n_sub) && offsetof(kmx_seq_edits, n_ins) == offsetof(SeqEdits, n_ins) &&
+              offsetof(kmx_seq_edits, out_len) == offsetof(SeqEdits, out_len), "SeqEdits (kmx_types.h) is the layout of kmx_seq_edits");
+
+static int edit_args(kmx_model *m, int min_support, int ops)
+{
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
+	if (ops < 1 || ops > 7) return fail(KMX_E_ARG, "ops = %d, not a non-empty subset of KMX_EDIT_OPS_SUB | _DEL | _INS", ops);
+	return KMX_OK;
+}
+
+// the call on device buffers, arguments checked, the handle's query lock held, n_seqs and n_bases > 0
+static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, u64 *d_edits, u64 capacity, u64 *n_edits, SeqEdits *d_rec)
+{
+	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece, pa = (piece + 255) / 256 * 256;
+	auto &F = m->qfeed;
+	if (ensure_correct_buffers(m, pa, 0, 0) != KMX_OK || F.d_edit_bits.ensure((size_t)((n_bases + 255) / 256 * 4 + 2), m->stream) != hipSuccess ||
+	    F.d_edit_cnt.ensure(2, m->stream) != hipSuccess)
+		return fail(KMX_E_NOMEM, "the buffers of a sequence edit could not be allocated");
+	kmxk::seq_edits_init(d_rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	HIPCHK(hipMemsetAsync(F.d_edit_cnt.get(), 0, 8, m->stream));
+	int par = 0;
+	for (u64 w0 = 0; w0 < n_bases; w0 += pa, par ^= 1)
+		kmxk::edit_weak_piece(m->md, d_seq, n_bases, d_offs, n_seqs, w0, std::min<u64>(pa, n_bases - w0), thr, F.d_edit_bits, F.d_seq_list, (u32)F.d_seq_list.cap(),
+		                      F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	const EditDev ed{d_rec, d_edits, d_edits ? capacity : 0, F.d_edit_cnt.get(), thr, min_support, ops};
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece)
+		kmxk::edit_sites_piece(m->md, d_seq, n_bases, d_offs, n_seqs, p0, std::min<u64>(piece, n_bases - p0), F.d_edit_bits, ed, F.d_corr_flags, m->stream, &m->prof);
+	unsigned long long found = 0;
+	HIPCHK(hipMemcpyAsync(&found, F.d_edit_cnt.get(), 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	HIPCHK(hipGetLastError());
+	if (n_edits) *n_edits = found;
+	if (found > capacity || (found && !d_edits)) return fail(KMX_E_RANGE, "%llu edits were found, the list has room for %llu", found, (unsigned long long)capacity);
+	if (found > 1) {
+		if (F.d_edit_alt.ensure((size_t)found, m->stream) != hipSuccess) return fail(KMX_E_NOMEM, "the buffers of a sequence edit could not be allocated");
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		const hipError_t e = kmxk::edit_sort(d_edits, F.d_edit_alt, found, F.d_edit_tmp, m->stream);
+		KPROF_END(&m->prof, m->stream);
+		if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of a sequence edit could not be allocated"); }
+		HIPCHK(e);
+	}
+	return KMX_OK;
+}
+
+static int kmx_edit_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops,
+                                  kmx_edit *d_edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *d_rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	TRY(edit_args(m, min_support, ops));
+	if (!n_seqs) return KMX_OK;
+	if (!d_offsets || !n_edits || (n_bases && !d_seq) || (capacity && !d_edits)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	*n_edits = 0;
+	if (!n_bases) {
+		kmxk::seq_edits_init((SeqEdits *)d_rec, (const u64 *)d_offsets, n_seqs, 0, m->k, m->stream, &m->prof);
+		return KMX_OK;
+	}
+	return edit_seqs_core(m, (const unsigned char *)d_seq, (const u64 *)d_offsets, n_seqs, n_bases, thr, min_support, ops, (u64 *)d_edits, capacity, (u64 *)n_edits, (SeqEdits *)d_rec);
+}
+
+static int kmx_edit_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops,
+                              kmx_edit *edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *rec)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	TRY(edit_args(m, min_support, ops));
+	if (!n_seqs) return KMX_OK;
+	TRY(check_offsets(offsets, n_seqs));
+	if (!n_edits || (capacity && !edits)) return fail(KMX_E_ARG, "null argument");
+	const u64 n_bases = offsets[n_seqs];
+	*n_edits = 0;
+	if (!n_bases) {
+		if (rec) for (u64 i = 0; i < n_seqs; i++) rec[i] = kmx_seq_edits{0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		return KMX_OK;
+	}
+	if (!seq) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	const u64 cap = std::min<u64>(capacity, n_bases / 3 + 1);          // more than that is never found
+	DevBuf<unsigned char> d_seq;
+	DevBuf<u64> d_offs, d_edits;
+	DevBuf<SeqEdits> d_rec;
+	if (d_seq.alloc(n_bases) != hipSuccess || d_offs.alloc(n_seqs + 1) != hipSuccess || (cap && d_edits.alloc(cap) != hipSuccess) || (rec && d_rec.alloc(n_seqs) != hipSuccess))
+		return fail(KMX_E_NOMEM, "device memory for %llu bases of %llu sequences could not be allocated", (unsigned long long)n_bases, (unsigned long long)n_seqs);
+	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });
+	HIPCHK(hipMemcpyAsync(d_seq, seq, n_bases, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	const int rc = edit_seqs_core(m, d_seq, d_offs, n_seqs, n_bases, thr, min_support, ops, cap ? d_edits.get() : nullptr, cap, (u64 *)n_edits, rec ? d_rec.get() : nullptr);
+	if (rc != KMX_OK && rc != KMX_E_RANGE) return rc;
+	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+	if (rc == KMX_OK && *n_edits) HIPCHK(hipMemcpyAsync(edits, d_edits.get(), *n_edits * 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	return rc;
+}
+
+// the definition of applying a list: per input position the inserted base, then the input byte, its SUB base or nothing
+static int kmx_apply_edits_impl(const char *seq, const uint64_t *offsets, uint64_t n_seqs, const kmx_edit *edits, uint64_t n_edits, char *seq_out, uint64_t out_capacity, uint64_t *offsets_out)
+{
+	if (!offsets || !offsets_out) return fail(KMX_E_ARG, "null argument");
+	TRY(check_offsets(offsets, n_seqs));
+	const u64 n_bases = offsets[n_seqs];
+	if ((n_bases && !seq) || (n_edits && !edits) || (out_capacity && !seq_out)) return fail(KMX_E_ARG, "null argument");
+	u64 n_ins = 0, n_del = 0;
+	for (u64 i = 0; i < n_edits; i++) {
+		const u64 e = edits[i], pos = e >> 8, op = (e >> 4) & 15, code = e & 15;
+		if (i && e <= edits[i - 1]) return fail(KMX_E_ARG, "the edit list is not strictly ascending at entry %llu", (unsigned long long)i);
+		if (pos >= n_bases || op < KMX_EDIT_SUB || op > KMX_EDIT_INS || code > 3 || (op == KMX_EDIT_DEL && code)) return fail(KMX_E_ARG, "entry %llu of the edit list is not an edit of this input", (unsigned long long)i);
+		if (i && (edits[i - 1] >> 8) == pos && op != KMX_EDIT_INS) return fail(KMX_E_ARG, "two of SUB / DEL at position %llu", (unsigned long long)pos);
+		n_ins += op == KMX_EDIT_INS;
+		n_del += op == KMX_EDIT_DEL;
+	}
+	if (n_bases + n_ins - n_del > out_capacity) return fail(KMX_E_RANGE, "the edited sequences take %llu bytes, seq_out has %llu", (unsigned long long)(n_bases + n_ins - n_del), (unsigned long long)out_capacity);
+	u64 i = 0, o = 0, u = 0;
+	for (u64 p = 0; p <= n_bases; p++) {
+		while (u <= n_seqs && offsets[u] == p) offsets_out[u++] = o;
+		if (p == n_bases) break;
+		char c = seq[p];
+		bool drop = false;
+		for (; i < n_edits && (edits[i] >> 8) == p; i++) {
+			const u64 op = (edits[i] >> 4) & 15;
+			if (op == KMX_EDIT_SUB) c = "ACGT"[edits[i] & 3];
+			else if (op == KMX_EDIT_DEL) drop = true;
+			else seq_out[o++] = "ACGT"[edits[i] & 3];
+		}
+		if (!drop) seq_out[o++] = c;
+	}
+	return KMX_OK;
+}
+
+// the same on the device; the list is not validated there: a list that is none gives wrong bytes, never a write outside
+// d_seq_out[0, out_capacity) / d_offsets_out[0, n_seqs].  Waits once, for the length of the output.
+static int kmx_apply_edits_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const kmx_edit *d_edits, uint64_t n_edits,
+                                    char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	if (!d_offsets || !d_offsets_out || (n_bases && !d_seq) || (n_edits && !d_edits) || (out_capacity && !d_seq_out)) return fail(KMX_E_ARG, "null argument");
+	if (n_edits >> 32) return fail(KMX_E_ARG, "more than 2^32 edits");
+	HIPCHK(hipSetDevice(m->device));
+	auto &F = m->qfeed;
+	if (F.d_edit_alt.ensure((size_t)(2 * (n_edits + 1)), m->stream) != hipSuccess || F.d_edit_cnt.ensure(2, m->stream) != hipSuccess)
+		return fail(KMX_E_NOMEM, "the buffers of an edit application could not be allocated");
+	KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+	const hipError_t e = kmxk::edit_apply((const unsigned char *)d_seq, (const u64 *)d_offsets, n_seqs, n_bases, (const u64 *)d_edits, n_edits, F.d_edit_alt, (unsigned char *)d_seq_out, out_capacity,
+	                                      (u64 *)d_offsets_out, F.d_edit_cnt.get() + 1, F.d_edit_tmp, m->stream);
+	KPROF_END(&m->prof, m->stream);
+	if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of an edit application could not be allocated"); }
+	HIPCHK(e);
+	unsigned long long tot = 0;
+	HIPCHK(hipMemcpyAsync(&tot, F.d_edit_cnt.get() + 1, 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	const u64 need = n_bases + (tot & 0xFFFFFFFFULL) - (tot >> 32);
+	if (need > out_capacity) return fail(KMX_E_RANGE, "the edited sequences take %llu bytes, d_seq_out has %llu", (unsigned long long)need, (unsigned long long)out_capacity);
+	return KMX_OK;
+}
+
 // ------------------------------------------------------------------------------------------ extension along unique paths
 // kmx_extend_seqs: seeds walked to the right through the model's de Bruijn graph (the rule: include/kmx.h; the kernels:
 // extend_kernels.h).  The seeds run in chunks of at most kExtChunk: the walk states and live lists on the handle are one
@@ -2981,6 +3150,10 @@ extern "C" int kmx_summarise_seqs(kmx_model *m, const char *seq, const uint64_t 
 extern "C" int kmx_summarise_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out) { return guarded([&] { return kmx_summarise_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, n_thr, d_out); }); }
 extern "C" int kmx_correct_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, char *seq_out, kmx_seq_correction *rec) { return guarded([&] { return kmx_correct_seqs_impl(m, seq, offsets, n_seqs, thr, min_support, seq_out, rec); }); }
 extern "C" int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec) { return guarded([&] { return kmx_correct_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, d_seq_out, d_rec); }); }
+extern "C" int kmx_edit_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops, kmx_edit *edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *rec) { return guarded([&] { return kmx_edit_seqs_impl(m, seq, offsets, n_seqs, thr, min_support, ops, edits, capacity, n_edits, rec); }); }
+extern "C" int kmx_edit_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, kmx_edit *d_edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *d_rec) { return guarded([&] { return kmx_edit_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, ops, d_edits, capacity, n_edits, d_rec); }); }
+extern "C" int kmx_apply_edits(const char *seq, const uint64_t *offsets, uint64_t n_seqs, const kmx_edit *edits, uint64_t n_edits, char *seq_out, uint64_t out_capacity, uint64_t *offsets_out) { return guarded([&] { return kmx_apply_edits_impl(seq, offsets, n_seqs, edits, n_edits, seq_out, out_capacity, offsets_out); }); }
+extern "C" int kmx_apply_edits_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const kmx_edit *d_edits, uint64_t n_edits, char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out) { return guarded([&] { return kmx_apply_edits_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_edits, n_edits, d_seq_out, out_capacity, d_offsets_out); }); }
 extern "C" int kmx_extend_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int max_ext, int depth, char *ext, kmx_seq_extension *rec) { return guarded([&] { return kmx_extend_seqs_impl(m, seq, offsets, n_seqs, thr, max_ext, depth, ext, rec); }); }
 extern "C" int kmx_extend_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec) { return guarded([&] { return kmx_extend_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, max_ext, depth, d_ext, d_rec); }); }
 extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }

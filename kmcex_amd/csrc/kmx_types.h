@@ -247,6 +247,20 @@ struct CorrDev {
 };
 #define KMX_CORR_HALO(k) (2 * (k) + 2)         // windows of weak bits a piece needs beyond each of its ends
 
+// kmx_edit_seqs: one record per sequence, the layout of kmx_seq_edits (include/kmx.h; kmx_api.hip asserts it) ...
+struct SeqEdits {
+	u64 n_windows, n_weak, n_runs, n_sites, n_sub, n_del, n_ins, n_ambiguous, n_unfixable, out_len;
+};
+// ... and where k_edit_sites leaves what it decides (edit_kernels.h): an edit goes to edits[(*count)++] as a kmx_edit when
+// there is room; *count is zero before the first piece and counts every edit found.  rec may be null.
+struct EditDev {
+	SeqEdits *rec;
+	u64 *edits;
+	u64 cap;
+	unsigned long long *count;
+	int thr, min_support, ops;
+};
+
 // kmx_extend_seqs: one record per seed, the layout of kmx_seq_extension (include/kmx.h; kmx_api.hip asserts it) ...
 struct SeqExtension {
 	u32 n_ext, stop;

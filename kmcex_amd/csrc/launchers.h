@@ -34,6 +34,9 @@ void seq_summary_finish(SeqSummary *, const u64 *, u64, u64, int, hipStream_t, K
 void summarise_seq(const ModelDev &, const unsigned char *, u64, u64, const u64 *, u64, u64, u64, const SeqSumDev &, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
 void seq_correction_init(SeqCorrection *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
 void correct_piece(const ModelDev &, const unsigned char *, u64, u64, u64, const u64 *, u64, u64, u64, u64, u64, u64 *, const CorrDev &, unsigned char *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void seq_edits_init(SeqEdits *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
+void edit_weak_piece(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int, u64 *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void edit_sites_piece(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, const u64 *, const EditDev &, unsigned char *, hipStream_t, KernelProf *);
 void extend_walks(const ModelDev &, const unsigned char *, u64, const u64 *, u32, const ExtDev &, u32 *, u32 *, int, hipStream_t, KernelProf *);
 void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
 void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
@@ -54,4 +57,7 @@ hipError_t count_piece(int, int, u64 *, u64 *, u64, u64, u32 *, unsigned long lo
 hipError_t count_merge(int, const u64 *, const u32 *, u64, const u64 *, const u32 *, u64, u64 *, u32 *, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t count_reduce(int, const u64 *, const u32 *, u64, u64 *, u32 *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t count_filter(int, const u64 *, const u32 *, u64, u32, u32, u32, u64 *, u32 *, unsigned char *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+// edit_device.hip: the edit list sorted (keys -> keys, alt is room for n more), and applied to the bases it was found on
+hipError_t edit_sort(u64 *keys, u64 *alt, u64 n, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t edit_apply(const unsigned char *, const u64 *, u64, u64, const u64 *, u64, u64 *, unsigned char *, u64, u64 *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
 }   // namespace kmxk
