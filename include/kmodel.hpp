@@ -268,6 +268,38 @@ public:
 		return out;
 	}
 
+	// Reads polished to a fixed point (kmx_polish_seqs; the rule is in kmx.h): seq_edit's rule iterated per read on the device
+	// until a pass finds nothing in it, or max_passes passes ran.  Returns the polished reads; rec, if given, receives one
+	// record per read (passes, whether it converged, the edits of every kind, the last pass's counters).
+	std::string seq_polish(const std::string &seq, int thr, int min_support = 1, int ops = 7, int max_passes = 8, kmx_seq_polish *rec = 0)
+	{
+		std::vector<kmx_seq_polish> r;
+		const std::string out = seq_polish(std::vector<std::string>(1, seq), thr, min_support, ops, max_passes, &r)[0];
+		if (rec) *rec = r[0];
+		return out;
+	}
+	std::vector<std::string> seq_polish(const std::vector<std::string> &seqs, int thr, int min_support = 1, int ops = 7, int max_passes = 8, std::vector<kmx_seq_polish> *rec = 0)
+	{
+		std::vector<uint64_t> off(seqs.size() + 1, 0), off_out(seqs.size() + 1, 0);
+		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+		std::string flat;
+		flat.reserve((size_t)off.back());
+		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		if (rec) rec->assign(seqs.size(), kmx_seq_polish());
+		std::string fixed(flat.size() + flat.size() / 16 + 64, '\0');
+		if (!seqs.empty()) {
+			int rc = kmx_polish_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
+			if (rc == KMX_E_RANGE && off_out.back() > fixed.size()) {   // offsets_out is complete: once more with the room it asks for
+				fixed.assign((size_t)off_out.back(), '\0');
+				rc = kmx_polish_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
+			}
+			check(rc);
+		}
+		std::vector<std::string> out(seqs.size());
+		for (size_t i = 0; i < seqs.size(); i++) out[i] = fixed.substr((size_t)off_out[i], (size_t)(off_out[i + 1] - off_out[i]));
+		return out;
+	}
+
 	// Seeds extended to the right along the unique path of k-mers answered >= thr (kmx_extend_seqs; the rule is in kmx.h):
 	// at most max_ext bases each, ties broken by a lookahead of `depth` (0 ... 3).  Returns the appended bases; rec, if given,
 	// receives one record per seed (why the walk stopped, the counts along it).

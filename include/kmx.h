@@ -343,7 +343,7 @@ int kmx_correct_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offs
  *   distinct sites are distinct and junctions lie inside their sequence, so (pos, op) is unique: one position carries at most
  *   one of SUB / DEL, possibly plus one INS.
  * Out of scope: more than one base per edit; two errors within k of each other stay substitution-only (both, len > k); more
- * than the two outer errors of a long run per call (call again on the output); quality values.                             */
+ * than the two outer errors of a long run per call (call again on the output, or kmx_polish_seqs); quality values.         */
 #define KMX_EDIT_OPS_SUB 1
 #define KMX_EDIT_OPS_DEL 2
 #define KMX_EDIT_OPS_INS 4
@@ -386,6 +386,62 @@ int kmx_apply_edits(const char *seq, const uint64_t *offsets, uint64_t n_seqs, c
  * wrong bytes, never a write outside d_seq_out[0, out_capacity) and d_offsets_out[0, n_seqs].  Needs no built model.       */
 int kmx_apply_edits_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const kmx_edit *d_edits, uint64_t n_edits,
                         char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out);
+
+/* Reads polished to a fixed point: kmx_edit_seqs' rule iterated per read, entirely on the device.  One pass of kmx_edit_seqs
+ * fixes at most the two outer errors of a long run, leaves two errors within k of each other as they are, and cannot decide
+ * an edit whose neighbour must be fixed first; the loop that handles them is this call.  kmx_edit_seqs decides everything
+ * about a sequence from that sequence's own bytes and the model's answers, so the definition is per sequence and order-free.
+ * For a sequence, x_0 is the input.  For p = 1 .. max_passes:
+ *   1. (E_p, r_p) = the edit list and the kmx_seq_edits record that kmx_edit_seqs(thr, min_support, ops) gives x_(p-1) as a
+ *      batch of its own.
+ *   2. E_p is empty: stop; the sequence has converged: n_passes = p, converged = 1.
+ *   3. Otherwise x_p = kmx_apply_edits(x_(p-1), E_p).
+ * If pass max_passes still produced edits, n_passes = max_passes and converged = 0.  The output is the last x.  An edit always
+ * changes the bytes (a SUB has c != x[a], DEL / INS change the length), so "no edits" is the fixed point: a sequence that
+ * found none would find none again, and retiring it after that pass is exact.  Consequences:
+ *   - the result is byte for byte that of the host loop: kmx_edit_seqs then kmx_apply_edits on the whole batch, repeated until
+ *     a pass returns an empty list or max_passes passes ran;
+ *   - it does not depend on the variant, the cut into pieces, or which reads share a batch;
+ *   - max_passes = 1 gives the reads of kmx_edit_seqs + kmx_apply_edits, and a record whose sums are that record's;
+ *   - with ops = KMX_EDIT_OPS_SUB it is iterated kmx_correct_seqs.
+ * Only the reads a pass edited are examined by the next one; a read that pass 1 leaves alone is never copied until the final
+ * gather.  Nothing guarantees an end in general (no read of the test data returns to a string it held before, and all have
+ * converged by pass 3), hence max_passes in [1, KMX_POLISH_MAX_PASSES].
+ * Out of scope: quality values; FASTQ in / out; a composed edit list in input coordinates (ambiguous once two passes touch
+ * one place: run kmx_edit_seqs pass by pass for lists); several GPUs; choosing thr.                                          */
+#define KMX_POLISH_MAX_PASSES 16
+typedef struct kmx_seq_polish {          /* one per sequence; 96 bytes, no padding */
+	uint64_t n_passes, converged;
+	uint64_t n_sub, n_del, n_ins;        /* sums over the passes that examined the sequence */
+	uint64_t out_len;                    /* length of the output read */
+	uint64_t n_windows, n_weak, n_runs, n_sites, n_ambiguous, n_unfixable;   /* of the last pass that examined it; when converged = 1 they describe the output read itself */
+} kmx_seq_polish;
+/* Sequences in the layout of kmx_query_seqs.  seq_out[out_capacity] receives the polished reads in the input's order,
+ * offsets_out[n_seqs + 1] the running sum of out_len, rec[n_seqs] the records (may be NULL), *passes_run (may be NULL) the
+ * largest n_passes.  offsets_out[n_seqs] > out_capacity: KMX_E_RANGE; records and offsets_out are complete, the bytes that fit
+ * are written, nothing is written at or behind seq_out[out_capacity].  KMX_E_ARG when max_passes is outside [1, 16], ops outside
+ * 1..7, min_support outside [1, 64], offsets[0] != 0, the offsets decrease, or seq_out overlaps seq (lengths change: there is no
+ * in-place form), all checked before anything runs; n_seqs == 0: KMX_OK, nothing written; no bases but n_seqs > 0: records with
+ * n_passes = 1, converged = 1 and zeros elsewhere, offsets_out all 0.  KMX_E_STATE before the model is built or loaded;
+ * KMX_E_NOMEM leaves the handle usable.  The bases go up once; reads, offsets and records come down once; nothing else crosses
+ * the link between passes.  Device memory, kept on the handle between calls: with B_p the bytes of the reads pass p examines
+ * (B_1 = n_bases, B_2 = the bytes of the reads pass 1 edited, ...), B_1 / 8 for the weak bits, 16 (B_1 / 3 + 1) for a pass's
+ * list and its sort, B_2 + B_3 for the two batches the passes alternate between, and a parking area for the reads that retire
+ * after pass 1 (those of pass max_passes go straight to seq_out): at most B_2 plus their insertions in all; about 150 bytes
+ * per sequence for records, lengths, homes and maps.  The host
+ * variant adds n_bases + min(offsets_out[n_seqs], out_capacity).  A query-class call, timed as kernel class 6 under
+ * kmx_set_profile(m, 1).                                                                                                   */
+int kmx_polish_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops, int max_passes,
+                    char *seq_out, uint64_t out_capacity, uint64_t *offsets_out /* [n_seqs + 1] */,
+                    kmx_seq_polish *rec /* [n_seqs] or NULL */, uint64_t *passes_run /* or NULL */);
+/* the same on DEVICE buffers d_seq[n_bases], d_offsets[n_seqs + 1], d_seq_out[out_capacity], d_offsets_out[n_seqs + 1],
+ * d_rec[n_seqs] (or NULL); passes_run is on the HOST.  Pass 1 reads d_seq in place.  Enqueued on the model's stream; it waits
+ * for the stream once per pass, where the pass's counts reach the host, and once for the final length (which rides on the last
+ * pass's wait when that is pass max_passes), nowhere else, and returns with the last copies into d_seq_out enqueued.  The offsets are not validated on the host: each is clamped into [0, n_bases] where it is read, so bad
+ * offsets give wrong reads (or KMX_E_ARG, when they claim more bytes than n_bases), never an access outside d_seq[0, n_bases),
+ * d_seq_out[0, out_capacity), d_offsets_out[0, n_seqs], d_rec[0, n_seqs).                                                   */
+int kmx_polish_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, int max_passes,
+                        char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out, kmx_seq_polish *d_rec /* or NULL */, uint64_t *passes_run /* HOST, or NULL */);
 
 /* Seeds extended to the right along unique k-mer paths: a walk through the de Bruijn graph the model implicitly holds (the
  * primitive of unitig construction, gap filling, seed-and-extend).  occ(s) is the answer kmx_query_ascii gives the k bytes s;

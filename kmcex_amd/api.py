@@ -49,7 +49,7 @@ ABI_SYMBOLS = [
     "kmx_create_on", "kmx_build_from_kmc_multi", "kmx_build_from_kmc_multi_ex", "kmx_range_begin", "kmx_range_buffers", "kmx_range_emit_dev", "kmx_range_verdict_dev", "kmx_range_resolve_dev", "kmx_range_commit_dev", "kmx_range_flush_dev", "kmx_range_inband", "kmx_range_verdict_inband_dev", "kmx_range_commit_inband_dev",
     "kmx_query_seqs", "kmx_query_seqs_dev", "kmx_summarise_seqs", "kmx_summarise_seqs_dev",
     "kmx_correct_seqs", "kmx_correct_seqs_dev",
-    "kmx_edit_seqs", "kmx_edit_seqs_dev", "kmx_apply_edits", "kmx_apply_edits_dev",
+    "kmx_edit_seqs", "kmx_edit_seqs_dev", "kmx_apply_edits", "kmx_apply_edits_dev", "kmx_polish_seqs", "kmx_polish_seqs_dev",
     "kmx_extend_seqs", "kmx_extend_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
 ]
@@ -70,6 +70,10 @@ SEQ_CORRECTION_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_
 # kmx_seq_edits of include/kmx.h (what KModel.seq_edit_flat returns beside the edit list): 10 x uint64
 SEQ_EDITS_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_weak", "n_runs", "n_sites", "n_sub", "n_del", "n_ins", "n_ambiguous", "n_unfixable", "out_len")])
 EDIT_OPS_SUB, EDIT_OPS_DEL, EDIT_OPS_INS = 1, 2, 4
+# kmx_seq_polish of include/kmx.h (what KModel.seq_polish_flat returns beside the reads): 12 x uint64
+SEQ_POLISH_DTYPE = np.dtype([(f, "<u8") for f in ("n_passes", "converged", "n_sub", "n_del", "n_ins", "out_len",
+                                                   "n_windows", "n_weak", "n_runs", "n_sites", "n_ambiguous", "n_unfixable")])
+POLISH_MAX_PASSES = 16
 EDIT_SUB, EDIT_DEL, EDIT_INS = 1, 2, 3
 # kmx_seq_extension of include/kmx.h (what KModel.seq_extend_flat returns beside the rows of appended bases): 32 bytes
 SEQ_EXTENSION_DTYPE = np.dtype([("n_ext", "<u4"), ("stop", "<u4"), ("seed_occ", "<i4"), ("min_occ", "<i4"), ("max_occ", "<i4"), ("n_lookahead", "<u4"), ("sum_occ", "<u8")])
@@ -186,6 +190,8 @@ def load_library():
     _sig(L, "kmx_edit_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, vp, u64, vp, vp])
     _sig(L, "kmx_apply_edits", [vp, vp, u64, vp, u64, vp, u64, vp])
     _sig(L, "kmx_apply_edits_dev", [vp, vp, vp, u64, u64, vp, u64, vp, u64, vp])
+    _sig(L, "kmx_polish_seqs", [vp, vp, vp, u64, i32, i32, i32, i32, vp, u64, vp, vp, vp])
+    _sig(L, "kmx_polish_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, i32, vp, u64, vp, vp, vp])
     _sig(L, "kmx_extend_seqs", [vp, vp, vp, u64, i32, i32, i32, vp, vp])
     _sig(L, "kmx_extend_seqs_dev", [vp, vp, vp, u64, u64, i32, i32, i32, vp, vp])
     _sig(L, "kmx_count_begin", [vp, i32])
@@ -658,6 +664,62 @@ class KModel:
         """kmx_apply_edits_dev: the (sorted) device list applied to the device bases it was found on; d_offsets_out: n_seqs + 1"""
         _chk(self.L.kmx_apply_edits_dev(self.h, d_seq_ptr, d_offsets_ptr, n_seqs, n_bases, d_edits_ptr or None, n_edits,
                                         d_seq_out_ptr or None, out_capacity, d_offsets_out_ptr))
+
+    def seq_polish_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, min_support: int = 1, ops: int = 7, max_passes: int = 8):
+        """kmx_polish_seqs: kmx_edit_seqs' rule iterated per read until a pass finds nothing in it, or max_passes passes ran
+        (the rule: include/kmx.h) -> (uint8 polished bases, uint64 offsets_out [n_seqs + 1], SEQ_POLISH_DTYPE records [n_seqs],
+        passes run).  The output's length is not known beforehand: the call is repeated with the exact room when the first
+        guess (the input's length and a sixteenth) is too small."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+        if offsets.size == 0:
+            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        n_bases = int(offsets[-1])
+        if n_bases > buf.size:
+            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        n_seqs = offsets.size - 1
+        rec = np.zeros(n_seqs, dtype=SEQ_POLISH_DTYPE)
+        off = np.zeros(n_seqs + 1, dtype=np.uint64)
+        passes = C.c_uint64(0)
+        cap = n_bases + n_bases // 16 + 64
+        while True:
+            out = np.empty(cap, dtype=np.uint8)
+            rc = self.L.kmx_polish_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, n_seqs, int(thr), int(min_support), int(ops), int(max_passes),
+                                        out.ctypes.data, out.size, off.ctypes.data, rec.ctypes.data, C.addressof(passes))
+            if rc == -5 and int(off[-1]) > cap:                      # KMX_E_RANGE: offsets_out is complete
+                cap = int(off[-1])
+                continue
+            _chk(rc)
+            return out[:int(off[-1])].copy(), off, rec, int(passes.value)
+
+    def seq_polish(self, seqs, thr: int, min_support: int = 1, ops: int = 7, max_passes: int = 8):
+        """seq_polish_flat for a str / bytes sequence (-> (polished bytes, record)) or a list of them (-> (list of polished
+        bytes, records))"""
+        single = isinstance(seqs, (str, bytes))
+        items = [seqs] if single else list(seqs)
+        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+        buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        out, off, rec, _ = self.seq_polish_flat(buf, offsets, thr, min_support, ops, max_passes)
+        fixed = [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(raw))]
+        return (fixed[0], rec[0]) if single else (fixed, rec)
+
+    def seq_polish_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int, ops: int, max_passes: int,
+                       d_seq_out_ptr: int, out_capacity: int, d_offsets_out_ptr: int, d_rec_ptr: int = 0) -> int:
+        """kmx_polish_seqs_dev: device buffers (d_seq_out: out_capacity bytes, not overlapping d_seq; d_offsets_out: n_seqs + 1
+        uint64; d_rec: n_seqs records of 96 bytes, or 0) -> the passes run.  KmxError -5 (KMX_E_RANGE) with .passes_run when
+        the reads need more than out_capacity bytes: d_offsets_out[n_seqs] says how many.  Waits once per pass and once for the
+        final length; returns with the gather enqueued."""
+        passes = C.c_uint64(0)
+        rc = self.L.kmx_polish_seqs_dev(self.h, d_seq_ptr or None, d_offsets_ptr or None, n_seqs, n_bases, int(thr), int(min_support), int(ops), int(max_passes),
+                                        d_seq_out_ptr or None, out_capacity, d_offsets_out_ptr or None, d_rec_ptr or None, C.addressof(passes))
+        try:
+            _chk(rc)
+        except KmxError as e:
+            e.passes_run = int(passes.value)
+            raise
+        return int(passes.value)
 
     def seq_extend_flat(self, buf: np.ndarray, offsets: np.ndarray, thr: int, max_ext: int, depth: int = 2):
         """kmx_extend_seqs: every seed walked to the right along the unique path of k-mers answered >= thr (the rule:

@@ -247,6 +247,15 @@ struct kmx_model {
 		DevBuf<u64> d_edit_bits, d_edit_alt;
 		DevBuf<unsigned long long> d_edit_cnt;
 		DevBuf<unsigned char> d_edit_tmp;
+		// kmx_polish_seqs*: one pass's edit list, its scan and its kmx_seq_edits records; kinds, targets and the scanned triples of
+		// the active reads; the two active batches (bytes, offsets, map to the caller's reads) that passes 2, 3, ... alternate
+		// between; a parking area per pass; the reads' homes, lengths and (when the caller wants none) records
+		DevBuf<u64> d_pol_edits, d_pol_escan, d_pol_delta, d_pol_home, d_pol_len, d_pol_offs[2], d_pol_ids[2];
+		DevBuf<unsigned char> d_pol_kind, d_pol_act[2], d_pol_park[POLISH_MAX_PASSES + 1];
+		DevBuf<SeqEdits> d_pol_re;
+		DevBuf<SeqPolish> d_pol_rec;
+		DevBuf<PolishTri> d_pol_tri;
+		PinBuf<u64> h_pol_cnt;                                     // where a pass's counts reach the host
 		// kmx_extend_seqs*: the walks of one chunk of seeds, the two lists of live walks and their three counters
 		DevBuf<ExtWalk> d_ext_walk;
 		DevBuf<u32> d_ext_lists, d_ext_cnt;
@@ -2391,8 +2400,9 @@ static int edit_args(kmx_model *m, int min_support, int ops)
 	return KMX_OK;
 }
 
-// the call on device buffers, arguments checked, the handle's query lock held, n_seqs and n_bases > 0
-static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, u64 *d_edits, u64 capacity, u64 *n_edits, SeqEdits *d_rec)
+// records, weak bits and sites of a batch on device buffers, enqueued: the edits lie unsorted in d_edits, their number in
+// d_edit_cnt[0].  Arguments checked, the handle's query lock held, n_seqs and n_bases > 0.
+static int edit_seqs_enqueue(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, u64 *d_edits, u64 capacity, SeqEdits *d_rec)
 {
 	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece, pa = (piece + 255) / 256 * 256;
 	auto &F = m->qfeed;
@@ -2408,12 +2418,13 @@ static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d
 	const EditDev ed{d_rec, d_edits, d_edits ? capacity : 0, F.d_edit_cnt.get(), thr, min_support, ops};
 	for (u64 p0 = 0; p0 < n_bases; p0 += piece)
 		kmxk::edit_sites_piece(m->md, d_seq, n_bases, d_offs, n_seqs, p0, std::min<u64>(piece, n_bases - p0), F.d_edit_bits, ed, F.d_corr_flags, m->stream, &m->prof);
-	unsigned long long found = 0;
-	HIPCHK(hipMemcpyAsync(&found, F.d_edit_cnt.get(), 8, hipMemcpyDeviceToHost, m->stream));
-	HIPCHK(hipStreamSynchronize(m->stream));
-	HIPCHK(hipGetLastError());
-	if (n_edits) *n_edits = found;
-	if (found > capacity || (found && !d_edits)) return fail(KMX_E_RANGE, "%llu edits were found, the list has room for %llu", found, (unsigned long long)capacity);
+	return KMX_OK;
+}
+
+// the list of `found` edits sorted (enqueued)
+static int edit_seqs_sort(kmx_model *m, u64 *d_edits, u64 found)
+{
+	auto &F = m->qfeed;
 	if (found > 1) {
 		if (F.d_edit_alt.ensure((size_t)found, m->stream) != hipSuccess) return fail(KMX_E_NOMEM, "the buffers of a sequence edit could not be allocated");
 		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
@@ -2423,6 +2434,19 @@ static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d
 		HIPCHK(e);
 	}
 	return KMX_OK;
+}
+
+// the call on device buffers: waits once, where the count reaches the host
+static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, u64 *d_edits, u64 capacity, u64 *n_edits, SeqEdits *d_rec)
+{
+	TRY(edit_seqs_enqueue(m, d_seq, d_offs, n_seqs, n_bases, thr, min_support, ops, d_edits, capacity, d_rec));
+	unsigned long long found = 0;
+	HIPCHK(hipMemcpyAsync(&found, m->qfeed.d_edit_cnt.get(), 8, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	HIPCHK(hipGetLastError());
+	if (n_edits) *n_edits = found;
+	if (found > capacity || (found && !d_edits)) return fail(KMX_E_RANGE, "%llu edits were found, the list has room for %llu", found, (unsigned long long)capacity);
+	return edit_seqs_sort(m, d_edits, found);
 }
 
 static int kmx_edit_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops,
@@ -2534,6 +2558,195 @@ static int kmx_apply_edits_dev_impl(kmx_model *m, const char *d_seq, const uint6
 	HIPCHK(hipStreamSynchronize(m->stream));
 	const u64 need = n_bases + (tot & 0xFFFFFFFFULL) - (tot >> 32);
 	if (need > out_capacity) return fail(KMX_E_RANGE, "the edited sequences take %llu bytes, d_seq_out has %llu", (unsigned long long)need, (unsigned long long)out_capacity);
+	return KMX_OK;
+}
+
+// ------------------------------------------------------------------------------------------ polishing to a fixed point
+// kmx_polish_seqs: kmx_edit_seqs' rule iterated per read until a pass finds nothing in it (the rule: include/kmx.h; what runs
+// between two passes: polish_device.hip).  Pass 1 reads the caller's buffers in place; pass p > 1 runs the same edit pipeline
+// on the reads pass p - 1 edited, compacted into one of two batches on the handle.  A pass waits once: the edit count and the
+// totals of the compaction's scan (reads that go on, their bytes, bytes parked) reach the host together, and size the sort,
+// the next batch and the parking area of the pass.
+static_assert(sizeof(kmx_seq_polish) == 96 && sizeof(SeqPolish) == 96, "kmx_seq_polish is 96 bytes");
+static_assert(offsetof(kmx_seq_polish, converged) == offsetof(SeqPolish, converged) && offsetof(kmx_seq_polish, out_len) == offsetof(SeqPolish, out_len) &&
+              offsetof(kmx_seq_polish, n_unfixable) == offsetof(SeqPolish, n_unfixable), "SeqPolish (kmx_types.h) is the layout of kmx_seq_polish");
+static_assert(KMX_POLISH_MAX_PASSES == POLISH_MAX_PASSES, "the pass limit of kmx_types.h is that of kmx.h");
+
+static bool spans_overlap(const void *a, u64 na, const void *b, u64 nb)
+{
+	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+	return na && nb && x < y + nb && y < x + na;
+}
+
+static int polish_args(kmx_model *m, int min_support, int ops, int max_passes)
+{
+	TRY(edit_args(m, min_support, ops));
+	if (max_passes < 1 || max_passes > KMX_POLISH_MAX_PASSES) return fail(KMX_E_ARG, "max_passes = %d, not in [1, %d]", max_passes, KMX_POLISH_MAX_PASSES);
+	return KMX_OK;
+}
+
+// The passes and the gather on device buffers, n_seqs and n_bases > 0.  d_rec[n_seqs] and d_offs_out[n_seqs + 1] are complete
+// and *total = d_offs_out[n_seqs] is on the host when it returns KMX_OK; out_of(total) is asked once, when the length is known,
+// for the output buffer (null: the call fails with what out_of reported), of which [0, min(total, out_cap)) is written by
+// kernels that are enqueued, not awaited.  A pass waits once: the edit count and the scan's totals arrive together.  When the
+// last pass is pass max_passes every length is final after its fold, so the offsets and the total ride on that wait too and
+// the pass writes its reads straight to their places in the output: no parking, no scan, no second wait.
+template <typename OutOf>
+static int polish_passes(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, int max_passes,
+                         SeqPolish *d_rec, u64 *d_offs_out, u64 out_cap, OutOf out_of, u64 *total, int *passes)
+{
+	auto &F = m->qfeed;
+	auto nomem = [] { return fail(KMX_E_NOMEM, "the buffers of a sequence polish could not be allocated"); };
+	auto rchk = [&](hipError_t e) { if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return nomem(); } HIPCHK(e); return (int)KMX_OK; };
+	auto timed = [&](hipError_t e) { KPROF_END(&m->prof, m->stream); return rchk(e); };
+	if (F.d_pol_home.ensure((size_t)n_seqs, m->stream) != hipSuccess || F.d_pol_len.ensure((size_t)(n_seqs + 1), m->stream) != hipSuccess) return nomem();
+	if (!F.h_pol_cnt.get() && F.h_pol_cnt.alloc(8) != hipSuccess) return nomem();
+	PolishHomes hm;
+	for (auto &a : hm.area) a = nullptr;
+	hm.area[0] = d_seq;
+	const unsigned char *act = d_seq;
+	const u64 *offs = d_offs, *ids = nullptr;
+	u64 n_act = n_seqs, n_bytes = n_bases, grown = 0;
+	u64 *h = F.h_pol_cnt;                                              // pinned: found, the three totals, the output's length
+	unsigned char *out = nullptr;
+	bool have_out = false;
+	// offsets that are none (the device variant does not validate them) can claim more bytes than there are, and more edits
+	auto bad_offsets = [] { return fail(KMX_E_ARG, "d_offsets are not the offsets of n_bases bases"); };
+	auto take_out = [&]() -> int {
+		*total = h[4];
+		if (*total > n_bases + grown) return bad_offsets();
+		out = out_of(*total);
+		have_out = true;
+		return out || !std::min<u64>(*total, out_cap) ? (int)KMX_OK : (int)KMX_E_NOMEM;
+	};
+	int p = 1;
+	for (;; p++) {
+		const bool last = p == max_passes;
+		const u64 cap = n_bytes / 3 + 1;                                // (always enough: include/kmx.h)
+		if (F.d_pol_edits.ensure((size_t)cap, m->stream) != hipSuccess || F.d_pol_re.ensure((size_t)n_act, m->stream) != hipSuccess ||
+		    F.d_pol_tri.ensure((size_t)(2 * (n_act + 1)), m->stream) != hipSuccess || F.d_pol_kind.ensure((size_t)n_act, m->stream) != hipSuccess ||
+		    F.d_pol_delta.ensure((size_t)n_act, m->stream) != hipSuccess) return nomem();
+		TRY(edit_seqs_enqueue(m, act, offs, n_act, n_bytes, thr, min_support, ops, F.d_pol_edits, cap, F.d_pol_re));
+		PolishTri *tri = last ? nullptr : F.d_pol_tri.get(), *sc = last ? nullptr : tri + (n_act + 1);
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		hipError_t e = kmxk::polish_fold(F.d_pol_re, offs, ids, n_act, n_bytes, d_rec, p, last, tri, sc, F.d_pol_kind, F.d_pol_home, F.d_pol_len, F.d_edit_tmp, m->stream);
+		if (e == hipSuccess && last) e = kmxk::polish_offsets(F.d_pol_len, n_seqs, d_offs_out, F.d_edit_tmp, m->stream);
+		TRY(timed(e));
+		HIPCHK(hipMemcpyAsync(h, F.d_edit_cnt.get(), 8, hipMemcpyDeviceToHost, m->stream));
+		if (last) HIPCHK(hipMemcpyAsync(h + 4, d_offs_out + n_seqs, 8, hipMemcpyDeviceToHost, m->stream));
+		else HIPCHK(hipMemcpyAsync(h + 1, sc + n_act, sizeof(PolishTri), hipMemcpyDeviceToHost, m->stream));
+		HIPCHK(hipStreamSynchronize(m->stream));                        // the pass's one wait
+		HIPCHK(hipGetLastError());
+		const u64 found = h[0];
+		const PolishTri tot = last ? PolishTri{0, 0, 0} : PolishTri{h[1], h[2], h[3]};
+		if (found > cap || tot.n > n_act || tot.next > n_bytes + found || tot.park > n_bytes + found) return bad_offsets();
+		grown += found;
+		if (last) TRY(take_out());
+		else if (!found && !tot.park) break;                            // pass 1 found nothing: every read stays where it is
+		TRY(edit_seqs_sort(m, F.d_pol_edits, found));
+		const int nb = p & 1;
+		if (F.d_pol_escan.ensure((size_t)(2 * (found + 1)), m->stream) != hipSuccess || (tot.park && F.d_pol_park[p].ensure((size_t)tot.park, m->stream) != hipSuccess) ||
+		    (tot.n && (F.d_pol_act[nb].ensure((size_t)tot.next, m->stream) != hipSuccess || F.d_pol_offs[nb].ensure((size_t)(tot.n + 1), m->stream) != hipSuccess ||
+		               F.d_pol_ids[nb].ensure((size_t)tot.n, m->stream) != hipSuccess))) return nomem();
+		if (tot.park) hm.area[p] = F.d_pol_park[p];
+		unsigned char *park = last ? out : (tot.park ? F.d_pol_park[p].get() : nullptr);
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		TRY(timed(kmxk::polish_apply(act, offs, ids, n_act, n_bytes, F.d_pol_kind, sc, F.d_pol_edits, found, F.d_pol_escan, p, last ? d_offs_out : nullptr, F.d_pol_delta,
+		                             tot.n ? F.d_pol_act[nb].get() : nullptr, tot.n ? tot.next : 0, tot.n ? F.d_pol_offs[nb].get() : nullptr, tot.n ? F.d_pol_ids[nb].get() : nullptr,
+		                             park, last ? std::min<u64>(*total, out_cap) : tot.park, F.d_pol_home, F.d_edit_tmp, m->stream)));
+		if (!tot.n) break;
+		act = F.d_pol_act[nb];
+		offs = F.d_pol_offs[nb];
+		ids = F.d_pol_ids[nb];
+		n_act = tot.n;
+		n_bytes = tot.next;
+	}
+	*passes = p;
+	if (!have_out) {
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		TRY(timed(kmxk::polish_offsets(F.d_pol_len, n_seqs, d_offs_out, F.d_edit_tmp, m->stream)));
+		HIPCHK(hipMemcpyAsync(h + 4, d_offs_out + n_seqs, 8, hipMemcpyDeviceToHost, m->stream));
+		HIPCHK(hipStreamSynchronize(m->stream));                        // the final length
+		TRY(take_out());
+	}
+	if (p > 1 || p != max_passes) {                                     // (max_passes = 1: pass 1 has placed every read)
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		kmxk::polish_gather(hm, F.d_pol_home, d_offs_out, n_seqs, out, std::min<u64>(*total, out_cap), m->stream);
+		KPROF_END(&m->prof, m->stream);
+	}
+	HIPCHK(hipGetLastError());
+	return KMX_OK;
+}
+
+static int kmx_polish_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, int max_passes,
+                                    char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out, kmx_seq_polish *d_rec, uint64_t *passes_run)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	TRY(polish_args(m, min_support, ops, max_passes));
+	if (!n_seqs) return KMX_OK;
+	if (!d_offsets || !d_offsets_out || (n_bases && !d_seq) || (out_capacity && !d_seq_out)) return fail(KMX_E_ARG, "null argument");
+	if (spans_overlap(d_seq, n_bases, d_seq_out, out_capacity)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
+	HIPCHK(hipSetDevice(m->device));
+	if (passes_run) *passes_run = 1;
+	if (!n_bases) {
+		KPROF_BEGIN(&m->prof, KC_QUERY, m->stream);
+		kmxk::polish_empty((SeqPolish *)d_rec, (u64 *)d_offsets_out, n_seqs, m->stream);
+		KPROF_END(&m->prof, m->stream);
+		HIPCHK(hipGetLastError());
+		return KMX_OK;
+	}
+	auto &F = m->qfeed;
+	if (!d_rec && F.d_pol_rec.ensure((size_t)n_seqs, m->stream) != hipSuccess) return fail(KMX_E_NOMEM, "the buffers of a sequence polish could not be allocated");
+	u64 total = 0;
+	int passes = 0;
+	TRY(polish_passes(m, (const unsigned char *)d_seq, (const u64 *)d_offsets, n_seqs, n_bases, thr, min_support, ops, max_passes, d_rec ? (SeqPolish *)d_rec : F.d_pol_rec.get(),
+	                  (u64 *)d_offsets_out, out_capacity, [&](u64) { return (unsigned char *)d_seq_out; }, &total, &passes));
+	if (passes_run) *passes_run = (u64)passes;
+	if (total > out_capacity) return fail(KMX_E_RANGE, "the polished sequences take %llu bytes, d_seq_out has %llu", (unsigned long long)total, (unsigned long long)out_capacity);
+	return KMX_OK;
+}
+
+// The host variant: bases and offsets go up once, reads, offsets and records come down once; the passes are the device variant's.
+static int kmx_polish_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops, int max_passes,
+                                char *seq_out, uint64_t out_capacity, uint64_t *offsets_out, kmx_seq_polish *rec, uint64_t *passes_run)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	std::lock_guard<std::mutex> lk(m->query_mu);
+	TRY(polish_args(m, min_support, ops, max_passes));
+	if (!n_seqs) return KMX_OK;
+	TRY(check_offsets(offsets, n_seqs));
+	const u64 n_bases = offsets[n_seqs];
+	if (!offsets_out || (n_bases && !seq) || (out_capacity && !seq_out)) return fail(KMX_E_ARG, "null argument");
+	if (spans_overlap(seq, n_bases, seq_out, out_capacity)) return fail(KMX_E_ARG, "seq_out overlaps seq");
+	if (passes_run) *passes_run = 1;
+	if (!n_bases) {
+		for (u64 i = 0; i <= n_seqs; i++) offsets_out[i] = 0;
+		if (rec) for (u64 i = 0; i < n_seqs; i++) rec[i] = kmx_seq_polish{1, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+		return KMX_OK;
+	}
+	HIPCHK(hipSetDevice(m->device));
+	DevBuf<unsigned char> d_seq, d_out;
+	DevBuf<u64> d_offs, d_oo;
+	DevBuf<SeqPolish> d_rec;
+	if (d_seq.alloc(n_bases) != hipSuccess || d_offs.alloc(n_seqs + 1) != hipSuccess || d_oo.alloc(n_seqs + 1) != hipSuccess || d_rec.alloc(n_seqs) != hipSuccess)
+		return fail(KMX_E_NOMEM, "device memory for %llu bases of %llu sequences could not be allocated", (unsigned long long)n_bases, (unsigned long long)n_seqs);
+	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });
+	HIPCHK(hipMemcpyAsync(d_seq, seq, n_bases, hipMemcpyHostToDevice, m->stream));
+	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	u64 total = 0;
+	int passes = 0;
+	const int rc = polish_passes(m, d_seq, d_offs, n_seqs, n_bases, thr, min_support, ops, max_passes, d_rec, d_oo, out_capacity,
+	                             [&](u64 t) { const u64 n = std::min<u64>(t, out_capacity); return n && d_out.alloc(n) == hipSuccess ? d_out.get() : nullptr; }, &total, &passes);
+	if (rc == KMX_E_NOMEM) return fail(KMX_E_NOMEM, "device memory for the polished bases could not be allocated");
+	TRY(rc);
+	if (passes_run) *passes_run = (u64)passes;
+	const u64 n_out = std::min<u64>(total, out_capacity);
+	if (n_out) HIPCHK(hipMemcpyAsync(seq_out, d_out.get(), n_out, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipMemcpyAsync(offsets_out, d_oo.get(), (n_seqs + 1) * 8, hipMemcpyDeviceToHost, m->stream));
+	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipStreamSynchronize(m->stream));
+	if (total > out_capacity) return fail(KMX_E_RANGE, "the polished sequences take %llu bytes, seq_out has %llu", (unsigned long long)total, (unsigned long long)out_capacity);
 	return KMX_OK;
 }
 
@@ -3154,6 +3367,8 @@ extern "C" int kmx_edit_seqs(kmx_model *m, const char *seq, const uint64_t *offs
 extern "C" int kmx_edit_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, kmx_edit *d_edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *d_rec) { return guarded([&] { return kmx_edit_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, ops, d_edits, capacity, n_edits, d_rec); }); }
 extern "C" int kmx_apply_edits(const char *seq, const uint64_t *offsets, uint64_t n_seqs, const kmx_edit *edits, uint64_t n_edits, char *seq_out, uint64_t out_capacity, uint64_t *offsets_out) { return guarded([&] { return kmx_apply_edits_impl(seq, offsets, n_seqs, edits, n_edits, seq_out, out_capacity, offsets_out); }); }
 extern "C" int kmx_apply_edits_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const kmx_edit *d_edits, uint64_t n_edits, char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out) { return guarded([&] { return kmx_apply_edits_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_edits, n_edits, d_seq_out, out_capacity, d_offsets_out); }); }
+extern "C" int kmx_polish_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops, int max_passes, char *seq_out, uint64_t out_capacity, uint64_t *offsets_out, kmx_seq_polish *rec, uint64_t *passes_run) { return guarded([&] { return kmx_polish_seqs_impl(m, seq, offsets, n_seqs, thr, min_support, ops, max_passes, seq_out, out_capacity, offsets_out, rec, passes_run); }); }
+extern "C" int kmx_polish_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, int max_passes, char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out, kmx_seq_polish *d_rec, uint64_t *passes_run) { return guarded([&] { return kmx_polish_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, min_support, ops, max_passes, d_seq_out, out_capacity, d_offsets_out, d_rec, passes_run); }); }
 extern "C" int kmx_extend_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int max_ext, int depth, char *ext, kmx_seq_extension *rec) { return guarded([&] { return kmx_extend_seqs_impl(m, seq, offsets, n_seqs, thr, max_ext, depth, ext, rec); }); }
 extern "C" int kmx_extend_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec) { return guarded([&] { return kmx_extend_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, thr, max_ext, depth, d_ext, d_rec); }); }
 extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs) { return guarded([&] { return kmx_count_seqs_impl(m, seq, offsets, n_seqs); }); }

@@ -261,6 +261,22 @@ struct EditDev {
 	int thr, min_support, ops;
 };
 
+// kmx_polish_seqs: one record per sequence, the layout of kmx_seq_polish (include/kmx.h; kmx_api.hip asserts it) ...
+struct SeqPolish {
+	u64 n_passes, converged, n_sub, n_del, n_ins, out_len, n_windows, n_weak, n_runs, n_sites, n_ambiguous, n_unfixable;
+};
+// ... what one pass hands the next (polish_device.hip): the reads that go on, their bytes after the edits, the bytes of the
+// reads that retire into this pass's parking area.  The host reads the totals where it reads the pass's edit count.
+struct PolishTri {
+	u64 n, next, park;
+};
+// ... and where a retired read lies: home[i] = area << 56 | offset, area 0 the caller's input (a read that pass 1 left alone
+// stays there), area p the parking area of pass p, POLISH_HOME_PLACED: already written to its place in the output
+enum { POLISH_MAX_PASSES = 16, POLISH_HOME_SHIFT = 56, POLISH_HOME_PLACED = 255 };
+struct PolishHomes {
+	const unsigned char *area[POLISH_MAX_PASSES + 1];
+};
+
 // kmx_extend_seqs: one record per seed, the layout of kmx_seq_extension (include/kmx.h; kmx_api.hip asserts it) ...
 struct SeqExtension {
 	u32 n_ext, stop;

@@ -60,4 +60,11 @@ hipError_t count_filter(int, const u64 *, const u32 *, u64, u32, u32, u32, u64 *
 // edit_device.hip: the edit list sorted (keys -> keys, alt is room for n more), and applied to the bases it was found on
 hipError_t edit_sort(u64 *keys, u64 *alt, u64 n, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t edit_apply(const unsigned char *, const u64 *, u64, u64, const u64 *, u64, u64 *, unsigned char *, u64, u64 *, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+// polish_device.hip: what runs between two passes of kmx_polish_seqs (fold + scan, then place + apply), the final offsets and gather
+void polish_empty(SeqPolish *, u64 *, u64, hipStream_t);
+hipError_t polish_fold(const SeqEdits *, const u64 *, const u64 *, u64, u64, SeqPolish *, int, bool, PolishTri *, PolishTri *, unsigned char *, u64 *, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t polish_apply(const unsigned char *, const u64 *, const u64 *, u64, u64, const unsigned char *, const PolishTri *, const u64 *, u64, u64 *, int, const u64 *, u64 *, unsigned char *, u64, u64 *, u64 *,
+                        unsigned char *, u64, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t polish_offsets(const u64 *, u64, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
+void polish_gather(const PolishHomes &, const u64 *, const u64 *, u64, unsigned char *, u64, hipStream_t);
 }   // namespace kmxk
