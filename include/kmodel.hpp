@@ -183,16 +183,12 @@ public:
 	}
 	std::vector<std::vector<int> > seq_to_occ(const std::vector<std::string> &seqs)
 	{
-		std::vector<uint64_t> off(seqs.size() + 1, 0);
-		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
-		std::vector<int32_t> occ((size_t)off.back());
-		if (!occ.empty()) check(kmx_query_seqs(h_, flat.data(), off.data(), seqs.size(), occ.data()));
+		const Flat f(seqs);
+		std::vector<int32_t> occ(f.bases.size());
+		if (!occ.empty()) check(kmx_query_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), occ.data()));
 		std::vector<std::vector<int> > out(seqs.size());
 		const size_t k = model_k();
-		for (size_t i = 0; i < seqs.size(); i++) out[i].assign(occ.begin() + (size_t)off[i], occ.begin() + (size_t)off[i] + windows(seqs[i].size(), k));
+		for (size_t i = 0; i < seqs.size(); i++) out[i].assign(occ.begin() + (size_t)f.off[i], occ.begin() + (size_t)f.off[i] + windows(seqs[i].size(), k));
 		return out;
 	}
 	// seq_to_occ's vector reduced per sequence on the device (kmx_summarise_seqs): n_windows, sum, min, max, the windows at or
@@ -206,13 +202,9 @@ public:
 	}
 	std::vector<kmx_seq_summary> seq_summary(const std::vector<std::string> &seqs, const std::vector<int> &thr = std::vector<int>())
 	{
-		std::vector<uint64_t> off(seqs.size() + 1, 0);
-		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		const Flat f(seqs);
 		std::vector<kmx_seq_summary> out(seqs.size());
-		check(kmx_summarise_seqs(h_, flat.data(), off.data(), seqs.size(), (const int32_t *)thr.data(), (int)thr.size(), out.data()));
+		check(kmx_summarise_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), (const int32_t *)thr.data(), (int)thr.size(), out.data()));
 		return out;
 	}
 
@@ -228,16 +220,10 @@ public:
 	}
 	std::vector<std::string> seq_correct(const std::vector<std::string> &seqs, int thr, int min_support = 1, std::vector<kmx_seq_correction> *rec = 0)
 	{
-		std::vector<uint64_t> off(seqs.size() + 1, 0);
-		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		Flat f(seqs);
 		if (rec) rec->assign(seqs.size(), kmx_seq_correction());
-		if (!flat.empty() || !seqs.empty()) check(kmx_correct_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, &flat[0], rec && !seqs.empty() ? &(*rec)[0] : 0));
-		std::vector<std::string> out(seqs.size());
-		for (size_t i = 0; i < seqs.size(); i++) out[i] = flat.substr((size_t)off[i], seqs[i].size());
-		return out;
+		if (!seqs.empty()) check(kmx_correct_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), thr, min_support, &f.bases[0], rec ? &(*rec)[0] : 0));
+		return split(f.bases, f.off);
 	}
 
 	// Substitutions and single-base insertions / deletions found from the k-mer spectrum and applied (kmx_edit_seqs and
@@ -252,20 +238,15 @@ public:
 	}
 	std::vector<std::string> seq_edit(const std::vector<std::string> &seqs, int thr, int min_support = 1, int ops = 7, std::vector<kmx_seq_edits> *rec = 0)
 	{
-		std::vector<uint64_t> off(seqs.size() + 1, 0), off_out(seqs.size() + 1, 0);
-		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		const Flat f(seqs);
+		std::vector<uint64_t> off_out(seqs.size() + 1, 0);
 		if (rec) rec->assign(seqs.size(), kmx_seq_edits());
-		std::vector<kmx_edit> edits((size_t)(off.back() / 3 + 1));
+		std::vector<kmx_edit> edits(f.bases.size() / 3 + 1);
 		uint64_t n_edits = 0;
-		if (!seqs.empty()) check(kmx_edit_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, &edits[0], edits.size(), &n_edits, rec ? &(*rec)[0] : 0));
-		std::string fixed(flat.size() + (size_t)n_edits, '\0');
-		check(kmx_apply_edits(flat.data(), off.data(), seqs.size(), &edits[0], n_edits, &fixed[0], fixed.size(), &off_out[0]));
-		std::vector<std::string> out(seqs.size());
-		for (size_t i = 0; i < seqs.size(); i++) out[i] = fixed.substr((size_t)off_out[i], (size_t)(off_out[i + 1] - off_out[i]));
-		return out;
+		if (!seqs.empty()) check(kmx_edit_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), thr, min_support, ops, &edits[0], edits.size(), &n_edits, rec ? &(*rec)[0] : 0));
+		std::string fixed(f.bases.size() + (size_t)n_edits, '\0');
+		check(kmx_apply_edits(f.bases.data(), f.off.data(), seqs.size(), &edits[0], n_edits, &fixed[0], fixed.size(), &off_out[0]));
+		return split(fixed, off_out);
 	}
 
 	// Reads polished to a fixed point (kmx_polish_seqs; the rule is in kmx.h): seq_edit's rule iterated per read on the device
@@ -280,24 +261,19 @@ public:
 	}
 	std::vector<std::string> seq_polish(const std::vector<std::string> &seqs, int thr, int min_support = 1, int ops = 7, int max_passes = 8, std::vector<kmx_seq_polish> *rec = 0)
 	{
-		std::vector<uint64_t> off(seqs.size() + 1, 0), off_out(seqs.size() + 1, 0);
-		for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seqs.size(); i++) flat += seqs[i];
+		const Flat f(seqs);
+		std::vector<uint64_t> off_out(seqs.size() + 1, 0);
 		if (rec) rec->assign(seqs.size(), kmx_seq_polish());
-		std::string fixed(flat.size() + flat.size() / 16 + 64, '\0');
+		std::string fixed(f.bases.size() + f.bases.size() / 16 + 64, '\0');
 		if (!seqs.empty()) {
-			int rc = kmx_polish_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
+			int rc = kmx_polish_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
 			if (rc == KMX_E_RANGE && off_out.back() > fixed.size()) {   // offsets_out is complete: once more with the room it asks for
 				fixed.assign((size_t)off_out.back(), '\0');
-				rc = kmx_polish_seqs(h_, flat.data(), off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
+				rc = kmx_polish_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), thr, min_support, ops, max_passes, &fixed[0], fixed.size(), &off_out[0], rec ? &(*rec)[0] : 0, 0);
 			}
 			check(rc);
 		}
-		std::vector<std::string> out(seqs.size());
-		for (size_t i = 0; i < seqs.size(); i++) out[i] = fixed.substr((size_t)off_out[i], (size_t)(off_out[i + 1] - off_out[i]));
-		return out;
+		return split(fixed, off_out);
 	}
 
 	// Seeds extended to the right along the unique path of k-mers answered >= thr (kmx_extend_seqs; the rule is in kmx.h):
@@ -315,15 +291,11 @@ public:
 	}
 	std::vector<std::string> seq_extend(const std::vector<std::string> &seeds, int thr, int max_ext, int depth = 2, std::vector<kmx_seq_extension> *rec = 0)
 	{
-		std::vector<uint64_t> off(seeds.size() + 1, 0);
-		for (size_t i = 0; i < seeds.size(); i++) off[i + 1] = off[i] + seeds[i].size();
-		std::string flat;
-		flat.reserve((size_t)off.back());
-		for (size_t i = 0; i < seeds.size(); i++) flat += seeds[i];
+		const Flat f(seeds);
 		const size_t row = max_ext > 0 ? (size_t)max_ext : 1;
 		std::vector<char> ext(seeds.size() * row + 1);
 		std::vector<kmx_seq_extension> r(seeds.size());
-		if (!seeds.empty()) check(kmx_extend_seqs(h_, flat.data(), off.data(), seeds.size(), thr, max_ext, depth, &ext[0], &r[0]));
+		if (!seeds.empty()) check(kmx_extend_seqs(h_, f.bases.data(), f.off.data(), seeds.size(), thr, max_ext, depth, &ext[0], &r[0]));
 		std::vector<std::string> out(seeds.size());
 		for (size_t i = 0; i < seeds.size(); i++) out[i].assign(&ext[i * row], r[i].n_ext);
 		if (rec) rec->swap(r);
@@ -382,6 +354,24 @@ private:
 		return st.k > 0 ? (size_t)st.k : 0;
 	}
 	static size_t windows(size_t len, size_t k) { return k && len >= k ? len - k + 1 : 0; }
+	// a vector of reads as the C calls take them: the bases joined end to end and offsets[n + 1]
+	struct Flat {
+		std::vector<uint64_t> off;
+		std::string bases;
+		explicit Flat(const std::vector<std::string> &seqs) : off(seqs.size() + 1, 0)
+		{
+			for (size_t i = 0; i < seqs.size(); i++) off[i + 1] = off[i] + seqs[i].size();
+			bases.reserve((size_t)off.back());
+			for (size_t i = 0; i < seqs.size(); i++) bases += seqs[i];
+		}
+	};
+	// ... and back: the sequences of a buffer, by its offsets
+	static std::vector<std::string> split(const std::string &buf, const std::vector<uint64_t> &off)
+	{
+		std::vector<std::string> out(off.size() - 1);
+		for (size_t i = 0; i + 1 < off.size(); i++) out[i] = buf.substr((size_t)off[i], (size_t)(off[i + 1] - off[i]));
+		return out;
+	}
 	static void die(const char *msg)
 	{
 		std::cout << msg << std::endl;

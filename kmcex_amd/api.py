@@ -300,15 +300,37 @@ def microbench(mode: int, nbytes: int, touches: int, iters: int = 3) -> float:
     return s.value
 
 
+def _flat_seqs(buf, offsets):
+    """(bases, offsets) as the C calls take them: flat contiguous uint8 and uint64 [n_seqs + 1], the offsets ending inside the bases"""
+    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if offsets.size == 0:
+        raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+    if int(offsets[-1]) > buf.size:
+        raise KmxError(-1, f"offsets end at {int(offsets[-1])}, past the {buf.size} bases given")
+    return buf, offsets
+
+
+def _join_seqs(seqs):
+    """a str / bytes sequence (single) or a list of them -> (single, the bytes of each, their uint8 bases joined end to end, uint64 offsets)"""
+    single = isinstance(seqs, (str, bytes))
+    raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in ([seqs] if single else list(seqs))]
+    offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
+    return single, raw, np.frombuffer(b"".join(raw), dtype=np.uint8), offsets
+
+
+def _split_seqs(buf, offsets):
+    """the bytes of every sequence of (bases, offsets)"""
+    return [buf[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(offsets.size - 1)]
+
+
 def apply_edits(buf: np.ndarray, offsets: np.ndarray, edits: np.ndarray):
     """kmx_apply_edits (host only, needs no GPU): an edit list applied to the bases it was found on -> (uint8 edited bases,
     uint64 offsets_out [n_seqs + 1])"""
     L = load_library()
-    buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    buf, offsets = _flat_seqs(buf, offsets)
     edits = np.ascontiguousarray(edits, dtype=np.uint64).reshape(-1)
-    if offsets.size == 0 or int(offsets[-1]) > buf.size:
-        raise KmxError(-1, "offsets must hold n_seqs + 1 entries and end inside the bases given")
     out = np.empty(int(offsets[-1]) + edits.size, dtype=np.uint8)
     off = np.zeros(offsets.size, dtype=np.uint64)
     _chk(L.kmx_apply_edits(buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, edits.ctypes.data, edits.size, out.ctypes.data, out.size, off.ctypes.data))
@@ -514,13 +536,8 @@ class KModel:
     def seq_to_occ_flat(self, buf: np.ndarray, offsets: np.ndarray) -> np.ndarray:
         """kmx_query_seqs: uint8 bases of sequences stored back to back, uint64 offsets[n_seqs + 1] -> int32[n_bases], aligned
         to the bases; -1 where no k-mer starts (the last k - 1 positions of each sequence)."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        buf, offsets = _flat_seqs(buf, offsets)
         n_bases = int(offsets[-1])
-        if n_bases > buf.size:
-            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
         out = np.empty(n_bases, dtype=np.int32)
         _chk(self.L.kmx_query_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, out.ctypes.data))
         return out
@@ -528,15 +545,10 @@ class KModel:
     def seq_to_occ(self, seqs):
         """kmer_to_occ of every overlapping k-mer of each sequence (str or bytes; one sequence or a list): one int32 array of
         max(len - k + 1, 0) answers per sequence (a list of them for a list)."""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        single, raw, flat, offsets = _join_seqs(seqs)
         k = self.stats().k
         if k == 0:
             raise KmxError(-4, "query before the model is built or loaded")
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        flat = np.frombuffer(b"".join(raw), dtype=np.uint8)
         occ = self.seq_to_occ_flat(flat, offsets) if raw else np.zeros(0, np.int32)
         res = [occ[int(offsets[i]):int(offsets[i]) + max(len(r) - k + 1, 0)] for i, r in enumerate(raw)]
         return res[0] if single else res
@@ -549,13 +561,7 @@ class KModel:
         """kmx_summarise_seqs: the answers of seq_to_occ_flat reduced per sequence on the device -> a structured array of
         n_seqs records (SEQ_SUMMARY_DTYPE: n_windows, sum, min, max, n_ge[3], first_below, last_below); thr: up to 3 int32
         thresholds, thr[0] also defines first_below / last_below."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
-        n_bases = int(offsets[-1])
-        if n_bases > buf.size:
-            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
+        buf, offsets = _flat_seqs(buf, offsets)
         t = np.ascontiguousarray(thr, dtype=np.int32).reshape(-1)
         out = np.zeros(offsets.size - 1, dtype=SEQ_SUMMARY_DTYPE)
         _chk(self.L.kmx_summarise_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1,
@@ -564,12 +570,8 @@ class KModel:
 
     def seq_summary(self, seqs, thr=()):
         """seq_summary_flat for a str / bytes sequence (-> one record) or a list of them (-> a structured array)"""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        res = self.seq_summary_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr)
+        single, _, buf, offsets = _join_seqs(seqs)
+        res = self.seq_summary_flat(buf, offsets, thr)
         return res[0] if single else res
 
     def seq_summary_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr, d_out_ptr: int) -> None:
@@ -582,13 +584,8 @@ class KModel:
         """kmx_correct_seqs: substitution errors corrected from the k-mer spectrum (the rule: include/kmx.h) -> (uint8 corrected
         bases [n_bases], SEQ_CORRECTION_DTYPE records [n_seqs]); a window is weak when its answer is below thr, a site is tried
         when at least min_support windows verify it."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        buf, offsets = _flat_seqs(buf, offsets)
         n_bases = int(offsets[-1])
-        if n_bases > buf.size:
-            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
         out = np.empty(n_bases, dtype=np.uint8)
         rec = np.zeros(offsets.size - 1, dtype=SEQ_CORRECTION_DTYPE)
         _chk(self.L.kmx_correct_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1, int(thr), int(min_support),
@@ -597,13 +594,9 @@ class KModel:
 
     def seq_correct(self, seqs, thr: int, min_support: int = 1):
         """seq_correct_flat for a str / bytes sequence (-> (bytes, record)) or a list of them (-> (list of bytes, records))"""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        out, rec = self.seq_correct_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr, min_support)
-        fixed = [out[int(offsets[i]):int(offsets[i + 1])].tobytes() for i in range(len(raw))]
+        single, _, buf, offsets = _join_seqs(seqs)
+        out, rec = self.seq_correct_flat(buf, offsets, thr, min_support)
+        fixed = _split_seqs(out, offsets)
         return (fixed[0], rec[0]) if single else (fixed, rec)
 
     def seq_correct_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int,
@@ -617,13 +610,8 @@ class KModel:
         """kmx_edit_seqs: substitutions and single-base insertions / deletions found from the k-mer spectrum (the rule:
         include/kmx.h) -> (uint64 edits, ascending: pos << 8 | op << 4 | code; SEQ_EDITS_DTYPE records [n_seqs]).  ops is a subset
         of EDIT_OPS_SUB | EDIT_OPS_DEL | EDIT_OPS_INS; apply_edits turns the list into the edited bases."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        buf, offsets = _flat_seqs(buf, offsets)
         n_bases = int(offsets[-1])
-        if n_bases > buf.size:
-            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
         rec = np.zeros(offsets.size - 1, dtype=SEQ_EDITS_DTYPE)
         edits = np.empty(n_bases // 3 + 1, dtype=np.uint64)        # always enough (include/kmx.h)
         n = C.c_uint64(0)
@@ -634,15 +622,9 @@ class KModel:
     def seq_edit(self, seqs, thr: int, min_support: int = 1, ops: int = 7):
         """seq_edit_flat and apply_edits for a str / bytes sequence (-> (edited bytes, record, edits)) or a list of them
         (-> (list of edited bytes, records, edits)); the positions of the edits are those of the reads joined end to end"""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        single, _, buf, offsets = _join_seqs(seqs)
         edits, rec = self.seq_edit_flat(buf, offsets, thr, min_support, ops)
-        out, off = apply_edits(buf, offsets, edits)
-        fixed = [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(raw))]
+        fixed = _split_seqs(*apply_edits(buf, offsets, edits))
         return (fixed[0], rec[0], edits) if single else (fixed, rec, edits)
 
     def seq_edit_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int, ops: int,
@@ -670,13 +652,8 @@ class KModel:
         (the rule: include/kmx.h) -> (uint8 polished bases, uint64 offsets_out [n_seqs + 1], SEQ_POLISH_DTYPE records [n_seqs],
         passes run).  The output's length is not known beforehand: the call is repeated with the exact room when the first
         guess (the input's length and a sixteenth) is too small."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
+        buf, offsets = _flat_seqs(buf, offsets)
         n_bases = int(offsets[-1])
-        if n_bases > buf.size:
-            raise KmxError(-1, f"offsets end at {n_bases}, past the {buf.size} bases given")
         n_seqs = offsets.size - 1
         rec = np.zeros(n_seqs, dtype=SEQ_POLISH_DTYPE)
         off = np.zeros(n_seqs + 1, dtype=np.uint64)
@@ -695,14 +672,9 @@ class KModel:
     def seq_polish(self, seqs, thr: int, min_support: int = 1, ops: int = 7, max_passes: int = 8):
         """seq_polish_flat for a str / bytes sequence (-> (polished bytes, record)) or a list of them (-> (list of polished
         bytes, records))"""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
+        single, _, buf, offsets = _join_seqs(seqs)
         out, off, rec, _ = self.seq_polish_flat(buf, offsets, thr, min_support, ops, max_passes)
-        fixed = [out[int(off[i]):int(off[i + 1])].tobytes() for i in range(len(raw))]
+        fixed = _split_seqs(out, off)
         return (fixed[0], rec[0]) if single else (fixed, rec)
 
     def seq_polish_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int, thr: int, min_support: int, ops: int, max_passes: int,
@@ -725,12 +697,7 @@ class KModel:
         """kmx_extend_seqs: every seed walked to the right along the unique path of k-mers answered >= thr (the rule:
         include/kmx.h) -> (uint8 appended bases [n_seqs, max_ext], 0 behind the n_ext of a row; SEQ_EXTENSION_DTYPE records
         [n_seqs]).  depth 0 ... 3 is the lookahead that breaks the ties the model's false positives cause."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
-        if int(offsets[-1]) > buf.size:
-            raise KmxError(-1, f"offsets end at {int(offsets[-1])}, past the {buf.size} bases given")
+        buf, offsets = _flat_seqs(buf, offsets)
         n_seqs = offsets.size - 1
         rows = int(max_ext) if 1 <= int(max_ext) <= 65536 else 1               # (an invalid max_ext is the library's to refuse)
         ext = np.empty((n_seqs, rows), dtype=np.uint8)
@@ -744,14 +711,10 @@ class KModel:
         appended bases of every seed.  left=True extends to the left instead: the walk of the seed's reverse complement,
         returned reverse-complemented again, so the result reads in the seed's direction and ends where the seed begins
         (for k > 32 the two strands of a k-mer need not get the same answer: include/kmx.h)."""
-        single = isinstance(seqs, (str, bytes))
-        items = [seqs] if single else list(seqs)
-        raw = [s.encode("latin-1") if isinstance(s, str) else bytes(s) for s in items]
+        single, raw, buf, offsets = _join_seqs(seqs)
         if left:
-            raw = [_REVCOMP[np.frombuffer(r, dtype=np.uint8)[::-1]].tobytes() for r in raw]
-        offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-        offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-        ext, rec = self.seq_extend_flat(np.frombuffer(b"".join(raw), dtype=np.uint8), offsets, thr, max_ext, depth)
+            _, raw, buf, offsets = _join_seqs([_REVCOMP[np.frombuffer(r, dtype=np.uint8)[::-1]].tobytes() for r in raw])
+        ext, rec = self.seq_extend_flat(buf, offsets, thr, max_ext, depth)
         out = [ext[i, :int(rec["n_ext"][i])] for i in range(len(raw))]
         out = [(_REVCOMP[e[::-1]] if left else e).tobytes() for e in out]
         return (out[0], rec[0]) if single else (out, rec)
@@ -776,18 +739,8 @@ class KModel:
     def count_seqs(self, seqs, offsets=None) -> None:
         """kmx_count_seqs: a str / bytes sequence or a list of them, or (uint8 buf, uint64 offsets[n_seqs + 1])"""
         if offsets is None:
-            items = [seqs] if isinstance(seqs, (str, bytes)) else list(seqs)
-            raw = [x.encode("latin-1") if isinstance(x, str) else bytes(x) for x in items]
-            offsets = np.zeros(len(raw) + 1, dtype=np.uint64)
-            offsets[1:] = np.cumsum([len(r) for r in raw], dtype=np.uint64)
-            buf = np.frombuffer(b"".join(raw), dtype=np.uint8)
-        else:
-            buf = np.ascontiguousarray(seqs, dtype=np.uint8).reshape(-1)
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
-        if offsets.size == 0:
-            raise KmxError(-1, "offsets must hold n_seqs + 1 entries")
-        if int(offsets[-1]) > buf.size:
-            raise KmxError(-1, f"offsets end at {int(offsets[-1])}, past the {buf.size} bases given")
+            _, _, seqs, offsets = _join_seqs(seqs)
+        buf, offsets = _flat_seqs(seqs, offsets)
         _chk(self.L.kmx_count_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, offsets.size - 1))
 
     def count_seqs_dev(self, d_seq_ptr: int, d_offsets_ptr: int, n_seqs: int, n_bases: int) -> None:

@@ -247,12 +247,14 @@ void seq_correction_init(SeqCorrection *rec, const u64 *offs, u64 n_seqs, u64 n_
 	KPROF_END(prof, st);
 }
 
-// one piece: the windows [p0, p0 + n_win) of an input of n_total bases, of which seq holds [g0, g1).  bits: room for the
-// windows [w0, w1) in whole tiles of SEQ_BT, where [w0, w1) = the piece and KMX_CORR_HALO(k) windows on both sides, cut to
-// [0, n_total) and to the windows whose bases are on hand; dlist holds cap >= w1 - w0 entries, dcnt is 0 on entry, dcnt_next
-// is zeroed for the next piece; flags: one byte per SEQ_BT windows of the piece.
-void correct_piece(const ModelDev &md, const unsigned char *seq, u64 g0, u64 g1, u64 n_total, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, u64 w0, u64 w1, u64 *bits, const CorrDev &cd, unsigned char *flags, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+// one piece: the windows [p0, p0 + n_win) of the input v views.  bits: room for the windows [w0, w1) in whole tiles of SEQ_BT,
+// where [w0, w1) = the piece and KMX_CORR_HALO(k) windows on both sides, cut to [0, n_total) and to the windows whose bases
+// are on hand; d (kmx_types.h) has room for w1 - w0 entries; flags: one byte per SEQ_BT windows of the piece.
+void correct_piece(const ModelDev &md, const SeqView &v, u64 p0, u64 n_win, u64 w0, u64 w1, u64 *bits, const CorrDev &cd, unsigned char *flags, const SeqDirty &d, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 g0 = v.g0, g1 = v.g1, n_total = v.n_total, *offs = v.offs, n_seqs = v.n_seqs;
+	u32 *dlist = d.list, cap = d.cap, *dcnt = d.cnt, *dcnt_next = d.cnt_next;
 	if (!n_win) return;
 	KPROF_BEGIN(prof, KC_QUERY, st);
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);

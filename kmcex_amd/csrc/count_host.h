@@ -155,7 +155,7 @@ static int kmx_count_seqs_impl(kmx_model *m, const char *seq, const uint64_t *of
 	const SlotShape shape = sc.shape();
 	auto &F = m->qfeed;
 	int rc = KMX_OK;
-	const int prc = query_pipeline(m, n_bases, 1, sc.workers(),
+	const int prc = query_pipeline(m, n_bases, 1, seq_workers(n_bases),
 		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
 			if (!rc) rc = count_launch(m, F.d_in[s], sc.nbytes_of(c), sc.bounds(F.d_in[s]), sc.seqs_of(c), 0, cn);

@@ -277,24 +277,28 @@ void seq_edits_init(SeqEdits *rec, const u64 *offs, u64 n_seqs, u64 n_bases, int
 	KPROF_END(prof, st);
 }
 
-// the weak bits of the windows [w0, w0 + n_win) of an input of n_total bases held in seq, w0 a multiple of SEQ_BT: whole words
-// of bits (bit p = window p) are written, up to the end of the piece's last tile.  dlist holds cap >= n_win entries, dcnt is
-// 0 on entry, dcnt_next is zeroed for the next piece.
-void edit_weak_piece(const ModelDev &md, const unsigned char *seq, u64 n_total, const u64 *offs, u64 n_seqs, u64 w0, u64 n_win, int thr, u64 *bits, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+// the weak bits of the windows [w0, w0 + n_win) of the input v holds whole, w0 a multiple of SEQ_BT: whole words of bits
+// (bit p = window p) are written, up to the end of the piece's last tile.  d (kmx_types.h) has room for n_win entries.
+void edit_weak_piece(const ModelDev &md, const SeqView &v, u64 w0, u64 n_win, int thr, u64 *bits, const SeqDirty &d, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 *offs = v.offs, n_seqs = v.n_seqs;
+	u32 *dlist = d.list, cap = d.cap, *dcnt = d.cnt, *dcnt_next = d.cnt_next;
 	if (!n_win) return;
 	KPROF_BEGIN(prof, KC_QUERY, st);
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);
 	const unsigned gw = (unsigned)((n_win + SEQ_BT - 1) / SEQ_BT);
 	u64 *b = bits + w0 / 64;
-	DISPATCH_W(words(md), hipLaunchKernelGGL(k_correct_weak<W>, dim3(gw), dim3(SEQ_BT), 0, st, md, seq, (u64)0, n_total, offs, n_seqs, w0, n_win, thr, b, dlist, cap, dcnt));
-	DISPATCH_W(words(md), hipLaunchKernelGGL(k_correct_weak_ascii_at<W>, dim3(SEQ_DIRTY_WGS), dim3(256), 0, st, md, gf, gb, seq, (u64)0, n_total, w0, n_win, thr, b, (const u32 *)dlist, cap, (const u32 *)dcnt, dcnt_next));
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_correct_weak<W>, dim3(gw), dim3(SEQ_BT), 0, st, md, seq, v.g0, v.g1, offs, n_seqs, w0, n_win, thr, b, dlist, cap, dcnt));
+	DISPATCH_W(words(md), hipLaunchKernelGGL(k_correct_weak_ascii_at<W>, dim3(SEQ_DIRTY_WGS), dim3(256), 0, st, md, gf, gb, seq, v.g0, v.g1, w0, n_win, thr, b, (const u32 *)dlist, cap, (const u32 *)dcnt, dcnt_next));
 	KPROF_END(prof, st);
 }
 
 // the sites of the windows [p0, p0 + n_win), once the bits of the whole input are written; flags: one byte per SEQ_BT windows
-void edit_sites_piece(const ModelDev &md, const unsigned char *seq, u64 n_total, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, const u64 *bits, const EditDev &ed, unsigned char *flags, hipStream_t st, KernelProf *prof)
+void edit_sites_piece(const ModelDev &md, const SeqView &v, u64 p0, u64 n_win, const u64 *bits, const EditDev &ed, unsigned char *flags, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 n_total = v.n_total, *offs = v.offs, n_seqs = v.n_seqs;
 	if (!n_win) return;
 	KPROF_BEGIN(prof, KC_QUERY, st);
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);

@@ -185,10 +185,14 @@ template <int W> __global__ __launch_bounds__(EXT_BT) void k_extend_step(ModelDe
 
 namespace kmxk {
 
-// a chunk of n seeds (seq, offs as k_extend_init takes them): xd.walk holds n states, lists 2 n entries, cnt 3 counters.
+// a chunk of n = v.n_seqs seeds (v.offs is the chunk's first offset; seq, offs as k_extend_init takes them): xd.walk holds
+// n states, lists 2 n entries, cnt 3 counters.
 // ceil(max_ext / steps) launches of k_extend_step finish every walk: a step appends a base or stops the walk.
-void extend_walks(const ModelDev &md, const unsigned char *seq, u64 n_bases, const u64 *offs, u32 n, const ExtDev &xd, u32 *lists, u32 *cnt, int steps, hipStream_t st, KernelProf *prof)
+void extend_walks(const ModelDev &md, const SeqView &v, const ExtDev &xd, u32 *lists, u32 *cnt, int steps, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 n_bases = v.g1, *offs = v.offs;                      // (where k_extend_init clamps the offsets: the end of the bases on hand)
+	const u32 n = (u32)v.n_seqs;
 	if (!n) return;
 	(void)hipMemsetAsync(cnt, 0, 3 * sizeof(u32), st);
 	KPROF_BEGIN(prof, KC_QUERY, st);

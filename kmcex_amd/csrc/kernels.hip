@@ -2974,9 +2974,13 @@ void query_ascii(const ModelDev &md, int L, const unsigned char *strs, int strid
 }
 
 // windows [p0, p0 + n_win) of the sequences (k_query_seq) + the ones it listed (k_query_ascii_at): two launches, no host wait.
-// dlist holds cap >= n_win entries; dcnt must be 0 on entry, dcnt_next is zeroed for the next piece.
-void query_seq(const ModelDev &md, const unsigned char *seq, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, int *out, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+// v holds the input from its first base (g0 = 0); the kernels' n_bases, where they clamp the offsets and end the staged bytes, is
+// the end of the bases on hand, v.g1; d (kmx_types.h) has room for n_win entries.
+void query_seq(const ModelDev &md, const SeqView &v, u64 p0, u64 n_win, int *out, const SeqDirty &d, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 n_bases = v.g1, *offs = v.offs, n_seqs = v.n_seqs;
+	u32 *dlist = d.list, cap = d.cap, *dcnt = d.cnt, *dcnt_next = d.cnt_next;
 	if (!n_win) return;
 	KPROF_BEGIN(prof, KC_QUERY, st);
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);
@@ -3000,10 +3004,13 @@ void seq_summary_finish(SeqSummary *rec, const u64 *offs, u64 n_seqs, u64 n_base
 	hipLaunchKernelGGL(k_seq_summary_finish, dim3((unsigned)((n_seqs + 255) / 256)), dim3(256), 0, st, rec, offs, n_seqs, n_bases, k);
 	KPROF_END(prof, st);
 }
-// ... and one piece, query_seq's two launches with its dirty list: the windows [p0, p0 + n_win), of which seq holds the bases
-// [g0, n_bases) (positions of the offsets), into sd.rec
-void summarise_seq(const ModelDev &md, const unsigned char *seq, u64 g0, u64 n_bases, const u64 *offs, u64 n_seqs, u64 p0, u64 n_win, const SeqSumDev &sd, u32 *dlist, u32 cap, u32 *dcnt, u32 *dcnt_next, hipStream_t st, KernelProf *prof)
+// ... and one piece, query_seq's two launches with its dirty list: the windows [p0, p0 + n_win), whose bases v has on hand,
+// into sd.rec.  The kernels' n_bases is the end of the bases on hand, v.g1 (seq_tile_window stages no byte at or behind it)
+void summarise_seq(const ModelDev &md, const SeqView &v, u64 p0, u64 n_win, const SeqSumDev &sd, const SeqDirty &d, hipStream_t st, KernelProf *prof)
 {
+	const unsigned char *seq = v.seq;
+	const u64 g0 = v.g0, n_bases = v.g1, *offs = v.offs, n_seqs = v.n_seqs;
+	u32 *dlist = d.list, cap = d.cap, *dcnt = d.cnt, *dcnt_next = d.cnt_next;
 	if (!n_win) return;
 	KPROF_BEGIN(prof, KC_QUERY, st);
 	const StrGeom gf = make_geom(md.k), gb = make_geom(md.k - 2);

@@ -23,6 +23,7 @@
 #include <functional>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -1789,10 +1790,18 @@ static int kmx_kmc_read_impl(const char *db_prefix, uint64_t *kmers, uint32_t *c
 // ------------------------------------------------------------------------------------------ query
 // Every query entry point holds m->query_mu from its first look at the handle to its return: the slots of m->qfeed (and
 // ensure_query_feed's reallocation of them), m->prof's event and span vectors and h_stats[ST_QUERY_*] are used by one
-// caller at a time.  The *_locked functions below expect the caller to hold it.
+// caller at a time.  The *_locked functions below expect the caller to hold it and to have found the model ST_READY (query_enter).
+// The entry of every query call: null model, then the lock (lk holds it until the caller returns), then the state.
+static int query_enter(kmx_model *m, std::unique_lock<std::mutex> &lk)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	lk = std::unique_lock<std::mutex>(m->query_mu);
+	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	return KMX_OK;
+}
+
 static int query_packed_dev_locked(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out)
 {
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	HIPCHK(hipSetDevice(m->device));
 	if (m->prof.count && m->d_stats) {                            // accounting (kmx_set_profile(m, 2)): never the timed kernel
 		kmxk::query(m->md, (const u64 *)d_kmers, n, d_out, m->stream, &m->prof, m->d_stats + ST_QUERY_NEIGH);
@@ -1809,16 +1818,15 @@ static int query_packed_dev_locked(kmx_model *m, const uint64_t *d_kmers, uint64
 
 static int kmx_query_packed_dev_impl(kmx_model *m, const uint64_t *d_kmers, uint64_t n, int32_t *d_out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	return query_packed_dev_locked(m, d_kmers, n, d_out);
 }
 
 static int kmx_query_packed_impl(kmx_model *m, const uint64_t *kmers, uint64_t n, int32_t *out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	if (!n) return KMX_OK;
 	HIPCHK(hipSetDevice(m->device));
 	DevBuf<uint64_t> dk;
@@ -1987,9 +1995,8 @@ static int query_pipeline(kmx_model *m, u64 n, size_t item_bytes, int T, STAGE s
 
 static int query_text(kmx_model *m, const KmxStrBatch &sb, uint64_t n, int32_t *out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);                  // both passes (packed, then the dirty strings' bytes) under one hold
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;                              // both passes (packed, then the dirty strings' bytes) under one hold
+	TRY(query_enter(m, lk));
 	const int len = sb.len, W = m->W;
 	if (len < 2 || len > 64 || sb.stride < len) return fail(KMX_E_ARG, "k-mer strings must hold 2..64 characters (got %d, stride %d)", len, sb.stride);
 	if (!n) return KMX_OK;
@@ -2038,37 +2045,54 @@ static const u64 kSeqChunk = u64(1) << 22;                     // bases per pinn
 
 // KMX_SEQ_CHUNK_BASES (test hook): pieces and host chunks of this many windows, so a test crosses many of their boundaries.
 // Read at every call (a test sets it after the library is loaded).
-static u64 seq_chunk_hook()
+static u64 seq_size(u64 dflt)
 {
 	const char *e = hook_env("KMX_SEQ_CHUNK_BASES");
 	const long long x = e ? atoll(e) : 0;
-	return x > 0 ? std::min<u64>((u64)x, kSeqPiece) : 0;
+	return x > 0 ? std::min<u64>((u64)x, kSeqPiece) : dflt;
 }
+static u64 seq_piece() { return seq_size(kSeqPiece); }          // windows per piece of a device variant
+static u64 seq_chunk() { return seq_size(kSeqChunk); }          // bases per chunk of a host variant
+// worker threads that stage the chunks of n_bases bases
+static int seq_workers(u64 n_bases) { return (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1)); }
+
+// The SeqDirty (kmx_types.h) of one piece after the other: the owner of the parity of the two counters.  Only
+// ensure_seq_scratch can make one (a call site holds an empty optional until then), so none exists whose counters were not zeroed.
+class SeqDirtyCursor;
+static int ensure_seq_scratch(kmx_model *m, u64 piece, std::optional<SeqDirtyCursor> &dirty);
+class SeqDirtyCursor {
+	u32 *list, cap, *cnt;
+	int odd = 1;
+	SeqDirtyCursor(u32 *l, u32 c, u32 *n) : list(l), cap(c), cnt(n) {}
+	friend int ensure_seq_scratch(kmx_model *, u64, std::optional<SeqDirtyCursor> &);
+
+public:
+	SeqDirty next() { odd ^= 1; return SeqDirty{list, cap, cnt + odd, cnt + (odd ^ 1)}; }
+};
 
 // (caller holds m->query_mu) the dirty list for pieces of `piece` windows + its two counters, both zeroed on the model's stream
-static int ensure_seq_scratch(kmx_model *m, u64 piece)
+static int ensure_seq_scratch(kmx_model *m, u64 piece, std::optional<SeqDirtyCursor> &dirty)
 {
 	auto &F = m->qfeed;
 	HIPCHK(F.d_seq_list.ensure(piece, m->stream));             // (waits first: an earlier _dev call may still be using the old list)
 	TRY(ensure(F.d_seq_cnt, 2, true, m->stream));
+	dirty = SeqDirtyCursor(F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt);
 	return KMX_OK;
 }
 
 static int kmx_query_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t *d_out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	if (!n_seqs || !n_bases) return KMX_OK;
 	if (!d_seq || !d_offsets || !d_out) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece;
-	TRY(ensure_seq_scratch(m, piece));
-	auto &F = m->qfeed;
-	int par = 0;
-	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1)
-		kmxk::query_seq(m->md, (const unsigned char *)d_seq, n_bases, (const u64 *)d_offsets, n_seqs, p0, std::min<u64>(piece, n_bases - p0), d_out,
-		                F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	const u64 piece = seq_piece();
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_seq_scratch(m, piece, dirty));
+	const SeqView v{(const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets, n_seqs};
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece)
+		kmxk::query_seq(m->md, v, p0, std::min<u64>(piece, n_bases - p0), d_out, dirty->next(), m->stream, &m->prof);
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
 }
@@ -2089,7 +2113,6 @@ struct SeqChunks {
 		  nc((n_bases + C - 1) / C), off_at((size_t)((C + 64 + 7) & ~u64(7))), n_bnd(nc, 0) {}
 	u64 nbytes_of(u64 c) const { const u64 c0 = c * C, cn = std::min<u64>(C, n_bases - c0); return std::min<u64>(cn + k - 1, n_bases - c0); }
 	SlotShape shape() { return SlotShape{C, off_at + 8 * (size_t)(C + 64), [this](u64 c) { return off_at + 8 * (size_t)n_bnd[c]; }}; }
-	int workers() const { return (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1)); }
 	// bases [lo, hi) of one chunk -> dst; the task holding the chunk's last window adds the chunk's halo and gets the slot back
 	unsigned char *stage_bases(u64 lo, u64 hi, unsigned char *dst) const
 	{
@@ -2131,29 +2154,49 @@ static int check_offsets(const uint64_t *offsets, uint64_t n_seqs)
 	return KMX_OK;
 }
 
+// Every device buffer a host variant of summarise, correct, edit or polish owns for the length of the call: the caller's
+// offsets, one record per sequence (want_rec), the bases when the call needs them whole (null: they stream through the
+// pinned slots instead), n_aux words of the call's own (the edit list; the offsets of the polished reads) and out (the
+// polished bases, allocated when their length is known).  upload allocates (failing is KMX_E_NOMEM) and enqueues the copies;
+// records enqueues the copy back.  However the call ends, the model's stream is drained before any of them goes.
+template <typename REC>
+struct SeqOnDevice {
+	kmx_model *m;
+	DevBuf<unsigned char> seq, out;
+	DevBuf<u64> offs, aux;
+	DevBuf<REC> rec;
+	~SeqOnDevice() { (void)hipStreamSynchronize(m->stream); }
+	int upload(const char *bases, const uint64_t *offsets, u64 n_seqs, bool want_rec, u64 n_aux = 0)
+	{
+		const u64 n_bases = bases ? offsets[n_seqs] : 0;
+		if ((bases && seq.alloc(n_bases) != hipSuccess) || offs.alloc(n_seqs + 1) != hipSuccess || (want_rec && rec.alloc(n_seqs) != hipSuccess) || (n_aux && aux.alloc(n_aux) != hipSuccess))
+			return fail(KMX_E_NOMEM, "device memory for %llu bases of %llu sequences could not be allocated", (unsigned long long)n_bases, (unsigned long long)n_seqs);
+		if (bases) HIPCHK(hipMemcpyAsync(seq, bases, n_bases, hipMemcpyHostToDevice, m->stream));
+		HIPCHK(hipMemcpyAsync(offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+		return KMX_OK;
+	}
+	int records(void *out, u64 n_seqs) { if (out) HIPCHK(hipMemcpyAsync(out, rec.get(), n_seqs * sizeof(REC), hipMemcpyDeviceToHost, m->stream)); return KMX_OK; }   // (null: none asked for)
+};
+
 static int kmx_query_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t *out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	if (!n_seqs) return KMX_OK;
 	TRY(check_offsets(offsets, n_seqs));
 	const u64 n_bases = offsets[n_seqs];
 	if (!n_bases) return KMX_OK;
 	if (!seq || !out) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 hook = seq_chunk_hook();
-	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, hook ? hook : kSeqChunk);
-	TRY(ensure_seq_scratch(m, sc.C));
+	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, seq_chunk());
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_seq_scratch(m, sc.C, dirty));
 	const SlotShape shape = sc.shape();
-	int par = 0;
 	auto &F = m->qfeed;
-	return query_pipeline(m, n_bases, 1, sc.workers(),
+	return query_pipeline(m, n_bases, 1, seq_workers(n_bases),
 		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
-			kmxk::query_seq(m->md, F.d_in[s], sc.nbytes_of(c), sc.bounds(F.d_in[s]), sc.seqs_of(c), 0, cn, F.d_out[s],
-			                F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
-			par ^= 1;
+			kmxk::query_seq(m->md, SeqView{F.d_in[s], 0, sc.nbytes_of(c), sc.nbytes_of(c), sc.bounds(F.d_in[s]), sc.seqs_of(c)}, 0, cn, F.d_out[s], dirty->next(), m->stream, &m->prof);
 		}, out, &shape);
 }
 
@@ -2173,31 +2216,29 @@ static int seq_thresholds(const int32_t *thr, int n_thr, kmx_seq_summary *recs, 
 
 // the handle's shared buffers for pieces / chunks of `piece` windows (the dirty list; slot_bytes != 0: the pinned slots too).
 // They only ever fail to allocate, and for this call that is KMX_E_NOMEM like its own buffers.
-static int ensure_summary_buffers(kmx_model *m, u64 piece, size_t slot_bytes)
+static int ensure_summary_buffers(kmx_model *m, u64 piece, size_t slot_bytes, std::optional<SeqDirtyCursor> &dirty)
 {
-	if (ensure_seq_scratch(m, piece) == KMX_OK && (!slot_bytes || ensure_query_feed(m, slot_bytes, 0) == KMX_OK)) return KMX_OK;
+	if (ensure_seq_scratch(m, piece, dirty) == KMX_OK && (!slot_bytes || ensure_query_feed(m, slot_bytes, 0) == KMX_OK)) return KMX_OK;
 	const std::string why = g_err;
 	return fail(KMX_E_NOMEM, "the buffers of a sequence summary could not be allocated (%s)", why.c_str());
 }
 
 static int kmx_summarise_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, const int32_t *thr, int n_thr, kmx_seq_summary *d_out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	SeqSumDev sd;
 	TRY(seq_thresholds(thr, n_thr, d_out, sd));
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || !d_out || (n_bases && !d_seq)) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece;
-	TRY(ensure_summary_buffers(m, piece, 0));
-	auto &F = m->qfeed;
+	const u64 piece = seq_piece();
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_summary_buffers(m, piece, 0, dirty));
 	kmxk::seq_summary_init(sd.rec, n_seqs, m->stream, &m->prof);
-	int par = 0;
-	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1)
-		kmxk::summarise_seq(m->md, (const unsigned char *)d_seq, 0, n_bases, (const u64 *)d_offsets, n_seqs, p0, std::min<u64>(piece, n_bases - p0), sd,
-		                    F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	const SeqView v{(const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets, n_seqs};
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece)
+		kmxk::summarise_seq(m->md, v, p0, std::min<u64>(piece, n_bases - p0), sd, dirty->next(), m->stream, &m->prof);
 	kmxk::seq_summary_finish(sd.rec, (const u64 *)d_offsets, n_seqs, n_bases, m->k, m->stream, &m->prof);
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -2209,9 +2250,8 @@ static int kmx_summarise_seqs_dev_impl(kmx_model *m, const char *d_seq, const ui
 // the whole input, of which they hold the bases [c * C, c * C + nbytes).  The records stay on the device until the end.
 static int kmx_summarise_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, const int32_t *thr, int n_thr, kmx_seq_summary *out)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	SeqSumDev sd;
 	TRY(seq_thresholds(thr, n_thr, nullptr, sd));
 	if (!n_seqs) return KMX_OK;
@@ -2224,29 +2264,22 @@ static int kmx_summarise_seqs_impl(kmx_model *m, const char *seq, const uint64_t
 	}
 	if (!seq) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	DevBuf<u64> d_offs;
-	DevBuf<SeqSummary> d_rec;
-	if (d_offs.alloc(n_seqs + 1) != hipSuccess || d_rec.alloc(n_seqs) != hipSuccess)
-		return fail(KMX_E_NOMEM, "device memory for the records and offsets of %llu sequences could not be allocated", (unsigned long long)n_seqs);
-	sd.rec = d_rec;
-	const u64 hook = seq_chunk_hook();
-	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, hook ? hook : kSeqChunk);
+	SeqOnDevice<SeqSummary> dev{m};
+	TRY(dev.upload(nullptr, offsets, n_seqs, true));
+	sd.rec = dev.rec;
+	SeqChunks sc(seq, offsets, n_seqs, (u64)m->k, seq_chunk());
 	const SlotShape shape = sc.bases_shape();
-	TRY(ensure_summary_buffers(m, sc.C, shape.slot_bytes));
-	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });   // (d_offs and d_rec go when this returns)
-	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_summary_buffers(m, sc.C, shape.slot_bytes, dirty));
 	kmxk::seq_summary_init(sd.rec, n_seqs, m->stream, &m->prof);
-	int par = 0;
 	auto &F = m->qfeed;
-	TRY(query_pipeline(m, n_bases, 1, sc.workers(),
+	TRY(query_pipeline(m, n_bases, 1, seq_workers(n_bases),
 		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage_bases(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
-			kmxk::summarise_seq(m->md, F.d_in[s], c * sc.C, c * sc.C + sc.nbytes_of(c), d_offs, n_seqs, c * sc.C, cn, sd,
-			                    F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
-			par ^= 1;
+			kmxk::summarise_seq(m->md, SeqView{F.d_in[s], c * sc.C, c * sc.C + sc.nbytes_of(c), n_bases, dev.offs, n_seqs}, c * sc.C, cn, sd, dirty->next(), m->stream, &m->prof);
 		}, (int32_t *)nullptr, &shape));
-	kmxk::seq_summary_finish(sd.rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
-	HIPCHK(hipMemcpyAsync(out, d_rec.get(), n_seqs * sizeof(kmx_seq_summary), hipMemcpyDeviceToHost, m->stream));
+	kmxk::seq_summary_finish(sd.rec, dev.offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	TRY(dev.records(out, n_seqs));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -2261,44 +2294,43 @@ static_assert(sizeof(kmx_seq_correction) == 64 && sizeof(SeqCorrection) == 64, "
 static_assert(offsetof(kmx_seq_correction, n_weak) == offsetof(SeqCorrection, n_weak) && offsetof(kmx_seq_correction, n_unfixable) == offsetof(SeqCorrection, n_unfixable),
               "SeqCorrection (kmx_types.h) is the layout of kmx_seq_correction");
 
-static bool ranges_overlap(const void *a, const void *b, u64 n)
+static bool spans_overlap(const void *a, u64 na, const void *b, u64 nb)
 {
 	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return x < y + n && y < x + n;
+	return na && nb && x < y + nb && y < x + na;
 }
 
 // the handle's buffers for pieces / chunks of `piece` windows: dirty list and weak bits with both halos, a flag per
 // workgroup (slot_bytes != 0: the pinned slots too, `answers` int32 words of output each).  Failing is KMX_E_NOMEM.
-static int ensure_correct_buffers(kmx_model *m, u64 piece, size_t slot_bytes, size_t answers)
+static int ensure_correct_buffers(kmx_model *m, u64 piece, size_t slot_bytes, size_t answers, std::optional<SeqDirtyCursor> &dirty)
 {
 	auto &F = m->qfeed;
 	const u64 ext = piece + 2 * KMX_CORR_HALO(64);
-	if (ensure_seq_scratch(m, ext) == KMX_OK && F.d_corr_bits.ensure((size_t)((ext + 255) / 256 * 4), m->stream) == hipSuccess &&
+	if (ensure_seq_scratch(m, ext, dirty) == KMX_OK && F.d_corr_bits.ensure((size_t)((ext + 255) / 256 * 4), m->stream) == hipSuccess &&
 	    F.d_corr_flags.ensure((size_t)((piece + 255) / 256), m->stream) == hipSuccess && (!slot_bytes || ensure_query_feed(m, slot_bytes, answers) == KMX_OK)) return KMX_OK;
 	return fail(KMX_E_NOMEM, "the buffers of a sequence correction could not be allocated");
 }
 
 static int kmx_correct_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, char *d_seq_out, kmx_seq_correction *d_rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || (n_bases && (!d_seq || !d_seq_out))) return fail(KMX_E_ARG, "null argument");
-	if (n_bases && ranges_overlap(d_seq, d_seq_out, n_bases)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
+	if (spans_overlap(d_seq, n_bases, d_seq_out, n_bases)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece, H = KMX_CORR_HALO(m->k);
-	TRY(ensure_correct_buffers(m, piece, 0, 0));
+	const u64 piece = seq_piece(), H = KMX_CORR_HALO(m->k);
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_correct_buffers(m, piece, 0, 0, dirty));
 	auto &F = m->qfeed;
 	kmxk::seq_correction_init((SeqCorrection *)d_rec, (const u64 *)d_offsets, n_seqs, n_bases, m->k, m->stream, &m->prof);
 	if (n_bases) HIPCHK(hipMemcpyAsync(d_seq_out, d_seq, n_bases, hipMemcpyDeviceToDevice, m->stream));
 	const CorrDev cd{(SeqCorrection *)d_rec, (unsigned char *)d_seq_out, nullptr, 0, thr, min_support};
-	int par = 0;
-	for (u64 p0 = 0; p0 < n_bases; p0 += piece, par ^= 1) {
+	const SeqView v{(const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets, n_seqs};
+	for (u64 p0 = 0; p0 < n_bases; p0 += piece) {
 		const u64 cn = std::min<u64>(piece, n_bases - p0);
-		kmxk::correct_piece(m->md, (const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets, n_seqs, p0, cn, p0 > H ? p0 - H : 0, std::min<u64>(p0 + cn + H, n_bases),
-		                    F.d_corr_bits, cd, F.d_corr_flags, F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+		kmxk::correct_piece(m->md, v, p0, cn, p0 > H ? p0 - H : 0, std::min<u64>(p0 + cn + H, n_bases), F.d_corr_bits, cd, F.d_corr_flags, dirty->next(), m->stream, &m->prof);
 	}
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -2315,9 +2347,8 @@ static int kmx_correct_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint
 static const size_t kCorrPad = 256;
 static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, char *seq_out, kmx_seq_correction *rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
 	if (!n_seqs) return KMX_OK;
 	TRY(check_offsets(offsets, n_seqs));
@@ -2327,19 +2358,18 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 		return KMX_OK;
 	}
 	if (!seq || !seq_out) return fail(KMX_E_ARG, "null argument");
-	if (seq_out != seq && ranges_overlap(seq, seq_out, n_bases)) return fail(KMX_E_ARG, "seq_out overlaps seq (only seq_out == seq is allowed)");
+	if (seq_out != seq && spans_overlap(seq, n_bases, seq_out, n_bases)) return fail(KMX_E_ARG, "seq_out overlaps seq (only seq_out == seq is allowed)");
 	HIPCHK(hipSetDevice(m->device));
-	DevBuf<u64> d_offs;
-	DevBuf<SeqCorrection> d_rec;
-	if (d_offs.alloc(n_seqs + 1) != hipSuccess || (rec && d_rec.alloc(n_seqs) != hipSuccess))
-		return fail(KMX_E_NOMEM, "device memory for the records and offsets of %llu sequences could not be allocated", (unsigned long long)n_seqs);
-	const u64 hook = seq_chunk_hook(), C = std::min<u64>(hook ? hook : kSeqChunk, n_bases), k = (u64)m->k, H = KMX_CORR_HALO(k);
+	SeqOnDevice<SeqCorrection> dev{m};
+	TRY(dev.upload(nullptr, offsets, n_seqs, rec != nullptr));
+	const u64 C = std::min<u64>(seq_chunk(), n_bases), k = (u64)m->k, H = KMX_CORR_HALO(k);
 	const u32 fix_cap = (u32)(C / 2 + 8), eager = (u32)std::min<u64>(C / 16 + 16, fix_cap);
 	auto g1_of = [&](u64 c0, u64 cn) { return std::min<u64>(c0 + cn + H + k - 1, n_bases); };
 	SlotShape shape{C, kCorrPad + (size_t)(C + H + k + 8), [&](u64 c) { const u64 c0 = c * C; return kCorrPad + (size_t)(g1_of(c0, std::min<u64>(C, n_bases - c0)) - c0); }};
 	shape.answers = 2 + (size_t)fix_cap;
 	shape.out_bytes = (2 + (size_t)eager) * 4;
-	TRY(ensure_correct_buffers(m, C, shape.slot_bytes, shape.answers));
+	std::optional<SeqDirtyCursor> dirty;
+	TRY(ensure_correct_buffers(m, C, shape.slot_bytes, shape.answers, dirty));
 	auto &F = m->qfeed;
 	std::vector<u64> fixes;                                        // position << 2 | code
 	shape.consume = [&](u64 c, int s) -> int {
@@ -2352,13 +2382,9 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 		catch (...) { return fail(KMX_E_NOMEM, "out of host memory"); }
 		return KMX_OK;
 	};
-	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });   // (d_offs and d_rec go when this returns)
-	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
-	kmxk::seq_correction_init(d_rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
-	CorrDev cd{d_rec, nullptr, nullptr, fix_cap, thr, min_support};
-	int par = 0;
-	const int T = (int)std::max<u64>(1, std::min<u64>(std::min(kmx_host_cpus(), 16), n_bases / 65536 + 1));
-	TRY(query_pipeline(m, n_bases, 1, T,
+	kmxk::seq_correction_init(dev.rec, dev.offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
+	CorrDev cd{dev.rec, nullptr, nullptr, fix_cap, thr, min_support};
+	TRY(query_pipeline(m, n_bases, 1, seq_workers(n_bases),
 		[&](int, u64 lo, u64 hi, unsigned char *dst) {
 			const u64 c0 = lo / C * C, cn = std::min<u64>(C, n_bases - c0);
 			unsigned char *slot = dst - (lo - c0);
@@ -2371,11 +2397,10 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 			const u64 c0 = c * C, hl = std::min<u64>(H, c0);
 			(void)hipMemsetAsync(F.d_out[s], 0, 8, m->stream);
 			cd.fix = (u32 *)F.d_out[s].get();
-			kmxk::correct_piece(m->md, F.d_in[s] + (kCorrPad - hl), c0 - hl, g1_of(c0, cn), n_bases, d_offs, n_seqs, c0, cn, c0 - hl, std::min<u64>(c0 + cn + H, n_bases),
-			                    F.d_corr_bits, cd, F.d_corr_flags, F.d_seq_list, (u32)F.d_seq_list.cap(), F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
-			par ^= 1;
+			const SeqView v{F.d_in[s] + (kCorrPad - hl), c0 - hl, g1_of(c0, cn), n_bases, dev.offs, n_seqs};
+			kmxk::correct_piece(m->md, v, c0, cn, c0 - hl, std::min<u64>(c0 + cn + H, n_bases), F.d_corr_bits, cd, F.d_corr_flags, dirty->next(), m->stream, &m->prof);
 		}, (int32_t *)nullptr, &shape));
-	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+	TRY(dev.records(rec, n_seqs));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	HIPCHK(hipGetLastError());
 	for (u64 f : fixes) seq_out[f >> 2] = "ACGT"[f & 3];
@@ -2392,9 +2417,8 @@ static_assert(sizeof(kmx_seq_edits) == 80 && sizeof(SeqEdits) == 80 && sizeof(km
 static_assert(offsetof(kmx_seq_edits, n_sub) == offsetof(SeqEdits, n_sub) && offsetof(kmx_seq_edits, n_ins) == offsetof(SeqEdits, n_ins) &&
               offsetof(kmx_seq_edits, out_len) == offsetof(SeqEdits, out_len), "SeqEdits (kmx_types.h) is the layout of kmx_seq_edits");
 
-static int edit_args(kmx_model *m, int min_support, int ops)
+static int edit_args(int min_support, int ops)
 {
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
 	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
 	if (ops < 1 || ops > 7) return fail(KMX_E_ARG, "ops = %d, not a non-empty subset of KMX_EDIT_OPS_SUB | _DEL | _INS", ops);
 	return KMX_OK;
@@ -2404,20 +2428,20 @@ static int edit_args(kmx_model *m, int min_support, int ops)
 // d_edit_cnt[0].  Arguments checked, the handle's query lock held, n_seqs and n_bases > 0.
 static int edit_seqs_enqueue(kmx_model *m, const unsigned char *d_seq, const u64 *d_offs, u64 n_seqs, u64 n_bases, int32_t thr, int min_support, int ops, u64 *d_edits, u64 capacity, SeqEdits *d_rec)
 {
-	const u64 hook = seq_chunk_hook(), piece = hook ? hook : kSeqPiece, pa = (piece + 255) / 256 * 256;
+	const u64 piece = seq_piece(), pa = (piece + 255) / 256 * 256;
 	auto &F = m->qfeed;
-	if (ensure_correct_buffers(m, pa, 0, 0) != KMX_OK || F.d_edit_bits.ensure((size_t)((n_bases + 255) / 256 * 4 + 2), m->stream) != hipSuccess ||
+	std::optional<SeqDirtyCursor> dirty;
+	if (ensure_correct_buffers(m, pa, 0, 0, dirty) != KMX_OK || F.d_edit_bits.ensure((size_t)((n_bases + 255) / 256 * 4 + 2), m->stream) != hipSuccess ||
 	    F.d_edit_cnt.ensure(2, m->stream) != hipSuccess)
 		return fail(KMX_E_NOMEM, "the buffers of a sequence edit could not be allocated");
 	kmxk::seq_edits_init(d_rec, d_offs, n_seqs, n_bases, m->k, m->stream, &m->prof);
 	HIPCHK(hipMemsetAsync(F.d_edit_cnt.get(), 0, 8, m->stream));
-	int par = 0;
-	for (u64 w0 = 0; w0 < n_bases; w0 += pa, par ^= 1)
-		kmxk::edit_weak_piece(m->md, d_seq, n_bases, d_offs, n_seqs, w0, std::min<u64>(pa, n_bases - w0), thr, F.d_edit_bits, F.d_seq_list, (u32)F.d_seq_list.cap(),
-		                      F.d_seq_cnt + par, F.d_seq_cnt + (par ^ 1), m->stream, &m->prof);
+	const SeqView v{d_seq, 0, n_bases, n_bases, d_offs, n_seqs};
+	for (u64 w0 = 0; w0 < n_bases; w0 += pa)
+		kmxk::edit_weak_piece(m->md, v, w0, std::min<u64>(pa, n_bases - w0), thr, F.d_edit_bits, dirty->next(), m->stream, &m->prof);
 	const EditDev ed{d_rec, d_edits, d_edits ? capacity : 0, F.d_edit_cnt.get(), thr, min_support, ops};
 	for (u64 p0 = 0; p0 < n_bases; p0 += piece)
-		kmxk::edit_sites_piece(m->md, d_seq, n_bases, d_offs, n_seqs, p0, std::min<u64>(piece, n_bases - p0), F.d_edit_bits, ed, F.d_corr_flags, m->stream, &m->prof);
+		kmxk::edit_sites_piece(m->md, v, p0, std::min<u64>(piece, n_bases - p0), F.d_edit_bits, ed, F.d_corr_flags, m->stream, &m->prof);
 	return KMX_OK;
 }
 
@@ -2452,9 +2476,9 @@ static int edit_seqs_core(kmx_model *m, const unsigned char *d_seq, const u64 *d
 static int kmx_edit_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops,
                                   kmx_edit *d_edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *d_rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	TRY(edit_args(m, min_support, ops));
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
+	TRY(edit_args(min_support, ops));
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || !n_edits || (n_bases && !d_seq) || (capacity && !d_edits)) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
@@ -2469,9 +2493,9 @@ static int kmx_edit_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_
 static int kmx_edit_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops,
                               kmx_edit *edits, uint64_t capacity, uint64_t *n_edits, kmx_seq_edits *rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	TRY(edit_args(m, min_support, ops));
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
+	TRY(edit_args(min_support, ops));
 	if (!n_seqs) return KMX_OK;
 	TRY(check_offsets(offsets, n_seqs));
 	if (!n_edits || (capacity && !edits)) return fail(KMX_E_ARG, "null argument");
@@ -2484,18 +2508,12 @@ static int kmx_edit_seqs_impl(kmx_model *m, const char *seq, const uint64_t *off
 	if (!seq) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
 	const u64 cap = std::min<u64>(capacity, n_bases / 3 + 1);          // more than that is never found
-	DevBuf<unsigned char> d_seq;
-	DevBuf<u64> d_offs, d_edits;
-	DevBuf<SeqEdits> d_rec;
-	if (d_seq.alloc(n_bases) != hipSuccess || d_offs.alloc(n_seqs + 1) != hipSuccess || (cap && d_edits.alloc(cap) != hipSuccess) || (rec && d_rec.alloc(n_seqs) != hipSuccess))
-		return fail(KMX_E_NOMEM, "device memory for %llu bases of %llu sequences could not be allocated", (unsigned long long)n_bases, (unsigned long long)n_seqs);
-	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });
-	HIPCHK(hipMemcpyAsync(d_seq, seq, n_bases, hipMemcpyHostToDevice, m->stream));
-	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
-	const int rc = edit_seqs_core(m, d_seq, d_offs, n_seqs, n_bases, thr, min_support, ops, cap ? d_edits.get() : nullptr, cap, (u64 *)n_edits, rec ? d_rec.get() : nullptr);
+	SeqOnDevice<SeqEdits> dev{m};
+	TRY(dev.upload(seq, offsets, n_seqs, rec != nullptr, cap));
+	const int rc = edit_seqs_core(m, dev.seq, dev.offs, n_seqs, n_bases, thr, min_support, ops, dev.aux, cap, (u64 *)n_edits, dev.rec);
 	if (rc != KMX_OK && rc != KMX_E_RANGE) return rc;
-	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
-	if (rc == KMX_OK && *n_edits) HIPCHK(hipMemcpyAsync(edits, d_edits.get(), *n_edits * 8, hipMemcpyDeviceToHost, m->stream));
+	TRY(dev.records(rec, n_seqs));
+	if (rc == KMX_OK && *n_edits) HIPCHK(hipMemcpyAsync(edits, dev.aux.get(), *n_edits * 8, hipMemcpyDeviceToHost, m->stream));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	return rc;
 }
@@ -2572,15 +2590,9 @@ static_assert(offsetof(kmx_seq_polish, converged) == offsetof(SeqPolish, converg
               offsetof(kmx_seq_polish, n_unfixable) == offsetof(SeqPolish, n_unfixable), "SeqPolish (kmx_types.h) is the layout of kmx_seq_polish");
 static_assert(KMX_POLISH_MAX_PASSES == POLISH_MAX_PASSES, "the pass limit of kmx_types.h is that of kmx.h");
 
-static bool spans_overlap(const void *a, u64 na, const void *b, u64 nb)
+static int polish_args(int min_support, int ops, int max_passes)
 {
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return na && nb && x < y + nb && y < x + na;
-}
-
-static int polish_args(kmx_model *m, int min_support, int ops, int max_passes)
-{
-	TRY(edit_args(m, min_support, ops));
+	TRY(edit_args(min_support, ops));
 	if (max_passes < 1 || max_passes > KMX_POLISH_MAX_PASSES) return fail(KMX_E_ARG, "max_passes = %d, not in [1, %d]", max_passes, KMX_POLISH_MAX_PASSES);
 	return KMX_OK;
 }
@@ -2681,9 +2693,9 @@ static int polish_passes(kmx_model *m, const unsigned char *d_seq, const u64 *d_
 static int kmx_polish_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int min_support, int ops, int max_passes,
                                     char *d_seq_out, uint64_t out_capacity, uint64_t *d_offsets_out, kmx_seq_polish *d_rec, uint64_t *passes_run)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	TRY(polish_args(m, min_support, ops, max_passes));
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
+	TRY(polish_args(min_support, ops, max_passes));
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || !d_offsets_out || (n_bases && !d_seq) || (out_capacity && !d_seq_out)) return fail(KMX_E_ARG, "null argument");
 	if (spans_overlap(d_seq, n_bases, d_seq_out, out_capacity)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
@@ -2711,9 +2723,9 @@ static int kmx_polish_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint6
 static int kmx_polish_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int min_support, int ops, int max_passes,
                                 char *seq_out, uint64_t out_capacity, uint64_t *offsets_out, kmx_seq_polish *rec, uint64_t *passes_run)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	TRY(polish_args(m, min_support, ops, max_passes));
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
+	TRY(polish_args(min_support, ops, max_passes));
 	if (!n_seqs) return KMX_OK;
 	TRY(check_offsets(offsets, n_seqs));
 	const u64 n_bases = offsets[n_seqs];
@@ -2726,25 +2738,19 @@ static int kmx_polish_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 		return KMX_OK;
 	}
 	HIPCHK(hipSetDevice(m->device));
-	DevBuf<unsigned char> d_seq, d_out;
-	DevBuf<u64> d_offs, d_oo;
-	DevBuf<SeqPolish> d_rec;
-	if (d_seq.alloc(n_bases) != hipSuccess || d_offs.alloc(n_seqs + 1) != hipSuccess || d_oo.alloc(n_seqs + 1) != hipSuccess || d_rec.alloc(n_seqs) != hipSuccess)
-		return fail(KMX_E_NOMEM, "device memory for %llu bases of %llu sequences could not be allocated", (unsigned long long)n_bases, (unsigned long long)n_seqs);
-	auto drained = scope_exit([&] { (void)hipStreamSynchronize(m->stream); });
-	HIPCHK(hipMemcpyAsync(d_seq, seq, n_bases, hipMemcpyHostToDevice, m->stream));
-	HIPCHK(hipMemcpyAsync(d_offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, m->stream));
+	SeqOnDevice<SeqPolish> dev{m};
+	TRY(dev.upload(seq, offsets, n_seqs, true, n_seqs + 1));
 	u64 total = 0;
 	int passes = 0;
-	const int rc = polish_passes(m, d_seq, d_offs, n_seqs, n_bases, thr, min_support, ops, max_passes, d_rec, d_oo, out_capacity,
-	                             [&](u64 t) { const u64 n = std::min<u64>(t, out_capacity); return n && d_out.alloc(n) == hipSuccess ? d_out.get() : nullptr; }, &total, &passes);
+	const int rc = polish_passes(m, dev.seq, dev.offs, n_seqs, n_bases, thr, min_support, ops, max_passes, dev.rec, dev.aux, out_capacity,
+	                             [&](u64 t) { const u64 n = std::min<u64>(t, out_capacity); return n && dev.out.alloc(n) == hipSuccess ? dev.out.get() : nullptr; }, &total, &passes);
 	if (rc == KMX_E_NOMEM) return fail(KMX_E_NOMEM, "device memory for the polished bases could not be allocated");
 	TRY(rc);
 	if (passes_run) *passes_run = (u64)passes;
 	const u64 n_out = std::min<u64>(total, out_capacity);
-	if (n_out) HIPCHK(hipMemcpyAsync(seq_out, d_out.get(), n_out, hipMemcpyDeviceToHost, m->stream));
-	HIPCHK(hipMemcpyAsync(offsets_out, d_oo.get(), (n_seqs + 1) * 8, hipMemcpyDeviceToHost, m->stream));
-	if (rec) HIPCHK(hipMemcpyAsync(rec, d_rec.get(), n_seqs * sizeof *rec, hipMemcpyDeviceToHost, m->stream));
+	if (n_out) HIPCHK(hipMemcpyAsync(seq_out, dev.out.get(), n_out, hipMemcpyDeviceToHost, m->stream));
+	HIPCHK(hipMemcpyAsync(offsets_out, dev.aux.get(), (n_seqs + 1) * 8, hipMemcpyDeviceToHost, m->stream));
+	TRY(dev.records(rec, n_seqs));
 	HIPCHK(hipStreamSynchronize(m->stream));
 	if (total > out_capacity) return fail(KMX_E_RANGE, "the polished sequences take %llu bytes, seq_out has %llu", (unsigned long long)total, (unsigned long long)out_capacity);
 	return KMX_OK;
@@ -2773,11 +2779,11 @@ static int extend_steps()
 	const long long x = e ? atoll(e) : 0;
 	return x > 0 ? (int)std::min<long long>(x, KMX_EXT_MAX_EXT_LIMIT) : kExtSteps;
 }
-static u64 extend_chunk_hook()
+static u64 extend_chunk(u64 dflt)
 {
 	const char *e = hook_env("KMX_EXTEND_CHUNK_SEEDS");
 	const long long x = e ? atoll(e) : 0;
-	return x > 0 ? std::min<u64>((u64)x, kExtChunk) : 0;
+	return x > 0 ? std::min<u64>((u64)x, kExtChunk) : dflt;
 }
 
 static int extend_args(int max_ext, int depth)
@@ -2797,14 +2803,13 @@ static int ensure_extend_buffers(kmx_model *m, u64 n)
 
 static int kmx_extend_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, int32_t thr, int max_ext, int depth, char *d_ext, kmx_seq_extension *d_rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	TRY(extend_args(max_ext, depth));
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || !d_ext || (n_bases && !d_seq)) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 hook = extend_chunk_hook(), C = std::min<u64>(hook ? hook : kExtChunk, n_seqs);
+	const u64 C = std::min<u64>(extend_chunk(kExtChunk), n_seqs);
 	TRY(ensure_extend_buffers(m, C));
 	auto &F = m->qfeed;
 	HIPCHK(hipMemsetAsync(d_ext, 0, (size_t)(n_seqs * (u64)max_ext), m->stream));
@@ -2812,7 +2817,7 @@ static int kmx_extend_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint6
 	for (u64 s0 = 0; s0 < n_seqs; s0 += C) {
 		const u64 cn = std::min<u64>(C, n_seqs - s0);
 		const ExtDev xd{F.d_ext_walk, d_rec ? (SeqExtension *)d_rec + s0 : nullptr, (unsigned char *)d_ext + s0 * (u64)max_ext, thr, (u32)max_ext, depth};
-		kmxk::extend_walks(m->md, (const unsigned char *)d_seq, n_bases, (const u64 *)d_offsets + s0, (u32)cn, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
+		kmxk::extend_walks(m->md, SeqView{(const unsigned char *)d_seq, 0, n_bases, n_bases, (const u64 *)d_offsets + s0, cn}, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
 	}
 	HIPCHK(hipGetLastError());
 	return KMX_OK;
@@ -2823,16 +2828,14 @@ static int kmx_extend_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint6
 // A chunk holds as many seeds as keep its rows within kExtRowBytes.
 static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, int32_t thr, int max_ext, int depth, char *ext, kmx_seq_extension *rec)
 {
-	if (!m) return fail(KMX_E_ARG, "null model");
-	std::lock_guard<std::mutex> lk(m->query_mu);
-	if (m->state != ST_READY) return fail(KMX_E_STATE, "query before the model is built or loaded");
+	std::unique_lock<std::mutex> lk;
+	TRY(query_enter(m, lk));
 	TRY(extend_args(max_ext, depth));
 	if (!n_seqs) return KMX_OK;
 	TRY(check_offsets(offsets, n_seqs));
 	if (!ext || (offsets[n_seqs] && !seq)) return fail(KMX_E_ARG, "null argument");
 	HIPCHK(hipSetDevice(m->device));
-	const u64 k = (u64)m->k, hook = extend_chunk_hook();
-	const u64 C = std::min<u64>(hook ? hook : std::min<u64>(kExtChunk, std::max<u64>(1, kExtRowBytes / (u64)max_ext)), n_seqs);
+	const u64 k = (u64)m->k, C = std::min<u64>(extend_chunk(std::min<u64>(kExtChunk, std::max<u64>(1, kExtRowBytes / (u64)max_ext))), n_seqs);
 	TRY(ensure_extend_buffers(m, C));
 	auto &F = m->qfeed;
 	PinBuf<unsigned char> h_tail;
@@ -2858,7 +2861,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 		HIPCHK(hipMemcpyAsync(d_offs, h_offs, (cn + 1) * 8, hipMemcpyHostToDevice, m->stream));
 		HIPCHK(hipMemsetAsync(d_rows, 0, (size_t)(cn * (u64)max_ext), m->stream));
 		const ExtDev xd{F.d_ext_walk, d_rec, d_rows, thr, (u32)max_ext, depth};
-		kmxk::extend_walks(m->md, d_tail, t, d_offs, (u32)cn, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
+		kmxk::extend_walks(m->md, SeqView{d_tail, 0, t, t, d_offs, cn}, xd, F.d_ext_lists, F.d_ext_cnt, steps, m->stream, &m->prof);
 		HIPCHK(hipGetLastError());
 		HIPCHK(hipMemcpyAsync(ext + s0 * (u64)max_ext, d_rows.get(), (size_t)(cn * (u64)max_ext), hipMemcpyDeviceToHost, m->stream));
 		if (rec) HIPCHK(hipMemcpyAsync(rec + s0, d_rec.get(), cn * sizeof *rec, hipMemcpyDeviceToHost, m->stream));

@@ -215,6 +215,24 @@ struct RoundProbe {
 	u32 *sink;
 };
 
+// The two argument blocks of the launchers that work along sequences (launchers.h); they unpack them into the kernels' parameters.
+// Which bases a launch holds: seq[0] is the base at position g0 of an input of n_total bases, [g0, g1) is on hand, and the
+// n_seqs + 1 offsets are in those positions (of the whole input, whatever part of it seq holds).
+struct SeqView {
+	const unsigned char *seq;
+	u64 g0, g1, n_total;
+	const u64 *offs;
+	u64 n_seqs;
+};
+// The dirty list of one piece: the windows with a byte outside ACGT, which the piece's first launch appends to list[*cnt++]
+// and its second launch answers.  list needs cap entries, one per window of the piece; *cnt is 0 on entry; the second launch
+// zeroes *cnt_next, the counter of the NEXT piece, so consecutive pieces alternate between two counters.
+struct SeqDirty {
+	u32 *list;
+	u32 cap;
+	u32 *cnt, *cnt_next;
+};
+
 // kmx_summarise_seqs: one record per sequence, the layout of kmx_seq_summary (include/kmx.h; kmx_api.hip asserts it) ...
 struct SeqSummary {
 	u64 n_windows, sum;

@@ -28,16 +28,16 @@ void range_resolve(const ModelDev &, const BlockDev &, const RangeDev &, const R
 void range_commit_apply(const ModelDev &, const RangeIn &, int, hipStream_t);
 void query(const ModelDev &, const u64 *, u64, int *, hipStream_t, KernelProf *, u64 *acct = nullptr);
 void query_ascii(const ModelDev &, int, const unsigned char *, int, u64, int *, hipStream_t);
-void query_seq(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void query_seq(const ModelDev &, const SeqView &, u64 p0, u64 n_win, int *, const SeqDirty &, hipStream_t, KernelProf *);
 void seq_summary_init(SeqSummary *, u64, hipStream_t, KernelProf *);
 void seq_summary_finish(SeqSummary *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
-void summarise_seq(const ModelDev &, const unsigned char *, u64, u64, const u64 *, u64, u64, u64, const SeqSumDev &, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void summarise_seq(const ModelDev &, const SeqView &, u64 p0, u64 n_win, const SeqSumDev &, const SeqDirty &, hipStream_t, KernelProf *);
 void seq_correction_init(SeqCorrection *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
-void correct_piece(const ModelDev &, const unsigned char *, u64, u64, u64, const u64 *, u64, u64, u64, u64, u64, u64 *, const CorrDev &, unsigned char *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
+void correct_piece(const ModelDev &, const SeqView &, u64 p0, u64 n_win, u64 w0, u64 w1, u64 *bits, const CorrDev &, unsigned char *flags, const SeqDirty &, hipStream_t, KernelProf *);
 void seq_edits_init(SeqEdits *, const u64 *, u64, u64, int, hipStream_t, KernelProf *);
-void edit_weak_piece(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, int, u64 *, u32 *, u32, u32 *, u32 *, hipStream_t, KernelProf *);
-void edit_sites_piece(const ModelDev &, const unsigned char *, u64, const u64 *, u64, u64, u64, const u64 *, const EditDev &, unsigned char *, hipStream_t, KernelProf *);
-void extend_walks(const ModelDev &, const unsigned char *, u64, const u64 *, u32, const ExtDev &, u32 *, u32 *, int, hipStream_t, KernelProf *);
+void edit_weak_piece(const ModelDev &, const SeqView &, u64 w0, u64 n_win, int thr, u64 *bits, const SeqDirty &, hipStream_t, KernelProf *);
+void edit_sites_piece(const ModelDev &, const SeqView &, u64 p0, u64 n_win, const u64 *bits, const EditDev &, unsigned char *flags, hipStream_t, KernelProf *);
+void extend_walks(const ModelDev &, const SeqView &, const ExtDev &, u32 *lists, u32 *cnt, int steps, hipStream_t, KernelProf *);
 void cells_from_disk(const unsigned char *, const unsigned char *, u64, cell_t *, u64, hipStream_t);
 void cells_to_disk(const cell_t *, u64, u64, int, unsigned char *, hipStream_t);
 void debug_hash(int, const u64 *, u64, const u32 *, int, int, u64 *, hipStream_t);
