@@ -302,6 +302,48 @@ public:
 		return out;
 	}
 
+	// The unitigs of a counted listing (the rule: kmx.h): the maximal non-branching paths of the de Bruijn graph whose nodes are
+	// the listed k-mers with count >= thr, one string each, in the rule's order; rec (optional) receives one kmx_unitig per
+	// string.  count_unitigs reads the listing init_reads / the last kmx_count_finish kept on the device; unitigs takes a
+	// listing of packed canonical k-mers (W = ceil(k/32) words each, strictly ascending) and needs no built model.  k is odd.
+	// Each call is two C calls, the sizing call and the call with exact room, and both rank the whole graph: twice the
+	// construction.  A caller who can bound the output calls kmx_count_unitigs / kmx_unitigs once.
+	std::vector<std::string> count_unitigs(uint32_t thr = 1, std::vector<kmx_unitig> *rec = 0)
+	{
+		uint64_t nu = 0, nb = 0;
+		check(kmx_count_unitigs(h_, thr, 0, 0, 0, 0, 0, &nu, &nb));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		check(kmx_count_unitigs(h_, thr, &bases[0], nb, &off[0], &r[0], nu, &nu, &nb));
+		r.resize((size_t)nu);
+		if (rec) rec->swap(r);
+		return split(bases, off);
+	}
+	std::vector<std::string> unitigs(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr = 1, std::vector<kmx_unitig> *rec = 0)
+	{
+		uint64_t nu = 0, nb = 0;
+		const uint64_t n = counts.size();
+		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitigs: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
+		check(kmx_unitigs(h_, k, kmers.data(), counts.data(), n, thr, 0, 0, 0, 0, 0, &nu, &nb));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		check(kmx_unitigs(h_, k, kmers.data(), counts.data(), n, thr, &bases[0], nb, &off[0], &r[0], nu, &nu, &nb));
+		r.resize((size_t)nu);
+		if (rec) rec->swap(r);
+		return split(bases, off);
+	}
+	// the unitigs as FASTA: one record per unitig, its header ">u<index> n_kmers=<m> mean_count=<sum / m, two decimals> circular=<0|1>"
+	static void write_unitigs_fasta(std::ostream &out, const std::vector<std::string> &strs, const std::vector<kmx_unitig> &rec)
+	{
+		char mean[32];
+		for (size_t u = 0; u < strs.size(); u++) {
+			std::snprintf(mean, sizeof mean, "%.2f", rec[u].n_kmers ? (double)rec[u].sum_count / (double)rec[u].n_kmers : 0.0);
+			out << ">u" << u << " n_kmers=" << rec[u].n_kmers << " mean_count=" << mean << " circular=" << (int)rec[u].circular << "\n" << strs[u] << "\n";
+		}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -536,6 +536,78 @@ int kmx_count_listing(kmx_model *m, uint64_t *kmers, uint32_t *counts, uint64_t 
  * libz.so.1 at run time (opened with dlopen; plain input does not).                                                       */
 int kmx_build_from_reads(kmx_model *m, int k, const char *input);
 
+/* ---- unitigs: the compacted de Bruijn graph of a counted listing, on the device.  A sorted listing is an exact membership
+ * structure (no tie-break, no false positives: unlike kmx_extend_seqs nothing here asks the model), and the maximal
+ * non-branching paths of its graph are what an assembler calls unitigs.
+ * Input: a listing of n packed k-mers (W = ceil(k/32) words each) with uint32 counts, strictly ascending as 2k-bit integers,
+ * each k-mer canonical in the counting rule's sense (the numeric minimum of the forward word and its reverse complement, for
+ * every k: not the model's k > 32 hashing quirk) -- what kmx_count_listing returns and what a KMC1-layout database lists -- and
+ * a threshold thr (uint32).  k must be ODD, in [5, 63]: an even k has k-mers equal to their own reverse complement, where a
+ * path can fold back onto itself (KMX_E_ARG).  n must be below 2^31 (KMX_E_ARG): oriented nodes are 32-bit words.
+ *   Nodes: the listed k-mers with count >= thr; idx(u) is a node's index in the listing.  An oriented k-mer is a k-byte string
+ *     x over ACGT whose canonical form canon(x) is a node.
+ *   Degrees: succ(x) = { x[1:] + c : c in A, C, G, T and canon(x[1:] + c) is a node }, pred(x) = { c + x[:-1] : likewise }; a
+ *     degree is the number of such c.  A neighbour that is x itself or rc(x) counts like any other.
+ *   Links: x -> y is a link iff succ(x) = {y}, pred(y) = {x} and canon(y) != canon(x): a homopolymer's self-loop and a hairpin
+ *     x -> rc(x) are edges but never links.  Links are symmetric under reverse complement (x -> y iff rc(y) -> rc(x)), and every
+ *     oriented k-mer has at most one link in and one link out, so the 2 n oriented k-mers fall into disjoint paths and cycles
+ *     that come in mirror pairs (P, rc(P)); for odd k, P != rc(P) and no component holds both orientations of a node.
+ *   Unitigs: one per mirror pair.  A path of m >= 1 k-mers x_1 .. x_m (x_1 has no link in, x_m no link out): for m = 1 the
+ *     representative is the canonical orientation; for m > 1, of P and rc(P) the one whose first node has the smaller listing
+ *     index (the two end nodes are distinct).  A cycle of m >= 2 k-mers: the representative starts at the cycle's node of
+ *     smallest listing index, in its canonical orientation, follows the links once round, and is spelled open with
+ *     circular = 1.  The string is x_1 followed by the last byte of each of x_2 .. x_m: m + k - 1 bytes of uppercase ACGT.
+ *   Order: ascending listing index of canon(x_1).  Every node lies in exactly one unitig, so the order is total.
+ * Every field of the record is an integer count, sum, minimum or maximum, and the result is a function of (listing, thr) alone:
+ * byte-identical across runs and variants.
+ * Out of scope: even k, n >= 2^31, tip clipping, bubble popping, edges between unitigs (GFA links), unsorted (KMC2-order)
+ * listings (sort them first), unitigs from the model's answers, several GPUs, choosing thr.                                 */
+typedef struct kmx_unitig {              /* one per unitig; 40 bytes, no padding */
+	uint64_t n_kmers;                    /* m; the string has m + k - 1 bytes */
+	uint64_t sum_count;                  /* over its nodes, of the listing's counts */
+	uint32_t min_count, max_count;       /* capped at cs when the listing is a session's */
+	uint64_t first_node;                 /* idx(canon(x_1)) */
+	uint8_t  circular;
+	uint8_t  n_pred;                     /* |pred(x_1)| */
+	uint8_t  n_succ;                     /* |succ(x_m)|; both are 1 for a cycle */
+	uint8_t  first_fwd;                  /* 1 iff x_1 is canonical */
+	uint8_t  reserved[4];                /* 0 */
+} kmx_unitig;
+/* On DEVICE buffers d_kmers[n * W], d_counts[n], on the model's stream; needs no built model (like kmx_apply_edits_dev) and
+ * leaves the model and a session's listing as they are.  d_seq_out[seq_capacity] and d_offsets_out[rec_capacity + 1] receive
+ * the unitigs in the layout of kmx_query_seqs (unitig u = d_seq_out[offsets[u] .. offsets[u + 1]), offsets[0] = 0), d_rec
+ * [rec_capacity] the records (may be NULL); *n_unitigs and *n_bases_out, on the HOST, the number of unitigs and of their bytes.
+ * d_seq_out == NULL: the sizing call, only the two counts are returned.  A capacity too small: KMX_E_RANGE, both counts are
+ * what is needed, nothing is written; rec_capacity = the nodes and seq_capacity = nodes * k always suffice.  The listing is
+ * validated on the device by the first pass: not strictly ascending, not canonical or wider than 2k bits is KMX_E_ARG, and no
+ * access ever leaves the buffers.  n == 0 or no count reaches thr: KMX_OK, 0 unitigs, offsets_out[0] = 0.  KMX_E_NOMEM leaves
+ * the handle usable and the listing intact.  Device memory, kept on the handle between calls: 61 to 65 bytes per listing
+ * entry (4 to 8 for the bucket index over the top bits, 2^ceil(log2 n) words; 9 for degrees and only-neighbours; 32 for the
+ * two copies of pointer and rank of both orientations and 16 for the two copies of their running minimum, which the marks and
+ * their scan reuse), plus the scan's scratch.  The host variants add what they stage there: the uploaded listing
+ * (n (8 W + 4) bytes, kmx_unitigs only) and the output (n_bases + 8 (n_unitigs + 1) + 40 n_unitigs bytes).  It waits
+ * for the stream once per doubling round (at most 2 ceil(log2 n) + 2, the second half only when the graph has a cycle), once
+ * for the validation and once for the counts, and returns with the emit enqueued.  Build-class calls (see the threading
+ * note of kmx_query_packed).                                                                                              */
+int kmx_unitigs_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr,
+                    char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out /* [rec_capacity + 1] */, kmx_unitig *d_rec /* or NULL */, uint64_t rec_capacity,
+                    uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */);
+/* the same on HOST buffers (seq_out == NULL: the sizing call); the listing is uploaded (n * (8 W + 4) bytes more) and the
+ * call returns when the output is complete                                                                               */
+int kmx_unitigs(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr,
+                char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out /* [rec_capacity + 1] */, kmx_unitig *rec /* or NULL */, uint64_t rec_capacity,
+                uint64_t *n_unitigs, uint64_t *n_bases_out);
+/* the same two on the listing the last kmx_count_finish kept, read where it lies (no copy): KMX_E_STATE when there is none,
+ * KMX_E_ARG for an even session k                                                                                        */
+int kmx_count_unitigs(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity,
+                      uint64_t *n_unitigs, uint64_t *n_bases_out);
+int kmx_count_unitigs_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity,
+                          uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */);
+/* where the last of these calls on the handle spent its time, measured only under kmx_set_profile(m, 1) (every phase then
+ * waits for the stream): seconds[4] = adjacency (with the validation and the index), links, ranking, emit (with the marks and
+ * their scan); *rounds = its doubling rounds (counted always)                                                             */
+int kmx_unitigs_last_phases(kmx_model *m, double *seconds /* [4] */, uint64_t *rounds);
+
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);
 /* get_model(save_dir) = header parse + KModel::load                        kmodel.hpp:680-696, :209-235

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "kmx_edit_seqs", "kmx_edit_seqs_dev", "kmx_apply_edits", "kmx_apply_edits_dev", "kmx_polish_seqs", "kmx_polish_seqs_dev",
     "kmx_extend_seqs", "kmx_extend_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
+    "kmx_unitigs", "kmx_unitigs_dev", "kmx_count_unitigs", "kmx_count_unitigs_dev", "kmx_unitigs_last_phases",
 ]
 
 
@@ -80,6 +81,19 @@ SEQ_EXTENSION_DTYPE = np.dtype([("n_ext", "<u4"), ("stop", "<u4"), ("seed_occ", 
 SEQ_EXTENSION_STOPS = {1: "DEAD_END", 2: "BRANCH", 3: "JOIN", 4: "CYCLE", 5: "MAX_EXT", 6: "BAD_SEED"}
 _REVCOMP = np.arange(256, dtype=np.uint8)
 _REVCOMP[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.frombuffer(b"TGCA", dtype=np.uint8)
+
+
+class Unitig(C.Structure):
+    """kmx_unitig of include/kmx.h: one per unitig, 40 bytes"""
+    _fields_ = [("n_kmers", C.c_uint64), ("sum_count", C.c_uint64), ("min_count", C.c_uint32), ("max_count", C.c_uint32),
+                ("first_node", C.c_uint64), ("circular", C.c_uint8), ("n_pred", C.c_uint8), ("n_succ", C.c_uint8),
+                ("first_fwd", C.c_uint8), ("reserved", C.c_uint8 * 4)]
+
+
+# the same record as a NumPy structured dtype (what KModel.unitigs / count_unitigs return beside the strings)
+UNITIG_DTYPE = np.dtype([("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count", "<u4"), ("max_count", "<u4"), ("first_node", "<u8"),
+                         ("circular", "u1"), ("n_pred", "u1"), ("n_succ", "u1"), ("first_fwd", "u1"), ("reserved", "u1", (4,))])
+UNITIG_PHASES = ["adjacency", "links", "ranking", "emit"]
 
 
 class RingList(C.Structure):
@@ -200,6 +214,12 @@ def load_library():
     _sig(L, "kmx_count_finish", [vp, C.POINTER(u64)])
     _sig(L, "kmx_count_listing", [vp, vp, vp, u64, C.POINTER(u64)])
     _sig(L, "kmx_build_from_reads", [vp, i32, C.c_char_p])
+    u32 = C.c_uint32
+    _sig(L, "kmx_unitigs", [vp, i32, vp, vp, u64, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_unitigs_dev", [vp, i32, vp, vp, u64, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_count_unitigs", [vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_count_unitigs_dev", [vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_unitigs_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -762,6 +782,63 @@ class KModel:
         counts = np.zeros(n.value, dtype=np.uint32)
         _chk(self.L.kmx_count_listing(self.h, kmers.ctypes.data, counts.ctypes.data, n.value, C.byref(n)))
         return (kmers[:, 0].copy() if W == 1 else kmers), counts
+
+    # ---- unitigs: the compacted de Bruijn graph of a counted listing (the rule: include/kmx.h)
+    def _unitigs_host(self, call):
+        """the sizing call, then the call with exact room -> (uint8 bases, uint64 offsets [n + 1], UNITIG_DTYPE records [n]).
+        Both calls rank the whole graph, so this costs the construction twice; tools/bench_unitigs.py times the bare C call."""
+        nu, nb = C.c_uint64(0), C.c_uint64(0)
+        _chk(call(None, 0, None, None, 0, C.byref(nu), C.byref(nb)))
+        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
+        off = np.zeros(nu.value + 1, dtype=np.uint64)
+        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
+        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, C.byref(nu), C.byref(nb)))
+        return buf[:nb.value], off, rec
+
+    def _unitigs_dev(self, call):
+        """the same on the model's device -> torch tensors (uint8 bases, int64 offsets [n + 1], uint8 records [n, 40]); twice the
+        construction as well"""
+        import torch
+        nu, nb = C.c_uint64(0), C.c_uint64(0)
+        _chk(call(None, 0, None, None, 0, C.byref(nu), C.byref(nb)))
+        dev = torch.device("cuda", self.stats().device)
+        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
+        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
+        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
+        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, C.byref(nu), C.byref(nb)))
+        return buf[:nb.value], off, rec
+
+    def unitigs(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1):
+        """kmx_unitigs: the unitigs of a listing (packed canonical k-mers, strictly ascending; uint32 counts; odd k in [5, 63])
+        whose nodes are the k-mers with count >= thr -> (buf, offsets, rec) in seq_to_occ_flat's layout.  Needs no built model."""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        n = counts.size
+        if kmers.size != n * ((int(k) + 31) // 32):
+            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
+        return self._unitigs_host(lambda *a: self.L.kmx_unitigs(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a))
+
+    def unitigs_dev(self, d_kmers, d_counts, k: int, thr: int = 1):
+        """kmx_unitigs_dev on torch tensors of the model's device (int64 / uint64 words, int32 / uint32 counts) -> torch tensors"""
+        n = d_counts.numel()
+        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
+            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
+        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
+        return self._unitigs_dev(lambda *a: self.L.kmx_unitigs_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a))
+
+    def count_unitigs(self, thr: int = 1):
+        """kmx_count_unitigs: the unitigs of the listing the last count_finish / init_reads kept, read where it lies"""
+        return self._unitigs_host(lambda *a: self.L.kmx_count_unitigs(self.h, int(thr), *a))
+
+    def count_unitigs_dev(self, thr: int = 1):
+        """kmx_count_unitigs_dev: the same, the output as torch tensors on the model's device"""
+        return self._unitigs_dev(lambda *a: self.L.kmx_count_unitigs_dev(self.h, int(thr), *a))
+
+    def unitigs_phases(self) -> dict:
+        """kmx_unitigs_last_phases: seconds per phase of the last unitig call (measured under set_profile(1)) and its rounds"""
+        sec, rounds = (C.c_double * 4)(), C.c_uint64(0)
+        _chk(self.L.kmx_unitigs_last_phases(self.h, sec, C.byref(rounds)))
+        return {**{n: sec[i] for i, n in enumerate(UNITIG_PHASES)}, "rounds": int(rounds.value)}
 
     # ---- persistence
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173

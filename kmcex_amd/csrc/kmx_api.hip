@@ -344,6 +344,19 @@ struct kmx_model {
 		bool listed = false;                                       // d_run[1] holds the listing of the last finish
 		u64 n_list = 0;
 	} cnt;
+	// kmx_unitigs* (unitig_host.h): the work arrays of a call, kept by capacity from call to call
+	struct UniState {
+		DevBuf<u32> d_start, d_succ1, d_pred1, d_mn, d_flag;       // d_mn: [2][2 n] ranks' minima, later the scanned marks; d_flag: [0] bad listing, [1 + t] round t moved
+		DevBuf<unsigned char> d_deg, d_tmp;
+		DevBuf<u64> d_pair[2];                                     // [2 n + 2] each: the rank state and its copy, later the marks
+		DevBuf<u64> d_km;                                          // the host variant's listing and its output
+		DevBuf<u32> d_cnt;
+		DevBuf<unsigned char> d_seq;
+		DevBuf<u64> d_offs;
+		DevBuf<Unitig> d_rec;
+		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit
+		u64 rounds = 0;                                            // doubling rounds of the last call
+	} uni;
 };
 
 static void prof_begin(KernelProf *p, int cls, hipStream_t st)
@@ -2871,6 +2884,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 }
 
 #include "count_host.h"
+#include "unitig_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3378,6 +3392,11 @@ extern "C" int kmx_count_seqs(kmx_model *m, const char *seq, const uint64_t *off
 extern "C" int kmx_count_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases) { return guarded([&] { return kmx_count_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases); }); }
 extern "C" int kmx_count_finish(kmx_model *m, uint64_t *n_listed) { return guarded([&] { return kmx_count_finish_impl(m, n_listed); }); }
 extern "C" int kmx_count_listing(kmx_model *m, uint64_t *kmers, uint32_t *counts, uint64_t capacity, uint64_t *n) { return guarded([&] { return kmx_count_listing_impl(m, kmers, counts, capacity, n); }); }
+extern "C" int kmx_unitigs_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_unitigs_dev_impl(m, k, d_kmers, d_counts, n, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, n_unitigs, n_bases_out); }); }
+extern "C" int kmx_unitigs(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_unitigs_impl(m, k, kmers, counts, n, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out); }); }
+extern "C" int kmx_count_unitigs(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_count_unitigs_impl(m, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out); }); }
+extern "C" int kmx_count_unitigs_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_count_unitigs_dev_impl(m, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, n_unitigs, n_bases_out); }); }
+extern "C" int kmx_unitigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitigs_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

@@ -320,6 +320,35 @@ struct ExtDev {
 	int depth;
 };
 
+// kmx_unitigs: one record per unitig, the layout of kmx_unitig (include/kmx.h; kmx_api.hip asserts it) ...
+struct Unitig {
+	u64 n_kmers, sum_count;
+	u32 min_count, max_count;
+	u64 first_node;
+	unsigned char circular, n_pred, n_succ, first_fwd, reserved[4];
+};
+// ... what the scan of the emit adds up per listing entry (unitigs that start there, their bytes) ...
+struct UniTot {
+	u64 n, len;
+};
+// ... and the work arrays of one call (unitig_kernels.h), views of the handle's buffers.  An ORIENTED node is 2 i + s: listing
+// entry i, s = 0 as listed (canonical), s = 1 its reverse complement; UNI_NONE = no such node.  n < 2^31, so it fits 32 bits.
+#define UNI_NONE 0xFFFFFFFFu
+enum { UNI_DEG_NODE = 0x40, UNI_DEG_CIRC = 0x80 };              // deg[i] = |succ| | |pred| << 3 of the listed orientation, | these
+struct UniDev {
+	const u64 *km;               // the listing: [n][W] k-mers, [n] counts
+	const u32 *cnt;
+	u64 n;
+	int k, W, bits, shift;       // start[] is indexed by the top `bits` bits of the 2k-bit k-mer = k-mer >> shift
+	u32 thr;
+	u32 *start;                  // [2^bits + 1]: the first entry whose prefix is at least p
+	u32 *succ1, *pred1;          // [n]: the only successor / predecessor of the listed orientation, or UNI_NONE
+	unsigned char *deg;          // [n]
+	u32 *err;                    // [1]: the listing is not strictly ascending, not canonical, or wider than 2k bits
+};
+// rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
+// index among the `rank` nodes from this one back (what a cycle is cut at)
+
 enum { SLOT_UNDECIDED = 0, SLOT_FAILED = 1, SLOT_INSERTED = 2, SLOT_CONTENDED = 3 };
 
 // Optional per-kernel-class timing with HIP events on the launch stream (bench.py's roofline leg).

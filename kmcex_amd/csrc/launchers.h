@@ -67,4 +67,13 @@ hipError_t polish_apply(const unsigned char *, const u64 *, const u64 *, u64, u6
                         unsigned char *, u64, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t polish_offsets(const u64 *, u64, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
 void polish_gather(const PolishHomes &, const u64 *, const u64 *, u64, unsigned char *, u64, hipStream_t);
+// unitig_device.hip: the phases of kmx_unitigs (index + validation, adjacency, links, a doubling round, the cut of the cycles,
+// marks + scan, emit)
+void unitig_index(const UniDev &, hipStream_t);
+void unitig_adjacency(const UniDev &, hipStream_t);
+void unitig_links(const UniDev &, u64 *, u32 *, hipStream_t);
+void unitig_round(const u64 *, const u32 *, u64 *, u32 *, u64, u32 *, hipStream_t);
+void unitig_cut(const UniDev &, const u64 *, const u32 *, u64 *, hipStream_t);
+hipError_t unitig_mark(const UniDev &, const u64 *, UniTot *, UniTot *, DevBuf<unsigned char> &tmp, hipStream_t);
+void unitig_emit(const UniDev &, const u64 *, const UniTot *, u64, unsigned char *, u64, u64 *, Unitig *, u64, hipStream_t);
 }   // namespace kmxk

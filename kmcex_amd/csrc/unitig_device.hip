@@ -1,0 +1,73 @@
+// unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*).  The host side that sizes the
+// buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.
+#include "hip_owned.h"
+#include "launchers.h"
+#include "unitig_kernels.h"
+#include <cstring>
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+inline unsigned nblk(u64 n) { return (unsigned)((n + 255) / 256); }
+
+struct TotPlus {
+	__host__ __device__ UniTot operator()(const UniTot &a, const UniTot &b) const { return UniTot{a.n + b.n, a.len + b.len}; }
+};
+
+}   // namespace
+
+namespace kmxk {
+
+// validation + the bucket index; *d.err is zero before
+void unitig_index(const UniDev &d, hipStream_t st)
+{
+	if (d.W == 1) hipLaunchKernelGGL(k_uni_index<1>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d);
+	else hipLaunchKernelGGL(k_uni_index<2>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d);
+}
+
+// degrees and only-neighbours of every entry
+void unitig_adjacency(const UniDev &d, hipStream_t st)
+{
+	if (!d.n) return;
+	if (d.W == 1) hipLaunchKernelGGL(k_uni_adj<1>, dim3(nblk(8 * d.n)), dim3(256), 0, st, d);
+	else hipLaunchKernelGGL(k_uni_adj<2>, dim3(nblk(8 * d.n)), dim3(256), 0, st, d);
+}
+
+// links in -> the rank state of the 2 n oriented nodes
+void unitig_links(const UniDev &d, u64 *pair, u32 *mn, hipStream_t st)
+{
+	if (d.n) hipLaunchKernelGGL(k_uni_init, dim3(nblk(2 * d.n)), dim3(256), 0, st, d, pair, mn);
+}
+
+// one round of doubling from (pin, mnin) into (pout, mnout); *moved is set when a node moved (mnin / mnout may be null)
+void unitig_round(const u64 *pin, const u32 *mnin, u64 *pout, u32 *mnout, u64 n, u32 *moved, hipStream_t st)
+{
+	if (n) hipLaunchKernelGGL(k_uni_round, dim3(nblk(2 * n)), dim3(256), 0, st, pin, mnin, pout, mnout, 2 * n, moved);
+}
+
+void unitig_cut(const UniDev &d, const u64 *pin, const u32 *mnin, u64 *pout, hipStream_t st)
+{
+	if (d.n) hipLaunchKernelGGL(k_uni_cut, dim3(nblk(2 * d.n)), dim3(256), 0, st, d, pin, mnin, pout);
+}
+
+// marks, then their exclusive scan: sc[i] = (unitigs, bytes) in front of entry i, sc[n] the totals
+hipError_t unitig_mark(const UniDev &d, const u64 *pair, UniTot *tot, UniTot *sc, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_uni_mark, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, tot);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const UniTot *)tot, sc, UniTot{0, 0}, (size_t)(d.n + 1), TotPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const UniTot *)tot, sc, UniTot{0, 0}, (size_t)(d.n + 1), TotPlus(), st));
+	return hipGetLastError();
+}
+
+// strings, offsets and records of n_uni unitigs; nothing is written at or behind seq[seq_cap], offs[rec_cap + 1], rec[rec_cap]
+void unitig_emit(const UniDev &d, const u64 *pair, const UniTot *sc, u64 n_uni, unsigned char *seq, u64 seq_cap, u64 *offs, Unitig *rec, u64 rec_cap, hipStream_t st)
+{
+	const u64 nr = n_uni < rec_cap ? n_uni : rec_cap;
+	if (rec && nr) hipLaunchKernelGGL(k_uni_rec_init, dim3(nblk(nr)), dim3(256), 0, st, rec, nr);
+	if (d.W == 1) hipLaunchKernelGGL(k_uni_emit<1>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, sc, seq, seq_cap, offs, rec, rec_cap);
+	else hipLaunchKernelGGL(k_uni_emit<2>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, sc, seq, seq_cap, offs, rec, rec_cap);
+}
+
+}   // namespace kmxk

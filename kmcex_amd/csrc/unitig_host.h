@@ -1,0 +1,231 @@
+// unitig_host.h -- kmx_unitigs*, kmx_count_unitigs*: the compacted de Bruijn graph of a sorted listing (the rule: include/kmx.h;
+// the kernels: unitig_kernels.h).  Included into kmx_api.hip after count_host.h, whose kept listing kmx_count_unitigs* read in
+// place.
+//
+// A call is two halves.  unitig_rank validates the listing, builds the adjacency and the links, ranks the 2 n oriented nodes by
+// pointer doubling (one stream wait per round: a word says whether anything moved), cuts what is left on cycles and ranks it
+// again, then marks the heads and scans the marks: the number of unitigs and of their bytes reach the host.  unitig_emit writes
+// strings, offsets and records.  Between the halves the device variant checks the caller's capacities and the host variant
+// sizes its own output.  The work arrays stay on the handle by capacity; nothing here touches the model or the listing.
+static_assert(sizeof(kmx_unitig) == 40 && sizeof(Unitig) == 40, "kmx_unitig is 40 bytes");
+static_assert(offsetof(kmx_unitig, min_count) == offsetof(Unitig, min_count) && offsetof(kmx_unitig, first_node) == offsetof(Unitig, first_node) &&
+              offsetof(kmx_unitig, circular) == offsetof(Unitig, circular) && offsetof(kmx_unitig, first_fwd) == offsetof(Unitig, first_fwd), "Unitig (kmx_types.h) is the layout of kmx_unitig");
+
+static const int kUniMaxBits = 26;                             // start[] has at most 2^26 + 1 entries; a bucket of 2^31 entries then holds 32
+
+static int unitig_args(int k, u64 n)
+{
+	if (k < 5 || k > 63 || !(k & 1)) return fail(KMX_E_ARG, "unitigs need an odd k in [5, 63], not %d (an even k has k-mers that are their own reverse complement)", k);
+	if (n >> 31) return fail(KMX_E_ARG, "%llu listing entries: unitigs take fewer than 2^31", (unsigned long long)n);
+	return KMX_OK;
+}
+
+static int uni_nomem() { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of the unitig construction could not be allocated"); }
+
+// a lap of the phase clock: only under kmx_set_profile(m, 1), where every phase waits for the stream
+struct UniClock {
+	kmx_model *m;
+	std::chrono::steady_clock::time_point t0;
+	explicit UniClock(kmx_model *mm) : m(mm) { if (m->prof.on) { hipStreamSynchronize(m->stream); t0 = std::chrono::steady_clock::now(); } }
+	void lap(int phase)
+	{
+		if (!m->prof.on) return;
+		hipStreamSynchronize(m->stream);
+		const auto t1 = std::chrono::steady_clock::now();
+		m->uni.phase_s[phase] += std::chrono::duration<double>(t1 - t0).count();
+		t0 = t1;
+	}
+};
+
+// the first half, on a device-resident listing.  On KMX_OK *n_uni / *n_bytes are the output's sizes, U.d_pair[*cur] the final
+// rank state, U.d_mn the scanned marks, and *d is the view the second half takes.
+static int unitig_rank(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, UniDev *d, int *cur, u64 *n_uni, u64 *n_bytes)
+{
+	auto &U = m->uni;
+	for (double &s : U.phase_s) s = 0;
+	U.rounds = 0;
+	*n_uni = *n_bytes = 0;
+	*cur = 0;
+	if (!n) return KMX_OK;
+	int lg = 0;
+	while ((u64(1) << lg) < n) lg++;                               // ceil(log2 n)
+	const int T = lg + 1;
+	d->km = d_km; d->cnt = d_cnt; d->n = n; d->k = k; d->W = (k + 31) / 32; d->thr = thr;
+	d->bits = std::min({2 * k, std::max(lg, 1), kUniMaxBits});
+	d->shift = 2 * k - d->bits;
+	const hipStream_t st = m->stream;
+	if (U.d_start.ensure((size_t(1) << d->bits) + 1, st) != hipSuccess || U.d_succ1.ensure(n, st) != hipSuccess || U.d_pred1.ensure(n, st) != hipSuccess ||
+	    U.d_deg.ensure(n, st) != hipSuccess || U.d_mn.ensure(4 * n + 4, st) != hipSuccess || U.d_flag.ensure(2 * (size_t)T + 2, st) != hipSuccess ||
+	    U.d_pair[0].ensure(2 * n + 2, st) != hipSuccess || U.d_pair[1].ensure(2 * n + 2, st) != hipSuccess)
+		return uni_nomem();
+	d->start = U.d_start; d->succ1 = U.d_succ1; d->pred1 = U.d_pred1; d->deg = U.d_deg; d->err = U.d_flag;
+	HIPCHK(hipMemsetAsync(U.d_flag, 0, (2 * (size_t)T + 2) * 4, st));
+	auto word = [&](int i, u32 *v) {                               // one stream wait
+		HIPCHK(hipMemcpyAsync(v, U.d_flag.get() + i, 4, hipMemcpyDeviceToHost, st));
+		HIPCHK(hipStreamSynchronize(st));
+		return (int)KMX_OK;
+	};
+	UniClock clk(m);
+	kmxk::unitig_index(*d, st);
+	u32 bad = 0;
+	TRY(word(0, &bad));
+	if (bad) return fail(KMX_E_ARG, "the listing is not strictly ascending, not canonical, or holds bits above 2k");
+	kmxk::unitig_adjacency(*d, st);
+	clk.lap(0);
+	kmxk::unitig_links(*d, U.d_pair[0], U.d_mn, st);
+	clk.lap(1);
+	u32 *mn[2] = {U.d_mn.get(), U.d_mn.get() + 2 * n};
+	int c = 0;
+	bool cycles = false;
+	for (int t = 1; t <= T; t++) {
+		kmxk::unitig_round(U.d_pair[c], mn[c], U.d_pair[c ^ 1], mn[c ^ 1], n, U.d_flag.get() + t, st);
+		c ^= 1;
+		U.rounds++;
+		u32 moved = 0;
+		TRY(word(t, &moved));
+		if (!moved) break;
+		cycles = t == T;                                           // every path has settled by now: what still moves goes round
+	}
+	if (cycles) {
+		kmxk::unitig_cut(*d, U.d_pair[c], mn[c], U.d_pair[c ^ 1], st);
+		c ^= 1;
+		u32 moved = 1;
+		for (int t = 1; t <= T && moved; t++) {
+			kmxk::unitig_round(U.d_pair[c], nullptr, U.d_pair[c ^ 1], nullptr, n, U.d_flag.get() + T + t, st);
+			c ^= 1;
+			U.rounds++;
+			TRY(word(T + t, &moved));
+		}
+		if (moved) return fail(KMX_E_ARG, "internal error: the cut cycles did not settle");
+	}
+	clk.lap(2);
+	UniTot *sc = (UniTot *)U.d_mn.get();
+	const hipError_t e = kmxk::unitig_mark(*d, U.d_pair[c], (UniTot *)U.d_pair[c ^ 1].get(), sc, U.d_tmp, st);
+	if (e == hipErrorOutOfMemory) return uni_nomem();
+	HIPCHK(e);
+	UniTot tot{0, 0};
+	HIPCHK(hipMemcpyAsync(&tot, sc + n, sizeof tot, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	clk.lap(3);
+	*cur = c;
+	*n_uni = tot.n;
+	*n_bytes = tot.len;
+	return KMX_OK;
+}
+
+// the second half: enqueued, not awaited (unless the phase clock runs)
+static int unitig_emit(kmx_model *m, const UniDev &d, int cur, u64 n, u64 n_uni, unsigned char *d_seq, u64 seq_cap, u64 *d_offs, Unitig *d_rec, u64 rec_cap)
+{
+	if (!n) { HIPCHK(hipMemsetAsync(d_offs, 0, 8, m->stream)); return KMX_OK; }
+	UniClock clk(m);
+	kmxk::unitig_emit(d, m->uni.d_pair[cur], (const UniTot *)m->uni.d_mn.get(), n_uni, d_seq, seq_cap, d_offs, d_rec, rec_cap, m->stream);
+	HIPCHK(hipGetLastError());
+	clk.lap(3);
+	return KMX_OK;
+}
+
+static int unitigs_dev_core(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, char *d_seq_out, u64 seq_cap, u64 *d_offs_out, kmx_unitig *d_rec, u64 rec_cap,
+                            uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	if (!n_unitigs || !n_bases_out) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = 0;
+	TRY(unitig_args(k, n));
+	if ((n && (!d_km || !d_cnt)) || (d_seq_out && !d_offs_out)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	UniDev d{};
+	int cur = 0;
+	u64 nu = 0, nb = 0;
+	TRY(unitig_rank(m, k, d_km, d_cnt, n, thr, &d, &cur, &nu, &nb));
+	*n_unitigs = nu;
+	*n_bases_out = nb;
+	if (!d_seq_out) return KMX_OK;                                 // the sizing call
+	if (nu > rec_cap || nb > seq_cap)
+		return fail(KMX_E_RANGE, "%llu unitigs of %llu bytes, the buffers hold %llu and %llu", (unsigned long long)nu, (unsigned long long)nb, (unsigned long long)rec_cap, (unsigned long long)seq_cap);
+	return unitig_emit(m, d, cur, n, nu, (unsigned char *)d_seq_out, seq_cap, d_offs_out, (Unitig *)d_rec, rec_cap);
+}
+
+static int kmx_unitigs_dev_impl(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, char *d_seq_out, uint64_t seq_capacity,
+                                uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	return unitigs_dev_core(m, k, (const u64 *)d_kmers, d_counts, n, thr, d_seq_out, seq_capacity, (u64 *)d_offsets_out, d_rec, rec_capacity, n_unitigs, n_bases_out);
+}
+
+// host buffers around a device-resident listing (the caller's, uploaded: up = true; or the session's)
+static int unitigs_host_core(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, char *seq_out, u64 seq_cap, uint64_t *offs_out, kmx_unitig *rec, u64 rec_cap,
+                             uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	auto &U = m->uni;
+	UniDev d{};
+	int cur = 0;
+	u64 nu = 0, nb = 0;
+	TRY(unitig_rank(m, k, d_km, d_cnt, n, thr, &d, &cur, &nu, &nb));
+	*n_unitigs = nu;
+	*n_bases_out = nb;
+	if (!seq_out) return KMX_OK;
+	if (nu > rec_cap || nb > seq_cap)
+		return fail(KMX_E_RANGE, "%llu unitigs of %llu bytes, the buffers hold %llu and %llu", (unsigned long long)nu, (unsigned long long)nb, (unsigned long long)rec_cap, (unsigned long long)seq_cap);
+	const hipStream_t st = m->stream;
+	if (U.d_seq.ensure(nb, st) != hipSuccess || U.d_offs.ensure(nu + 1, st) != hipSuccess || (rec && U.d_rec.ensure(nu, st) != hipSuccess)) return uni_nomem();
+	TRY(unitig_emit(m, d, cur, n, nu, U.d_seq, nb, U.d_offs, rec ? U.d_rec.get() : nullptr, nu));
+	if (nb) HIPCHK(hipMemcpyAsync(seq_out, U.d_seq, nb, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(offs_out, U.d_offs, (nu + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (rec && nu) HIPCHK(hipMemcpyAsync(rec, U.d_rec, nu * sizeof(Unitig), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return KMX_OK;
+}
+
+static int kmx_unitigs_impl(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, char *seq_out, uint64_t seq_capacity,
+                            uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	if (!m || !n_unitigs || !n_bases_out) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = 0;
+	TRY(unitig_args(k, n));
+	if ((n && (!kmers || !counts)) || (seq_out && !offsets_out)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	auto &U = m->uni;
+	const u64 W = (u64)(k + 31) / 32;
+	if (n) {
+		if (U.d_km.ensure(n * W, m->stream) != hipSuccess || U.d_cnt.ensure(n, m->stream) != hipSuccess) return uni_nomem();
+		HIPCHK(hipMemcpyAsync(U.d_km, kmers, n * W * 8, hipMemcpyHostToDevice, m->stream));
+		HIPCHK(hipMemcpyAsync(U.d_cnt, counts, n * 4, hipMemcpyHostToDevice, m->stream));
+	}
+	return unitigs_host_core(m, k, U.d_km, U.d_cnt, n, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out);
+}
+
+static int count_unitigs_listing(kmx_model *m, const char *who)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	if (!m->cnt.listed) return fail(KMX_E_STATE, "%s: no listing (kmx_count_finish has not run since the last kmx_count_begin or build)", who);
+	return KMX_OK;
+}
+
+static int kmx_count_unitigs_dev_impl(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity,
+                                      uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	TRY(count_unitigs_listing(m, "kmx_count_unitigs_dev"));
+	auto &C = m->cnt;
+	return unitigs_dev_core(m, C.k, C.d_run[1], C.d_runc[1], C.n_list, thr, d_seq_out, seq_capacity, (u64 *)d_offsets_out, d_rec, rec_capacity, n_unitigs, n_bases_out);
+}
+
+static int kmx_count_unitigs_impl(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity,
+                                  uint64_t *n_unitigs, uint64_t *n_bases_out)
+{
+	TRY(count_unitigs_listing(m, "kmx_count_unitigs"));
+	if (!n_unitigs || !n_bases_out || (seq_out && !offsets_out)) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = 0;
+	auto &C = m->cnt;
+	TRY(unitig_args(C.k, C.n_list));
+	HIPCHK(hipSetDevice(m->device));
+	return unitigs_host_core(m, C.k, C.d_run[1], C.d_runc[1], C.n_list, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out);
+}
+
+// seconds[4]: adjacency (with validation and the index), links, ranking, emit (with the marks and their scan) of the last call
+// on this handle, measured only under kmx_set_profile(m, 1); *rounds: its doubling rounds
+static int kmx_unitigs_last_phases_impl(kmx_model *m, double *seconds, uint64_t *rounds)
+{
+	if (!m || !seconds || !rounds) return fail(KMX_E_ARG, "null argument");
+	for (int i = 0; i < 4; i++) seconds[i] = m->uni.phase_s[i];
+	*rounds = m->uni.rounds;
+	return KMX_OK;
+}

@@ -1,0 +1,271 @@
+// unitig_kernels.h -- kmx_unitigs: the compacted de Bruijn graph of a sorted listing (the rule: include/kmx.h).
+//
+// The listing is its own exact membership structure: a k-mer is a node iff a search of the sorted k-mers finds it with a count
+// of at least thr.  The kernels, in the order the host runs them (unitig_device.hip, unitig_host.h):
+//   k_uni_index   one pass over the listing: validates it (strictly ascending, canonical, nothing above bit 2k) and fills
+//                 start[p] = the first entry whose top `bits` bits are at least p, so a probe searches one bucket of a few
+//                 entries instead of the whole listing;
+//   k_uni_adj     a group of 8 lanes per entry asks the 8 neighbours of its listed orientation (4 successors, 4 predecessors);
+//                 one ballot gives the degrees, and where a side has exactly one neighbour that lane leaves its oriented index;
+//   k_uni_init    per ORIENTED node (2 n of them) the link in, from the two entries' degrees; rank state: a node without a
+//                 link in is a head;
+//   k_uni_round   one round of pointer doubling along the links in, from one copy of the state into the other (a head is the
+//                 node of rank 0, never "a node that points at itself": a cycle of 2^j nodes does that too); a word tells
+//                 the host that something moved.  After ceil(log2 n) + 1 rounds only nodes on cycles still move; their running
+//                 minimum of the listing index has covered the whole cycle by then;
+//   k_uni_cut     nodes that have not settled lie on cycles: each cycle is cut in front of its smallest entry in the listed
+//                 orientation (and the mirror cycle behind that entry's reverse complement), then ranked again like a path;
+//   k_uni_mark    per entry: which of its two orientations lies on the representative (the path of a mirror pair whose head
+//                 has the smaller listing index; a single node as listed), whether it is the head, the unitig's length;
+//   k_uni_emit    per entry, after the scan of the marks: its bytes (all k at the head, the last one otherwise), its count into
+//                 the record with integer atomics, and at the head the rest of the record.
+// No lane walks a path: the longest unitig costs rounds (log), never a loop.  Every store is checked against its capacity.
+#pragma once
+#include "device_common.h"
+#include "kmx_types.h"
+
+struct UniK {                                                  // a k-mer as a 2k-bit integer, right-aligned in 128 bits
+	u64 hi, lo;
+};
+
+template <int W> __device__ __forceinline__ UniK uni_load(const u64 *km, u64 i)
+{
+	if (W == 1) return UniK{0, km[i]};
+	return UniK{km[2 * i], km[2 * i + 1]};
+}
+__device__ __forceinline__ bool uni_less(UniK a, UniK b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+__device__ __forceinline__ bool uni_eq(UniK a, UniK b) { return a.hi == b.hi && a.lo == b.lo; }
+__device__ __forceinline__ UniK uni_shr(UniK a, int s)         // 0 <= s < 128
+{
+	if (s == 0) return a;
+	if (s >= 64) return UniK{0, a.hi >> (s - 64)};
+	return UniK{a.hi >> s, (a.lo >> s) | (a.hi << (64 - s))};
+}
+__device__ __forceinline__ UniK uni_mask(int k)                // 2k is never 64: k is odd
+{
+	if (2 * k < 64) return UniK{0, (1ULL << (2 * k)) - 1};
+	return UniK{(1ULL << (2 * k - 64)) - 1, ~0ULL};
+}
+__device__ __forceinline__ UniK uni_rc(UniK x, int k)
+{
+	const UniK m = uni_mask(k);
+	const UniK c{~x.hi & m.hi, ~x.lo & m.lo};
+	return uni_shr(UniK{rev2_u64(c.lo), rev2_u64(c.hi)}, 128 - 2 * k);
+}
+__device__ __forceinline__ UniK uni_succ(UniK x, int k, u32 c)  // x[1:] + c
+{
+	const UniK m = uni_mask(k);
+	return UniK{((x.hi << 2) | (x.lo >> 62)) & m.hi, ((x.lo << 2) | c) & m.lo};
+}
+__device__ __forceinline__ UniK uni_pred(UniK x, int k, u32 c)  // c + x[:-1]
+{
+	UniK y = uni_shr(x, 2);
+	const int s = 2 * k - 2;
+	if (s < 64) y.lo |= (u64)c << s; else y.hi |= (u64)c << (s - 64);
+	return y;
+}
+__device__ __forceinline__ u32 uni_prefix(const UniDev &d, UniK x)
+{
+	const u64 p = uni_shr(x, d.shift).lo, top = (1ULL << d.bits) - 1;
+	return (u32)(p < top ? p : top);                            // (a valid k-mer never exceeds top; a listing that does is refused)
+}
+
+// the entry holding the canonical k-mer q, or UNI_NONE: one bucket of start[], then a binary search inside it
+template <int W> __device__ __forceinline__ u32 uni_find(const UniDev &d, UniK q)
+{
+	const u32 p = uni_prefix(d, q);
+	u64 lo = d.start[p], hi = d.start[p + 1];
+	if (hi > d.n) hi = d.n;
+	while (lo < hi) {
+		const u64 mid = (lo + hi) >> 1;
+		if (uni_less(uni_load<W>(d.km, mid), q)) lo = mid + 1; else hi = mid;
+	}
+	return lo < d.n && uni_eq(uni_load<W>(d.km, lo), q) ? (u32)lo : UNI_NONE;
+}
+
+// thread i <= n; entry i fills start[] for the prefixes behind entry i - 1's up to its own, thread n the rest up to 2^bits
+template <int W> __global__ __launch_bounds__(256) void k_uni_index(UniDev d)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i > d.n) return;
+	u64 p0 = 0, p1 = 1ULL << d.bits;                             // start[p0 .. p1] = i
+	if (i < d.n) {
+		const UniK x = uni_load<W>(d.km, i), m = uni_mask(d.k);
+		bool bad = (x.hi & ~m.hi) != 0 || (x.lo & ~m.lo) != 0 || uni_less(uni_rc(x, d.k), x);
+		p1 = uni_prefix(d, x);
+		if (i) {
+			const UniK w = uni_load<W>(d.km, i - 1);
+			bad = bad || !uni_less(w, x);
+			p0 = (u64)uni_prefix(d, w) + 1;
+		}
+		if (bad) *d.err = 1;
+	}
+	else if (i) p0 = (u64)uni_prefix(d, uni_load<W>(d.km, i - 1)) + 1;
+	for (u64 p = p0; p <= p1; p++) d.start[p] = (u32)i;
+}
+
+// 8 lanes per entry: lanes 0..3 the successors x[1:] + c, lanes 4..7 the predecessors c + x[:-1] of the listed orientation
+template <int W> __global__ __launch_bounds__(256) void k_uni_adj(UniDev d)
+{
+	const u64 g = (u64)blockIdx.x * 256 + threadIdx.x, i = g >> 3;
+	const u32 l = threadIdx.x & 7, c = l & 3;
+	bool hit = false;
+	u32 tgt = UNI_NONE;
+	const bool node = i < d.n && d.cnt[i] >= d.thr;
+	if (node) {
+		const UniK x = uni_load<W>(d.km, i);
+		const UniK y = l < 4 ? uni_succ(x, d.k, c) : uni_pred(x, d.k, c), r = uni_rc(y, d.k);
+		const bool fwd = !uni_less(r, y);
+		const u32 j = uni_find<W>(d, fwd ? y : r);
+		if (j != UNI_NONE && d.cnt[j] >= d.thr) { hit = true; tgt = 2 * j + (fwd ? 0u : 1u); }
+	}
+	const u64 b = __ballot(hit);
+	const u32 m8 = (u32)(b >> (threadIdx.x & 56)) & 0xFFu;       // the 8 lanes of this entry (a wave holds 8 whole groups)
+	if (i >= d.n) return;
+	const u32 ns = __popc(m8 & 15u), np = __popc(m8 >> 4);
+	if (l == 0) {
+		d.deg[i] = node ? (unsigned char)(ns | (np << 3) | UNI_DEG_NODE) : (unsigned char)0;
+		if (ns != 1) d.succ1[i] = UNI_NONE;
+		if (np != 1) d.pred1[i] = UNI_NONE;
+	}
+	if (hit && l < 4 && ns == 1) d.succ1[i] = tgt;
+	if (hit && l >= 4 && np == 1) d.pred1[i] = tgt;
+}
+
+__device__ __forceinline__ u32 uni_outdeg(const unsigned char *deg, u32 x) { const u32 g = deg[x >> 1]; return (x & 1) ? (g >> 3) & 7u : g & 7u; }
+__device__ __forceinline__ u32 uni_indeg(const unsigned char *deg, u32 x) { const u32 g = deg[x >> 1]; return (x & 1) ? g & 7u : (g >> 3) & 7u; }
+// the link into oriented node x, or UNI_NONE: its only predecessor, whose only successor is x, of another entry.  The
+// predecessors of a reverse complement are the successors of the listed orientation, mirrored.
+__device__ __forceinline__ u32 uni_link_in(const UniDev &d, u32 x)
+{
+	const u32 i = x >> 1;
+	if (!(d.deg[i] & UNI_DEG_NODE)) return UNI_NONE;
+	u32 p = (x & 1) ? d.succ1[i] : d.pred1[i];
+	if (p == UNI_NONE) return UNI_NONE;
+	if (x & 1) p ^= 1u;
+	if ((p >> 1) == i || (p >> 1) >= d.n || uni_outdeg(d.deg, p) != 1) return UNI_NONE;
+	return p;
+}
+__device__ __forceinline__ u64 uni_pair(u32 ptr, u32 rank) { return (u64)ptr << 32 | rank; }
+
+__global__ __launch_bounds__(256) void k_uni_init(UniDev d, u64 *pair, u32 *mn)
+{
+	const u64 x = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (x >= 2 * d.n) return;
+	const u32 p = uni_link_in(d, (u32)x);
+	pair[x] = p == UNI_NONE ? uni_pair((u32)x, 0) : uni_pair(p, 1);
+	mn[x] = (u32)(x >> 1);
+}
+
+// A head has rank 0 (and points at itself); a node has settled when its pointer is a head.  "Points at itself" alone would not
+// do: on a cycle of 2^j nodes every pointer comes back to its own node after round j, with rank 2^j.  Ranks on a cycle only
+// grow (they saturate instead of wrapping to 0), so nothing on a cycle ever looks like a head.  mn may be null (after the cut
+// nothing lies on a cycle).
+__device__ __forceinline__ u32 uni_rank_add(u32 a, u32 b) { const u64 s = (u64)a + b; return s > 0xFFFFFFFFULL ? 0xFFFFFFFFu : (u32)s; }
+__global__ __launch_bounds__(256) void k_uni_round(const u64 *pin, const u32 *mnin, u64 *pout, u32 *mnout, u64 n2, u32 *moved)
+{
+	const u64 x = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (x >= n2) return;
+	const u64 a = pin[x];
+	const u32 p = (u32)(a >> 32);
+	u64 o = a;
+	u32 m = mnin ? mnin[x] : 0;
+	if ((u32)a != 0 && p < n2) {
+		const u64 b = pin[p];
+		if ((u32)b != 0) {
+			o = uni_pair((u32)(b >> 32), uni_rank_add((u32)a, (u32)b));
+			if (mnin) { const u32 mp = mnin[p]; m = mp < m ? mp : m; }
+			*moved = 1;
+		}
+	}
+	pout[x] = o;
+	if (mnout) mnout[x] = m;
+}
+
+// after the last round: what has not settled lies on a cycle whose smallest entry is mn[x]
+__global__ __launch_bounds__(256) void k_uni_cut(UniDev d, const u64 *pin, const u32 *mnin, u64 *pout)
+{
+	const u64 x = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (x >= 2 * d.n) return;
+	const u64 a = pin[x];
+	const u32 p = (u32)(a >> 32);
+	if ((u32)a == 0 || p >= 2 * d.n || (u32)pin[p] == 0) { pout[x] = a; return; }   // a head, or its pointer is one: settled
+	const u32 s = 2 * mnin[x];                                   // the representative starts here ...
+	u32 in = uni_link_in(d, (u32)x);
+	if ((u32)x == s || in == (s ^ 1u)) in = UNI_NONE;            // ... and its mirror ends at the reverse complement
+	pout[x] = in == UNI_NONE ? uni_pair((u32)x, 0) : uni_pair(in, 1);
+	d.deg[x >> 1] |= UNI_DEG_CIRC;                               // (both orientations write the same byte value)
+}
+
+// where entry i lies: s = its orientation on the representative, h = the representative's head, r = its rank there, m = the
+// unitig's k-mers, hm = the head of the mirror path (the reverse complement of the representative's tail)
+struct UniPlace {
+	u32 s, h, r, m, hm;
+};
+__device__ __forceinline__ UniPlace uni_place(const u64 *pair, u64 i)
+{
+	const u64 a = pair[2 * i], b = pair[2 * i + 1];
+	const u32 ha = (u32)(a >> 32), hb = (u32)(b >> 32), ra = (u32)a, rb = (u32)b;
+	const bool fwd = (ha >> 1) <= (hb >> 1);                     // equal only for a single node: as listed
+	return fwd ? UniPlace{0, ha, ra, ra + rb + 1, hb} : UniPlace{1, hb, rb, ra + rb + 1, ha};
+}
+
+// thread i <= n: tot[i] = (1, bytes) where a unitig starts at entry i, tot[n] = (0, 0): the exclusive scan ends with the totals
+__global__ __launch_bounds__(256) void k_uni_mark(UniDev d, const u64 *pair, UniTot *tot)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i > d.n) return;
+	UniTot t{0, 0};
+	if (i < d.n && (d.deg[i] & UNI_DEG_NODE)) {
+		const UniPlace q = uni_place(pair, i);
+		if (q.r == 0) t = UniTot{1, (u64)q.m + (u64)d.k - 1};
+	}
+	tot[i] = t;
+}
+
+__global__ __launch_bounds__(256) void k_uni_rec_init(Unitig *rec, u64 n)
+{
+	const u64 u = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (u < n) rec[u] = Unitig{0, 0, 0xFFFFFFFFu, 0, 0, 0, 0, 0, 0, {0, 0, 0, 0}};
+}
+
+// thread i <= n (sc: the scanned marks, sc[n] the totals).  seq[seq_cap], offs[rec_cap + 1], rec[rec_cap] (may be null).
+template <int W> __global__ __launch_bounds__(256) void k_uni_emit(UniDev d, const u64 *pair, const UniTot *sc, unsigned char *seq, u64 seq_cap, u64 *offs, Unitig *rec, u64 rec_cap)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i > d.n) return;
+	if (i == d.n) { if (sc[i].n <= rec_cap) offs[sc[i].n] = sc[i].len; return; }
+	if (!(d.deg[i] & UNI_DEG_NODE)) return;
+	const UniPlace q = uni_place(pair, i);
+	if ((q.h >> 1) >= d.n) return;
+	const UniTot at = sc[q.h >> 1];
+	UniK x = uni_load<W>(d.km, i);
+	if (q.s) x = uni_rc(x, d.k);
+	const u32 c = d.cnt[i];
+	if (rec && at.n < rec_cap) {
+		Unitig *R = rec + at.n;
+		atomicAdd((unsigned long long *)&R->sum_count, (unsigned long long)c);
+		atomicMin(&R->min_count, c);
+		atomicMax(&R->max_count, c);
+	}
+	if (q.r) {
+		const u64 o = at.len + (u64)d.k - 1 + q.r;
+		if (o < seq_cap) seq[o] = (unsigned char)"ACGT"[x.lo & 3];
+		return;
+	}
+	if (at.n <= rec_cap) offs[at.n] = at.len;
+	for (int j = 0; j < d.k; j++) {
+		const u64 o = at.len + (u64)j;
+		if (o < seq_cap) seq[o] = (unsigned char)"ACGT"[uni_shr(x, 2 * (d.k - 1 - j)).lo & 3];
+	}
+	if (rec && at.n < rec_cap) {
+		Unitig *R = rec + at.n;
+		const u32 tail = q.hm ^ 1u;
+		R->n_kmers = q.m;
+		R->first_node = q.h >> 1;
+		R->circular = (d.deg[q.h >> 1] & UNI_DEG_CIRC) ? 1 : 0;
+		R->n_pred = (unsigned char)uni_indeg(d.deg, q.h);
+		R->n_succ = (unsigned char)((tail >> 1) < d.n ? uni_outdeg(d.deg, tail) : 0);
+		R->first_fwd = (unsigned char)!(q.h & 1);
+	}
+}
