@@ -1,7 +1,14 @@
 """kmx_unitigs*, kmx_count_unitigs* on the MI355X: strings, offsets and records equal, byte for byte, what the plain-Python
-restatement of the rule (tests/unitigs_ref.py) gives, for the host and the device variant; closure; the edges."""
+restatement of the rule (tests/unitigs_ref.py) gives, for the host and the device variant, on every case of U.CASES (linear
+pieces, isolated cycles, dense and complete graphs, tangles at one- and two-word k, extreme counts and thresholds, one bucket
+of the index) and on sweeps that stay out of the fixture: every cycle length from 2 to 130 alone in its listing, paths of
+exactly 2^j - 1, 2^j and 2^j + 1 nodes, listing sizes around the launch geometry; the documented round bounds; the tight
+capacity of the complete graph; refusals of bad listings in one and two words; calls of every size and word count in turn on
+one handle; a counted session; closure; allocation failure; the FASTA of the facade and the driver."""
 import ctypes as C
 import functools
+import json
+import os
 
 import numpy as np
 import pytest
@@ -20,6 +27,24 @@ def ref(name):
     """(k, thr, packed k-mers, counts, k-mer strings, (buf, off, rec) of the restatement), computed once"""
     k, thr, km, cnt, strs, recs = U.case(name)
     return k, thr, U.pack(km, k), np.asarray(cnt, dtype=np.uint32), km, U.flat(strs, recs)
+
+
+@functools.lru_cache(maxsize=None)
+def fixture():
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "unitigs_golden.json")) as f:
+        return json.load(f)["cases"]
+
+
+def listed(seqs, k, thr=1):
+    """(packed k-mers, counts, recs, (buf, off, rec)) of the restatement for sequences that are no case"""
+    km, cnt = U.listing_of(U.count_kmers(seqs, k))
+    strs, recs = U.unitigs(km, cnt, k, thr)
+    return U.pack(km, k), np.asarray(cnt, dtype=np.uint32), recs, U.flat(strs, recs)
+
+
+def lg(n):
+    """ceil(log2 n)"""
+    return (n - 1).bit_length()
 
 
 def same(got, want, what=""):
@@ -45,14 +70,88 @@ def run_dev(m, km, cnt, k, thr):
 @pytest.mark.parametrize("name", [n for n in U.CASES if not n.startswith("reads")])
 def test_equals_the_restatement(name):
     """small k with self-loops and hairpins; isolated cycles, alone and beside a path; linear pieces; one path of thousands of
-    k-mers (more than 12 doubling rounds); two-word k-mers, circular and linear"""
+    k-mers (more than 12 doubling rounds); two-word k-mers, circular and linear; the complete graphs of k = 5 and 7 and random
+    subsets of every density down to 0.02 at k = 11, with counts of 0 and 0xFFFFFFFF, sums above 2^32, thr = 0 and
+    thr = 0xFFFFFFFF; tangles (bubbles, tips, a hairpin, self-loops, nine cycles, the largest canonical k-mers) at k = 31 and in
+    two words up to k = 63, at thr 1 and 2; every cycle length from 2 to 130 in one listing; a cycle that closes at thr = 2 only;
+    a listing in one bucket of the index.  The rounds stay within the bounds of include/kmx.h: 2 ceil(log2 n) + 2, and
+    ceil(log2 n) + 1 where nothing is circular (a path is never ranked twice)"""
     k, thr, km, cnt, _, want = ref(name)
     m = KModel(1, 1023, NH, NB)
     same(m.unitigs(km, cnt, k, thr), want, "host")
+    rounds = m.unitigs_phases()["rounds"]
+    assert rounds <= 2 * lg(len(cnt)) + 2, (rounds, len(cnt))
+    if fixture()[name]["circular"] == 0:
+        assert rounds <= lg(len(cnt)) + 1, (rounds, len(cnt))
     if name == "k15_long_path":
-        assert m.unitigs_phases()["rounds"] > 12
+        assert rounds > 12
     same(run_dev(m, km, cnt, k, thr), want, "device")
     same(m.unitigs(km, cnt, k, thr), want, "second call on the same handle")
+
+
+@pytest.mark.parametrize("k", [31, 33])
+def test_every_cycle_length_alone(k):
+    """a cycle of L nodes and nothing else, L = 2 .. 130 (below k the string is periodic): n = L, so the round limit is as tight
+    as it gets, and the running minimum has to cover the cycle within it"""
+    m = KModel(1, 1023, NH, NB)
+    for L, s in U.all_cycles(k).items():
+        km, cnt, recs, want = listed([s], k)
+        assert len(cnt) == L and [(r["n_kmers"], r["circular"]) for r in recs] == [(L, 1)], L
+        same(m.unitigs(km, cnt, k, 1), want, f"host, L = {L}")
+        assert m.unitigs_phases()["rounds"] <= 2 * lg(L) + 2, L
+        same(run_dev(m, km, cnt, k, 1), want, f"device, L = {L}")
+
+
+PATH_LENGTHS = (1, 2, 3, 4, 5, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025)
+
+
+@pytest.mark.parametrize("k", [15, 31, 33, 63])
+def test_exact_path_lengths(k):
+    """a path of exactly m nodes and nothing else: it settles within ceil(log2 m) + 1 rounds (the last one moves nothing) and is
+    not taken for a cycle, also where m = n = 2^j"""
+    m = KModel(1, 1023, NH, NB)
+    for n in PATH_LENGTHS:
+        km, cnt, recs, want = listed([U.rand_seq(n + k - 1, 5000 + n)], k)
+        assert len(cnt) == n and [(r["n_kmers"], r["circular"]) for r in recs] == [(n, 0)], n
+        got = m.unitigs(km, cnt, k, 1)
+        same(got, want, f"host, m = {n}")
+        assert int(got[2]["circular"].sum()) == 0
+        assert m.unitigs_phases()["rounds"] <= lg(max(n, 2)) + 1, n
+        same(run_dev(m, km, cnt, k, 1), want, f"device, m = {n}")
+
+
+def test_listing_sizes_at_the_launch_edges():
+    """n + 1 threads in blocks of 256 (index, mark, emit), 32 entries per block (adjacency): the first n entries of a dense
+    listing, which are a listing"""
+    k, thr, km, cnt, km_s, _ = ref("k7_half_thr1")
+    m = KModel(1, 1023, NH, NB)
+    for n in (1, 2, 31, 32, 33, 255, 256, 257, 511, 512, 513):
+        want = U.flat(*U.unitigs(km_s[:n], cnt[:n].tolist(), k, thr))
+        same(m.unitigs(km[:n], cnt[:n], k, thr), want, f"host, n = {n}")
+        same(run_dev(m, km[:n], cnt[:n], k, thr), want, f"device, n = {n}")
+
+
+def test_the_tight_capacity():
+    """the complete graph: every node its own unitig of k bytes, so rec_capacity = nodes and seq_capacity = nodes * k are
+    needed in full; they suffice, and one less of either is KMX_E_RANGE with nothing written"""
+    import torch
+    k, thr, km, cnt, _, (wbuf, woff, wrec) = ref("k5_complete")
+    m = KModel(1, 1023, NH, NB)
+    d_km = torch.from_numpy(km.view(np.int64)).cuda()
+    d_cnt = torch.from_numpy(cnt.view(np.int32)).cuda()
+    args = (k, d_km.data_ptr(), d_cnt.data_ptr(), len(cnt), thr)
+    nu = len(cnt)
+    nb = nu * k
+    assert (len(wrec), len(wbuf)) == (nu, nb)
+    rc, gu, gb, seq, offs, rec = raw(m, m.L.kmx_unitigs_dev, args, nb, nu)
+    assert (rc, gu, gb) == (0, nu, nb)
+    assert seq[:nb].tobytes() == wbuf.tobytes() and np.all(seq[nb:] == 0xA5)
+    assert np.array_equal(offs[:nu + 1].view(np.uint64), woff) and np.all(offs[nu + 1:] == -6)
+    assert rec[:nu * 40].tobytes() == wrec.tobytes() and np.all(rec[nu * 40:] == 0xA5)
+    for sc, rcap in ((nb - 1, nu), (nb, nu - 1)):
+        rc, gu, gb, seq, offs, rec = raw(m, m.L.kmx_unitigs_dev, args, sc, rcap)
+        assert (rc, gu, gb) == (-5, nu, nb)
+        assert np.all(seq == 0xA5) and np.all(offs == -6) and np.all(rec == 0xA5)
 
 
 @pytest.mark.parametrize("thr", [1, 3])
@@ -194,6 +293,96 @@ def test_bad_listings_and_arguments():
     nu, nb = C.c_uint64(0), C.c_uint64(0)
     assert m.L.kmx_unitigs_dev(m.h, 31, None, None, 1 << 31, 1, None, 0, None, None, 0, C.byref(nu), C.byref(nb)) == -1
     same(m.unitigs(km, cnt, k, 1), want, "after the refusals")       # the handle is still usable
+
+
+def refused(m, km, cnt, k, what):
+    for call in (m.unitigs, lambda *a: run_dev(m, *a)):
+        with pytest.raises(KmxError) as e:
+            call(np.ascontiguousarray(km), cnt[:len(km)], k, 1)
+        assert e.value.code == -1, what
+
+
+@pytest.mark.parametrize("k", [33, 63])
+def test_bad_listings_in_two_words(k):
+    """the order lies in the high words alone, or in the low words alone; the first, the last and the entries on both sides of a
+    block of 256 threads; the mask of the high word.  KMX_E_ARG from both variants, and the handle answers the next call"""
+    seq = U.rand_seq(300 + k - 1, 70 + k)
+    km, cnt, _, want = listed([seq], k)
+    km_s = U.unpack(km, k)
+    assert km.shape == (300, 2)
+    m = KModel(1, 1023, NH, NB)
+    i, j = next((i, j) for i in range(300) for j in range(i + 1, 300) if km[i, 0] < km[j, 0] and km[i, 1] > km[j, 1])
+    refused(m, km[[j, i]], cnt, k, "high words descending, low words ascending")
+    same(m.unitigs(km[[i, j]], cnt[:2], k, 1), U.flat(*U.unitigs([km_s[i], km_s[j]], [1, 1], k, 1)), "the two in their order")
+    a, b = U.equal_high_words(k, k)
+    pair = U.pack([a, b], k)
+    assert pair[0, 0] == pair[1, 0] and pair[0, 1] < pair[1, 1]
+    refused(m, pair[[1, 0]], cnt, k, "equal high words, low words descending")
+    same(m.unitigs(pair, cnt[:2], k, 1), U.flat(*U.unitigs([a, b], [1, 1], k, 1)), "the two in their order")
+    dup = km.copy()
+    dup[-1] = dup[-2]
+    refused(m, dup, cnt, k, "the last two entries equal")
+    for x in (0, 255):
+        swapped = km.copy()
+        swapped[[x, x + 1]] = swapped[[x + 1, x]]
+        refused(m, swapped, cnt, k, f"entries {x} and {x + 1} swapped")
+    noncanon = km.copy()
+    i = next(j for j, s in enumerate(km_s) if (j == 0 or U.rc(s) > km_s[j - 1]) and (j + 1 == len(km_s) or U.rc(s) < km_s[j + 1]))
+    noncanon[i] = U.pack([U.rc(km_s[i])], k)[0]                    # still ascending, no longer canonical
+    assert U.unpack(noncanon, k) == sorted(U.unpack(noncanon, k))
+    refused(m, noncanon, cnt, k, "not canonical")
+    wide = km.copy()
+    wide[-1, 0] |= np.uint64(1) << np.uint64(2 * k - 64)             # bit 2k of the k-mer, the lowest the mask cuts: 66 or 126
+    refused(m, wide, cnt, k, "bit 2k")
+    if k == 63:
+        top = km.copy()
+        top[-1, 0] |= np.uint64(1) << np.uint64(63)                  # bit 127, the highest of the two words
+        refused(m, top, cnt, k, "bit 127")
+    same(m.unitigs(km, cnt, k, 1), want, "host after the refusals")
+    same(run_dev(m, km, cnt, k, 1), want, "device after the refusals")
+
+
+def test_bad_listing_bit_62_at_k31():
+    """bit 62 is bit 2k at the widest one-word k: the one-word mask stops right below it"""
+    k = 31
+    km, cnt, _, want = listed([U.rand_seq(300 + k - 1, 70 + k)], k)
+    m = KModel(1, 1023, NH, NB)
+    wide = km.copy()
+    wide[-1] |= np.uint64(1) << np.uint64(62)
+    refused(m, wide, cnt, k, "bit 62")
+    same(m.unitigs(km, cnt, k, 1), want, "host after the refusal")
+    same(run_dev(m, km, cnt, k, 1), want, "device after the refusal")
+
+
+def test_one_handle_through_sizes_and_word_counts():
+    """the work arrays stay on the handle by capacity: a small call after a large one, two words after one and back, a counted
+    session in between.  Every answer is the restatement's, and a fresh handle gives the reused one's bytes: the output is a
+    function of (listing, thr) alone"""
+    m = KModel(1, 1023, NH, NB)
+
+    def host(name):
+        k, thr, km, cnt, _, want = ref(name)
+        got = m.unitigs(km, cnt, k, thr)
+        same(got, want, name)
+        return got
+
+    first = host("k11_sparse")
+    host("k5_cycle2")
+    host("tangle_k63_thr1")
+    host("k7_complete")
+    host("tangle_k31_thr2")
+    k, thr, km, cnt, _, want = ref("tangle_k31_thr1")
+    m.count_begin(k)
+    m.count_seqs(U.CASES["tangle_k31_thr1"]()[2])
+    assert m.count_finish() == len(cnt)
+    counted = m.count_unitigs(thr)
+    same(counted, want, "count_unitigs")
+    k, thr, km, cnt, _, want = ref("tangle_k33_thr1")
+    same(run_dev(m, km, cnt, k, thr), want, "tangle_k33_thr1, device")
+    same(m.count_unitigs(1), counted, "count_unitigs again")
+    k, thr, km, cnt, _, _ = ref("k11_sparse")
+    same(m.unitigs(km, cnt, k, thr), first, "k11_sparse again on the used handle")
+    same(KModel(1, 1023, NH, NB).unitigs(km, cnt, k, thr), first, "k11_sparse on a fresh handle")
 
 
 def test_no_listing_and_even_session_k():

@@ -1,6 +1,7 @@
 """CPU: the unitig rule of include/kmx.h restated in plain Python (tests/unitigs_ref.py) has the properties the rule promises on
 every case, equals its fixture, and the library's new entry points refuse bad arguments before they need a device."""
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -25,9 +26,10 @@ def fixture():
 @pytest.mark.parametrize("name", list(U.CASES))
 def test_properties_and_fixture(name, fixture):
     """every node in exactly one unitig, consecutive k-mers linked, no node twice or in both orientations, links symmetric,
-    maximality, the order (U.check); and the output is the fixture's"""
+    maximality, the order (U.check), on a listing that is one (strictly ascending, canonical); and the output is the fixture's"""
     from make_unitigs_golden import entry
     k, thr, km, cnt, strs, recs = U.case(name)
+    assert all(a < b for a, b in zip(km, km[1:])) and all(len(x) == k and U.canon(x) == x for x in km), "the case is no listing"
     U.check(km, cnt, k, thr, strs, recs)
     got = entry(name)
     assert got == fixture[name]
@@ -44,6 +46,82 @@ def test_fixture_holds_every_case(fixture):
     assert fixture["k7_cycle2_and_line"]["circular"] == 1 and fixture["k7_cycles_2_32_30_and_line"]["circular"] == 3
     assert fixture["k15_long_path"]["longest"] > 4096              # more than 12 doubling rounds
     assert fixture["reads_thr1"]["unitigs"] > 100 * fixture["reads_thr3"]["unitigs"]
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    """U.case, computed once for the tests below that only read it"""
+    return U.case(name)
+
+
+def shapes(name):
+    """(self-loops, hairpin edges, branching nodes) among the nodes of a case, an edge counted once"""
+    k, thr, km, cnt, _, _ = case(name)
+    g = U.Graph(km, cnt, k, thr)
+    loops = hairpins = branching = 0
+    for x in g.idx:
+        loops += x in g.succ(x)                                # (rc(x) -> rc(x) is the same edge)
+        hairpins += (U.rc(x) in g.succ(x)) + (x in g.succ(U.rc(x)))
+        branching += len(g.succ(x)) > 1 or len(g.pred(x)) > 1
+    return loops, hairpins, branching
+
+
+DENSE = ("k5_complete", "k5_dense_thr3", "k7_complete", "k7_half_thr1", "k7_half_thr3", "k7_tenth", "k9_dense", "k11_sparse")
+
+
+def test_dense_cases_hold_what_they_are_for(fixture):
+    """the complete graph is the tight case of "rec_capacity = the nodes and seq_capacity = nodes * k always suffice"; the random
+    subsets have every local shape, and counts at both ends of their range"""
+    e = fixture["k5_complete"]
+    assert (e["n"], e["nodes"], e["unitigs"], e["longest"], e["bases"]) == (512, 512, 512, 1, 512 * 5)
+    assert fixture["k7_complete"]["n"] == fixture["k7_complete"]["unitigs"] == 4 ** 7 // 2
+    assert 35000 < fixture["k11_sparse"]["n"] < 45000
+    assert fixture["k7_tenth"]["thr"] == 0 and fixture["k9_dense"]["thr"] == 0xFFFFFFFF
+    assert 0 in case("k7_tenth")[3] and fixture["k7_tenth"]["nodes"] == fixture["k7_tenth"]["n"]
+    assert 0 < fixture["k9_dense"]["nodes"] < fixture["k9_dense"]["n"] // 3
+    loops = hairpins = 0
+    recs = []
+    for name in DENSE:
+        lo, ha, _ = shapes(name)
+        loops, hairpins = loops + lo, hairpins + ha
+        recs += case(name)[5]
+    assert loops >= 1 and hairpins >= 1
+    assert any(r["n_kmers"] >= 2 for r in recs) and any(r["first_fwd"] == 0 for r in recs)
+    assert any(r["sum_count"] >= 2 ** 32 for r in recs)
+    assert any(r["min_count"] == 0 for r in recs) and any(r["max_count"] == 0xFFFFFFFF for r in recs)
+
+
+@pytest.mark.parametrize("k", [31, 33, 35, 47, 61, 63])
+def test_tangles_hold_every_local_shape(k, fixture):
+    recs = case(f"tangle_k{k}_thr1")[5]
+    loops, hairpins, branching = shapes(f"tangle_k{k}_thr1")
+    assert sum(r["circular"] for r in recs) >= 5 and sum(r["first_fwd"] == 0 for r in recs) >= 10
+    assert loops >= 1 and hairpins >= 1 and branching >= 20
+    assert fixture[f"tangle_k{k}_thr2"]["circular"] >= 1 and fixture[f"tangle_k{k}_thr2"]["longest"] > 100
+
+
+def test_cycle_cases(fixture):
+    """every cycle length from 2 to 130 in one listing; a cycle that exists at one threshold only; one bucket of the index"""
+    e = fixture["k31_all_cycles"]
+    recs = case("k31_all_cycles")[5]
+    assert (e["n"], e["unitigs"], e["circular"]) == (9184, 130, 129)
+    assert sorted(r["n_kmers"] for r in recs if r["circular"]) == list(range(2, 131))
+    assert [r["n_kmers"] for r in recs if not r["circular"]] == [670]
+    assert fixture["cycle_only_above_thr_at1"]["circular"] == 0 and fixture["cycle_only_above_thr_at1"]["nodes"] > 40
+    e = fixture["cycle_only_above_thr"]
+    assert (e["thr"], e["nodes"], e["unitigs"], e["circular"], e["longest"]) == (2, 40, 1, 1, 40)
+    km = case("one_bucket")[2]
+    assert sum(x.startswith("A" * 20) for x in km) >= 600 and km[-1].startswith("T" * 13)
+
+
+@pytest.mark.parametrize("k", [5, 31, 33, 63])
+def test_periodic_spells_a_cycle_below_k(k):
+    for L in (2, 3, 4, 5, 7, 8, 9):
+        s = U.periodic(L, k, L)
+        km, cnt = U.listing_of(U.count_kmers([s], k))
+        strs, recs = U.unitigs(km, cnt, k, 1)
+        U.check(km, cnt, k, 1, strs, recs)
+        assert len(s) == L + k - 1 and len(km) == L and [(r["n_kmers"], r["circular"]) for r in recs] == [(L, 1)]
 
 
 def test_hand_built_graphs():

@@ -212,7 +212,119 @@ def small_k_case():
     return [s[:100] + "AAAAAAAAA" + s[100:] + "ACGTACGTACG"]
 
 
-CASES = {                                                      # name -> (k, thr, sequences)
+def periodic(L: int, k: int, seed: int) -> str:
+    """a random string of period L repeated to L + k - 1 bytes: a cycle of exactly L nodes, also for L < k (a draw whose L
+    windows are not L distinct canonical k-mers -- a shorter period, a window that is another's reverse complement -- or have
+    an edge besides the cycle's own, as happens at a small k, is drawn again)"""
+    r = random.Random(seed)
+    while True:
+        p = "".join(r.choice("ACGT") for _ in range(L))
+        s = (p * ((L + k - 1) // L + 1))[:L + k - 1]
+        km, cnt = listing_of(count_kmers([s], k))
+        g = Graph(km, cnt, k, 1)
+        if len(km) == L and all(len(g.succ(x)) == 1 and len(g.pred(x)) == 1 for x in km):
+            return s
+
+
+PALETTE = (1, 2, 3, 5, 0xFFFFFFFF)
+
+
+def dense(k: int, density: float, seed: int, counts=PALETTE):
+    """-> (k-mers ascending, counts): every canonical k-mer kept with probability `density`, its count drawn from `counts`"""
+    r = random.Random(seed)
+    km, cnt = [], []
+    for v in range(4 ** k):
+        if r.random() < density:
+            x = "".join("ACGT"[(v >> (2 * (k - 1 - j))) & 3] for j in range(k))
+            if x <= rc(x):
+                km.append(x)
+                cnt.append(r.choice(counts))
+    return km, cnt
+
+
+def top_run(k: int) -> str:
+    """T..TA..A: its windows T^j A^(k-j), j <= k // 2, are canonical as they stand and lie at the top of a listing"""
+    return "T" * (k // 2) + "A" * (k + 2)
+
+
+def tangle(k: int, seed: int):
+    """sequences whose graph has every local shape at a k where random subsets of the k-mers have no edges at all: a genome
+    twice, substituted fragments of it in both orientations (bubbles and tips, single-copy), a palindromic junction (a hairpin
+    edge), homopolymer runs (self-loops), the largest canonical k-mers, and isolated cycles, every other one twice"""
+    r = random.Random(seed)
+
+    def rs(n):
+        return "".join(r.choice("ACGT") for _ in range(n))
+
+    g = rs(400)
+    seqs = [g, g]
+    length = 2 * k + 20
+    for j in range(30):
+        p = r.randrange(len(g) - length + 1)
+        s = list(g[p:p + length])
+        for _ in range(2):
+            q = r.randrange(length)
+            s[q] = r.choice([c for c in "ACGT" if c != s[q]])
+        s = "".join(s)
+        seqs.append(rc(s) if j % 2 else s)
+    h = rs(k + 8)
+    seqs.append(h + rc(h))
+    seqs.append(rs(k) + "C" * (k + 5) + rs(k))
+    seqs.append(top_run(k))
+    for j, L in enumerate((2, 3, 4, 5, 31, 32, 33, 64, 65)):
+        c = periodic(L, k, 100 * seed + L)
+        seqs += [c, c] if j % 2 else [c]
+    return seqs
+
+
+def all_cycles(k: int, lengths=range(2, 131)):
+    """{L: periodic(L, k, 1000 + L)}: the cycles the tests run one by one, and k31_all_cycles in one listing"""
+    return {L: periodic(L, k, 1000 + L) for L in lengths}
+
+
+def cycle_and_tip():
+    """a cycle of 40 nodes given twice and a single-copy tip that leaves it behind its third node: with the tip's k-mers (thr = 1)
+    that node has two successors and nothing is circular; without them (thr = 2) the cycle closes"""
+    k = 21
+    c = periodic(40, k, 41)
+    t0 = next(b for b in "ACGT" if b != c[3 + k - 1])
+    return [c, c, c[3:3 + k - 1] + t0 + rand_seq(15, 42)]
+
+
+def one_bucket():
+    """-> (k, thr, k-mers, counts): 600 31-mers that share their first 20 bases (the windows of A^23 + 11 random bases that start
+    with A^20, in families that share 8 of the 11, so that they branch), and behind them the run of top_run(31)"""
+    k, r = 31, random.Random(43)
+    roots = ["".join(r.choice("ACGT") for _ in range(8)) for _ in range(40)]
+    got = {}
+    while len(got) < 600:
+        s = "A" * 23 + r.choice(roots) + "".join(r.choice("ACGT") for _ in range(3))
+        for x, c in count_kmers([s], k).items():
+            if x.startswith("A" * 20):
+                got[x] = got.get(x, 0) + c
+    both = {x: got[x] for x in sorted(got)[:600]}
+    for x, c in count_kmers([top_run(k)], k).items():
+        both[x] = both.get(x, 0) + c
+    return (k, 1) + listing_of(both)
+
+
+def equal_high_words(k: int, seed: int):
+    """-> two canonical k-mers (k > 32), ascending, that share their first k - 32 bases: packed, their high words are equal"""
+    r = random.Random(seed)
+    head = "A" + "".join(r.choice("ACGT") for _ in range(k - 33))
+    both = set()
+    while len(both) < 2:
+        x = head + "".join(r.choice("ACGT") for _ in range(32))
+        if canon(x) == x:
+            both.add(x)
+    return sorted(both)
+
+
+def _listing(k, thr, listing):
+    return (k, thr) + tuple(listing)
+
+
+CASES = {                                                      # name -> (k, thr, sequences) or (k, thr, k-mers, counts)
     "k5_loops_hairpins": lambda: (5, 1, small_k_case()),
     "k7_cycle30": lambda: (7, 1, [circular_seq(30, 7, 2)]),
     "k7_cycle40": lambda: (7, 1, [circular_seq(40, 7, 4)]),
@@ -230,12 +342,30 @@ CASES = {                                                      # name -> (k, thr
     "k63_linear": lambda: (63, 1, [rand_seq(500, 35)]),
     "reads_thr1": lambda: (21, 1, noisy_reads(rand_seq(5000, 36), 1000, 100, 0.01, 37)),
     "reads_thr3": lambda: (21, 3, noisy_reads(rand_seq(5000, 36), 1000, 100, 0.01, 37)),
+    # every canonical k-mer, or a random subset: nodes of degree 3 and 4 on both sides, hairpins, self-loops, mirror pairs
+    "k5_complete": lambda: _listing(5, 1, dense(5, 1.0, 50, (1,))),
+    "k5_dense_thr3": lambda: _listing(5, 3, dense(5, 1.0, 51)),
+    "k7_complete": lambda: _listing(7, 1, dense(7, 1.0, 52)),
+    "k7_half_thr1": lambda: _listing(7, 1, dense(7, 0.5, 53)),
+    "k7_half_thr3": lambda: _listing(7, 3, dense(7, 0.5, 53)),
+    "k7_tenth": lambda: _listing(7, 0, dense(7, 0.1, 54, (0,) + PALETTE)),     # thr = 0: a count of 0 is a node
+    "k9_dense": lambda: _listing(9, 0xFFFFFFFF, dense(9, 0.1, 55)),            # the largest thr: a fifth of the entries are nodes
+    "k11_sparse": lambda: _listing(11, 2, dense(11, 0.02, 56)),
+    **{f"tangle_k{k}_thr{thr}": (lambda k=k, thr=thr: (k, thr, tangle(k, k))) for k in (31, 33, 35, 47, 61, 63) for thr in (1, 2)},
+    "k31_all_cycles": lambda: (31, 1, list(all_cycles(31).values()) + [rand_seq(700, 57)]),
+    "cycle_only_above_thr": lambda: (21, 2, cycle_and_tip()),
+    "cycle_only_above_thr_at1": lambda: (21, 1, cycle_and_tip()),
+    "one_bucket": one_bucket,
 }
 
 
 def case(name: str):
-    """-> (k, thr, k-mers, counts, strs, recs)"""
-    k, thr, seqs = CASES[name]()
-    km, cnt = listing_of(count_kmers(seqs, k))
+    """-> (k, thr, k-mers, counts, strs, recs), the caller's own: a caller that asks twice keeps them itself"""
+    c = CASES[name]()
+    if len(c) == 3:
+        k, thr, seqs = c
+        km, cnt = listing_of(count_kmers(seqs, k))
+    else:
+        k, thr, km, cnt = c
     strs, recs = unitigs(km, cnt, k, thr)
     return k, thr, km, cnt, strs, recs
