@@ -220,18 +220,57 @@ __device__ __forceinline__ void commit_touches(const ModelDev &md, const Touches
 }
 
 // ------------------------------------------------------------------------------------------ pass 1
-// get_km_kmer_count (kmodel.hpp:423-428): histogram of the bf_num lowest counts.
+// sum over the 64 lanes of a wave (every lane takes part and gets the sum)
+template <typename T> __device__ __forceinline__ T wave_sum(T v)
+{
+#pragma unroll
+	for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+	return v;
+}
+
+// get_km_kmer_count (kmodel.hpp:423-428): histogram of the bf_num lowest counts.  A stream: 16-byte loads from the first
+// aligned count on, four of them in flight per lane, a grid sized to the device; the up to three counts before the first
+// and after the last full vector are read one by one.  One atomic per counter and workgroup.
+struct HistTally {
+	u64 f0 = 0, f1 = 0, f2 = 0, bad = 0;
+	__device__ __forceinline__ void add(u32 c, int ci, int cs, int bf_num)
+	{
+		const bool out = c < (u32)ci || c > (u32)cs;
+		const u32 d = c - (u32)ci;
+		bad += out;
+		f0 += !out && d == 0 && bf_num > 0;
+		f1 += !out && d == 1 && bf_num > 1;
+		f2 += !out && d == 2 && bf_num > 2;
+	}
+	__device__ __forceinline__ void add4(const uint4 &q, int ci, int cs, int bf_num) { add(q.x, ci, cs, bf_num); add(q.y, ci, cs, bf_num); add(q.z, ci, cs, bf_num); add(q.w, ci, cs, bf_num); }
+};
 __global__ __launch_bounds__(256) void k_histogram(const u32 *counts, u64 n, int ci, int cs, int bf_num, u64 *n_bf, u64 *stats)
 {
-	u64 local[3] = {0, 0, 0}, bad = 0;
-	for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
-		u32 c = counts[i];
-		if (c < (u32)ci || c > (u32)cs) bad++;
-		else if (c < (u32)(ci + bf_num)) local[c - ci]++;
+	__shared__ unsigned long long s_sum[4];
+	if (threadIdx.x < 4) s_sum[threadIdx.x] = 0;
+	__syncthreads();
+	const u64 to_aligned = ((16 - ((uintptr_t)counts & 15)) & 15) >> 2;
+	const u64 head = to_aligned < n ? to_aligned : n, nv = (n - head) >> 2, tail = head + (nv << 2);
+	const uint4 *v = reinterpret_cast<const uint4 *>(counts + head);
+	const u64 T = (u64)gridDim.x * 256, g = (u64)blockIdx.x * 256 + threadIdx.x;
+	HistTally h;
+	u64 i = g;
+	for (; i + 3 * T < nv; i += 4 * T) {
+		const uint4 q0 = v[i], q1 = v[i + T], q2 = v[i + 2 * T], q3 = v[i + 3 * T];
+		h.add4(q0, ci, cs, bf_num); h.add4(q1, ci, cs, bf_num); h.add4(q2, ci, cs, bf_num); h.add4(q3, ci, cs, bf_num);
 	}
-	for (int f = 0; f < 3; f++)
-		if (local[f]) atomicAdd(n_bf + f, local[f]);
-	if (bad) atomicAdd(stats + ST_BAD_COUNT, bad);
+	for (; i < nv; i += T) h.add4(v[i], ci, cs, bf_num);
+	if (g < head) h.add(counts[g], ci, cs, bf_num);
+	if (g < n - tail) h.add(counts[tail + g], ci, cs, bf_num);
+	const u64 w0 = wave_sum(h.f0), w1 = wave_sum(h.f1), w2 = wave_sum(h.f2), wb = wave_sum(h.bad);
+	if ((threadIdx.x & 63) == 0) {
+		if (w0) atomicAdd(&s_sum[0], (unsigned long long)w0);
+		if (w1) atomicAdd(&s_sum[1], (unsigned long long)w1);
+		if (w2) atomicAdd(&s_sum[2], (unsigned long long)w2);
+		if (wb) atomicAdd(&s_sum[3], (unsigned long long)wb);
+	}
+	__syncthreads();
+	if (threadIdx.x < 4 && s_sum[threadIdx.x]) atomicAdd(threadIdx.x < 3 ? n_bf + threadIdx.x : stats + ST_BAD_COUNT, (u64)s_sum[threadIdx.x]);
 }
 
 // block-wide exclusive scan of one int per thread over the first 256 threads (the other threads of a larger workgroup
@@ -313,94 +352,181 @@ __device__ __forceinline__ void kmback_emit_body(const ModelDev &md, const Block
 // Pass 2 front end (kmodel.hpp:70-73): Bloom-class k-mers are inserted right here (commutative ORs, any
 // order); coupled-array k-mers are compacted, in listing order, into the staging stream.
 #define CLS_TILE KMX_CLS_TILE
+// k_classify_count: a workgroup owns a span of CLS_SPAN k-mers, i.e. CLS_SPAN / CLS_TILE tiles of the per-tile counts that
+// k_scan_tiles and k_classify_scatter work on.  It reads the span's counts as a stream (one 16-byte load per lane and 1024
+// k-mers, all of them issued before the first is looked at), classifies in registers, and gathers the span's Bloom-class
+// k-mers in an LDS list, so that all hashing passes but the last run with every lane busy.  The list holds half a span, which
+// keeps four workgroups on a CU beside the stage of bs_block_emit; a span with more Bloom-class k-mers is listed half by half.
+#define CLS_SPAN (4 * CLS_TILE)
+static_assert(CLS_TILE % 1024 == 0 && CLS_SPAN / CLS_TILE == 4 && CLS_TILE < (1 << 16), "four 16-bit tile counters in one 64-bit word");
+static_assert(CLS_SPAN <= (1 << 14), "a list entry: 14 bits of offset in the span, the Bloom class above them");
 template <int W, int NHM> __global__ __launch_bounds__(256) void k_classify_count(ModelDev md, const u64 *kmers, const u32 *counts, u64 n, int *tile_cnt, u64 *stats, BitScatter bs)
 {
 	constexpr int K = 2 * NHM - 3;                                   // (nh-1) + (nh-2) positions of one Bloom-class k-mer
+	constexpr int NL = CLS_SPAN / 1024;                              // loads per lane: load l covers k-mers [1024 l, 1024 (l + 1)) of the span, lane x four from 4 x on
 	BS_LDS(K);
-	__shared__ int s_cnt, s_nb;
-	__shared__ unsigned short s_bloom[CLS_TILE];                     // the tile's Bloom-class k-mers (offsets in the tile)
-	if (threadIdx.x == 0) { s_cnt = 0; s_nb = 0; }
+	__shared__ unsigned long long s_tiles;                           // the tiles' coupled-array k-mers, 16 bits per tile
+	constexpr int CAP = CLS_SPAN / 2;                                // the list's capacity: a span with more Bloom-class k-mers goes through it half by half
+	__shared__ int s_nb, s_half, s_bad;                              // s_half: the Bloom-class k-mers of the span's first half | of its second half << 16
+	__shared__ unsigned short s_bloom[CAP];                          // Bloom-class k-mers: offset in the span | class << 14
+	const int lane = threadIdx.x & 63;
+	if (threadIdx.x == 0) { s_tiles = 0; s_nb = 0; s_half = 0; s_bad = 0; }
 	__syncthreads();
-	int mine = 0;
-	u64 base = (u64)blockIdx.x * CLS_TILE;
-	for (int q = 0; q < CLS_TILE / 256; q++) {
-		u64 i = base + (u64)q * 256 + threadIdx.x;
-		if (i >= n) break;
-		u32 c = counts[i];
-		if (c < (u32)md.ci || c > (u32)md.cs) { atomicAdd(stats + ST_BAD_COUNT, 1ULL); continue; }
-		if (c < (u32)(md.ci + md.bf_num)) {
-			if (md.bloom_direct) {
-				int f = (int)(c - (u32)md.ci);
-				u64 v[W];
-				load_kmer<W>(kmers, i, v);
-				Aligned<W> al = left_align<W>(v, md.k);
-				Premixed<W> pf = premix_string<W>(al, md.gfull);
-				bloom_insert_pm<W>(pf, md.gfull, md.bf[f], md.bf_mod[f], md.nh - 1);                 // kmodel.hpp:474
-				Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
-				bloom_insert_pm<W>(pb, md.gback, md.bf_back[f], md.bf_back_mod[f], md.nh - 2);       // kmodel.hpp:475-476
-			} else s_bloom[atomicAdd(&s_nb, 1)] = (unsigned short)(q * 256 + threadIdx.x);
-		} else mine++;
-	}
-	if (mine) atomicAdd(&s_cnt, mine);
-	__syncthreads();
-	if (threadIdx.x == 0) tile_cnt[blockIdx.x] = s_cnt;
-	if (md.bloom_direct) return;
-	// the Bloom-class k-mers of the tile, 256 at a time: their bit addresses in the slab go to the BitScatter
-	const int nbl = s_nb;
-	for (int c0 = 0; c0 < nbl; c0 += 256) {                          // uniform
-		u64 v[K];
-		u32 valid = 0;
-		if (c0 + (int)threadIdx.x < nbl) {
-			const u64 i = base + s_bloom[c0 + threadIdx.x];
-			const int f = (int)(counts[i] - (u32)md.ci);
-			u64 km[W];
-			load_kmer<W>(kmers, i, km);
-			Aligned<W> al = left_align<W>(km, md.k);
-			Premixed<W> pf = premix_string<W>(al, md.gfull);
-			Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
+	const u64 base = (u64)blockIdx.x * CLS_SPAN;
+	u32 c[NL][4], live = ~0u;                                        // live: bit 4 l + e = that count exists
+	if (base + CLS_SPAN <= n && !((uintptr_t)counts & 15)) {         // (uniform)
 #pragma unroll
-			for (int j = 0; j < NHM - 1; j++)
-				if (j < md.nh - 1 && md.bf_mod[f].d) {
-					const u64 pos = mod_u64(murmur_seeded<W>(pf, md.gfull, c_seeds[j]), md.bf_mod[f]);
-					v[j] = ((md.bf_woff[f] + (pos >> 5)) << 5) | bit_in_word32(pos);
-					valid |= 1u << j;
-				}
-#pragma unroll
-			for (int j = 0; j < NHM - 2; j++)
-				if (j < md.nh - 2 && md.bf_back_mod[f].d) {
-					const u64 pos = mod_u64(murmur_seeded<W>(pb, md.gback, c_seeds[j]), md.bf_back_mod[f]);
-					v[NHM - 1 + j] = ((md.bf_back_woff[f] + (pos >> 5)) << 5) | bit_in_word32(pos);
-					valid |= 1u << (NHM - 1 + j);
-				}
+		for (int l = 0; l < NL; l++) {
+			const uint4 q = *reinterpret_cast<const uint4 *>(counts + base + l * 1024 + 4 * threadIdx.x);
+			c[l][0] = q.x; c[l][1] = q.y; c[l][2] = q.z; c[l][3] = q.w;
 		}
-		bs_block_emit<K>(bs, v, valid, s_bs_cnt, s_bs_off, s_bs_base, s_bs_tmp, s_bs_stage);
+	} else {                                                         // the last span of a launch, or a pointer that is not 16-byte aligned
+		live = 0;
+#pragma unroll
+		for (int l = 0; l < NL; l++)
+#pragma unroll
+			for (int e = 0; e < 4; e++) {
+				const u64 i = base + l * 1024 + 4 * threadIdx.x + e;
+				c[l][e] = 0;
+				if (i < n) { c[l][e] = counts[i]; live |= 1u << (4 * l + e); }
+			}
+	}
+	u32 bmask = 0;                                                   // bit 4 l + e: a Bloom-class k-mer ...
+	u64 fcode = 0, mine = 0;                                         // ... of class (fcode >> 2 (4 l + e)) & 3
+	int bad = 0;
+#pragma unroll
+	for (int l = 0; l < NL; l++)
+#pragma unroll
+		for (int e = 0; e < 4; e++) {
+			const int x = 4 * l + e;
+			const u32 cc = c[l][e];
+			const bool is_live = (live >> x) & 1u, out = cc < (u32)md.ci || cc > (u32)md.cs, bloom = is_live && !out && cc < (u32)(md.ci + md.bf_num);
+			bad += is_live && out;
+			bmask |= (u32)bloom << x;
+			fcode |= (u64)(bloom ? cc - (u32)md.ci : 0u) << (2 * x);
+			mine += (u64)(is_live && !out && !bloom) << (16 * (l / (CLS_TILE / 1024)));
+		}
+	constexpr u32 FIRST_HALF = (1u << (2 * NL)) - 1;                 // the loads of the span's first half
+	mine = wave_sum(mine);
+	bad = wave_sum(bad);
+	const int half = wave_sum(__popc(bmask & FIRST_HALF) | (__popc(bmask & ~FIRST_HALF) << 16));
+	if (lane == 0) {
+		atomicAdd(&s_tiles, (unsigned long long)mine);
+		if (half) atomicAdd(&s_half, half);
+		if (bad) atomicAdd(&s_bad, bad);
+	}
+	if (md.bloom_direct) {
+		while (bmask) {
+			const int x = __ffs(bmask) - 1;
+			bmask &= bmask - 1;
+			const u64 i = base + (x >> 2) * 1024 + 4 * threadIdx.x + (x & 3);
+			const int f = (int)(fcode >> (2 * x)) & 3;
+			u64 v[W];
+			load_kmer<W>(kmers, i, v);
+			Aligned<W> al = left_align<W>(v, md.k);
+			Premixed<W> pf = premix_string<W>(al, md.gfull);
+			bloom_insert_pm<W>(pf, md.gfull, md.bf[f], md.bf_mod[f], md.nh - 1);                 // kmodel.hpp:474
+			Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
+			bloom_insert_pm<W>(pb, md.gback, md.bf_back[f], md.bf_back_mod[f], md.nh - 2);       // kmodel.hpp:475-476
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < CLS_SPAN / CLS_TILE && base + (u64)threadIdx.x * CLS_TILE < n)
+		tile_cnt[blockIdx.x * (CLS_SPAN / CLS_TILE) + threadIdx.x] = (int)((s_tiles >> (16 * threadIdx.x)) & 0xffff);
+	if (threadIdx.x == 0 && s_bad) atomicAdd(stats + ST_BAD_COUNT, (u64)s_bad);
+	if (md.bloom_direct) return;
+	// the Bloom-class k-mers of the span are listed (one LDS atomic per wave reserves the wave's run) and hashed 256 at a time:
+	// their bit addresses in the slab go to the BitScatter.  Each half of the span fits the list whatever its mixture.
+	const int rounds = (s_half & 0xffff) + (s_half >> 16) <= CAP ? 1 : 2;
+	for (int r = 0; r < rounds; r++) {                               // uniform
+		u32 todo = rounds == 1 ? bmask : r == 0 ? bmask & FIRST_HALF : bmask & ~FIRST_HALF;
+		const int mine_b = __popc(todo);
+		int incl = mine_b;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const int t = __shfl_up(incl, d, 64);
+			if (lane >= d) incl += t;
+		}
+		int wbase = 0;
+		if (lane == 63 && incl) wbase = atomicAdd(&s_nb, incl);
+		int pos = __shfl(wbase, 63, 64) + incl - mine_b;
+		while (todo) {
+			const int x = __ffs(todo) - 1;
+			todo &= todo - 1;
+			s_bloom[pos++] = (unsigned short)(((x >> 2) * 1024 + 4 * (int)threadIdx.x + (x & 3)) | ((int)((fcode >> (2 * x)) & 3) << 14));
+		}
+		__syncthreads();
+		const int nbl = s_nb;
+		for (int c0 = 0; c0 < nbl; c0 += 256) {                      // uniform
+			u64 v[K];
+			u32 valid = 0;
+			if (c0 + (int)threadIdx.x < nbl) {
+				const u32 e = s_bloom[c0 + threadIdx.x];
+				const u64 i = base + (e & 0x3fffu);
+				const int f = (int)(e >> 14);
+				u64 km[W];
+				load_kmer<W>(kmers, i, km);
+				Aligned<W> al = left_align<W>(km, md.k);
+				Premixed<W> pf = premix_string<W>(al, md.gfull);
+				Premixed<W> pb = premix_string<W>(drop_first_base<W>(al), md.gback);
+#pragma unroll
+				for (int j = 0; j < NHM - 1; j++)
+					if (j < md.nh - 1 && md.bf_mod[f].d) {
+						const u64 pos = mod_u64(murmur_seeded<W>(pf, md.gfull, c_seeds[j]), md.bf_mod[f]);
+						v[j] = ((md.bf_woff[f] + (pos >> 5)) << 5) | bit_in_word32(pos);
+						valid |= 1u << j;
+					}
+#pragma unroll
+				for (int j = 0; j < NHM - 2; j++)
+					if (j < md.nh - 2 && md.bf_back_mod[f].d) {
+						const u64 pos = mod_u64(murmur_seeded<W>(pb, md.gback, c_seeds[j]), md.bf_back_mod[f]);
+						v[NHM - 1 + j] = ((md.bf_back_woff[f] + (pos >> 5)) << 5) | bit_in_word32(pos);
+						valid |= 1u << (NHM - 1 + j);
+					}
+			}
+			bs_block_emit<K>(bs, v, valid, s_bs_cnt, s_bs_off, s_bs_base, s_bs_tmp, s_bs_stage);
+		}
+		__syncthreads();                                             // every thread has read s_nb and its list entries
+		if (threadIdx.x == 0) s_nb = 0;
+		__syncthreads();
 	}
 }
 
-// exclusive scan of up to 2^20 tile counts by one workgroup; total -> *total_out
-__global__ __launch_bounds__(1024) void k_scan_tiles(const int *cnt, int *off, int n_tiles, int *total_out)
+// exclusive scan of the tile counts, one workgroup per chunk of tiles_per_chunk tiles (blockIdx.x = chunk; the last chunk
+// has what is left): offsets relative to the chunk start, the chunk's total -> totals[chunk].  Four consecutive counts per
+// thread, a shuffle scan in the wave, one step across the 16 waves.
+__global__ __launch_bounds__(1024) void k_scan_tiles(const int *cnt, int *off, int n_tiles, int tiles_per_chunk, int *totals)
 {
-	__shared__ int s[1024];
-	__shared__ int carry;
-	if (threadIdx.x == 0) carry = 0;
-	__syncthreads();
-	for (int base = 0; base < n_tiles; base += 1024) {
-		int i = base + threadIdx.x;
-		int v = i < n_tiles ? cnt[i] : 0;
-		s[threadIdx.x] = v;
-		__syncthreads();
-		for (int d = 1; d < 1024; d <<= 1) {
-			int t = threadIdx.x >= d ? s[threadIdx.x - d] : 0;
-			__syncthreads();
-			s[threadIdx.x] += t;
-			__syncthreads();
+	__shared__ int s_w[16];
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int t0 = blockIdx.x * tiles_per_chunk, nt = n_tiles - t0 < tiles_per_chunk ? n_tiles - t0 : tiles_per_chunk;
+	cnt += t0;
+	off += t0;
+	int carry = 0;
+	for (int b = 0; b < nt; b += 4096) {                             // uniform
+		const int i = b + 4 * threadIdx.x;
+		int v[4], sum = 0;
+#pragma unroll
+		for (int e = 0; e < 4; e++) { v[e] = i + e < nt ? cnt[i + e] : 0; sum += v[e]; }
+		int incl = sum;
+#pragma unroll
+		for (int d = 1; d < 64; d <<= 1) {
+			const int t = __shfl_up(incl, d, 64);
+			if (lane >= d) incl += t;
 		}
-		if (i < n_tiles) off[i] = carry + s[threadIdx.x] - v;
+		if (lane == 63) s_w[wave] = incl;
 		__syncthreads();
-		if (threadIdx.x == 1023) carry += s[1023];
-		__syncthreads();
+		int wbase = 0, tot = 0;
+#pragma unroll
+		for (int w = 0; w < 16; w++) { const int t = s_w[w]; wbase += w < wave ? t : 0; tot += t; }
+		__syncthreads();                                             // (s_w is written again in the next step)
+		int o = carry + wbase + incl - sum;
+#pragma unroll
+		for (int e = 0; e < 4; e++)
+			if (i + e < nt) { off[i + e] = o; o += v[e]; }
+		carry += tot;
 	}
-	if (threadIdx.x == 0) *total_out = carry;
+	if (threadIdx.x == 0) totals[blockIdx.x] = carry;
 }
 
 // compaction of the coupled-array k-mers of a tile into the staging stream, in listing order: lane-contiguous loads, a
@@ -2750,11 +2876,20 @@ namespace kmxk {
 static inline int words(const ModelDev &md) { return (md.k + 31) / 32; }
 void bs_apply(const BitScatter &bs, hipStream_t st);
 
+// a grid-stride stream kernel's grid: `per_cu` workgroups per compute unit of the current device
+static unsigned stream_grid(int per_cu)
+{
+	int dev = 0, cus = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+	return (unsigned)(cus * per_cu);
+}
+
 void histogram(const u32 *counts, u64 n, int ci, int cs, int bf_num, u64 *n_bf, u64 *stats, hipStream_t st)
 {
 	if (!n) return;
-	u64 blocks = (n + 255) / 256;
-	if (blocks > 4096) blocks = 4096;
+	u64 blocks = (n + 4095) / 4096;                                  // 16 counts per thread and step
+	const u64 cap = stream_grid(8);
+	if (blocks > cap) blocks = cap;
 	hipLaunchKernelGGL(k_histogram, dim3((unsigned)blocks), dim3(256), 0, st, counts, n, ci, cs, bf_num, n_bf, stats);
 }
 
@@ -2763,8 +2898,8 @@ int classify_tiles(u64 n) { return (int)((n + CLS_TILE - 1) / CLS_TILE); }
 
 // Front end of `n` k-mers cut into chunks of `chunk` k-mers (a multiple of CLS_TILE): the Bloom-class k-mers are inserted
 // (directly, or a chunk at a time through the BitScatter `bs`, swept after every `sweep_every` chunks and at the end) and
-// the coupled-array k-mers are counted per tile; one small scan per chunk turns the counts into offsets relative to the
-// chunk start and the chunk's total (totals[c]).
+// the coupled-array k-mers are counted per tile; one scan launch (a workgroup per chunk) turns the counts into offsets
+// relative to the chunk start and the chunk's total (totals[c]).
 void classify_count(const ModelDev &md, const u64 *kmers, const u32 *counts, u64 n, u64 chunk, int *tile_cnt, int *tile_off, int *totals, u64 *stats, const BitScatter &bs, int sweep_every, hipStream_t st, KernelProf *prof)
 {
 	if (!n) return;
@@ -2775,15 +2910,12 @@ void classify_count(const ModelDev &md, const u64 *kmers, const u32 *counts, u64
 	int since = 0;
 	for (u64 lo = 0; lo < n; lo += piece) {
 		const u64 c = n - lo < piece ? n - lo : piece;
-		const int t0 = (int)(lo / CLS_TILE), nt = classify_tiles(c);
-		DISPATCH_W_NH(W_, md.nh, hipLaunchKernelGGL((k_classify_count<W, NHM>), dim3(nt), dim3(256), 0, st, md, kmers + lo * W_, counts + lo, c, tile_cnt + t0, stats, bs));
+		const int t0 = (int)(lo / CLS_TILE), ns = (int)((c + CLS_SPAN - 1) / CLS_SPAN);
+		DISPATCH_W_NH(W_, md.nh, hipLaunchKernelGGL((k_classify_count<W, NHM>), dim3(ns), dim3(256), 0, st, md, kmers + lo * W_, counts + lo, c, tile_cnt + t0, stats, bs));
 		if (!md.bloom_direct && (++since >= sweep_every || lo + piece >= n)) { bs_apply(bs, st); since = 0; }
 	}
 	KPROF_END(prof, st);
-	for (int c = 0, t0 = 0; t0 < tiles; c++, t0 += tiles_per_chunk) {
-		const int nt = tiles - t0 < tiles_per_chunk ? tiles - t0 : tiles_per_chunk;
-		hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, st, (const int *)(tile_cnt + t0), tile_off + t0, nt, totals + c);
-	}
+	hipLaunchKernelGGL(k_scan_tiles, dim3((tiles + tiles_per_chunk - 1) / tiles_per_chunk), dim3(1024), 0, st, (const int *)tile_cnt, tile_off, tiles, tiles_per_chunk, totals);
 }
 
 void classify_scatter(const ModelDev &md, const u64 *kmers, const u32 *counts, u64 n, const int *tile_off, u64 *stg_kmers, u32 *stg_counts, u64 stg_base, hipStream_t st)

@@ -1025,11 +1025,11 @@ static int ensure_front_end(kmx_model *m, u64 n)
 	return KMX_OK;
 }
 
-// Pass 2 for one batch (kmodel.hpp:68-74).  The batch is cut into chunks of kChunk k-mers.  The front end of chunk 0
-// (classification + Bloom insert, commutative) runs on the model's stream; the front end of all later chunks runs as
-// ONE launch on a side stream, underneath the ordered coupled-array rounds of the earlier chunks, which leave the
-// memory system idle in their latency-bound tails.  The compaction into the staging stream and the rounds stay in
-// order on the model's stream.
+// Pass 2 for one batch (kmodel.hpp:68-74).  The batch is cut into chunks of kChunk k-mers.  The front end of the WHOLE
+// batch (classification + Bloom insert, commutative: one k_classify_count launch per chunk, the sweeps of the bit-set,
+// one k_scan_tiles launch for all chunks) runs first, on the model's stream, and the host waits once for the chunk
+// totals.  Then, chunk by chunk and in order on the same stream: the compaction into the staging stream and the
+// ordered coupled-array rounds of every full block.
 static int kmx_insert_batch_dev_impl(kmx_model *m, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
