@@ -532,7 +532,8 @@ int kmx_count_finish(kmx_model *m, uint64_t *n_listed);
 int kmx_count_listing(kmx_model *m, uint64_t *kmers, uint32_t *counts, uint64_t capacity, uint64_t *n);
 /* begin + count + finish on reads from files: a FASTQ or FASTA path (plain or gzip, detected from the content) or "@list",
  * a file of paths, one per line.  FASTQ records have their sequence on one line; FASTA records join their lines; a '\r'
- * at a line end is dropped.  A malformed or truncated record: KMX_E_IO naming the file and the record.  gzip needs
+ * at a line end is dropped.  A malformed or truncated record: KMX_E_IO naming the file and the record; a gzip stream that
+ * ends early or is damaged: KMX_E_IO naming the file, also where the part that decodes ends on a whole record.  gzip needs
  * libz.so.1 at run time (opened with dlopen; plain input does not).                                                       */
 int kmx_build_from_reads(kmx_model *m, int k, const char *input);
 

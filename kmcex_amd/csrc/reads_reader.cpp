@@ -35,6 +35,7 @@ struct Zlib {
 	void *(*open)(const char *, const char *) = nullptr;
 	int (*read)(void *, void *, unsigned) = nullptr;
 	int (*close)(void *) = nullptr;
+	const char *(*error)(void *, int *) = nullptr;
 };
 static const Zlib &zlib()
 {
@@ -45,6 +46,7 @@ static const Zlib &zlib()
 			r.open = (void *(*)(const char *, const char *))dlsym(r.h, "gzopen");
 			r.read = (int (*)(void *, void *, unsigned))dlsym(r.h, "gzread");
 			r.close = (int (*)(void *))dlsym(r.h, "gzclose");
+			r.error = (const char *(*)(void *, int *))dlsym(r.h, "gzerror");
 		}
 		return r;
 	}();
@@ -55,7 +57,15 @@ class GzSource : public ByteSource {
 public:
 	explicit GzSource(void *gz) : gz_(gz) {}
 	~GzSource() override { zlib().close(gz_); }
-	long read(char *p, size_t n) override { return zlib().read(gz_, p, (unsigned)std::min<size_t>(n, 1u << 30)); }
+	// gzread hands out what a stream that ends early (or is damaged after some good blocks) still decodes and then reports
+	// the end of the file; only gzerror tells that from a whole stream (Z_OK = 0, Z_STREAM_END = 1)
+	long read(char *p, size_t n) override
+	{
+		const int r = zlib().read(gz_, p, (unsigned)std::min<size_t>(n, 1u << 30));
+		int e = 0;
+		zlib().error(gz_, &e);
+		return e < 0 ? -1 : r;
+	}
 private:
 	void *gz_;
 };
@@ -103,7 +113,7 @@ bool ReadsReader::open_next()
 	if (nm == 2 && mg[0] == 0x1f && mg[1] == 0x8b) {
 		fclose(f);
 		const Zlib &z = zlib();
-		if (!z.open || !z.read || !z.close) { err_ = path + ": gzip input, but libz.so.1 cannot be loaded"; return false; }
+		if (!z.open || !z.read || !z.close || !z.error) { err_ = path + ": gzip input, but libz.so.1 cannot be loaded"; return false; }
 		void *gz = z.open(path.c_str(), "rb");
 		if (!gz) { err_ = "cannot open " + path; return false; }
 		src_.reset(new GzSource(gz));

@@ -297,6 +297,17 @@ def test_failed_session_keeps_the_model(tmp_path):
         m.init_reads(bad, k)
     assert e.value.code == -3 and "cut.fq" in str(e.value) and "record" in str(e.value)
     assert np.array_equal(m.kmer_to_occ_packed(q), before)
+    # a gzip file cut short: what still decodes may well end on a whole record, and is a read error all the same
+    cut_gz = str(tmp_path / "cut.fq.gz")
+    CR.write_fastq(cut_gz, reads_for(k)[:400], gz=True)
+    with open(cut_gz, "rb") as f:
+        data = f.read()
+    with open(cut_gz, "wb") as f:
+        f.write(data[:len(data) // 2])
+    with pytest.raises(KmxError) as e:
+        m.init_reads(cut_gz, k)
+    assert e.value.code == -3 and "cut.fq.gz" in str(e.value) and "read error" in str(e.value)
+    assert np.array_equal(m.kmer_to_occ_packed(q), before)
     with pytest.raises(KmxError) as e:
         m.init_reads(str(tmp_path / "missing.fq"), k)
     assert e.value.code == -3

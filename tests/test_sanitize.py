@@ -1,5 +1,6 @@
 """The CPU-side code under AddressSanitizer + UBSan (GPU sanitizers are not available on the pool): the product's KMC
-listing reader and the oracle, driven by tests/asan_driver.cpp on the committed tiny database."""
+listing reader and the oracle, driven by tests/asan_driver.cpp on the committed tiny database.  The FASTQ / FASTA reader runs
+under the same sanitizers in tests/test_reads_reader_cpu.py, driven by tests/reads_reader_driver.cpp."""
 import os
 import subprocess
 
