@@ -5,6 +5,8 @@
 //     -g   count the input's k-mers on the GPU (KModel::init_reads) instead of running KMC; no KMC database is written
 //     -u<thr>  with -g and an odd k: also write the unitigs of the counted k-mers with count >= thr (1 when omitted) as FASTA to
 //          <working_directory>/<basename(output_file_name)>/unitigs.fa (KModel::count_unitigs)
+//     -G   with -u: also write the unitig graph (the unitigs and the edges between them) as GFA 1 to unitigs.gfa beside
+//          unitigs.fa (KModel::count_unitig_graph)
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -19,7 +21,7 @@
 
 struct Params {
 	int k = 31, num_hash = 7, num_bit = 5, ci = 1, cs = 1023, t = 4;
-	bool gpu_count = false;
+	bool gpu_count = false, gfa = false;
 	long unitig_thr = -1;                                          // -u: the threshold, -1 = no unitigs
 	std::string input, output, workdir = "/tmp";
 };
@@ -37,6 +39,7 @@ static bool parse(int argc, char **argv, Params &p)
 		else if (!strncmp(a, "-t", 2)) p.t = atoi(a + 2);
 		else if (!strncmp(a, "-k", 2)) p.k = atoi(a + 2);
 		else if (!strcmp(a, "-g")) p.gpu_count = true;
+		else if (!strcmp(a, "-G")) p.gfa = true;
 		else if (!strncmp(a, "-u", 2)) {
 			char *end = nullptr;
 			p.unitig_thr = a[2] ? strtol(a + 2, &end, 10) : 1;
@@ -48,6 +51,7 @@ static bool parse(int argc, char **argv, Params &p)
 	p.output = argv[argc - 2];
 	p.workdir = argv[argc - 1];
 	if (p.unitig_thr >= 0 && (!p.gpu_count || !(p.k & 1))) return false;   // the unitigs come from the listing -g keeps; the rule needs an odd k
+	if (p.gfa && p.unitig_thr < 0) return false;                   // the graph is the unitigs' own
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -59,7 +63,8 @@ int main(int argc, char **argv)
 		             "USAGE  kmcEx [options] <input_file_name|@list> <output_file_name> <working_directory>\n"
 		             "       -k<len> (31) -t<threads> (4) -ci<min count> (1) -cs<max count> (1023) -nh<hashes> (7) -nb<arrays> (5)\n"
 		             "       -g  count the k-mers of the FASTQ / FASTA input on the GPU instead of running KMC\n"
-		             "       -u<thr>  with -g and an odd k: write the unitigs of the k-mers with count >= thr (1) to <saved model>/unitigs.fa\n";
+		             "       -u<thr>  with -g and an odd k: write the unitigs of the k-mers with count >= thr (1) to <saved model>/unitigs.fa\n"
+		             "       -G  with -u<thr>: also write the unitigs and the edges between them as GFA 1 to <saved model>/unitigs.gfa\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -85,12 +90,21 @@ int main(int argc, char **argv)
 	km->save(dir);
 	if (p.unitig_thr >= 0) {
 		std::vector<kmx_unitig> rec;
-		const std::vector<std::string> strs = km->count_unitigs((uint32_t)p.unitig_thr, &rec);
+		std::vector<uint64_t> link_offsets;
+		std::vector<uint32_t> links;
+		const std::vector<std::string> strs = p.gfa ? km->count_unitig_graph((uint32_t)p.unitig_thr, &rec, &link_offsets, &links) : km->count_unitigs((uint32_t)p.unitig_thr, &rec);
 		std::ofstream fa((dir + "/unitigs.fa").c_str());
 		KModel::write_unitigs_fasta(fa, strs, rec);
 		fa.close();
 		if (!fa) { std::cout << "could not write " << dir << "/unitigs.fa" << std::endl; return 1; }
 		std::cout << "   unitigs (count >= " << p.unitig_thr << ")              :     " << strs.size() << std::endl;
+		if (p.gfa) {
+			std::ofstream gf((dir + "/unitigs.gfa").c_str());
+			KModel::write_unitigs_gfa(gf, strs, rec, link_offsets, links, p.k);
+			gf.close();
+			if (!gf) { std::cout << "could not write " << dir << "/unitigs.gfa" << std::endl; return 1; }
+			std::cout << "   edges between unitigs                :     " << links.size() << std::endl;
+		}
 	}
 	delete km;
 	return 0;

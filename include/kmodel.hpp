@@ -344,6 +344,60 @@ public:
 		}
 	}
 
+	// The unitig graph (the rule: kmx.h): the unitigs as above and the edges between the oriented unitigs o = 2 u + d (d = 1: the
+	// reverse complement) as CSR: the edges of o are links[link_offsets[o] .. link_offsets[o + 1]), each the target o'.  The
+	// twins of count_unitigs and unitigs: a sizing call plus one call.
+	std::vector<std::string> count_unitig_graph(uint32_t thr, std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links)
+	{
+		uint64_t nu = 0, nb = 0, nl = 0;
+		check(kmx_count_unitig_graph(h_, thr, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		std::vector<uint32_t> lk((size_t)nl + 1, 0);
+		check(kmx_count_unitig_graph(h_, thr, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl));
+		r.resize((size_t)nu);
+		lk.resize((size_t)nl);
+		if (rec) rec->swap(r);
+		if (link_offsets) link_offsets->swap(lo);
+		if (links) links->swap(lk);
+		return split(bases, off);
+	}
+	std::vector<std::string> unitig_graph(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr, std::vector<kmx_unitig> *rec,
+	                                      std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links)
+	{
+		uint64_t nu = 0, nb = 0, nl = 0;
+		const uint64_t n = counts.size();
+		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitig_graph: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
+		check(kmx_unitig_graph(h_, k, kmers.data(), counts.data(), n, thr, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		std::vector<uint32_t> lk((size_t)nl + 1, 0);
+		check(kmx_unitig_graph(h_, k, kmers.data(), counts.data(), n, thr, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl));
+		r.resize((size_t)nu);
+		lk.resize((size_t)nl);
+		if (rec) rec->swap(r);
+		if (link_offsets) link_offsets->swap(lo);
+		if (links) links->swap(lk);
+		return split(bases, off);
+	}
+	// the unitig graph as GFA 1: "H\tVN:Z:1.0", one "S\tu<index>\t<string>\tLN:i:<len>\tKC:i:<sum_count>" per unitig, and one
+	// "L\tu<a>\t<+|->\tu<b>\t<+|->\t<k-1>M" per mirror pair of edges: a -> b is written iff (a, b) <= (b ^ 1, a ^ 1) as pairs, so
+	// a self-mirror edge (a hairpin) once.  Rows follow the order of a, then the CSR order.
+	static void write_unitigs_gfa(std::ostream &out, const std::vector<std::string> &strs, const std::vector<kmx_unitig> &rec, const std::vector<uint64_t> &link_offsets,
+	                              const std::vector<uint32_t> &links, int k)
+	{
+		out << "H\tVN:Z:1.0\n";
+		for (size_t u = 0; u < strs.size(); u++) out << "S\tu" << u << "\t" << strs[u] << "\tLN:i:" << strs[u].size() << "\tKC:i:" << rec[u].sum_count << "\n";
+		for (uint64_t a = 0; a + 1 < link_offsets.size(); a++)
+			for (uint64_t e = link_offsets[a]; e < link_offsets[a + 1] && e < links.size(); e++) {
+				const uint64_t b = links[(size_t)e], mb = b ^ 1, ma = a ^ 1;
+				if (a < mb || (a == mb && b <= ma))
+					out << "L\tu" << (a >> 1) << "\t" << ((a & 1) ? '-' : '+') << "\tu" << (b >> 1) << "\t" << ((b & 1) ? '-' : '+') << "\t" << (k - 1) << "M\n";
+			}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -561,8 +561,8 @@ int kmx_build_from_reads(kmx_model *m, int k, const char *input);
  *   Order: ascending listing index of canon(x_1).  Every node lies in exactly one unitig, so the order is total.
  * Every field of the record is an integer count, sum, minimum or maximum, and the result is a function of (listing, thr) alone:
  * byte-identical across runs and variants.
- * Out of scope: even k, n >= 2^31, tip clipping, bubble popping, edges between unitigs (GFA links), unsorted (KMC2-order)
- * listings (sort them first), unitigs from the model's answers, several GPUs, choosing thr.                                 */
+ * Out of scope: even k, n >= 2^31, tip clipping, bubble popping, unsorted (KMC2-order) listings (sort them first), unitigs
+ * from the model's answers, several GPUs, choosing thr.  The edges between unitigs: kmx_unitig_graph below.            */
 typedef struct kmx_unitig {              /* one per unitig; 40 bytes, no padding */
 	uint64_t n_kmers;                    /* m; the string has m + k - 1 bytes */
 	uint64_t sum_count;                  /* over its nodes, of the listing's counts */
@@ -608,6 +608,53 @@ int kmx_count_unitigs_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t 
  * waits for the stream): seconds[4] = adjacency (with the validation and the index), links, ranking, emit (with the marks and
  * their scan); *rounds = its doubling rounds (counted always)                                                             */
 int kmx_unitigs_last_phases(kmx_model *m, double *seconds /* [4] */, uint64_t *rounds);
+
+/* ---- the unitig graph: the edges between the unitigs of the rule above, as CSR.  Take the result of the unitig rule for
+ * (listing, thr): U unitigs, strings s_u of m_u k-mers each.
+ *   Oriented unitig o = 2 u + d: d = 0 is s_u as emitted, d = 1 its reverse complement.  first(o) and last(o) are the first
+ *     and the last k bytes of the oriented string.
+ *   Edges out of o: for c in A, C, G, T in that order, y = last(o)[1:] + c; if canon(y) is a node there is an edge o -> o',
+ *     where o' is the one oriented unitig with first(o') = y.  It exists (an edge that leaves a unitig's end is no link, so y
+ *     has no link in and starts its oriented path) and is unique (for odd k every oriented k-mer lies in exactly one oriented
+ *     unitig, at one place).  A homopolymer's self-loop gives o -> o, a hairpin 2u -> 2u+1 or 2u+1 -> 2u, and a circular unitig
+ *     has exactly 2u -> 2u and 2u+1 -> 2u+1: the closing link, once per orientation.
+ *   Every edge overlaps by k - 1 bytes: the last k - 1 bytes of the source's oriented string are the first k - 1 of the target's.
+ * So out-degree(2u) = n_succ and out-degree(2u+1) = n_pred of record u; n_links is the sum of n_pred + n_succ over the records;
+ * a -> b is an edge iff (b ^ 1) -> (a ^ 1) is; no edge appears twice; and the oriented edges of the node graph are exactly the
+ * links inside unitigs plus the edges reported here.
+ * Output: link_offsets[2 U + 1] (uint64, link_offsets[0] = 0) and links[n_links] (uint32, the target o'; U <= n < 2^31): the
+ * edges of o are links[link_offsets[o] .. link_offsets[o + 1]), in the order of c.  A function of (listing, thr) alone,
+ * byte-identical across runs and variants.
+ * The four calls take the arguments of their kmx_*unitigs* twins in the same order, with link_offsets [2 rec_capacity + 1],
+ * links [link_capacity] and link_capacity in front of the counts and *n_links (HOST) behind them; strings, offsets and records
+ * are byte for byte the twin's.  seq_out == NULL: the sizing call, the three counts only.  A capacity too small, link_capacity
+ * included: KMX_E_RANGE, all three counts are what is needed, nothing is written; link_capacity = 8 * nodes always suffices.
+ * link_offsets == NULL or links == NULL with seq_out != NULL: KMX_E_ARG (also where n_links is 0).  n == 0 or no count reaches
+ * thr: KMX_OK, link_offsets[0] = 0, *n_links = 0.  The other argument checks, KMX_E_STATE, KMX_E_NOMEM (the handle stays usable,
+ * the listing intact), the build-class threading note and the waits are the twins': the number of links reaches the host in the
+ * wait that fetches the other two counts, so there is no wait more.  Device memory: none beside the twin's per listing entry
+ * (the link counts and their scan, 16 bytes per entry, live in the copy of the rank state that the marks have left free, the
+ * head and tail entry of every unitig in the two arrays of only-neighbours, which nothing reads once the ranks stand).  The
+ * host variants stage 8 (2 U + 1) + 4 n_links bytes more for the two arrays.
+ * Out of scope: tip clipping and bubble popping (they start from these edges), and what the unitig rule leaves out.       */
+int kmx_unitig_graph_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr,
+                         char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out /* [rec_capacity + 1] */, kmx_unitig *d_rec /* or NULL */, uint64_t rec_capacity,
+                         uint64_t *d_link_offsets /* [2 * rec_capacity + 1] */, uint32_t *d_links, uint64_t link_capacity,
+                         uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */, uint64_t *n_links /* HOST */);
+int kmx_unitig_graph(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr,
+                     char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out /* [rec_capacity + 1] */, kmx_unitig *rec /* or NULL */, uint64_t rec_capacity,
+                     uint64_t *link_offsets /* [2 * rec_capacity + 1] */, uint32_t *links, uint64_t link_capacity,
+                     uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links);
+int kmx_count_unitig_graph(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity,
+                           uint64_t *link_offsets /* [2 * rec_capacity + 1] */, uint32_t *links, uint64_t link_capacity,
+                           uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links);
+int kmx_count_unitig_graph_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity,
+                               uint64_t *d_link_offsets /* [2 * rec_capacity + 1] */, uint32_t *d_links, uint64_t link_capacity,
+                               uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */, uint64_t *n_links /* HOST */);
+/* kmx_unitigs_last_phases with a fifth figure: seconds[4] = the edges between unitigs (their counts at the heads and the scan,
+ * the links kernel), 0 after a call that asked for none.  kmx_unitigs_last_phases reports its four as before, after old and
+ * new calls alike.                                                                                                        */
+int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

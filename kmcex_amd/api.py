@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "kmx_extend_seqs", "kmx_extend_seqs_dev",
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
     "kmx_unitigs", "kmx_unitigs_dev", "kmx_count_unitigs", "kmx_count_unitigs_dev", "kmx_unitigs_last_phases",
+    "kmx_unitig_graph", "kmx_unitig_graph_dev", "kmx_count_unitig_graph", "kmx_count_unitig_graph_dev", "kmx_unitig_graph_last_phases",
 ]
 
 
@@ -94,6 +95,7 @@ class Unitig(C.Structure):
 UNITIG_DTYPE = np.dtype([("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count", "<u4"), ("max_count", "<u4"), ("first_node", "<u8"),
                          ("circular", "u1"), ("n_pred", "u1"), ("n_succ", "u1"), ("first_fwd", "u1"), ("reserved", "u1", (4,))])
 UNITIG_PHASES = ["adjacency", "links", "ranking", "emit"]
+UNITIG_GRAPH_PHASES = UNITIG_PHASES + ["unitig_links"]
 
 
 class RingList(C.Structure):
@@ -220,6 +222,11 @@ def load_library():
     _sig(L, "kmx_count_unitigs", [vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
     _sig(L, "kmx_count_unitigs_dev", [vp, u32, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64)])
     _sig(L, "kmx_unitigs_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
+    _sig(L, "kmx_unitig_graph", [vp, i32, vp, vp, u64, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_unitig_graph_dev", [vp, i32, vp, vp, u64, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_count_unitig_graph", [vp, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_count_unitig_graph_dev", [vp, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
+    _sig(L, "kmx_unitig_graph_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -839,6 +846,69 @@ class KModel:
         sec, rounds = (C.c_double * 4)(), C.c_uint64(0)
         _chk(self.L.kmx_unitigs_last_phases(self.h, sec, C.byref(rounds)))
         return {**{n: sec[i] for i, n in enumerate(UNITIG_PHASES)}, "rounds": int(rounds.value)}
+
+    # ---- the unitig graph: the unitigs and the edges between them as CSR over the 2 U oriented unitigs (the rule: include/kmx.h)
+    def _unitig_graph_host(self, call):
+        """the sizing call, then the call with exact room -> the tuple of _unitigs_host + (uint64 link_offsets [2 n + 1], uint32
+        links [n_links])"""
+        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl)))
+        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
+        off = np.zeros(nu.value + 1, dtype=np.uint64)
+        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
+        loff = np.zeros(2 * nu.value + 1, dtype=np.uint64)
+        links = np.empty(max(nl.value, 1), dtype=np.uint32)
+        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, loff.ctypes.data, links.ctypes.data, nl.value,
+                  C.byref(nu), C.byref(nb), C.byref(nl)))
+        return buf[:nb.value], off, rec, loff, links[:nl.value]
+
+    def _unitig_graph_dev(self, call):
+        """the same on the model's device -> torch tensors: those of _unitigs_dev + (int64 link_offsets [2 n + 1], int32 links
+        [n_links], the bits of the uint32 targets)"""
+        import torch
+        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl)))
+        dev = torch.device("cuda", self.stats().device)
+        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
+        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
+        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
+        loff = torch.zeros(2 * nu.value + 1, dtype=torch.int64, device=dev)
+        links = torch.empty(max(nl.value, 1), dtype=torch.int32, device=dev)
+        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, loff.data_ptr(), links.data_ptr(), nl.value,
+                  C.byref(nu), C.byref(nb), C.byref(nl)))
+        return buf[:nb.value], off, rec, loff, links[:nl.value]
+
+    def unitig_graph(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1):
+        """kmx_unitig_graph: unitigs() and the edges between the oriented unitigs o = 2 u + d (d = 1: the reverse complement) ->
+        (buf, offsets, rec, link_offsets, links); the edges of o are links[link_offsets[o]:link_offsets[o + 1]]"""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        n = counts.size
+        if kmers.size != n * ((int(k) + 31) // 32):
+            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
+        return self._unitig_graph_host(lambda *a: self.L.kmx_unitig_graph(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a))
+
+    def unitig_graph_dev(self, d_kmers, d_counts, k: int, thr: int = 1):
+        """kmx_unitig_graph_dev on torch tensors of the model's device (as unitigs_dev) -> torch tensors"""
+        n = d_counts.numel()
+        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
+            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
+        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
+        return self._unitig_graph_dev(lambda *a: self.L.kmx_unitig_graph_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a))
+
+    def count_unitig_graph(self, thr: int = 1):
+        """kmx_count_unitig_graph: the unitig graph of the listing the last count_finish / init_reads kept"""
+        return self._unitig_graph_host(lambda *a: self.L.kmx_count_unitig_graph(self.h, int(thr), *a))
+
+    def count_unitig_graph_dev(self, thr: int = 1):
+        """kmx_count_unitig_graph_dev: the same, the output as torch tensors on the model's device"""
+        return self._unitig_graph_dev(lambda *a: self.L.kmx_count_unitig_graph_dev(self.h, int(thr), *a))
+
+    def unitig_graph_phases(self) -> dict:
+        """kmx_unitig_graph_last_phases: unitigs_phases() plus "unitig_links", the seconds spent on the edges between unitigs"""
+        sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_graph_last_phases(self.h, sec, C.byref(rounds)))
+        return {**{n: sec[i] for i, n in enumerate(UNITIG_GRAPH_PHASES)}, "rounds": int(rounds.value)}
 
     # ---- persistence
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173

@@ -354,7 +354,9 @@ struct kmx_model {
 		DevBuf<unsigned char> d_seq;
 		DevBuf<u64> d_offs;
 		DevBuf<Unitig> d_rec;
-		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit
+		DevBuf<u64> d_loffs;                                       // the host variant's link_offsets and links (kmx_unitig_graph)
+		DevBuf<u32> d_links;
+		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit, links between unitigs
 		u64 rounds = 0;                                            // doubling rounds of the last call
 	} uni;
 };
@@ -3397,6 +3399,11 @@ extern "C" int kmx_unitigs(kmx_model *m, int k, const uint64_t *kmers, const uin
 extern "C" int kmx_count_unitigs(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_count_unitigs_impl(m, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out); }); }
 extern "C" int kmx_count_unitigs_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out) { return guarded([&] { return kmx_count_unitigs_dev_impl(m, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, n_unitigs, n_bases_out); }); }
 extern "C" int kmx_unitigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitigs_last_phases_impl(m, seconds, rounds); }); }
+extern "C" int kmx_unitig_graph_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_unitig_graph_dev_impl(m, k, d_kmers, d_counts, n, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
+extern "C" int kmx_unitig_graph(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_unitig_graph_impl(m, k, kmers, counts, n, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
+extern "C" int kmx_count_unitig_graph(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_count_unitig_graph_impl(m, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
+extern "C" int kmx_count_unitig_graph_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_count_unitig_graph_dev_impl(m, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
+extern "C" int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_graph_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

@@ -76,4 +76,7 @@ void unitig_round(const u64 *, const u32 *, u64 *, u32 *, u64, u32 *, hipStream_
 void unitig_cut(const UniDev &, const u64 *, const u32 *, u64 *, hipStream_t);
 hipError_t unitig_mark(const UniDev &, const u64 *, UniTot *, UniTot *, DevBuf<unsigned char> &tmp, hipStream_t);
 void unitig_emit(const UniDev &, const u64 *, const UniTot *, u64, unsigned char *, u64, u64 *, Unitig *, u64, hipStream_t);
+// ... and of kmx_unitig_graph: the link counts at the heads + their scan, the edges between oriented unitigs
+hipError_t unitig_link_mark(const UniDev &, const u64 *, const UniTot *, u64 *, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
+void unitig_link_emit(const UniDev &, const u64 *, const UniTot *, const u64 *, u64, u64 *, u64, u32 *, u64, hipStream_t);
 }   // namespace kmxk

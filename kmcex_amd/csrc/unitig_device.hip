@@ -1,4 +1,4 @@
-// unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*).  The host side that sizes the
+// unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*).  The host side that sizes the
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
@@ -68,6 +68,25 @@ void unitig_emit(const UniDev &d, const u64 *pair, const UniTot *sc, u64 n_uni, 
 	if (rec && nr) hipLaunchKernelGGL(k_uni_rec_init, dim3(nblk(nr)), dim3(256), 0, st, rec, nr);
 	if (d.W == 1) hipLaunchKernelGGL(k_uni_emit<1>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, sc, seq, seq_cap, offs, rec, rec_cap);
 	else hipLaunchKernelGGL(k_uni_emit<2>, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, sc, seq, seq_cap, offs, rec, rec_cap);
+}
+
+// per-head link counts into lc, then their exclusive scan: lsc[i] = the edges of the unitigs in front of entry i, lsc[n] the
+// total; the head and tail entry of every unitig into d.succ1 and d.pred1 (sc: the scanned marks)
+hipError_t unitig_link_mark(const UniDev &d, const u64 *pair, const UniTot *sc, u64 *lc, u64 *lsc, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_uni_lmark, dim3(nblk(d.n + 1)), dim3(256), 0, st, d, pair, sc, lc);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const u64 *)lc, lsc, (u64)0, (size_t)(d.n + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const u64 *)lc, lsc, (u64)0, (size_t)(d.n + 1), rocprim::plus<u64>(), st));
+	return hipGetLastError();
+}
+
+// the CSR of the edges between the 2 n_uni oriented unitigs, 8 lanes per unitig; nothing is written at or behind loffs[2 rec_cap + 1], links[link_cap]
+void unitig_link_emit(const UniDev &d, const u64 *pair, const UniTot *sc, const u64 *lsc, u64 n_uni, u64 *loffs, u64 rec_cap, u32 *links, u64 link_cap, hipStream_t st)
+{
+	if (d.W == 1) hipLaunchKernelGGL(k_uni_links<1>, dim3(nblk(8 * (n_uni + 1))), dim3(256), 0, st, d, pair, sc, lsc, n_uni, loffs, rec_cap, links, link_cap);
+	else hipLaunchKernelGGL(k_uni_links<2>, dim3(nblk(8 * (n_uni + 1))), dim3(256), 0, st, d, pair, sc, lsc, n_uni, loffs, rec_cap, links, link_cap);
 }
 
 }   // namespace kmxk

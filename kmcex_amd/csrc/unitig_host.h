@@ -7,6 +7,10 @@
 // again, then marks the heads and scans the marks: the number of unitigs and of their bytes reach the host.  unitig_emit writes
 // strings, offsets and records.  Between the halves the device variant checks the caller's capacities and the host variant
 // sizes its own output.  The work arrays stay on the handle by capacity; nothing here touches the model or the listing.
+//
+// kmx_unitig_graph*, kmx_count_unitig_graph* are the same calls with the edges between unitigs: the first half also counts the
+// edges at the heads and scans the counts (in the copy of the rank state the marks have left free, so no new work array), and
+// their total comes with the unitig totals in the same wait; the second half also writes link_offsets and links.
 static_assert(sizeof(kmx_unitig) == 40 && sizeof(Unitig) == 40, "kmx_unitig is 40 bytes");
 static_assert(offsetof(kmx_unitig, min_count) == offsetof(Unitig, min_count) && offsetof(kmx_unitig, first_node) == offsetof(Unitig, first_node) &&
               offsetof(kmx_unitig, circular) == offsetof(Unitig, circular) && offsetof(kmx_unitig, first_fwd) == offsetof(Unitig, first_fwd), "Unitig (kmx_types.h) is the layout of kmx_unitig");
@@ -38,13 +42,16 @@ struct UniClock {
 };
 
 // the first half, on a device-resident listing.  On KMX_OK *n_uni / *n_bytes are the output's sizes, U.d_pair[*cur] the final
-// rank state, U.d_mn the scanned marks, and *d is the view the second half takes.
-static int unitig_rank(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, UniDev *d, int *cur, u64 *n_uni, u64 *n_bytes)
+// rank state, U.d_mn the scanned marks, and *d is the view the second half takes.  n_links (null: no edges are asked for): the
+// number of edges between unitigs; U.d_pair[*cur ^ 1] + n + 1 then holds the scanned link counts, and U.d_succ1 / U.d_pred1
+// the head and the tail entry of every unitig.
+static int unitig_rank(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, UniDev *d, int *cur, u64 *n_uni, u64 *n_bytes, u64 *n_links = nullptr)
 {
 	auto &U = m->uni;
 	for (double &s : U.phase_s) s = 0;
 	U.rounds = 0;
 	*n_uni = *n_bytes = 0;
+	if (n_links) *n_links = 0;
 	*cur = 0;
 	if (!n) return KMX_OK;
 	int lg = 0;
@@ -105,8 +112,16 @@ static int unitig_rank(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u
 	HIPCHK(e);
 	UniTot tot{0, 0};
 	HIPCHK(hipMemcpyAsync(&tot, sc + n, sizeof tot, hipMemcpyDeviceToHost, st));
+	if (n_links) {                                                 // the marks' copy of the rank state is free again
+		clk.lap(3);
+		u64 *lc = U.d_pair[c ^ 1].get();
+		const hipError_t el = kmxk::unitig_link_mark(*d, U.d_pair[c], sc, lc, lc + n + 1, U.d_tmp, st);
+		if (el == hipErrorOutOfMemory) return uni_nomem();
+		HIPCHK(el);
+		HIPCHK(hipMemcpyAsync(n_links, lc + 2 * n + 1, 8, hipMemcpyDeviceToHost, st));
+	}
 	HIPCHK(hipStreamSynchronize(st));
-	clk.lap(3);
+	clk.lap(n_links ? 4 : 3);
 	*cur = c;
 	*n_uni = tot.n;
 	*n_bytes = tot.len;
@@ -122,6 +137,23 @@ static int unitig_emit(kmx_model *m, const UniDev &d, int cur, u64 n, u64 n_uni,
 	HIPCHK(hipGetLastError());
 	clk.lap(3);
 	return KMX_OK;
+}
+
+// the edges, beside the emit: enqueued, not awaited (unless the phase clock runs)
+static int unitig_link_emit(kmx_model *m, const UniDev &d, int cur, u64 n, u64 n_uni, u64 *d_loffs, u64 rec_cap, u32 *d_links, u64 link_cap)
+{
+	if (!n) { HIPCHK(hipMemsetAsync(d_loffs, 0, 8, m->stream)); return KMX_OK; }
+	UniClock clk(m);
+	kmxk::unitig_link_emit(d, m->uni.d_pair[cur], (const UniTot *)m->uni.d_mn.get(), m->uni.d_pair[cur ^ 1].get() + n + 1, n_uni, d_loffs, rec_cap, d_links, link_cap, m->stream);
+	HIPCHK(hipGetLastError());
+	clk.lap(4);
+	return KMX_OK;
+}
+
+static int uni_range(u64 nu, u64 nb, u64 nl, u64 rec_cap, u64 seq_cap, u64 link_cap)
+{
+	return fail(KMX_E_RANGE, "%llu unitigs of %llu bytes with %llu links, the buffers hold %llu, %llu and %llu", (unsigned long long)nu, (unsigned long long)nb, (unsigned long long)nl,
+	            (unsigned long long)rec_cap, (unsigned long long)seq_cap, (unsigned long long)link_cap);
 }
 
 static int unitigs_dev_core(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, char *d_seq_out, u64 seq_cap, u64 *d_offs_out, kmx_unitig *d_rec, u64 rec_cap,
@@ -220,12 +252,121 @@ static int kmx_count_unitigs_impl(kmx_model *m, uint32_t thr, char *seq_out, uin
 	return unitigs_host_core(m, C.k, C.d_run[1], C.d_runc[1], C.n_list, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, n_unitigs, n_bases_out);
 }
 
+// ---- kmx_unitig_graph*: the twins above with link_offsets [2 rec_cap + 1] and links [link_cap]
+static int unitig_graph_dev_core(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, char *d_seq_out, u64 seq_cap, u64 *d_offs_out, kmx_unitig *d_rec, u64 rec_cap,
+                                 u64 *d_loffs, u32 *d_links, u64 link_cap, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	if (!n_unitigs || !n_bases_out || !n_links) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = *n_links = 0;
+	TRY(unitig_args(k, n));
+	if ((n && (!d_km || !d_cnt)) || (d_seq_out && (!d_offs_out || !d_loffs || !d_links))) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	UniDev d{};
+	int cur = 0;
+	u64 nu = 0, nb = 0, nl = 0;
+	TRY(unitig_rank(m, k, d_km, d_cnt, n, thr, &d, &cur, &nu, &nb, &nl));
+	*n_unitigs = nu;
+	*n_bases_out = nb;
+	*n_links = nl;
+	if (!d_seq_out) return KMX_OK;                                 // the sizing call
+	if (nu > rec_cap || nb > seq_cap || nl > link_cap) return uni_range(nu, nb, nl, rec_cap, seq_cap, link_cap);
+	TRY(unitig_emit(m, d, cur, n, nu, (unsigned char *)d_seq_out, seq_cap, d_offs_out, (Unitig *)d_rec, rec_cap));
+	return unitig_link_emit(m, d, cur, n, nu, d_loffs, rec_cap, d_links, link_cap);
+}
+
+static int kmx_unitig_graph_dev_impl(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, char *d_seq_out, uint64_t seq_capacity,
+                                     uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity,
+                                     uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	if (!m) return fail(KMX_E_ARG, "null model");
+	return unitig_graph_dev_core(m, k, (const u64 *)d_kmers, d_counts, n, thr, d_seq_out, seq_capacity, (u64 *)d_offsets_out, d_rec, rec_capacity, (u64 *)d_link_offsets, d_links, link_capacity,
+	                             n_unitigs, n_bases_out, n_links);
+}
+
+static int unitig_graph_host_core(kmx_model *m, int k, const u64 *d_km, const u32 *d_cnt, u64 n, u32 thr, char *seq_out, u64 seq_cap, uint64_t *offs_out, kmx_unitig *rec, u64 rec_cap,
+                                  uint64_t *loffs_out, uint32_t *links_out, u64 link_cap, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	auto &U = m->uni;
+	UniDev d{};
+	int cur = 0;
+	u64 nu = 0, nb = 0, nl = 0;
+	TRY(unitig_rank(m, k, d_km, d_cnt, n, thr, &d, &cur, &nu, &nb, &nl));
+	*n_unitigs = nu;
+	*n_bases_out = nb;
+	*n_links = nl;
+	if (!seq_out) return KMX_OK;
+	if (nu > rec_cap || nb > seq_cap || nl > link_cap) return uni_range(nu, nb, nl, rec_cap, seq_cap, link_cap);
+	const hipStream_t st = m->stream;
+	if (U.d_seq.ensure(nb, st) != hipSuccess || U.d_offs.ensure(nu + 1, st) != hipSuccess || (rec && U.d_rec.ensure(nu, st) != hipSuccess) ||
+	    U.d_loffs.ensure(2 * nu + 1, st) != hipSuccess || U.d_links.ensure(nl, st) != hipSuccess)
+		return uni_nomem();
+	TRY(unitig_emit(m, d, cur, n, nu, U.d_seq, nb, U.d_offs, rec ? U.d_rec.get() : nullptr, nu));
+	TRY(unitig_link_emit(m, d, cur, n, nu, U.d_loffs, nu, U.d_links, nl));
+	if (nb) HIPCHK(hipMemcpyAsync(seq_out, U.d_seq, nb, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(offs_out, U.d_offs, (nu + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (rec && nu) HIPCHK(hipMemcpyAsync(rec, U.d_rec, nu * sizeof(Unitig), hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(loffs_out, U.d_loffs, (2 * nu + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (nl) HIPCHK(hipMemcpyAsync(links_out, U.d_links, nl * 4, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));
+	return KMX_OK;
+}
+
+static int kmx_unitig_graph_impl(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, char *seq_out, uint64_t seq_capacity,
+                                 uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity,
+                                 uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	if (!m || !n_unitigs || !n_bases_out || !n_links) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = *n_links = 0;
+	TRY(unitig_args(k, n));
+	if ((n && (!kmers || !counts)) || (seq_out && (!offsets_out || !link_offsets || !links))) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	auto &U = m->uni;
+	const u64 W = (u64)(k + 31) / 32;
+	if (n) {
+		if (U.d_km.ensure(n * W, m->stream) != hipSuccess || U.d_cnt.ensure(n, m->stream) != hipSuccess) return uni_nomem();
+		HIPCHK(hipMemcpyAsync(U.d_km, kmers, n * W * 8, hipMemcpyHostToDevice, m->stream));
+		HIPCHK(hipMemcpyAsync(U.d_cnt, counts, n * 4, hipMemcpyHostToDevice, m->stream));
+	}
+	return unitig_graph_host_core(m, k, U.d_km, U.d_cnt, n, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links);
+}
+
+static int kmx_count_unitig_graph_dev_impl(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity,
+                                           uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	TRY(count_unitigs_listing(m, "kmx_count_unitig_graph_dev"));
+	auto &C = m->cnt;
+	return unitig_graph_dev_core(m, C.k, C.d_run[1], C.d_runc[1], C.n_list, thr, d_seq_out, seq_capacity, (u64 *)d_offsets_out, d_rec, rec_capacity, (u64 *)d_link_offsets, d_links, link_capacity,
+	                             n_unitigs, n_bases_out, n_links);
+}
+
+static int kmx_count_unitig_graph_impl(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity,
+                                       uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links)
+{
+	TRY(count_unitigs_listing(m, "kmx_count_unitig_graph"));
+	if (!n_unitigs || !n_bases_out || !n_links || (seq_out && (!offsets_out || !link_offsets || !links))) return fail(KMX_E_ARG, "null argument");
+	*n_unitigs = *n_bases_out = *n_links = 0;
+	auto &C = m->cnt;
+	TRY(unitig_args(C.k, C.n_list));
+	HIPCHK(hipSetDevice(m->device));
+	return unitig_graph_host_core(m, C.k, C.d_run[1], C.d_runc[1], C.n_list, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links);
+}
+
 // seconds[4]: adjacency (with validation and the index), links, ranking, emit (with the marks and their scan) of the last call
 // on this handle, measured only under kmx_set_profile(m, 1); *rounds: its doubling rounds
 static int kmx_unitigs_last_phases_impl(kmx_model *m, double *seconds, uint64_t *rounds)
 {
 	if (!m || !seconds || !rounds) return fail(KMX_E_ARG, "null argument");
 	for (int i = 0; i < 4; i++) seconds[i] = m->uni.phase_s[i];
+	*rounds = m->uni.rounds;
+	return KMX_OK;
+}
+
+// seconds[5]: the four of kmx_unitigs_last_phases, then the links between unitigs (their counts and scan, the links kernel): 0
+// after a call that asked for no edges
+static int kmx_unitig_graph_last_phases_impl(kmx_model *m, double *seconds, uint64_t *rounds)
+{
+	if (!m || !seconds || !rounds) return fail(KMX_E_ARG, "null argument");
+	for (int i = 0; i < 5; i++) seconds[i] = m->uni.phase_s[i];
 	*rounds = m->uni.rounds;
 	return KMX_OK;
 }

@@ -19,6 +19,13 @@
 //                 has the smaller listing index; a single node as listed), whether it is the head, the unitig's length;
 //   k_uni_emit    per entry, after the scan of the marks: its bytes (all k at the head, the last one otherwise), its count into
 //                 the record with integer atomics, and at the head the rest of the record.
+// kmx_unitig_graph* add the edges between unitigs (the rule: include/kmx.h), after the ranking and beside the emit:
+//   k_uni_lmark   per entry: at a head, the edges that leave its unitig's two ends (n_pred + n_succ), to be scanned, and the
+//                 unitig's head and tail entry into two lists by unitig number;
+//   k_uni_links   a group of 8 lanes per unitig: lanes 0..3 append a base to the representative's last k-mer (the tail entry),
+//                 lanes 4..7 to the reverse complement of its first (the head entry); a neighbour that is found is the first
+//                 k-mer of one oriented unitig, whose number its own place gives; one ballot gives the slot.  Interior
+//                 entries are never visited.
 // No lane walks a path: the longest unitig costs rounds (log), never a loop.  Every store is checked against its capacity.
 #pragma once
 #include "device_common.h"
@@ -267,5 +274,76 @@ template <int W> __global__ __launch_bounds__(256) void k_uni_emit(UniDev d, con
 		R->n_pred = (unsigned char)uni_indeg(d.deg, q.h);
 		R->n_succ = (unsigned char)((tail >> 1) < d.n ? uni_outdeg(d.deg, tail) : 0);
 		R->first_fwd = (unsigned char)!(q.h & 1);
+	}
+}
+
+// ---- edges between unitigs.  An oriented unitig is 2 u + d: d = 0 as emitted, d = 1 its reverse complement.
+
+// thread i <= n (sc: the scanned marks): lc[i] = the edges out of both orientations of the unitig whose head is entry i, 0
+// elsewhere and at i = n; head_of[u], tail_of[u] = the head and the tail entry of unitig u.  The two lists take the place of
+// succ1 and pred1, which nothing reads once the ranks stand.
+__global__ __launch_bounds__(256) void k_uni_lmark(UniDev d, const u64 *pair, const UniTot *sc, u64 *lc)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	if (i > d.n) return;
+	u64 t = 0;
+	if (i < d.n && (d.deg[i] & UNI_DEG_NODE)) {
+		const UniPlace q = uni_place(pair, i);
+		const u32 tail = q.hm ^ 1u;
+		if (q.r == 0 && (q.h >> 1) < d.n && (tail >> 1) < d.n) {
+			t = uni_indeg(d.deg, q.h) + uni_outdeg(d.deg, tail);
+			const u64 u = sc[i].n;
+			if (u < d.n) { d.succ1[u] = (u32)i; d.pred1[u] = tail >> 1; }
+		}
+	}
+	lc[i] = t;
+}
+
+// 8 lanes per unitig u <= n_uni (sc: the scanned marks, lsc: the scanned counts of k_uni_lmark; lsc[n] the total; head_of and
+// tail_of: d.succ1 and d.pred1 as k_uni_lmark left them).  Lanes 0..3 append c to the tail entry's k-mer as it lies on the
+// representative: the row of 2 u, which starts at lsc[head of u]; lanes 4..7 to the reverse complement of the head entry's:
+// the row of 2 u + 1, behind the n_succ edges of the other.  loffs[2 rec_cap + 1], links[link_cap]; the group of u = n_uni
+// writes the last offset.
+template <int W> __global__ __launch_bounds__(256) void k_uni_links(UniDev d, const u64 *pair, const UniTot *sc, const u64 *lsc, u64 n_uni, u64 *loffs, u64 rec_cap, u32 *links, u64 link_cap)
+{
+	const u64 g = (u64)blockIdx.x * 256 + threadIdx.x, u = g >> 3;
+	const u32 l = threadIdx.x & 7, c = l & 3;
+	bool hit = false;
+	u32 to = 0;
+	u64 row = 0;
+	const u32 head = u < n_uni && u < d.n ? d.succ1[u] : UNI_NONE;
+	const u32 i = head == UNI_NONE ? UNI_NONE : l < 4 ? d.pred1[u] : head;
+	if (i < d.n && head < d.n && (d.deg[i] & UNI_DEG_NODE)) {
+		const UniPlace q = uni_place(pair, i);
+		const u32 tail = q.hm ^ 1u;
+		const bool mine = (q.h >> 1) == head && (l < 4 ? q.r + 1 == q.m : q.r == 0);
+		if (mine && (tail >> 1) < d.n) {
+			const u32 ns = uni_outdeg(d.deg, tail);
+			row = lsc[head] + (l < 4 ? 0 : ns);
+			if (l == 4 && 2 * u + 1 <= 2 * rec_cap) { loffs[2 * u] = row - ns; loffs[2 * u + 1] = row; }
+			// the entry as the source's last k-mer: on the representative for d = 0, on its mirror for d = 1
+			UniK x = uni_load<W>(d.km, i);
+			if ((q.s != 0) != (l >= 4)) x = uni_rc(x, d.k);
+			if (l < 4 ? uni_outdeg(d.deg, 2 * i + q.s) : uni_outdeg(d.deg, 2 * i + (q.s ^ 1u))) {
+				const UniK y = uni_succ(x, d.k, c), r = uni_rc(y, d.k);
+				const bool fwd = !uni_less(r, y);
+				const u32 j = uni_find<W>(d, fwd ? y : r);
+				if (j != UNI_NONE && (d.deg[j] & UNI_DEG_NODE)) {
+					// y starts its oriented unitig: the representative of j's unitig if y is j's orientation there, else its mirror
+					const UniPlace p = uni_place(pair, j);
+					if ((p.h >> 1) < d.n) {
+						hit = true;
+						to = (u32)(2 * sc[p.h >> 1].n) + ((fwd ? 0u : 1u) == p.s ? 0u : 1u);
+					}
+				}
+			}
+		}
+	}
+	const u64 b = __ballot(hit);
+	const u32 m4 = (u32)(b >> ((threadIdx.x & 56) + (l & 4))) & 0xFu;  // the 4 lanes of this row
+	if (u == n_uni && l == 0 && 2 * n_uni <= 2 * rec_cap) loffs[2 * n_uni] = lsc[d.n];
+	if (hit) {
+		const u64 o = row + __popc(m4 & ((1u << c) - 1u));
+		if (o < link_cap) links[o] = to;
 	}
 }

@@ -6,7 +6,9 @@ checks: the device variant's bytes equal the host variant's on the whole input, 
 of `--slice` bases both equal the plain-Python restatement of the rule (tests/unitigs_ref.py).  Then, for thr = 1 and thr = 3, warmed,
 the median of 5 calls with [min, max]: seconds, nodes/s and unitigs/s, the N50 of the unitigs, and (from one further call under
 set_profile(1), where every phase waits for the stream) the seconds per phase -- adjacency, links, ranking with its round
-count, emit.  Yardsticks that are not the code under test: kmx_query_packed_dev's k-mers/s on the same 8 n neighbour k-mers
+count, emit.  Beside each of these, on the same listing and interleaved call by call with the above, kmx_count_unitig_graph_dev
+(the same with the edges between unitigs): its seconds and nodes/s, n_links, and links_s, the seconds of its links phase under
+set_profile(1); the slice check covers its link_offsets and links (tests/unitig_links_ref.py).  Yardsticks that are not the code under test: kmx_query_packed_dev's k-mers/s on the same 8 n neighbour k-mers
 (the model answers the same 8 questions per node, inexactly), and the same session's kmx_count_finish time.
 usage: python tools/bench_unitigs.py [--genome 100000000] [--coverage 10] [--slice 20000]"""
 import argparse
@@ -81,17 +83,22 @@ def main():
     sb, sn = make_reads(a.slice, a.coverage, L, seed=6)
     sreads = [sb[i * L:(i + 1) * L].tobytes().decode() for i in range(sn)]
     skm, scnt = U.listing_of(U.count_kmers(sreads, K))
-    ok_ref = True
+    import unitig_links_ref as UL
+    ok_ref = ok_links = True
     ms = KModel(1, 65535, a.nh, a.nb)
     ms.count_begin(K)
     ms.count_seqs(sb, np.arange(sn + 1, dtype=np.uint64) * np.uint64(L))
     ms.count_finish()
     for thr in (1, 3):
-        want = U.flat(*U.unitigs(skm, scnt, K, thr))
-        want = tuple(x.tobytes() for x in want)
+        sstrs, srecs = U.unitigs(skm, scnt, K, thr)
+        want = tuple(x.tobytes() for x in U.flat(sstrs, srecs))
+        wantg = want + tuple(x.tobytes() for x in UL.flat_links(UL.links(skm, scnt, K, thr, sstrs)))
+        ok_links = ok_links and tuple(np.asarray(x).tobytes() for x in ms.count_unitig_graph(thr)) == wantg
+        ok_links = ok_links and tuple(x.cpu().numpy().tobytes() for x in ms.count_unitig_graph_dev(thr)) == wantg
         got = ms.count_unitigs(thr)
         ok_ref = ok_ref and tuple(np.asarray(x).tobytes() for x in got) == want and from_dev(ms.count_unitigs_dev(thr)) == want
     res["slice_equals_reference"] = ok_ref
+    res["slice_links_equal_reference"] = ok_links
     del ms
 
     # the session
@@ -112,9 +119,12 @@ def main():
 
     # check 2: device variant == host variant on the whole input
     ok_host = True
-    nu, nb = C.c_uint64(0), C.c_uint64(0)
+    nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
     for thr in (1, 3):
+        gg = m.count_unitig_graph_dev(thr)
+        loff, lks = gg[3], gg[4]
         got = m.count_unitigs_dev(thr)
+        ok_host = ok_host and from_dev(gg[:3]) == from_dev(got)
         host = m.count_unitigs(thr)
         ok_host = ok_host and from_dev(got) == tuple(np.asarray(x).tobytes() for x in host)
         buf, off, rec = got
@@ -122,7 +132,10 @@ def main():
         lens = (off[1:] - off[:-1]).cpu().numpy()
         r["n50"] = n50(lens)
         r["nodes"] = int(lens.sum() - (K - 1) * len(lens))
-        times = []
+        r["n_links"] = int(lks.numel())
+        times, gtimes = [], []
+        graph_args = (m.h, thr, gg[0].data_ptr(), gg[0].numel(), gg[1].data_ptr(), gg[2].data_ptr(), gg[2].shape[0], loff.data_ptr(), lks.data_ptr(), lks.numel(),
+                      C.byref(nu), C.byref(nb), C.byref(nl))
         for it in range(6):                                        # the first call above warmed the buffers; one more, then 5
             torch.cuda.synchronize()
             t = time.perf_counter()
@@ -132,7 +145,17 @@ def main():
                 raise SystemExit(f"kmx_count_unitigs_dev failed: {rc}")
             if it:
                 times.append(time.perf_counter() - t)
+            torch.cuda.synchronize()                               # the graph call in turn with its twin
+            t = time.perf_counter()
+            rc = m.L.kmx_count_unitig_graph_dev(*graph_args)
+            torch.cuda.synchronize()
+            if rc:
+                raise SystemExit(f"kmx_count_unitig_graph_dev failed: {rc}")
+            if it:
+                gtimes.append(time.perf_counter() - t)
         r["seconds"] = med(times)
+        r["graph_seconds"] = med(gtimes)
+        r["graph_nodes_per_s"] = round(r["nodes"] / r["graph_seconds"][0])
         r["nodes_per_s"] = round(r["nodes"] / r["seconds"][0])
         r["unitigs_per_s"] = round(r["unitigs"] / r["seconds"][0])
         m.set_profile(1)
@@ -143,8 +166,16 @@ def main():
         ph = m.unitigs_phases()
         r["phase_s"] = {p: round(ph[p], 4) for p in ("adjacency", "links", "ranking", "emit")}
         r["rounds"] = ph["rounds"]
+        m.set_profile(1)
+        m.L.kmx_count_unitig_graph_dev(*graph_args)
+        torch.cuda.synchronize()
+        m.set_profile(0)
+        m.kernel_times(reset=True)
+        gph = m.unitig_graph_phases()
+        r["links_s"] = round(gph["unitig_links"], 4)
+        r["graph_phase_s"] = {p: round(gph[p], 4) for p in ("adjacency", "links", "ranking", "emit", "unitig_links")}
         res[f"thr{thr}"] = r
-        del got, buf, off, rec, host
+        del got, buf, off, rec, host, gg, loff, lks, graph_args
         torch.cuda.empty_cache()
     res["dev_equals_host"] = ok_host
 
@@ -169,7 +200,7 @@ def main():
     res["query_packed_dev_kmers_per_s"] = round(8 * n / res["query_packed_dev_8n_s"][0])
     res["adjacency_questions_per_s"] = round(8 * n / max(res["thr1"]["phase_s"]["adjacency"], 1e-9))
     print(json.dumps(res), flush=True)
-    sys.exit(0 if ok_ref and ok_host else 1)
+    sys.exit(0 if ok_ref and ok_links and ok_host else 1)
 
 
 if __name__ == "__main__":
