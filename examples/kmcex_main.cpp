@@ -7,6 +7,8 @@
 //          <working_directory>/<basename(output_file_name)>/unitigs.fa (KModel::count_unitigs)
 //     -G   with -u: also write the unitig graph (the unitigs and the edges between them) as GFA 1 to unitigs.gfa beside
 //          unitigs.fa (KModel::count_unitig_graph)
+//     -C<len>  with -u<thr>, thr >= 1: clean the graph first (tips, islands and bubbles of at most len k-mers, 2 k when omitted, at
+//          most 16 rounds; KModel::count_unitig_graph_clean): unitigs.fa, and unitigs.gfa with -G, then hold the cleaned graph
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -23,6 +25,7 @@ struct Params {
 	int k = 31, num_hash = 7, num_bit = 5, ci = 1, cs = 1023, t = 4;
 	bool gpu_count = false, gfa = false;
 	long unitig_thr = -1;                                          // -u: the threshold, -1 = no unitigs
+	long clean_len = -1;                                           // -C: the cap of tips and bubbles in k-mers, 0 = 2 k, -1 = no cleaning
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -40,6 +43,11 @@ static bool parse(int argc, char **argv, Params &p)
 		else if (!strncmp(a, "-k", 2)) p.k = atoi(a + 2);
 		else if (!strcmp(a, "-g")) p.gpu_count = true;
 		else if (!strcmp(a, "-G")) p.gfa = true;
+		else if (!strncmp(a, "-C", 2)) {
+			char *end = nullptr;
+			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
+			if (a[2] && (*end || p.clean_len < 1 || p.clean_len > 0xFFFFFFFFL)) return false;   // not a length
+		}
 		else if (!strncmp(a, "-u", 2)) {
 			char *end = nullptr;
 			p.unitig_thr = a[2] ? strtol(a + 2, &end, 10) : 1;
@@ -52,6 +60,7 @@ static bool parse(int argc, char **argv, Params &p)
 	p.workdir = argv[argc - 1];
 	if (p.unitig_thr >= 0 && (!p.gpu_count || !(p.k & 1))) return false;   // the unitigs come from the listing -g keeps; the rule needs an odd k
 	if (p.gfa && p.unitig_thr < 0) return false;                   // the graph is the unitigs' own
+	if (p.clean_len >= 0 && p.unitig_thr < 1) return false;        // cleaning removes nodes by "count below thr"
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -64,7 +73,8 @@ int main(int argc, char **argv)
 		             "       -k<len> (31) -t<threads> (4) -ci<min count> (1) -cs<max count> (1023) -nh<hashes> (7) -nb<arrays> (5)\n"
 		             "       -g  count the k-mers of the FASTQ / FASTA input on the GPU instead of running KMC\n"
 		             "       -u<thr>  with -g and an odd k: write the unitigs of the k-mers with count >= thr (1) to <saved model>/unitigs.fa\n"
-		             "       -G  with -u<thr>: also write the unitigs and the edges between them as GFA 1 to <saved model>/unitigs.gfa\n";
+		             "       -G  with -u<thr>: also write the unitigs and the edges between them as GFA 1 to <saved model>/unitigs.gfa\n"
+		             "       -C<len>  with -u<thr>, thr >= 1: clip tips, pop bubbles and drop islands of at most len k-mers (2 k) first\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -92,7 +102,15 @@ int main(int argc, char **argv)
 		std::vector<kmx_unitig> rec;
 		std::vector<uint64_t> link_offsets;
 		std::vector<uint32_t> links;
-		const std::vector<std::string> strs = p.gfa ? km->count_unitig_graph((uint32_t)p.unitig_thr, &rec, &link_offsets, &links) : km->count_unitigs((uint32_t)p.unitig_thr, &rec);
+		kmx_clean_stats cs;
+		const uint32_t cap = (uint32_t)(p.clean_len > 0 ? p.clean_len : 2 * p.k);
+		const kmx_clean_params cp = {KMX_CLEAN_TIPS | KMX_CLEAN_ISLANDS | KMX_CLEAN_BUBBLES, cap, cap, 16};
+		const std::vector<std::string> strs = p.clean_len >= 0 ? km->count_unitig_graph_clean((uint32_t)p.unitig_thr, cp, &rec, &link_offsets, &links, &cs)
+		                                      : p.gfa          ? km->count_unitig_graph((uint32_t)p.unitig_thr, &rec, &link_offsets, &links)
+		                                                       : km->count_unitigs((uint32_t)p.unitig_thr, &rec);
+		if (p.clean_len >= 0)
+			std::cout << "   cleaning (at most " << cap << " k-mers)        :     " << cs.rounds_run << " rounds" << (cs.converged ? "" : " (not converged)") << ", " << cs.n_tips << " tips, "
+			          << cs.n_islands << " islands, " << cs.n_bubbles << " bubbles, " << cs.n_kmers_removed << " k-mers removed; " << cs.n_unitigs_before << " unitigs before" << std::endl;
 		std::ofstream fa((dir + "/unitigs.fa").c_str());
 		KModel::write_unitigs_fasta(fa, strs, rec);
 		fa.close();

@@ -382,6 +382,49 @@ public:
 		if (links) links->swap(lk);
 		return split(bases, off);
 	}
+	// The cleaned unitig graph (the rule: kmx.h): count_unitig_graph / unitig_graph after tips, islands and bubbles have been
+	// removed round by round under params; stats (optional) receives what was removed, removed (optional) the round per listing
+	// entry.  write_unitigs_fasta and write_unitigs_gfa take the result as they take the twins'.
+	std::vector<std::string> count_unitig_graph_clean(uint32_t thr, const kmx_clean_params &params, std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets,
+	                                                  std::vector<uint32_t> *links, kmx_clean_stats *stats = 0)
+	{
+		uint64_t nu = 0, nb = 0, nl = 0;
+		check(kmx_count_unitig_graph_clean(h_, thr, &params, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl, 0, 0));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		std::vector<uint32_t> lk((size_t)nl + 1, 0);
+		check(kmx_count_unitig_graph_clean(h_, thr, &params, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl, 0, stats));
+		r.resize((size_t)nu);
+		lk.resize((size_t)nl);
+		if (rec) rec->swap(r);
+		if (link_offsets) link_offsets->swap(lo);
+		if (links) links->swap(lk);
+		return split(bases, off);
+	}
+	std::vector<std::string> unitig_graph_clean(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr, const kmx_clean_params &params,
+	                                            std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links, kmx_clean_stats *stats = 0,
+	                                            std::vector<uint8_t> *removed = 0)
+	{
+		uint64_t nu = 0, nb = 0, nl = 0;
+		const uint64_t n = counts.size();
+		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitig_graph_clean: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
+		check(kmx_unitig_graph_clean(h_, k, kmers.data(), counts.data(), n, thr, &params, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl, 0, 0));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		std::vector<uint32_t> lk((size_t)nl + 1, 0);
+		std::vector<uint8_t> rm((size_t)n + 1, 0);
+		check(kmx_unitig_graph_clean(h_, k, kmers.data(), counts.data(), n, thr, &params, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl, removed ? &rm[0] : 0, stats));
+		r.resize((size_t)nu);
+		lk.resize((size_t)nl);
+		rm.resize((size_t)n);
+		if (rec) rec->swap(r);
+		if (link_offsets) link_offsets->swap(lo);
+		if (links) links->swap(lk);
+		if (removed) removed->swap(rm);
+		return split(bases, off);
+	}
 	// the unitig graph as GFA 1: "H\tVN:Z:1.0", one "S\tu<index>\t<string>\tLN:i:<len>\tKC:i:<sum_count>" per unitig, and one
 	// "L\tu<a>\t<+|->\tu<b>\t<+|->\t<k-1>M" per mirror pair of edges: a -> b is written iff (a, b) <= (b ^ 1, a ^ 1) as pairs, so
 	// a self-mirror edge (a hairpin) once.  Rows follow the order of a, then the CSR order.

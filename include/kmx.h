@@ -561,8 +561,9 @@ int kmx_build_from_reads(kmx_model *m, int k, const char *input);
  *   Order: ascending listing index of canon(x_1).  Every node lies in exactly one unitig, so the order is total.
  * Every field of the record is an integer count, sum, minimum or maximum, and the result is a function of (listing, thr) alone:
  * byte-identical across runs and variants.
- * Out of scope: even k, n >= 2^31, tip clipping, bubble popping, unsorted (KMC2-order) listings (sort them first), unitigs
- * from the model's answers, several GPUs, choosing thr.  The edges between unitigs: kmx_unitig_graph below.            */
+ * Out of scope: even k, n >= 2^31, unsorted (KMC2-order) listings (sort them first), unitigs from the model's answers,
+ * several GPUs, choosing thr.  The edges between unitigs: kmx_unitig_graph below; tip clipping, bubble popping and the
+ * removal of islands: kmx_unitig_graph_clean below that.                                                                 */
 typedef struct kmx_unitig {              /* one per unitig; 40 bytes, no padding */
 	uint64_t n_kmers;                    /* m; the string has m + k - 1 bytes */
 	uint64_t sum_count;                  /* over its nodes, of the listing's counts */
@@ -636,7 +637,8 @@ int kmx_unitigs_last_phases(kmx_model *m, double *seconds /* [4] */, uint64_t *r
  * (the link counts and their scan, 16 bytes per entry, live in the copy of the rank state that the marks have left free, the
  * head and tail entry of every unitig in the two arrays of only-neighbours, which nothing reads once the ranks stand).  The
  * host variants stage 8 (2 U + 1) + 4 n_links bytes more for the two arrays.
- * Out of scope: tip clipping and bubble popping (they start from these edges), and what the unitig rule leaves out.       */
+ * Out of scope: what the unitig rule leaves out.  Tip clipping and bubble popping start from these edges:
+ * kmx_unitig_graph_clean below.                                                                                          */
 int kmx_unitig_graph_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr,
                          char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out /* [rec_capacity + 1] */, kmx_unitig *d_rec /* or NULL */, uint64_t rec_capacity,
                          uint64_t *d_link_offsets /* [2 * rec_capacity + 1] */, uint32_t *d_links, uint64_t link_capacity,
@@ -655,6 +657,82 @@ int kmx_count_unitig_graph_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint
  * the links kernel), 0 after a call that asked for none.  kmx_unitigs_last_phases reports its four as before, after old and
  * new calls alike.                                                                                                        */
 int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
+
+/* ---- cleaning the unitig graph: tips clipped, bubbles popped, islands dropped, round by round until nothing goes.  The input
+ * is that of kmx_unitig_graph (a strictly ascending canonical listing, odd k in [5, 63], n < 2^31) with
+ *   thr >= 1 (thr = 0 is KMX_E_ARG: a removed node is one whose count lies below thr);
+ *   ops, a non-empty subset of KMX_CLEAN_TIPS | KMX_CLEAN_ISLANDS | KMX_CLEAN_BUBBLES;
+ *   max_tip >= 1 and max_bubble >= 1, in k-mers; max_rounds in [1, KMX_CLEAN_MAX_ROUNDS]     (KMX_E_ARG otherwise).
+ * N_0 is the set of nodes of (listing, thr).  For round r = 1 .. max_rounds: G_r is the unitig graph of the node set N_(r-1) (U
+ * unitigs, their records, out[o] = the row of oriented unitig o), in[t] = { s ^ 1 : s in out[t ^ 1] }, and R_r the set of
+ * unitigs removed this round.  R_r empty: stop, converged = 1, the output is G_r.  Otherwise N_r = N_(r-1) minus every node of
+ * a unitig in R_r.  If round max_rounds still removed something, the output is the unitig graph of N_max_rounds and
+ * converged = 0.  A non-circular unitig u falls into at most one class, read from its record alone:
+ *   Island: n_pred == 0 && n_succ == 0 && n_kmers <= max_tip.  Removed iff ops & ISLANDS.
+ *   Short tip: short_tip[u] = !circular && n_kmers <= max_tip && (n_pred == 0) != (n_succ == 0).  Let o = 2u if n_succ > 0, else
+ *     2u + 1: the orientation that leaves through the attached end.  With ops & TIPS, u is removed iff EVERY t in out[o] has
+ *     some s in in[t] with s >> 1 != u and tip_beats[s >> 1, u], where tip_beats[w, u] holds iff !short_tip[w], or the pair
+ *     (n_kmers, sum_count) of w is lexicographically greater than u's, or the pairs are equal and w < u.
+ *   Arm: arm[u] = !circular && n_kmers <= max_bubble && n_pred == 1 && n_succ == 1.  Let b be the one entry of out[2u] and a the
+ *     one entry of out[2u + 1].  If b >> 1 == u or a >> 1 == u (a self-loop or a hairpin), u is not removed.  With
+ *     ops & BUBBLES, u is removed iff some p in in[b] satisfies all of: v = p >> 1 != u, arm[v], out[p] == {b},
+ *     out[p ^ 1] == {a}, and the pair (sum_count, n_kmers) of v is lexicographically greater than u's, or equal and v < u.
+ * Circular unitigs and unitigs longer than the caps are never removed.  Every decision of a round is taken on G_r alone, so the
+ * result is a function of (listing, thr, parameters): byte-identical across runs and variants.  Consequences:
+ *   1. No junction is orphaned: if t is an oriented unitig of a unitig that survives round r and in[t] was not empty, in[t]
+ *      still holds a survivor (the best-keyed competitor at a junction is never removed).
+ *   2. The uncleaned capacities always suffice: links between surviving nodes stay links, so unitigs only merge; U, the byte
+ *      count and n_links of the output never exceed those of kmx_unitig_graph on the same (listing, thr).
+ *   3. Original coordinates: first_node and all records are in the ORIGINAL listing's indices; sum / min / max_count are the
+ *      original counts.
+ *   4. A no-op is exact: with nothing to remove the output is byte for byte that of kmx_unitig_graph, rounds_run = 1,
+ *      converged = 1.
+ * Out of scope: bubbles whose arms hold more than one unitig; coverage-ratio or mean-coverage criteria and low-coverage edge
+ * removal; P / W lines; several GPUs; choosing thr and the caps.                                                          */
+#define KMX_CLEAN_TIPS        1
+#define KMX_CLEAN_ISLANDS     2
+#define KMX_CLEAN_BUBBLES     4
+#define KMX_CLEAN_MAX_ROUNDS 64
+typedef struct kmx_clean_params { uint32_t ops, max_tip, max_bubble, max_rounds; } kmx_clean_params;          /* 16 bytes */
+typedef struct kmx_clean_stats  { uint64_t rounds_run, converged, n_tips, n_islands, n_bubbles,
+                                  n_kmers_removed, n_unitigs_before, n_links_before; } kmx_clean_stats;       /* 64 bytes */
+/* The four calls take the arguments of their kmx_*unitig_graph* twins in the same order, with params (HOST) directly behind thr
+ * and, at the end, removed [n] or NULL (a DEVICE buffer in the _dev forms) and stats (HOST) or NULL.  removed[i] is the round
+ * (1-based) that removed entry i, 0 for an entry that survives or never was a node.  rounds_run counts the round that found
+ * nothing; n_unitigs_before / n_links_before are the counts of kmx_unitig_graph on the same (listing, thr).  The sizing call
+ * (seq_out == NULL; the counts are those of the CLEANED graph), KMX_E_RANGE, KMX_E_ARG, KMX_E_STATE, KMX_E_NOMEM, the
+ * build-class threading note and "nothing written on a short capacity" are the twins'; stats and the three counts are complete
+ * on KMX_E_RANGE, and removed, where given, counts as written (also by the sizing call).  The caller's counts, a session's
+ * listing and the model are never written: a following kmx_count_unitig_graph at the same thr returns what it did before.
+ * How it runs: a working copy of the counts (4 n bytes, kept on the handle) in which removal writes 0, so a round is the
+ * construction of the twin on (k-mers, working counts, thr), its records, link_offsets and links written into the handle's
+ * staging buffers (40 U + 8 (2 U + 1) + 8 (U + 1) + 4 n_links bytes, in the _dev forms too; no strings), one kernel that takes
+ * the verdicts (8 lanes per unitig: its record, its two rows, the rows of at most 4 targets, the records of at most 16
+ * competitors; U verdict bytes) and one per listing entry that zeroes the working counts.  Device memory beside the twin's:
+ * these 4 n + U bytes and the staging; the host variants stage removed (n bytes) when it is asked for.  Waits: those of the
+ * twin once per round, plus ONE per round for the round's four counters; the round that removes nothing is the final graph and
+ * is emitted from the rank state that stands.  When round max_rounds still removed something the construction runs once more. */
+int kmx_unitig_graph_clean_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, const kmx_clean_params *params /* HOST */,
+                               char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out /* [rec_capacity + 1] */, kmx_unitig *d_rec /* or NULL */, uint64_t rec_capacity,
+                               uint64_t *d_link_offsets /* [2 * rec_capacity + 1] */, uint32_t *d_links, uint64_t link_capacity,
+                               uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */, uint64_t *n_links /* HOST */,
+                               uint8_t *d_removed /* [n] or NULL */, kmx_clean_stats *stats /* HOST, or NULL */);
+int kmx_unitig_graph_clean(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, const kmx_clean_params *params,
+                           char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out /* [rec_capacity + 1] */, kmx_unitig *rec /* or NULL */, uint64_t rec_capacity,
+                           uint64_t *link_offsets /* [2 * rec_capacity + 1] */, uint32_t *links, uint64_t link_capacity,
+                           uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *removed /* [n] or NULL */, kmx_clean_stats *stats /* or NULL */);
+int kmx_count_unitig_graph_clean(kmx_model *m, uint32_t thr, const kmx_clean_params *params, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec,
+                                 uint64_t rec_capacity, uint64_t *link_offsets /* [2 * rec_capacity + 1] */, uint32_t *links, uint64_t link_capacity,
+                                 uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *removed /* [n] or NULL */, kmx_clean_stats *stats /* or NULL */);
+int kmx_count_unitig_graph_clean_dev(kmx_model *m, uint32_t thr, const kmx_clean_params *params /* HOST */, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out,
+                                     kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets /* [2 * rec_capacity + 1] */, uint32_t *d_links, uint64_t link_capacity,
+                                     uint64_t *n_unitigs /* HOST */, uint64_t *n_bases_out /* HOST */, uint64_t *n_links /* HOST */,
+                                     uint8_t *d_removed /* [n] or NULL */, kmx_clean_stats *stats /* HOST, or NULL */);
+/* the five figures of kmx_unitig_graph_last_phases summed over the rounds of the last cleaning call on the handle (a round's
+ * emit is the one into the staging buffers; the emit of the final graph into the caller's buffers is not added), then
+ * seconds[5] = the decisions and the removal; *rounds = its doubling rounds, summed likewise.  After a cleaning call the two
+ * older phase calls report these sums.                                                                                    */
+int kmx_unitig_clean_last_phases(kmx_model *m, double *seconds /* [6] */, uint64_t *rounds);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "kmx_count_begin", "kmx_count_seqs", "kmx_count_seqs_dev", "kmx_count_finish", "kmx_count_listing", "kmx_build_from_reads",
     "kmx_unitigs", "kmx_unitigs_dev", "kmx_count_unitigs", "kmx_count_unitigs_dev", "kmx_unitigs_last_phases",
     "kmx_unitig_graph", "kmx_unitig_graph_dev", "kmx_count_unitig_graph", "kmx_count_unitig_graph_dev", "kmx_unitig_graph_last_phases",
+    "kmx_unitig_graph_clean", "kmx_unitig_graph_clean_dev", "kmx_count_unitig_graph_clean", "kmx_count_unitig_graph_clean_dev", "kmx_unitig_clean_last_phases",
 ]
 
 
@@ -96,6 +97,19 @@ UNITIG_DTYPE = np.dtype([("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count",
                          ("circular", "u1"), ("n_pred", "u1"), ("n_succ", "u1"), ("first_fwd", "u1"), ("reserved", "u1", (4,))])
 UNITIG_PHASES = ["adjacency", "links", "ranking", "emit"]
 UNITIG_GRAPH_PHASES = UNITIG_PHASES + ["unitig_links"]
+UNITIG_CLEAN_PHASES = UNITIG_GRAPH_PHASES + ["clean"]
+CLEAN_TIPS, CLEAN_ISLANDS, CLEAN_BUBBLES = 1, 2, 4
+CLEAN_MAX_ROUNDS = 64
+
+
+class CleanParams(C.Structure):
+    """kmx_clean_params of include/kmx.h: 16 bytes"""
+    _fields_ = [("ops", C.c_uint32), ("max_tip", C.c_uint32), ("max_bubble", C.c_uint32), ("max_rounds", C.c_uint32)]
+
+
+class CleanStats(C.Structure):
+    """kmx_clean_stats of include/kmx.h: 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("rounds_run", "converged", "n_tips", "n_islands", "n_bubbles", "n_kmers_removed", "n_unitigs_before", "n_links_before")]
 
 
 class RingList(C.Structure):
@@ -227,6 +241,11 @@ def load_library():
     _sig(L, "kmx_count_unitig_graph", [vp, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
     _sig(L, "kmx_count_unitig_graph_dev", [vp, u32, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)])
     _sig(L, "kmx_unitig_graph_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
+    _sig(L, "kmx_unitig_graph_clean", [vp, i32, vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
+    _sig(L, "kmx_unitig_graph_clean_dev", [vp, i32, vp, vp, u64, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
+    _sig(L, "kmx_count_unitig_graph_clean", [vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
+    _sig(L, "kmx_count_unitig_graph_clean_dev", [vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
+    _sig(L, "kmx_unitig_clean_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -909,6 +928,88 @@ class KModel:
         sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
         _chk(self.L.kmx_unitig_graph_last_phases(self.h, sec, C.byref(rounds)))
         return {**{n: sec[i] for i, n in enumerate(UNITIG_GRAPH_PHASES)}, "rounds": int(rounds.value)}
+
+    # ---- cleaning the unitig graph: tips, islands and bubbles removed round by round (the rule: include/kmx.h)
+    @staticmethod
+    def _clean_params(k, ops, max_tip, max_bubble, max_rounds):
+        return CleanParams(int(ops), int(2 * k if max_tip is None else max_tip), int(2 * k if max_bubble is None else max_bubble), int(max_rounds))
+
+    def _unitig_clean_host(self, call, n):
+        """the sizing call, then the call with exact room -> the tuple of _unitig_graph_host + (uint8 removed [n], stats dict)"""
+        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        st = CleanStats()
+        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl), None, None))
+        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
+        off = np.zeros(nu.value + 1, dtype=np.uint64)
+        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
+        loff = np.zeros(2 * nu.value + 1, dtype=np.uint64)
+        links = np.empty(max(nl.value, 1), dtype=np.uint32)
+        removed = np.zeros(max(n, 1), dtype=np.uint8)
+        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, loff.ctypes.data, links.ctypes.data, nl.value,
+                  C.byref(nu), C.byref(nb), C.byref(nl), removed.ctypes.data, C.addressof(st)))
+        return buf[:nb.value], off, rec, loff, links[:nl.value], removed[:n], {f: int(getattr(st, f)) for f, _ in CleanStats._fields_}
+
+    def _unitig_clean_dev(self, call, n):
+        """the same on the model's device -> the torch tensors of _unitig_graph_dev + (uint8 removed [n], stats dict)"""
+        import torch
+        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        st = CleanStats()
+        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl), None, None))
+        dev = torch.device("cuda", self.stats().device)
+        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
+        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
+        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
+        loff = torch.zeros(2 * nu.value + 1, dtype=torch.int64, device=dev)
+        links = torch.empty(max(nl.value, 1), dtype=torch.int32, device=dev)
+        removed = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, loff.data_ptr(), links.data_ptr(), nl.value,
+                  C.byref(nu), C.byref(nb), C.byref(nl), removed.data_ptr(), C.addressof(st)))
+        return buf[:nb.value], off, rec, loff, links[:nl.value], removed[:n], {f: int(getattr(st, f)) for f, _ in CleanStats._fields_}
+
+    def unitig_graph_clean(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
+        """kmx_unitig_graph_clean: unitig_graph() after tips (CLEAN_TIPS), islands (CLEAN_ISLANDS) and bubbles (CLEAN_BUBBLES) of at
+        most max_tip / max_bubble k-mers (2 k when None) have been removed round by round -> (buf, offsets, rec, link_offsets,
+        links, removed, stats): removed[i] is the round that removed listing entry i (0: it stays), stats a dict of kmx_clean_stats"""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        n = counts.size
+        if kmers.size != n * ((int(k) + 31) // 32):
+            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
+        P = self._clean_params(int(k), ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_clean_host(lambda *a: self.L.kmx_unitig_graph_clean(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), C.addressof(P), *a), n)
+
+    def unitig_graph_clean_dev(self, d_kmers, d_counts, k: int, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
+        """kmx_unitig_graph_clean_dev on torch tensors of the model's device (as unitigs_dev) -> torch tensors and the stats dict"""
+        n = d_counts.numel()
+        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
+            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
+        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
+        P = self._clean_params(int(k), ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_clean_dev(lambda *a: self.L.kmx_unitig_graph_clean_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), C.addressof(P), *a), n)
+
+    def _count_listing_size(self):
+        n = C.c_uint64(0)
+        _chk(self.L.kmx_count_listing(self.h, None, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def count_unitig_graph_clean(self, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
+        """kmx_count_unitig_graph_clean: the cleaned unitig graph of the listing the last count_finish / init_reads kept"""
+        k = getattr(self, "_count_k", 0) or self.stats().k
+        P = self._clean_params(k, ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_clean_host(lambda *a: self.L.kmx_count_unitig_graph_clean(self.h, int(thr), C.addressof(P), *a), self._count_listing_size())
+
+    def count_unitig_graph_clean_dev(self, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
+        """kmx_count_unitig_graph_clean_dev: the same, the output as torch tensors on the model's device"""
+        k = getattr(self, "_count_k", 0) or self.stats().k
+        P = self._clean_params(k, ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_clean_dev(lambda *a: self.L.kmx_count_unitig_graph_clean_dev(self.h, int(thr), C.addressof(P), *a), self._count_listing_size())
+
+    def unitig_clean_phases(self) -> dict:
+        """kmx_unitig_clean_last_phases: unitig_graph_phases() summed over the rounds of the last cleaning call, plus "clean", the
+        seconds spent on the decisions and the removal"""
+        sec, rounds = (C.c_double * 6)(), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_clean_last_phases(self.h, sec, C.byref(rounds)))
+        return {**{n: sec[i] for i, n in enumerate(UNITIG_CLEAN_PHASES)}, "rounds": int(rounds.value)}
 
     # ---- persistence
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173

@@ -356,7 +356,10 @@ struct kmx_model {
 		DevBuf<Unitig> d_rec;
 		DevBuf<u64> d_loffs;                                       // the host variant's link_offsets and links (kmx_unitig_graph)
 		DevBuf<u32> d_links;
-		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit, links between unitigs
+		DevBuf<u32> d_wcnt;                                        // kmx_*unitig_graph_clean*: the working copy of the counts (a removed node's is 0), ...
+		DevBuf<unsigned char> d_verdict, d_removed;                // ... a verdict per unitig of the round, the host variant's removed[], ...
+		DevBuf<unsigned long long> d_cctr;                         // ... [4] tips, islands, bubbles, k-mers removed this round
+		double phase_s[6] = {0, 0, 0, 0, 0, 0};                    // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit, links between unitigs, cleaning (decisions and removal)
 		u64 rounds = 0;                                            // doubling rounds of the last call
 	} uni;
 };
@@ -3404,6 +3407,11 @@ extern "C" int kmx_unitig_graph(kmx_model *m, int k, const uint64_t *kmers, cons
 extern "C" int kmx_count_unitig_graph(kmx_model *m, uint32_t thr, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_count_unitig_graph_impl(m, thr, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
 extern "C" int kmx_count_unitig_graph_dev(kmx_model *m, uint32_t thr, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links) { return guarded([&] { return kmx_count_unitig_graph_dev_impl(m, thr, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links); }); }
 extern "C" int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_graph_last_phases_impl(m, seconds, rounds); }); }
+extern "C" int kmx_unitig_graph_clean_dev(kmx_model *m, int k, const uint64_t *d_kmers, const uint32_t *d_counts, uint64_t n, uint32_t thr, const kmx_clean_params *params, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *d_removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_unitig_graph_clean_dev_impl(m, k, d_kmers, d_counts, n, thr, params, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links, d_removed, stats); }); }
+extern "C" int kmx_unitig_graph_clean(kmx_model *m, int k, const uint64_t *kmers, const uint32_t *counts, uint64_t n, uint32_t thr, const kmx_clean_params *params, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_unitig_graph_clean_impl(m, k, kmers, counts, n, thr, params, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links, removed, stats); }); }
+extern "C" int kmx_count_unitig_graph_clean(kmx_model *m, uint32_t thr, const kmx_clean_params *params, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_count_unitig_graph_clean_impl(m, thr, params, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links, removed, stats); }); }
+extern "C" int kmx_count_unitig_graph_clean_dev(kmx_model *m, uint32_t thr, const kmx_clean_params *params, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *d_removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_count_unitig_graph_clean_dev_impl(m, thr, params, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links, d_removed, stats); }); }
+extern "C" int kmx_unitig_clean_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_clean_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

@@ -346,6 +346,16 @@ struct UniDev {
 	unsigned char *deg;          // [n]
 	u32 *err;                    // [1]: the listing is not strictly ascending, not canonical, or wider than 2k bits
 };
+// ... and the graph a cleaning round decides on (kmx_*unitig_graph_clean*): what the two emits wrote for the working counts.  A
+// verdict is 0 or the KMX_CLEAN_* bit of what removes the unitig.
+enum { UNI_CLEAN_TIPS = 1, UNI_CLEAN_ISLANDS = 2, UNI_CLEAN_BUBBLES = 4 };
+struct UniClean {
+	const Unitig *rec;           // [n_uni]
+	const u64 *loffs;            // [2 n_uni + 1]
+	const u32 *links;            // [n_links]
+	u64 n_uni, n_links;
+	u32 ops, max_tip, max_bubble;
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

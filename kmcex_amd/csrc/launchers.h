@@ -79,4 +79,7 @@ void unitig_emit(const UniDev &, const u64 *, const UniTot *, u64, unsigned char
 // ... and of kmx_unitig_graph: the link counts at the heads + their scan, the edges between oriented unitigs
 hipError_t unitig_link_mark(const UniDev &, const u64 *, const UniTot *, u64 *, u64 *, DevBuf<unsigned char> &tmp, hipStream_t);
 void unitig_link_emit(const UniDev &, const u64 *, const UniTot *, const u64 *, u64, u64 *, u64, u32 *, u64, hipStream_t);
+// ... and of kmx_unitig_graph_clean: a round's verdicts (one byte per unitig; the kind counters), the removal (the working counts, removed[], the k-mer counter)
+void unitig_clean(const UniClean &, unsigned char *, unsigned long long *, hipStream_t);
+void unitig_drop(const UniDev &, const u64 *, const UniTot *, const unsigned char *, u64, u32 *, unsigned char *, unsigned char, unsigned long long *, hipStream_t);
 }   // namespace kmxk

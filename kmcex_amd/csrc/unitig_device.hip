@@ -1,4 +1,4 @@
-// unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*).  The host side that sizes the
+// unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*, kmx_*unitig_graph_clean*).  The host side that sizes the
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
@@ -87,6 +87,18 @@ void unitig_link_emit(const UniDev &d, const u64 *pair, const UniTot *sc, const 
 {
 	if (d.W == 1) hipLaunchKernelGGL(k_uni_links<1>, dim3(nblk(8 * (n_uni + 1))), dim3(256), 0, st, d, pair, sc, lsc, n_uni, loffs, rec_cap, links, link_cap);
 	else hipLaunchKernelGGL(k_uni_links<2>, dim3(nblk(8 * (n_uni + 1))), dim3(256), 0, st, d, pair, sc, lsc, n_uni, loffs, rec_cap, links, link_cap);
+}
+
+// one verdict byte per unitig of the graph the two emits wrote (c), the three kind counters into cnt[0..2]
+void unitig_clean(const UniClean &c, unsigned char *verdict, unsigned long long *cnt, hipStream_t st)
+{
+	if (c.n_uni) hipLaunchKernelGGL(k_uni_clean, dim3(nblk(8 * c.n_uni)), dim3(256), 0, st, c, verdict, cnt);
+}
+
+// the working counts of the unitigs with a verdict to 0, their entries' round into removed (may be null), their number into cnt[3]
+void unitig_drop(const UniDev &d, const u64 *pair, const UniTot *sc, const unsigned char *verdict, u64 n_uni, u32 *wcnt, unsigned char *removed, unsigned char round, unsigned long long *cnt, hipStream_t st)
+{
+	if (d.n) hipLaunchKernelGGL(k_uni_drop, dim3(nblk(d.n)), dim3(256), 0, st, d, pair, sc, verdict, n_uni, wcnt, removed, round, cnt);
 }
 
 }   // namespace kmxk

@@ -347,3 +347,115 @@ template <int W> __global__ __launch_bounds__(256) void k_uni_links(UniDev d, co
 		if (o < link_cap) links[o] = to;
 	}
 }
+
+// ---- cleaning (kmx_*unitig_graph_clean*; the rule: include/kmx.h).  A round reads the records and the CSR the two emits have
+// written for the working counts, takes one verdict per unitig, and zeroes the working counts of the unitigs that go.
+//   k_uni_clean   a group of 8 lanes per unitig: its record, its two rows, the rows of at most 4 targets and the records of at
+//                 most 16 competitors; one verdict byte per unitig (0, or the KMX_CLEAN_* bit of what removes it) and, per wave,
+//                 one integer atomic per kind (ballot + popcount);
+//   k_uni_drop    per entry: a node's unitig number from its place and the scanned marks, as in k_uni_emit; a set verdict
+//                 zeroes the working count, stores the round, and counts the k-mer (one atomic per wave).
+// No lane walks a unitig.
+__device__ __forceinline__ bool uni_short_tip(const Unitig &r, u32 max_tip) { return !r.circular && r.n_kmers <= max_tip && (r.n_pred == 0) != (r.n_succ == 0); }
+__device__ __forceinline__ bool uni_arm(const Unitig &r, u32 max_bubble) { return !r.circular && r.n_kmers <= max_bubble && r.n_pred == 1 && r.n_succ == 1; }
+// entry e of the row of oriented unitig o, or UNI_NONE where the row is shorter (or anything lies outside the arrays)
+__device__ __forceinline__ u32 uni_row_at(const UniClean &c, u64 o, u32 e)
+{
+	if (o >= 2 * c.n_uni) return UNI_NONE;
+	const u64 a = c.loffs[o], b = c.loffs[o + 1];
+	if (a + e >= b || a + e >= c.n_links) return UNI_NONE;
+	const u32 t = c.links[a + e];
+	return t < 2 * c.n_uni ? t : UNI_NONE;
+}
+
+// 8 lanes per unitig u < n_uni.  A tip: lane l looks at target l >> 1 of the attached end's row and at entries 2 (l & 1) and
+// 2 (l & 1) + 1 of in(target); the target is answered when one of its two lanes found a competitor that beats u.  An arm: lanes
+// 0..3 look at one entry of in(b) each.  cnt[3]: tips, islands, bubbles of this round.
+// The records and the CSR are the ones the two emits of this round have just written on the same stream, so a row count outside
+// [1, 4], an offset behind n_links or a target behind 2 U cannot occur; the checks only keep every access inside the arrays.
+// Where one fails the lane finds no competitor, so the verdict falls to "stays": a damaged CSR would remove too little and
+// never read or write out of bounds, and it raises no error of its own.
+__global__ __launch_bounds__(256) void k_uni_clean(UniClean c, unsigned char *verdict, unsigned long long *cnt)
+{
+	const u64 g = (u64)blockIdx.x * 256 + threadIdx.x, u = g >> 3;
+	const u32 l = threadIdx.x & 7;
+	bool ok = false;
+	u32 kind = 0, n_tgt = 0;
+	if (u < c.n_uni) {
+		const Unitig r = c.rec[u];
+		if (r.circular) kind = 0;
+		else if (r.n_pred == 0 && r.n_succ == 0) kind = r.n_kmers <= c.max_tip ? UNI_CLEAN_ISLANDS : 0;
+		else if (uni_short_tip(r, c.max_tip)) {
+			kind = UNI_CLEAN_TIPS;
+			const u64 o = r.n_succ > 0 ? 2 * u : 2 * u + 1;
+			n_tgt = r.n_succ > 0 ? r.n_succ : r.n_pred;
+			const u32 t = uni_row_at(c, o, l >> 1);
+			if (t != UNI_NONE) {
+				for (u32 e = 2 * (l & 1); e < 2 * (l & 1) + 2; e++) {
+					const u32 s1 = uni_row_at(c, t ^ 1u, e);
+					if (s1 == UNI_NONE) continue;
+					const u64 w = (s1 ^ 1u) >> 1;
+					if (w == u) continue;
+					const Unitig q = c.rec[w];
+					ok = ok || !uni_short_tip(q, c.max_tip) || q.n_kmers > r.n_kmers || (q.n_kmers == r.n_kmers && (q.sum_count > r.sum_count || (q.sum_count == r.sum_count && w < u)));
+				}
+			}
+		}
+		else if (uni_arm(r, c.max_bubble)) {
+			kind = UNI_CLEAN_BUBBLES;
+			const u32 b = uni_row_at(c, 2 * u, 0), a = uni_row_at(c, 2 * u + 1, 0);
+			if (b != UNI_NONE && a != UNI_NONE && (b >> 1) != u && (a >> 1) != u && l < 4) {
+				const u32 p1 = uni_row_at(c, b ^ 1u, l);
+				if (p1 != UNI_NONE) {
+					const u32 p = p1 ^ 1u;
+					const u64 v = p >> 1;
+					if (v != u) {
+						const Unitig q = c.rec[v];
+						ok = uni_arm(q, c.max_bubble) && uni_row_at(c, p, 0) == b && uni_row_at(c, p ^ 1u, 0) == a &&
+						     (q.sum_count > r.sum_count || (q.sum_count == r.sum_count && (q.n_kmers > r.n_kmers || (q.n_kmers == r.n_kmers && v < u))));
+					}
+				}
+			}
+		}
+	}
+	const u64 bal = __ballot(ok);
+	const u32 m8 = (u32)(bal >> (threadIdx.x & 56)) & 0xFFu;     // the 8 lanes of this unitig
+	bool go = false;
+	if (kind == UNI_CLEAN_ISLANDS) go = true;
+	else if (kind == UNI_CLEAN_TIPS) {
+		go = n_tgt >= 1 && n_tgt <= 4;
+		for (u32 j = 0; j < n_tgt && j < 4; j++) go = go && ((m8 >> (2 * j)) & 3u) != 0;
+	}
+	else if (kind == UNI_CLEAN_BUBBLES) go = m8 != 0;
+	if (!(kind & c.ops)) go = false;
+	const u32 v = go ? kind : 0u;
+	if (u < c.n_uni && l == 0) verdict[u] = (unsigned char)v;
+	const u64 bt = __ballot(l == 0 && v == UNI_CLEAN_TIPS), bi = __ballot(l == 0 && v == UNI_CLEAN_ISLANDS), bb = __ballot(l == 0 && v == UNI_CLEAN_BUBBLES);
+	if ((threadIdx.x & 63) == 0) {
+		if (bt) atomicAdd(cnt + 0, (unsigned long long)__popcll(bt));
+		if (bi) atomicAdd(cnt + 1, (unsigned long long)__popcll(bi));
+		if (bb) atomicAdd(cnt + 2, (unsigned long long)__popcll(bb));
+	}
+}
+
+// thread i < n (sc: the scanned marks).  wcnt[n]: the working counts d.cnt views; removed[n] may be null; cnt[3]: the k-mers
+// removed this round
+__global__ __launch_bounds__(256) void k_uni_drop(UniDev d, const u64 *pair, const UniTot *sc, const unsigned char *verdict, u64 n_uni, u32 *wcnt, unsigned char *removed, unsigned char round,
+                                                  unsigned long long *cnt)
+{
+	const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+	bool go = false;
+	if (i < d.n && (d.deg[i] & UNI_DEG_NODE)) {
+		const UniPlace q = uni_place(pair, i);
+		if ((q.h >> 1) < d.n) {
+			const u64 u = sc[q.h >> 1].n;
+			go = u < n_uni && verdict[u] != 0;
+		}
+	}
+	if (go) {
+		wcnt[i] = 0;
+		if (removed) removed[i] = round;
+	}
+	const u64 b = __ballot(go);
+	if ((threadIdx.x & 63) == 0 && b) atomicAdd(cnt + 3, (unsigned long long)__popcll(b));
+}
