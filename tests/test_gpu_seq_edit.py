@@ -460,6 +460,7 @@ def test_allocation_failures(k, monkeypatch):
     buf, off = R.flatten(reads)
     w_ed, w_rec, _ = E.oracle_edit(o, buf, off, k, 1, 1, 7)
     assert w_rec["n_sites"].sum() > 100                            # (at k = 55 the two strands of a k-mer hash apart: sites are tried, none is fixed)
+    # (edits that ARE made at k > 32, on models of as-asked listings: tests/test_gpu_two_word_seqs.py)
     assert k > 32 or (len(w_ed) > 50 and w_rec["n_del"].sum() > 10 and w_rec["n_ins"].sum() > 10)
 
     def fresh():

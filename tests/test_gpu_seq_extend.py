@@ -136,6 +136,7 @@ def test_two_words_and_small_k():
             print("k55 thr", thr, "depth", depth, X.tallies(want[1]))
     # (above k = 32 the reference canonicalises through one word, so most windows of a genome are not found again and the
     # walks are short: the CPU oracle appends 284 bases to these seeds at thr = ci, depth 2)
+    # (walks that run on and look ahead at k = 32 ... 64, on models of as-asked listings: tests/test_gpu_two_word_seqs.py)
     assert X.tallies(_gpu_rule(m, buf, offsets, k, ci, 200, 2)[1])["n_ext"] >= 200
     for name in ("k4_full", "k4_part", "k5_part", "k7_part", "k9", "k13"):
         _, k, ci, cs, nh, nb, _, seed = SK.CASE[name]
