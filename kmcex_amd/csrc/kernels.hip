@@ -1778,11 +1778,21 @@ template <int W, int NHM> __global__ __launch_bounds__(256) void k_reorder(Model
 
 // ------------------------------------------------------------------------------------------ partitioned bit-set: the sweep
 // One workgroup per bin: the bin's slice of the filter is swept tile by tile (2^20 positions in LDS); a tile collects
-// its bits with LDS atomics and is OR-ed back with coalesced whole-word accesses.  Only this workgroup writes these
-// words during the launch (producers that met a full bin used atomics in EARLIER launches).
+// its bits with LDS atomics and is OR-ed back with coalesced accesses.  Only this workgroup writes these words during
+// the launch (producers that met a full bin used atomics in EARLIER launches).
+// The sweep is a stream: a lane loads BS_SWEEP_LOADS x 16 bytes of the bin's tuples before it consumes the first (64 KB
+// in flight per CU at 4); the filter words of the tile are requested before the barrier that ends the tile, eight loads per
+// lane, and OR-ed back 16 bytes per lane.
+#define BS_SWEEP_LOADS 4                                         // (2 and 8 measured 6 % slower, profiles/bitset_sweep_ab.txt)
+#define BS_TILE_VECS (BS_TILE_WORDS / 4 / 1024)                  // 16-byte pieces of a whole tile per thread
+__device__ __forceinline__ void bs_tile_or(u32 *s_tile, u32 o, u32 t0, u32 tw)
+{
+	const u32 w = (o >> 5) - t0;
+	if (w < tw) atomicOr(&s_tile[w], 1u << (o & 31));             // (o >> 5) < t0 wraps to a huge value: skipped too
+}
 __global__ __launch_bounds__(1024) void k_bs_apply(BitScatter bs)
 {
-	__shared__ u32 s_tile[BS_TILE_WORDS];
+	__shared__ __align__(16) u32 s_tile[BS_TILE_WORDS];
 	const u32 TW = 1u << (bs.tlog2 - 5);                             // words per tile (BS_TILE_WORDS outside the test hook)
 	const u32 b = blockIdx.x;
 	u32 cnt = (u32)bs.cnt[b];
@@ -1793,20 +1803,74 @@ __global__ __launch_bounds__(1024) void k_bs_apply(BitScatter bs)
 	const u32 nw = (u32)((bs.nwords - word0) < wpb ? (bs.nwords - word0) : wpb);
 	const u32 *tup = bs.tup + (u64)b * bs.cap;
 	u32 *words = bs.words + word0;
+	// the bin's tuples: `head` single ones up to the first 16-byte boundary (the capacity need not be a multiple of 4), nvec
+	// pieces of four, the last cnt - head - 4 nvec single again; nothing at or beyond cnt is read
+	u32 head = (u32)((16 - ((uintptr_t)tup & 15)) & 15) >> 2;
+	if (head > cnt) head = cnt;
+	const u32 nvec = (cnt - head) >> 2, nedge = cnt - 4 * nvec;      // nedge = head + tail <= 6
+	const uint4 *tup4 = (const uint4 *)(tup + head);
+	// the bin's words: 16 bytes per lane when the bin starts on a 16-byte boundary -- every tile then does, TW >= 32 --, the
+	// last nw & 3 words of a partial bin one by one; a bin of 1 or 2 words (wshift 5, 6) has no boundary to offer
+	const bool wide = ((uintptr_t)words & 15) == 0;
+	uint4 *s_tile4 = (uint4 *)s_tile;
+	for (u32 i = threadIdx.x, n4 = ((nw < TW ? nw : TW) + 3) >> 2; i < n4; i += 1024) s_tile4[i] = make_uint4(0, 0, 0, 0);
+	__syncthreads();
 	for (u32 t0 = 0; t0 < nw; t0 += TW) {
-		const u32 tw = nw - t0 < TW ? nw - t0 : TW;
-		for (u32 w = threadIdx.x; w < tw; w += 1024) s_tile[w] = 0;
-		__syncthreads();
-		for (u32 q = threadIdx.x; q < cnt; q += 1024) {
-			const u32 o = tup[q], w = (o >> 5) - t0;
-			if (w < tw) atomicOr(&s_tile[w], 1u << (o & 31));         // (o >> 5) < t0 wraps to a huge value: skipped too
+		const u32 tw = nw - t0 < TW ? nw - t0 : TW, tw4 = wide ? tw >> 2 : 0;
+		const bool more = t0 + TW < nw;
+		uint4 *words4 = (uint4 *)(words + t0);
+		for (u32 base = 0; base < nvec; base += 1024 * BS_SWEEP_LOADS) {
+			uint4 v[BS_SWEEP_LOADS];
+#pragma unroll
+			for (int j = 0; j < BS_SWEEP_LOADS; j++) {               // every load before the first atomic; beyond the end: the last piece again, unused
+				const u32 i = base + j * 1024 + threadIdx.x;
+				v[j] = tup4[i < nvec ? i : nvec - 1];
+			}
+#pragma unroll
+			for (int j = 0; j < BS_SWEEP_LOADS; j++)
+				if (base + j * 1024 + threadIdx.x < nvec) {
+					bs_tile_or(s_tile, v[j].x, t0, tw);
+					bs_tile_or(s_tile, v[j].y, t0, tw);
+					bs_tile_or(s_tile, v[j].z, t0, tw);
+					bs_tile_or(s_tile, v[j].w, t0, tw);
+				}
+		}
+		if (threadIdx.x < nedge) bs_tile_or(s_tile, tup[threadIdx.x < head ? threadIdx.x : 4 * nvec + threadIdx.x], t0, tw);
+		// OR the tile back: what the filter holds there is requested before the barrier, every piece of a thread at once
+		uint4 old[BS_TILE_VECS], x[BS_TILE_VECS];
+#pragma unroll
+		for (int j = 0; j < BS_TILE_VECS; j++) {
+			const u32 i = j * 1024 + threadIdx.x;
+			old[j] = make_uint4(0, 0, 0, 0);
+			if (i < tw4) old[j] = words4[i];
 		}
 		__syncthreads();
-		for (u32 w = threadIdx.x; w < tw; w += 1024) {
-			const u32 x = s_tile[w];
-			if (x) words[t0 + w] |= x;
+#pragma unroll
+		for (int j = 0; j < BS_TILE_VECS; j++) {
+			const u32 i = j * 1024 + threadIdx.x;
+			x[j] = make_uint4(0, 0, 0, 0);
+			if (i < tw4) x[j] = s_tile4[i];
 		}
-		__syncthreads();
+#pragma unroll
+		for (int j = 0; j < BS_TILE_VECS; j++)                       // (x is zero beyond the tile)
+			if (x[j].x | x[j].y | x[j].z | x[j].w)
+				words4[j * 1024 + threadIdx.x] = make_uint4(old[j].x | x[j].x, old[j].y | x[j].y, old[j].z | x[j].z, old[j].w | x[j].w);
+		// a thread clears what it has read for the next tile (whose words are no more than this one's)
+		if (more) {
+#pragma unroll
+			for (int j = 0; j < BS_TILE_VECS; j++) {
+				const u32 i = j * 1024 + threadIdx.x;
+				if (i < tw4) s_tile4[i] = make_uint4(0, 0, 0, 0);
+			}
+		}
+		for (u32 w = 4 * tw4 + threadIdx.x; w < tw; w += 1024) {
+			const u32 y = s_tile[w];
+			if (y) {
+				words[t0 + w] |= y;
+				if (more) s_tile[w] = 0;
+			}
+		}
+		if (more) __syncthreads();
 	}
 	if (threadIdx.x == 0) bs.cnt[b] = 0;
 }
