@@ -9,6 +9,9 @@
 //          unitigs.fa (KModel::count_unitig_graph)
 //     -C<len>  with -u<thr>, thr >= 1: clean the graph first (tips, islands and bubbles of at most len k-mers, 2 k when omitted, at
 //          most 16 rounds; KModel::count_unitig_graph_clean): unitigs.fa, and unitigs.gfa with -G, then hold the cleaned graph
+//     -M   with -u<thr>: read the input a second time (plain FASTA / FASTQ, not gzip, not @list) and map its reads onto the
+//          unitigs written (KModel::count_unitig_map_begin, seq_to_unitigs): reads.paths.tsv (read, start in read, windows,
+//          unitig, strand, offset) and unitigs.hits.tsv (unitig, mapped windows) beside unitigs.fa
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -23,7 +26,7 @@
 
 struct Params {
 	int k = 31, num_hash = 7, num_bit = 5, ci = 1, cs = 1023, t = 4;
-	bool gpu_count = false, gfa = false;
+	bool gpu_count = false, gfa = false, map = false;
 	long unitig_thr = -1;                                          // -u: the threshold, -1 = no unitigs
 	long clean_len = -1;                                           // -C: the cap of tips and bubbles in k-mers, 0 = 2 k, -1 = no cleaning
 	std::string input, output, workdir = "/tmp";
@@ -43,6 +46,7 @@ static bool parse(int argc, char **argv, Params &p)
 		else if (!strncmp(a, "-k", 2)) p.k = atoi(a + 2);
 		else if (!strcmp(a, "-g")) p.gpu_count = true;
 		else if (!strcmp(a, "-G")) p.gfa = true;
+		else if (!strcmp(a, "-M")) p.map = true;
 		else if (!strncmp(a, "-C", 2)) {
 			char *end = nullptr;
 			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
@@ -61,7 +65,37 @@ static bool parse(int argc, char **argv, Params &p)
 	if (p.unitig_thr >= 0 && (!p.gpu_count || !(p.k & 1))) return false;   // the unitigs come from the listing -g keeps; the rule needs an odd k
 	if (p.gfa && p.unitig_thr < 0) return false;                   // the graph is the unitigs' own
 	if (p.clean_len >= 0 && p.unitig_thr < 1) return false;        // cleaning removes nodes by "count below thr"
+	if (p.map && p.unitig_thr < 0) return false;                   // the reads are mapped onto the unitigs written
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
+}
+
+// the next reads of a plain FASTA (records may span lines) or FASTQ (four lines each) stream, up to about max_bases of them
+static bool next_reads(std::istream &in, std::vector<std::string> &reads, size_t max_bases)
+{
+	reads.clear();
+	size_t bases = 0;
+	std::string line, seq;
+	while (bases < max_bases && in.peek() != EOF) {
+		if (!std::getline(in, line)) break;
+		if (!line.empty() && line[line.size() - 1] == '\r') line.erase(line.size() - 1);
+		if (line.empty()) continue;
+		if (line[0] == '@') {
+			if (!std::getline(in, seq)) return false;
+			if (!seq.empty() && seq[seq.size() - 1] == '\r') seq.erase(seq.size() - 1);
+			if (!std::getline(in, line) || line.empty() || line[0] != '+' || !std::getline(in, line)) return false;
+		} else if (line[0] == '>') {
+			seq.clear();
+			while (in.peek() != EOF && in.peek() != '>') {
+				if (!std::getline(in, line)) break;
+				if (!line.empty() && line[line.size() - 1] == '\r') line.erase(line.size() - 1);
+				seq += line;
+			}
+		} else
+			return false;
+		bases += seq.size();
+		reads.push_back(seq);
+	}
+	return true;
 }
 
 int main(int argc, char **argv)
@@ -74,7 +108,8 @@ int main(int argc, char **argv)
 		             "       -g  count the k-mers of the FASTQ / FASTA input on the GPU instead of running KMC\n"
 		             "       -u<thr>  with -g and an odd k: write the unitigs of the k-mers with count >= thr (1) to <saved model>/unitigs.fa\n"
 		             "       -G  with -u<thr>: also write the unitigs and the edges between them as GFA 1 to <saved model>/unitigs.gfa\n"
-		             "       -C<len>  with -u<thr>, thr >= 1: clip tips, pop bubbles and drop islands of at most len k-mers (2 k) first\n";
+		             "       -C<len>  with -u<thr>, thr >= 1: clip tips, pop bubbles and drop islands of at most len k-mers (2 k) first\n"
+		             "       -M  with -u<thr>: map the reads of the (plain FASTA / FASTQ) input onto the unitigs: reads.paths.tsv, unitigs.hits.tsv\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -122,6 +157,34 @@ int main(int argc, char **argv)
 			gf.close();
 			if (!gf) { std::cout << "could not write " << dir << "/unitigs.gfa" << std::endl; return 1; }
 			std::cout << "   edges between unitigs                :     " << links.size() << std::endl;
+		}
+		if (p.map) {
+			std::ifstream in(p.input.c_str());
+			const int c0 = in.peek();
+			if (!in || p.input[0] == '@' || (c0 != '>' && c0 != '@')) { std::cout << "-M reads a plain FASTA / FASTQ file, which " << p.input << " is not" << std::endl; return 1; }
+			std::ofstream paths((dir + "/reads.paths.tsv").c_str());
+			std::vector<uint64_t> hits(strs.size(), 0), seg_offsets;
+			std::vector<std::string> reads;
+			uint64_t n_reads = 0, n_segs = 0, n_win = 0, n_mapped = 0;
+			km->count_unitig_map_begin(strs);
+			for (bool ok = true; in.peek() != EOF;) {
+				ok = next_reads(in, reads, size_t(1) << 26);
+				if (!ok) { std::cout << p.input << " is no FASTA / FASTQ file at read " << n_reads + reads.size() << std::endl; return 1; }
+				std::vector<kmx_seq_map> rec_m;
+				const std::vector<kmx_map_segment> segs = km->seq_to_unitigs(reads, &seg_offsets, &rec_m, &hits);
+				std::vector<uint64_t> off(reads.size() + 1, 0);
+				for (size_t i = 0; i < reads.size(); i++) { off[i + 1] = off[i] + reads[i].size(); n_win += rec_m[i].n_windows; n_mapped += rec_m[i].n_mapped; }
+				KModel::write_paths_tsv(paths, segs, seg_offsets, off, n_reads);
+				n_reads += reads.size();
+				n_segs += segs.size();
+			}
+			km->unitig_map_end();
+			paths.close();
+			std::ofstream ht((dir + "/unitigs.hits.tsv").c_str());
+			KModel::write_hits_tsv(ht, hits);
+			ht.close();
+			if (!paths || !ht) { std::cout << "could not write " << dir << "/reads.paths.tsv or unitigs.hits.tsv" << std::endl; return 1; }
+			std::cout << "   reads mapped onto the unitigs        :     " << n_reads << " reads, " << n_segs << " segments, " << n_mapped << " of " << n_win << " windows" << std::endl;
 		}
 	}
 	delete km;

@@ -441,6 +441,55 @@ public:
 			}
 	}
 
+	// Reads mapped onto the unitigs (the rule: kmx.h): a session on the object.  unitig_map_begin takes a listing (packed canonical
+	// k-mers, strictly ascending, odd k) and a unitig set as any of the calls above returns it; count_unitig_map_begin works on the
+	// listing init_reads / the last kmx_count_finish kept.  seq_to_unitigs maps a batch of reads: the segments in ascending
+	// position, seg_offsets [n + 1] their CSR by read, rec one kmx_seq_map per read, and hits, which it ADDS the mapped windows
+	// per unitig to (the caller sizes it to the unitig set and zeroes it).  It gives room for every window, so it never comes back
+	// short; a caller who can bound the segments calls kmx_unitig_map_seqs itself.
+	void unitig_map_begin(const std::vector<uint64_t> &kmers, int k, const std::vector<std::string> &unitigs)
+	{
+		const Flat f(unitigs);
+		const uint64_t W = (uint64_t)((k + 31) / 32);
+		if (kmers.size() % W) { std::cout << "unitig_map_begin: " << kmers.size() << " words are no whole k-mers" << std::endl; exit(1); }
+		check(kmx_unitig_map_begin(h_, k, kmers.data(), kmers.size() / W, f.bases.data(), f.off.data(), unitigs.size()));
+	}
+	void count_unitig_map_begin(const std::vector<std::string> &unitigs)
+	{
+		const Flat f(unitigs);
+		check(kmx_count_unitig_map_begin(h_, f.bases.data(), f.off.data(), unitigs.size()));
+	}
+	std::vector<kmx_map_segment> seq_to_unitigs(const std::vector<std::string> &seqs, std::vector<uint64_t> *seg_offsets = 0, std::vector<kmx_seq_map> *rec = 0, std::vector<uint64_t> *hits = 0)
+	{
+		const Flat f(seqs);
+		std::vector<kmx_map_segment> segs((size_t)f.off.back() + 1);
+		std::vector<uint64_t> so(seqs.size() + 1, 0);
+		std::vector<kmx_seq_map> r(seqs.size() + 1);
+		uint64_t n = 0;
+		check(kmx_unitig_map_seqs(h_, f.bases.data(), f.off.data(), seqs.size(), &segs[0], f.off.back(), &n, &so[0], &r[0], hits && !hits->empty() ? &(*hits)[0] : 0));
+		segs.resize((size_t)n);
+		r.resize(seqs.size());
+		if (seg_offsets) seg_offsets->swap(so);
+		if (rec) rec->swap(r);
+		return segs;
+	}
+	void unitig_map_end() { check(kmx_unitig_map_end(h_)); }
+	// the segments as a table, one "<read>\t<start in read>\t<windows>\tu<unitig>\t<+|->\t<offset>" per segment; first_read is the
+	// index of the batch's first read and offsets [n + 1] the batch's own (a segment's pos is flat inside its batch) ...
+	static void write_paths_tsv(std::ostream &out, const std::vector<kmx_map_segment> &segs, const std::vector<uint64_t> &seg_offsets, const std::vector<uint64_t> &offsets, uint64_t first_read = 0)
+	{
+		for (size_t i = 0; i + 1 < seg_offsets.size() && i + 1 < offsets.size(); i++)
+			for (uint64_t e = seg_offsets[i]; e < seg_offsets[i + 1] && e < segs.size(); e++) {
+				const kmx_map_segment &s = segs[(size_t)e];
+				out << first_read + i << "\t" << s.pos - offsets[i] << "\t" << s.n_windows << "\tu" << (s.o >> 1) << "\t" << ((s.o & 1) ? '-' : '+') << "\t" << s.off << "\n";
+			}
+	}
+	// ... and the hits, one "u<unitig>\t<hits>" per unitig
+	static void write_hits_tsv(std::ostream &out, const std::vector<uint64_t> &hits)
+	{
+		for (size_t u = 0; u < hits.size(); u++) out << "u" << u << "\t" << hits[u] << "\n";
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -734,6 +734,83 @@ int kmx_count_unitig_graph_clean_dev(kmx_model *m, uint32_t thr, const kmx_clean
  * older phase calls report these sums.                                                                                    */
 int kmx_unitig_clean_last_phases(kmx_model *m, double *seconds /* [6] */, uint64_t *rounds);
 
+/* ---- mapping reads onto the unitigs: where every window of a read lies in the graph, as runs along oriented unitigs.
+ * The index.  Input: a listing of n packed canonical k-mers, strictly ascending, odd k in [5, 63], n < 2^31 (the conditions of
+ *   kmx_unitigs; counts are not needed), and a set of U sequences in the layout of kmx_query_seqs (useq, uoffsets); sequence u
+ *   has m_u = len_u - k + 1 >= 1 windows.  Window j of sequence u, the k bytes y, gives entry idx(canon(y)) the PLACE (u, j, f),
+ *   f = 0 iff y is canonical.  The set is valid iff every byte is uppercase ACGT, every window is a listed k-mer, and no entry
+ *   receives two places; anything else is KMX_E_ARG, found on the device (a compare-and-swap from "no place" that raises an
+ *   error word) without ever leaving the buffers.  An entry that receives no place has none: a thresholded-out or cleaned-away
+ *   k-mer.  The output of every kmx_*unitigs*, kmx_*unitig_graph* and kmx_*unitig_graph_clean* call on that listing is a valid set.
+ * A window.  Reads are in the layout of kmx_query_seqs; bases follow the COUNTING rule (ACGT and acgt are bases, every other
+ *   byte is not; windows never span two sequences).  The window x at flat position p is MAPPED iff its k bytes are bases and
+ *   canon(x) has a place (u, j, f).  With d = f ^ (x is not canonical) it lies on oriented unitig o = 2 u + d, the o of
+ *   kmx_unitig_graph, at offset off = j for d = 0 and m_u - 1 - j for d = 1: one base further along the read inside a unitig is
+ *   off + 1 in either orientation.
+ * Segments.  Window p STARTS a segment iff it is mapped and it is the first window of its read, or p - 1 is unmapped, or
+ *   o(p - 1) != o(p), or off(p - 1) + 1 != off(p); it ENDS one under the mirror condition on p + 1.  A segment is the record below;
+ *   segments are listed in ascending pos, and seg_offsets[n_seqs + 1] is their CSR by read.  Going once round a circular unitig
+ *   starts a new segment at off = 0.
+ * Every decision looks at one window and its neighbour, so the list is a function of (listing, unitig set, reads) alone:
+ * byte-identical across runs, variants and piece sizes.  Consequences:
+ *   (a) for every segment, the bytes [off, off + n_windows + k - 1) of the oriented unitig string are the read's bytes
+ *       [pos, pos + n_windows + k - 1), upper-cased;
+ *   (b) with the unitig set of kmx_count_unitigs(thr = 1) of a session with ci = 1 whose counts stay below cs, and the reads
+ *       that were counted: n_mapped is the number of counted windows of every read, and hits[u] == rec[u].sum_count;
+ *   (c) on a cleaned graph, a window whose k-mer is listed is unmapped exactly when its entry has removed[i] != 0 or a count
+ *       below thr.
+ * Out of scope: even k; mismatches or indels between read and graph (a read with an error maps on both sides of it, with a
+ * gap of unmapped windows between: polish first); joining segments across gaps; GFA P / W lines (a read starts and ends
+ * mid-unitig, which those lines cannot say); paired reads; several GPUs.                                                  */
+typedef struct kmx_map_segment {         /* 24 bytes, no padding */
+	uint64_t pos;                        /* flat position of its first window */
+	uint32_t n_windows;
+	uint32_t o;                          /* 2 u + d */
+	uint32_t off;                        /* of the window at pos */
+	uint32_t reserved;                   /* 0 */
+} kmx_map_segment;
+typedef struct kmx_seq_map {             /* one per read; 64 bytes */
+	uint64_t n_windows;                  /* max(len - k + 1, 0) */
+	uint64_t n_mapped;
+	uint64_t n_segments;
+	uint64_t n_gaps;                     /* mapped windows whose predecessor in the read exists and is unmapped, the first mapped window not counted */
+	uint64_t first_mapped, last_mapped;  /* window indices inside the read; both n_windows when nothing maps */
+	uint64_t longest;                    /* the largest n_windows of its segments, 0 if none */
+	uint64_t reserved;                   /* 0 */
+} kmx_seq_map;
+/* A session on the handle, in the style of kmx_count_begin / _seqs / _finish; it needs no built model.  begin borrows the
+ * caller's DEVICE listing d_kmers[n * W], which must stay valid and unchanged until kmx_unitig_map_end; the unitig set is read
+ * during begin only.  It builds a bucket index of the listing (4 to 8 bytes per entry), the place table (8 bytes per entry:
+ * u << 32 | f << 31 | j, all ones for none) and m_u (4 U bytes), and waits once, for the error words.  A begin inside a session
+ * ends that session first; a begin that fails leaves none.  Build-class calls (see the threading note of kmx_query_packed). */
+int kmx_unitig_map_begin_dev(kmx_model *m, int k, const uint64_t *d_kmers, uint64_t n, const char *d_useq, const uint64_t *d_uoffsets /* [n_unitigs + 1] */,
+                             uint64_t n_unitigs, uint64_t n_ubases);
+/* the same on HOST buffers: the listing is uploaded and the session keeps its own copy (uoffsets are checked on the host) */
+int kmx_unitig_map_begin(kmx_model *m, int k, const uint64_t *kmers, uint64_t n, const char *useq, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs);
+/* the same two on the listing the last kmx_count_finish kept, read where it lies: KMX_E_STATE when there is none, KMX_E_ARG for
+ * an even session k.  Whatever drops that listing (kmx_count_begin, a build from other data, kmx_destroy) ends the session.   */
+int kmx_count_unitig_map_begin(kmx_model *m, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs);
+int kmx_count_unitig_map_begin_dev(kmx_model *m, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases);
+/* One batch of reads.  segs[capacity] receives the segments, *n_segs (HOST in both forms) their number, seg_offsets
+ * [n_seqs + 1] the CSR, rec[n_seqs] the records (or NULL), and hits[n_unitigs] (or NULL) is ADDED to: hits[u] += the mapped
+ * windows on unitig u in either orientation, so a caller accumulates over batches and zeroes the array itself.  segs == NULL:
+ * the sizing call.  More segments than capacity: KMX_E_RANGE; *n_segs is the number needed, seg_offsets, records and hits are
+ * complete, the content of segs is unspecified and nothing is written at or behind segs[capacity]; capacity = n_bases always
+ * suffices.  The host form checks the offsets (KMX_E_ARG); the _dev form clamps them where they are read, exactly as
+ * kmx_query_seqs_dev does, so bad offsets give wrong segments and never an access outside the buffers.  Outside a session:
+ * KMX_E_STATE.  KMX_E_NOMEM leaves the handle and the session usable.  n_seqs == 0: KMX_OK, nothing written.  Reads without
+ * bases: empty records, all-zero seg_offsets.  Device memory beside the index: 20 bytes per window of a chunk of 2^22 windows
+ * plus the scan's scratch, whatever n_bases is; the host form also stages its output there.  The _dev form enqueues everything
+ * on the model's stream and waits once, for *n_segs; the host form sends the bases through the handle's pinned slots in pieces
+ * of one chunk (so it shares them with the query calls: one such call at a time) and only segments, offsets, records and hits
+ * come back.                                                                                                              */
+int kmx_unitig_map_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, kmx_map_segment *segs /* or NULL */, uint64_t capacity, uint64_t *n_segs,
+                        uint64_t *seg_offsets /* [n_seqs + 1] */, kmx_seq_map *rec /* or NULL */, uint64_t *hits /* [n_unitigs] or NULL */);
+int kmx_unitig_map_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, kmx_map_segment *d_segs /* or NULL */, uint64_t capacity,
+                            uint64_t *n_segs /* HOST */, uint64_t *d_seg_offsets /* [n_seqs + 1] */, kmx_seq_map *d_rec /* or NULL */, uint64_t *d_hits /* [n_unitigs] or NULL */);
+/* ends the session and frees its index; KMX_E_STATE outside one */
+int kmx_unitig_map_end(kmx_model *m);
+
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);
 /* get_model(save_dir) = header parse + KModel::load                        kmodel.hpp:680-696, :209-235

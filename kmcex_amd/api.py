@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "kmx_unitigs", "kmx_unitigs_dev", "kmx_count_unitigs", "kmx_count_unitigs_dev", "kmx_unitigs_last_phases",
     "kmx_unitig_graph", "kmx_unitig_graph_dev", "kmx_count_unitig_graph", "kmx_count_unitig_graph_dev", "kmx_unitig_graph_last_phases",
     "kmx_unitig_graph_clean", "kmx_unitig_graph_clean_dev", "kmx_count_unitig_graph_clean", "kmx_count_unitig_graph_clean_dev", "kmx_unitig_clean_last_phases",
+    "kmx_unitig_map_begin", "kmx_unitig_map_begin_dev", "kmx_count_unitig_map_begin", "kmx_count_unitig_map_begin_dev", "kmx_unitig_map_seqs", "kmx_unitig_map_seqs_dev", "kmx_unitig_map_end",
 ]
 
 
@@ -110,6 +111,21 @@ class CleanParams(C.Structure):
 class CleanStats(C.Structure):
     """kmx_clean_stats of include/kmx.h: 64 bytes"""
     _fields_ = [(f, C.c_uint64) for f in ("rounds_run", "converged", "n_tips", "n_islands", "n_bubbles", "n_kmers_removed", "n_unitigs_before", "n_links_before")]
+
+
+class MapSegment(C.Structure):
+    """kmx_map_segment of include/kmx.h: a run of a read's windows along one oriented unitig, 24 bytes"""
+    _fields_ = [("pos", C.c_uint64), ("n_windows", C.c_uint32), ("o", C.c_uint32), ("off", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class SeqMap(C.Structure):
+    """kmx_seq_map of include/kmx.h: one per read, 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_windows", "n_mapped", "n_segments", "n_gaps", "first_mapped", "last_mapped", "longest", "reserved")]
+
+
+# the same two as NumPy structured dtypes (what KModel.seq_to_unitigs returns)
+SEQ_SEGMENT_DTYPE = np.dtype([("pos", "<u8"), ("n_windows", "<u4"), ("o", "<u4"), ("off", "<u4"), ("reserved", "<u4")])
+SEQ_MAP_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_mapped", "n_segments", "n_gaps", "first_mapped", "last_mapped", "longest", "reserved")])
 
 
 class RingList(C.Structure):
@@ -246,6 +262,13 @@ def load_library():
     _sig(L, "kmx_count_unitig_graph_clean", [vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
     _sig(L, "kmx_count_unitig_graph_clean_dev", [vp, u32, vp, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64), vp, vp])
     _sig(L, "kmx_unitig_clean_last_phases", [vp, C.POINTER(C.c_double), C.POINTER(u64)])
+    _sig(L, "kmx_unitig_map_begin", [vp, i32, vp, u64, vp, vp, u64])
+    _sig(L, "kmx_unitig_map_begin_dev", [vp, i32, vp, u64, vp, vp, u64, u64])
+    _sig(L, "kmx_count_unitig_map_begin", [vp, vp, vp, u64])
+    _sig(L, "kmx_count_unitig_map_begin_dev", [vp, vp, vp, u64, u64])
+    _sig(L, "kmx_unitig_map_seqs", [vp, vp, vp, u64, vp, u64, C.POINTER(u64), vp, vp, vp])
+    _sig(L, "kmx_unitig_map_seqs_dev", [vp, vp, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp, vp])
+    _sig(L, "kmx_unitig_map_end", [vp])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -1012,6 +1035,77 @@ class KModel:
         return {**{n: sec[i] for i, n in enumerate(UNITIG_CLEAN_PHASES)}, "rounds": int(rounds.value)}
 
     # ---- persistence
+    # ---- mapping reads onto the unitigs (the rule: include/kmx.h): a session on the handle, begin .. seq_to_unitigs .. end
+    def unitig_map_begin(self, kmers: np.ndarray, k: int, ubuf: np.ndarray, uoffsets: np.ndarray) -> None:
+        """kmx_unitig_map_begin: the index of a listing (packed canonical k-mers, strictly ascending, odd k in [5, 63]) and a
+        unitig set (ubuf, uoffsets) in seq_to_occ_flat's layout, as any of the unitig calls returns it.  Needs no built model."""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        W = (int(k) + 31) // 32
+        if kmers.size % W:
+            raise KmxError(-1, f"{kmers.size} words are no whole k-mers at k = {k}")
+        ubuf, uoffsets = _flat_seqs(ubuf, uoffsets)
+        _chk(self.L.kmx_unitig_map_begin(self.h, int(k), kmers.ctypes.data, kmers.size // W, ubuf.ctypes.data, uoffsets.ctypes.data, uoffsets.size - 1))
+        self._map_units = uoffsets.size - 1
+
+    def unitig_map_begin_dev(self, d_kmers, k: int, d_ubuf, d_uoffsets) -> None:
+        """kmx_unitig_map_begin_dev on torch tensors of the model's device; d_kmers is borrowed until unitig_map_end (keep it alive)"""
+        n = d_kmers.numel() // ((int(k) + 31) // 32)
+        _chk(self.L.kmx_unitig_map_begin_dev(self.h, int(k), d_kmers.data_ptr(), n, d_ubuf.data_ptr(), d_uoffsets.data_ptr(), d_uoffsets.numel() - 1, d_ubuf.numel()))
+        self._map_units = d_uoffsets.numel() - 1
+        self._map_listing = d_kmers
+
+    def count_unitig_map_begin(self, ubuf: np.ndarray, uoffsets: np.ndarray) -> None:
+        """kmx_count_unitig_map_begin: the same on the listing the last count_finish / init_reads kept, read where it lies"""
+        ubuf, uoffsets = _flat_seqs(ubuf, uoffsets)
+        _chk(self.L.kmx_count_unitig_map_begin(self.h, ubuf.ctypes.data, uoffsets.ctypes.data, uoffsets.size - 1))
+        self._map_units = uoffsets.size - 1
+
+    def count_unitig_map_begin_dev(self, d_ubuf, d_uoffsets) -> None:
+        """kmx_count_unitig_map_begin_dev: the unitig set as torch tensors on the model's device"""
+        _chk(self.L.kmx_count_unitig_map_begin_dev(self.h, d_ubuf.data_ptr(), d_uoffsets.data_ptr(), d_uoffsets.numel() - 1, d_ubuf.numel()))
+        self._map_units = d_uoffsets.numel() - 1
+
+    def unitig_map_end(self) -> None:
+        _chk(self.L.kmx_unitig_map_end(self.h))
+        self._map_listing = None
+
+    def seq_to_unitigs_flat(self, buf: np.ndarray, offsets: np.ndarray, capacity=None, records: bool = True, hits=None):
+        """kmx_unitig_map_seqs on (uint8 bases, uint64 offsets [n_seqs + 1]) -> (SEQ_SEGMENT_DTYPE segments, uint64 seg_offsets
+        [n_seqs + 1], SEQ_MAP_DTYPE records [n_seqs] or None).  hits (uint64 [n_unitigs], optional) is ADDED to.  capacity None:
+        room for every window, so the call never comes back short; a number: that many segments (KmxError KMX_E_RANGE when short)."""
+        buf, offsets = _flat_seqs(buf, offsets)
+        n_seqs = offsets.size - 1
+        cap = int(offsets[-1]) if capacity is None else int(capacity)
+        segs = np.zeros(cap, dtype=SEQ_SEGMENT_DTYPE)
+        so = np.zeros(n_seqs + 1, dtype=np.uint64)
+        rec = np.zeros(n_seqs, dtype=SEQ_MAP_DTYPE) if records else None
+        if hits is not None and (hits.dtype != np.uint64 or not hits.flags.c_contiguous or hits.size < getattr(self, "_map_units", 0)):
+            raise KmxError(-1, "hits must be a contiguous uint64 array with one entry per unitig")
+        ns = C.c_uint64(0)
+        _chk(self.L.kmx_unitig_map_seqs(self.h, buf.ctypes.data, offsets.ctypes.data, n_seqs, segs.ctypes.data, cap, C.byref(ns), so.ctypes.data,
+                                        rec.ctypes.data if records else None, hits.ctypes.data if hits is not None else None))
+        return segs[:ns.value].copy(), so, rec
+
+    def seq_to_unitigs(self, seqs, hits=None):
+        """the same for a str / bytes read or a list of them -> (segments, seg_offsets, records)"""
+        _, _, buf, offsets = _join_seqs(seqs)
+        return self.seq_to_unitigs_flat(buf, offsets, hits=hits)
+
+    def seq_to_unitigs_dev(self, d_seq, d_offsets, d_segs=None, d_seg_offsets=None, d_rec=None, d_hits=None):
+        """kmx_unitig_map_seqs_dev on torch tensors of the model's device: d_seq uint8 [n_bases], d_offsets int64 [n_seqs + 1];
+        d_segs uint8 [capacity, 24] (None: the sizing call), d_seg_offsets int64 [n_seqs + 1] (None: allocated), d_rec uint8
+        [n_seqs, 64] or None, d_hits int64 [n_unitigs] or None (added to) -> (the number of segments, d_seg_offsets)."""
+        import torch
+        n_seqs = d_offsets.numel() - 1
+        if d_seg_offsets is None:
+            d_seg_offsets = torch.zeros(n_seqs + 1, dtype=torch.int64, device=d_seq.device)
+        ns = C.c_uint64(0)
+        _chk(self.L.kmx_unitig_map_seqs_dev(self.h, d_seq.data_ptr(), d_offsets.data_ptr(), n_seqs, d_seq.numel(),
+                                            d_segs.data_ptr() if d_segs is not None else None, d_segs.shape[0] if d_segs is not None else 0, C.byref(ns),
+                                            d_seg_offsets.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, d_hits.data_ptr() if d_hits is not None else None))
+        return ns.value, d_seg_offsets
+
+
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173
         _chk(self.L.kmx_save(self.h, save_dir.encode()))
 

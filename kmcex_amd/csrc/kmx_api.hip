@@ -362,7 +362,31 @@ struct kmx_model {
 		double phase_s[6] = {0, 0, 0, 0, 0, 0};                    // under kmx_set_profile(m, 1): adjacency (with the index), links, ranking, emit, links between unitigs, cleaning (decisions and removal)
 		u64 rounds = 0;                                            // doubling rounds of the last call
 	} uni;
+	// kmx_unitig_map_* (map_host.h): a session's index -- the listing's bucket index, the place of every entry, m_u -- and the
+	// work arrays of one chunk of windows, kept by capacity from batch to batch
+	struct MapState {
+		bool on = false;                                           // between kmx_*unitig_map_begin* and kmx_unitig_map_end
+		bool from_count = false;                                   // the listing is cnt.d_run[1]: what drops that ends the session
+		MapDev dev{};
+		DevBuf<u64> d_km;                                          // the host variant's copy of the listing
+		DevBuf<u32> d_start, d_mu, d_err;                          // d_err: [0] bad listing, [1] bad unitig set
+		DevBuf<u64> d_place;
+		DevBuf<u64> d_code, d_spos, d_state;                       // per chunk: codes, segment starts; [2] segments so far, the open segment's start
+		DevBuf<u32> d_ex;                                          // the scanned start flags
+		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
+	} map;
 };
+
+// the end of a map session: its index and work arrays go (after the stream has drained)
+static void map_drop(kmx_model *m)
+{
+	auto &S = m->map;
+	if (S.d_start || S.d_place || S.d_code || S.d_km) hipStreamSynchronize(m->stream);
+	S.d_km.reset(); S.d_start.reset(); S.d_mu.reset(); S.d_err.reset(); S.d_place.reset();
+	S.d_code.reset(); S.d_spos.reset(); S.d_state.reset(); S.d_ex.reset(); S.d_tmp.reset();
+	S.dev = MapDev{};
+	S.on = S.from_count = false;
+}
 
 static void prof_begin(KernelProf *p, int cls, hipStream_t st)
 {
@@ -494,6 +518,7 @@ static void free_count(kmx_model *m, bool listing)
 	C.on = false;
 	C.piece = C.fill = C.D = C.windows = 0;
 	if (listing || !C.listed) {
+		if (m->map.on && m->map.from_count) map_drop(m);             // the map session reads the listing where it lies
 		C.d_run[1].reset(); C.d_runc[1].reset();
 		C.listed = false;
 		C.n_list = 0;
@@ -2890,6 +2915,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 
 #include "count_host.h"
 #include "unitig_host.h"
+#include "map_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3412,6 +3438,13 @@ extern "C" int kmx_unitig_graph_clean(kmx_model *m, int k, const uint64_t *kmers
 extern "C" int kmx_count_unitig_graph_clean(kmx_model *m, uint32_t thr, const kmx_clean_params *params, char *seq_out, uint64_t seq_capacity, uint64_t *offsets_out, kmx_unitig *rec, uint64_t rec_capacity, uint64_t *link_offsets, uint32_t *links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_count_unitig_graph_clean_impl(m, thr, params, seq_out, seq_capacity, offsets_out, rec, rec_capacity, link_offsets, links, link_capacity, n_unitigs, n_bases_out, n_links, removed, stats); }); }
 extern "C" int kmx_count_unitig_graph_clean_dev(kmx_model *m, uint32_t thr, const kmx_clean_params *params, char *d_seq_out, uint64_t seq_capacity, uint64_t *d_offsets_out, kmx_unitig *d_rec, uint64_t rec_capacity, uint64_t *d_link_offsets, uint32_t *d_links, uint64_t link_capacity, uint64_t *n_unitigs, uint64_t *n_bases_out, uint64_t *n_links, uint8_t *d_removed, kmx_clean_stats *stats) { return guarded([&] { return kmx_count_unitig_graph_clean_dev_impl(m, thr, params, d_seq_out, seq_capacity, d_offsets_out, d_rec, rec_capacity, d_link_offsets, d_links, link_capacity, n_unitigs, n_bases_out, n_links, d_removed, stats); }); }
 extern "C" int kmx_unitig_clean_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_clean_last_phases_impl(m, seconds, rounds); }); }
+extern "C" int kmx_unitig_map_begin_dev(kmx_model *m, int k, const uint64_t *d_kmers, uint64_t n, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases) { return guarded([&] { return kmx_unitig_map_begin_dev_impl(m, k, d_kmers, n, d_useq, d_uoffsets, n_unitigs, n_ubases); }); }
+extern "C" int kmx_unitig_map_begin(kmx_model *m, int k, const uint64_t *kmers, uint64_t n, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs) { return guarded([&] { return kmx_unitig_map_begin_impl(m, k, kmers, n, useq, uoffsets, n_unitigs); }); }
+extern "C" int kmx_count_unitig_map_begin_dev(kmx_model *m, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases) { return guarded([&] { return kmx_count_unitig_map_begin_dev_impl(m, d_useq, d_uoffsets, n_unitigs, n_ubases); }); }
+extern "C" int kmx_count_unitig_map_begin(kmx_model *m, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs) { return guarded([&] { return kmx_count_unitig_map_begin_impl(m, useq, uoffsets, n_unitigs); }); }
+extern "C" int kmx_unitig_map_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, kmx_map_segment *d_segs, uint64_t capacity, uint64_t *n_segs, uint64_t *d_seg_offsets, kmx_seq_map *d_rec, uint64_t *d_hits) { return guarded([&] { return kmx_unitig_map_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_segs, capacity, n_segs, d_seg_offsets, d_rec, d_hits); }); }
+extern "C" int kmx_unitig_map_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, kmx_map_segment *segs, uint64_t capacity, uint64_t *n_segs, uint64_t *seg_offsets, kmx_seq_map *rec, uint64_t *hits) { return guarded([&] { return kmx_unitig_map_seqs_impl(m, seq, offsets, n_seqs, segs, capacity, n_segs, seg_offsets, rec, hits); }); }
+extern "C" int kmx_unitig_map_end(kmx_model *m) { return guarded([&] { return kmx_unitig_map_end_impl(m); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

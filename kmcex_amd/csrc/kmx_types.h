@@ -356,6 +356,40 @@ struct UniClean {
 	u64 n_uni, n_links;
 	u32 ops, max_tip, max_bubble;
 };
+// kmx_unitig_map_*: a segment and a per-read record, the layouts of kmx_map_segment and kmx_seq_map (include/kmx.h; map_host.h
+// asserts them) ...
+struct MapSeg {
+	u64 pos;
+	u32 n_windows, o, off, reserved;
+};
+struct SeqMap {
+	u64 n_windows, n_mapped, n_segments, n_gaps, first_mapped, last_mapped, longest, reserved;
+};
+// ... the index of a session (map_kernels.h): the listing with its bucket index (d: km, n, k, W, bits, shift, start, err), the
+// place of every entry, u << 32 | f << 31 | j or MAP_NONE, and the windows of every unitig ...
+#define MAP_NONE (~0ULL)
+struct MapDev {
+	UniDev d;
+	u64 *place;                  // [n]
+	u32 *mu;                     // [U]
+	u64 U;
+};
+// ... and the work arrays of one chunk of at most `cap` windows.  A window's code is o << 32 | off, or MAP_NONE when it is not
+// mapped; code[0] is the window in front of the chunk (what the previous chunk left), code[1 + i] window p0 + i.
+struct MapChunk {
+	u64 *code;                   // [cap + 1]
+	u32 *ex;                     // [cap + 1]: the exclusive scan of the start flags; ex[n_win] their number
+	u64 *spos;                   // [cap]: where the chunk's l-th segment starts
+	u64 *state;                  // [2]: segments in front of the chunk; the start of the last segment begun so far
+};
+// ... and where the segments and what is kept per read go: segs[cap] (may be null), so[n_seqs + 1] (counts, scanned at the
+// end), rec[n_seqs] (may be null)
+struct MapOut {
+	MapSeg *segs;
+	u64 cap;
+	u64 *so;
+	SeqMap *rec;
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

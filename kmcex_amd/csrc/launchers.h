@@ -82,4 +82,9 @@ void unitig_link_emit(const UniDev &, const u64 *, const UniTot *, const u64 *, 
 // ... and of kmx_unitig_graph_clean: a round's verdicts (one byte per unitig; the kind counters), the removal (the working counts, removed[], the k-mer counter)
 void unitig_clean(const UniClean &, unsigned char *, unsigned long long *, hipStream_t);
 void unitig_drop(const UniDev &, const u64 *, const UniTot *, const unsigned char *, u64, u32 *, unsigned char *, unsigned char, unsigned long long *, hipStream_t);
+// unitig_device.hip, behind those: kmx_unitig_map_*: the place table of a session; per batch the records' start, one chunk of windows, the end
+void map_index(const MapDev &, const unsigned char *, const u64 *, u64, hipStream_t);
+void map_rec_init(SeqMap *, u64, hipStream_t);
+hipError_t map_chunk(const MapDev &, const SeqView &, u64, u64, const MapChunk &, const MapOut &, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t map_finish(const MapOut &, const u64 *, u64, u64, int, DevBuf<unsigned char> &tmp, hipStream_t);
 }   // namespace kmxk

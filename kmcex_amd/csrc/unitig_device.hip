@@ -1,8 +1,10 @@
 // unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*, kmx_*unitig_graph_clean*).  The host side that sizes the
-// buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.
+// buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.  Behind them the launchers of map_kernels.h (kmx_unitig_map_*), which
+// search the same listing through the same bucket index; their host side is map_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
+#include "map_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -99,6 +101,51 @@ void unitig_clean(const UniClean &c, unsigned char *verdict, unsigned long long 
 void unitig_drop(const UniDev &d, const u64 *pair, const UniTot *sc, const unsigned char *verdict, u64 n_uni, u32 *wcnt, unsigned char *removed, unsigned char round, unsigned long long *cnt, hipStream_t st)
 {
 	if (d.n) hipLaunchKernelGGL(k_uni_drop, dim3(nblk(d.n)), dim3(256), 0, st, d, pair, sc, verdict, n_uni, wcnt, removed, round, cnt);
+}
+
+// ---- kmx_unitig_map_* (map_kernels.h)
+
+// m_u and the place of every window of the unitig set; M.place is all ones and *M.d.err zero before
+void map_index(const MapDev &M, const unsigned char *useq, const u64 *uoffs, u64 n_ubases, hipStream_t st)
+{
+	if (!M.U || !n_ubases) return;
+	hipLaunchKernelGGL(k_map_mu, dim3(nblk(M.U)), dim3(256), 0, st, M, uoffs, n_ubases);
+	if (M.d.W == 1) hipLaunchKernelGGL(k_map_index<1>, dim3(nblk(n_ubases)), dim3(256), 0, st, M, useq, uoffs, n_ubases);
+	else hipLaunchKernelGGL(k_map_index<2>, dim3(nblk(n_ubases)), dim3(256), 0, st, M, useq, uoffs, n_ubases);
+}
+
+void map_rec_init(SeqMap *rec, u64 n_seqs, hipStream_t st)
+{
+	if (rec && n_seqs) hipLaunchKernelGGL(k_map_rec_init, dim3(nblk(n_seqs)), dim3(256), 0, st, rec, n_seqs);
+}
+
+// the windows [p0, p0 + n_win) of the reads: codes, the scan of the start flags, starts, ends, and the state for the next chunk
+hipError_t map_chunk(const MapDev &M, const SeqView &v, u64 p0, u64 n_win, const MapChunk &C, const MapOut &O, unsigned long long *hits, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	if (!n_win) return hipSuccess;
+	const unsigned grid = (unsigned)((n_win + MAP_WIN - 1) / MAP_WIN);
+	if (M.d.W == 1) hipLaunchKernelGGL(k_map_windows<1>, dim3(grid), dim3(MAP_BT), 0, st, M, v, p0, n_win, C.code, hits);
+	else hipLaunchKernelGGL(k_map_windows<2>, dim3(grid), dim3(MAP_BT), 0, st, M, v, p0, n_win, C.code, hits);
+	auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), MapStartFlag{C.code, n_win});
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, flags, C.ex, 0u, (size_t)(n_win + 1), rocprim::plus<u32>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, flags, C.ex, 0u, (size_t)(n_win + 1), rocprim::plus<u32>(), st));
+	hipLaunchKernelGGL(k_map_starts, dim3(nblk(n_win)), dim3(256), 0, st, C, O, v.offs, v.n_seqs, v.n_total, p0, n_win);
+	hipLaunchKernelGGL(k_map_ends, dim3(nblk(n_win)), dim3(256), 0, st, C, O, v.offs, v.n_seqs, v.n_total, p0, n_win);
+	hipLaunchKernelGGL(k_map_advance, dim3(1), dim3(1), 0, st, C, n_win);
+	return hipGetLastError();
+}
+
+// behind the last chunk: the records are completed, the segments per read become the CSR (O.so[n_seqs] is 0 before)
+hipError_t map_finish(const MapOut &O, const u64 *offs, u64 n_seqs, u64 n_total, int k, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	if (O.rec && n_seqs) hipLaunchKernelGGL(k_map_rec_finish, dim3(nblk(n_seqs)), dim3(256), 0, st, O.rec, O.so, offs, n_seqs, n_total, k);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const u64 *)O.so, O.so, (u64)0, (size_t)(n_seqs + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const u64 *)O.so, O.so, (u64)0, (size_t)(n_seqs + 1), rocprim::plus<u64>(), st));
+	return hipGetLastError();
 }
 
 }   // namespace kmxk
