@@ -310,29 +310,11 @@ public:
 	// construction.  A caller who can bound the output calls kmx_count_unitigs / kmx_unitigs once.
 	std::vector<std::string> count_unitigs(uint32_t thr = 1, std::vector<kmx_unitig> *rec = 0)
 	{
-		uint64_t nu = 0, nb = 0;
-		check(kmx_count_unitigs(h_, thr, 0, 0, 0, 0, 0, &nu, &nb));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		check(kmx_count_unitigs(h_, thr, &bases[0], nb, &off[0], &r[0], nu, &nu, &nb));
-		r.resize((size_t)nu);
-		if (rec) rec->swap(r);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"count_unitigs", 0, 0, 0, 0, thr, 0}, rec, 0, 0, 0, 0);
 	}
 	std::vector<std::string> unitigs(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr = 1, std::vector<kmx_unitig> *rec = 0)
 	{
-		uint64_t nu = 0, nb = 0;
-		const uint64_t n = counts.size();
-		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitigs: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
-		check(kmx_unitigs(h_, k, kmers.data(), counts.data(), n, thr, 0, 0, 0, 0, 0, &nu, &nb));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		check(kmx_unitigs(h_, k, kmers.data(), counts.data(), n, thr, &bases[0], nb, &off[0], &r[0], nu, &nu, &nb));
-		r.resize((size_t)nu);
-		if (rec) rec->swap(r);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"unitigs", 0, &kmers, &counts, k, thr, 0}, rec, 0, 0, 0, 0);
 	}
 	// the unitigs as FASTA: one record per unitig, its header ">u<index> n_kmers=<m> mean_count=<sum / m, two decimals> circular=<0|1>"
 	static void write_unitigs_fasta(std::ostream &out, const std::vector<std::string> &strs, const std::vector<kmx_unitig> &rec)
@@ -349,38 +331,12 @@ public:
 	// twins of count_unitigs and unitigs: a sizing call plus one call.
 	std::vector<std::string> count_unitig_graph(uint32_t thr, std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links)
 	{
-		uint64_t nu = 0, nb = 0, nl = 0;
-		check(kmx_count_unitig_graph(h_, thr, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		std::vector<uint32_t> lk((size_t)nl + 1, 0);
-		check(kmx_count_unitig_graph(h_, thr, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl));
-		r.resize((size_t)nu);
-		lk.resize((size_t)nl);
-		if (rec) rec->swap(r);
-		if (link_offsets) link_offsets->swap(lo);
-		if (links) links->swap(lk);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"count_unitig_graph", 1, 0, 0, 0, thr, 0}, rec, link_offsets, links, 0, 0);
 	}
 	std::vector<std::string> unitig_graph(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr, std::vector<kmx_unitig> *rec,
 	                                      std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links)
 	{
-		uint64_t nu = 0, nb = 0, nl = 0;
-		const uint64_t n = counts.size();
-		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitig_graph: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
-		check(kmx_unitig_graph(h_, k, kmers.data(), counts.data(), n, thr, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		std::vector<uint32_t> lk((size_t)nl + 1, 0);
-		check(kmx_unitig_graph(h_, k, kmers.data(), counts.data(), n, thr, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl));
-		r.resize((size_t)nu);
-		lk.resize((size_t)nl);
-		if (rec) rec->swap(r);
-		if (link_offsets) link_offsets->swap(lo);
-		if (links) links->swap(lk);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"unitig_graph", 1, &kmers, &counts, k, thr, 0}, rec, link_offsets, links, 0, 0);
 	}
 	// The cleaned unitig graph (the rule: kmx.h): count_unitig_graph / unitig_graph after tips, islands and bubbles have been
 	// removed round by round under params; stats (optional) receives what was removed, removed (optional) the round per listing
@@ -388,42 +344,13 @@ public:
 	std::vector<std::string> count_unitig_graph_clean(uint32_t thr, const kmx_clean_params &params, std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets,
 	                                                  std::vector<uint32_t> *links, kmx_clean_stats *stats = 0)
 	{
-		uint64_t nu = 0, nb = 0, nl = 0;
-		check(kmx_count_unitig_graph_clean(h_, thr, &params, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl, 0, 0));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		std::vector<uint32_t> lk((size_t)nl + 1, 0);
-		check(kmx_count_unitig_graph_clean(h_, thr, &params, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl, 0, stats));
-		r.resize((size_t)nu);
-		lk.resize((size_t)nl);
-		if (rec) rec->swap(r);
-		if (link_offsets) link_offsets->swap(lo);
-		if (links) links->swap(lk);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"count_unitig_graph_clean", 2, 0, 0, 0, thr, &params}, rec, link_offsets, links, stats, 0);
 	}
 	std::vector<std::string> unitig_graph_clean(const std::vector<uint64_t> &kmers, const std::vector<uint32_t> &counts, int k, uint32_t thr, const kmx_clean_params &params,
 	                                            std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links, kmx_clean_stats *stats = 0,
 	                                            std::vector<uint8_t> *removed = 0)
 	{
-		uint64_t nu = 0, nb = 0, nl = 0;
-		const uint64_t n = counts.size();
-		if (kmers.size() != n * (uint64_t)((k + 31) / 32)) { std::cout << "unitig_graph_clean: " << kmers.size() << " words for " << n << " counts" << std::endl; exit(1); }
-		check(kmx_unitig_graph_clean(h_, k, kmers.data(), counts.data(), n, thr, &params, 0, 0, 0, 0, 0, 0, 0, 0, &nu, &nb, &nl, 0, 0));
-		std::string bases((size_t)nb + 1, '\0');
-		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
-		std::vector<kmx_unitig> r((size_t)nu + 1);
-		std::vector<uint32_t> lk((size_t)nl + 1, 0);
-		std::vector<uint8_t> rm((size_t)n + 1, 0);
-		check(kmx_unitig_graph_clean(h_, k, kmers.data(), counts.data(), n, thr, &params, &bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl, &nu, &nb, &nl, removed ? &rm[0] : 0, stats));
-		r.resize((size_t)nu);
-		lk.resize((size_t)nl);
-		rm.resize((size_t)n);
-		if (rec) rec->swap(r);
-		if (link_offsets) link_offsets->swap(lo);
-		if (links) links->swap(lk);
-		if (removed) removed->swap(rm);
-		return split(bases, off);
+		return unitig_call(UnitigAsk{"unitig_graph_clean", 2, &kmers, &counts, k, thr, &params}, rec, link_offsets, links, stats, removed);
 	}
 	// the unitig graph as GFA 1: "H\tVN:Z:1.0", one "S\tu<index>\t<string>\tLN:i:<len>\tKC:i:<sum_count>" per unitig, and one
 	// "L\tu<a>\t<+|->\tu<b>\t<+|->\t<k-1>M" per mirror pair of edges: a -> b is written iff (a, b) <= (b ^ 1, a ^ 1) as pairs, so
@@ -559,6 +486,65 @@ private:
 		std::vector<std::string> out(off.size() - 1);
 		for (size_t i = 0; i + 1 < off.size(); i++) out[i] = buf.substr((size_t)off[i], (size_t)(off[i + 1] - off[i]));
 		return out;
+	}
+	// one of the six unitig calls: tier 0 the strings, 1 with the links, 2 cleaned under params; kmers == 0: the counted session's
+	// listing.  room: seq, seq_capacity, offsets, rec, rec_capacity, link_offsets, links, link_capacity as the C calls take them.
+	struct UnitigAsk {
+		const char *name;
+		int tier;
+		const std::vector<uint64_t> *kmers;
+		const std::vector<uint32_t> *counts;
+		int k;
+		uint32_t thr;
+		const kmx_clean_params *params;
+	};
+	struct UnitigRoom {
+		char *seq;
+		uint64_t seq_cap;
+		uint64_t *off;
+		kmx_unitig *rec;
+		uint64_t rec_cap;
+		uint64_t *lo;
+		uint32_t *lk;
+		uint64_t link_cap;
+	};
+	int unitig_c_call(const UnitigAsk &a, const UnitigRoom &r, uint64_t *nu, uint64_t *nb, uint64_t *nl, uint8_t *removed, kmx_clean_stats *stats)
+	{
+		if (!a.kmers)
+			return a.tier == 0 ? kmx_count_unitigs(h_, a.thr, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, nu, nb)
+			     : a.tier == 1 ? kmx_count_unitig_graph(h_, a.thr, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, r.lo, r.lk, r.link_cap, nu, nb, nl)
+			                   : kmx_count_unitig_graph_clean(h_, a.thr, a.params, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, r.lo, r.lk, r.link_cap, nu, nb, nl, removed, stats);
+		const uint64_t *km = a.kmers->data();
+		const uint32_t *cnt = a.counts->data();
+		const uint64_t n = a.counts->size();
+		return a.tier == 0 ? kmx_unitigs(h_, a.k, km, cnt, n, a.thr, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, nu, nb)
+		     : a.tier == 1 ? kmx_unitig_graph(h_, a.k, km, cnt, n, a.thr, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, r.lo, r.lk, r.link_cap, nu, nb, nl)
+		                   : kmx_unitig_graph_clean(h_, a.k, km, cnt, n, a.thr, a.params, r.seq, r.seq_cap, r.off, r.rec, r.rec_cap, r.lo, r.lk, r.link_cap, nu, nb, nl, removed, stats);
+	}
+	// the sizing call, room for exactly that, the call, and the strings split; every output but the strings is optional
+	std::vector<std::string> unitig_call(const UnitigAsk &a, std::vector<kmx_unitig> *rec, std::vector<uint64_t> *link_offsets, std::vector<uint32_t> *links, kmx_clean_stats *stats,
+	                                     std::vector<uint8_t> *removed)
+	{
+		uint64_t nu = 0, nb = 0, nl = 0;
+		const uint64_t n = a.kmers ? a.counts->size() : 0;
+		if (a.kmers && a.kmers->size() != n * (uint64_t)((a.k + 31) / 32)) { std::cout << a.name << ": " << a.kmers->size() << " words for " << n << " counts" << std::endl; exit(1); }
+		const UnitigRoom none = {0, 0, 0, 0, 0, 0, 0, 0};
+		check(unitig_c_call(a, none, &nu, &nb, &nl, 0, 0));
+		std::string bases((size_t)nb + 1, '\0');
+		std::vector<uint64_t> off((size_t)nu + 1, 0), lo(2 * (size_t)nu + 1, 0);
+		std::vector<kmx_unitig> r((size_t)nu + 1);
+		std::vector<uint32_t> lk((size_t)nl + 1, 0);
+		std::vector<uint8_t> rm((size_t)n + 1, 0);
+		const UnitigRoom room = {&bases[0], nb, &off[0], &r[0], nu, &lo[0], &lk[0], nl};
+		check(unitig_c_call(a, room, &nu, &nb, &nl, removed ? &rm[0] : 0, stats));
+		r.resize((size_t)nu);
+		lk.resize((size_t)nl);
+		rm.resize((size_t)n);
+		if (rec) rec->swap(r);
+		if (link_offsets) link_offsets->swap(lo);
+		if (links) links->swap(lk);
+		if (removed) removed->swap(rm);
+		return split(bases, off);
 	}
 	static void die(const char *msg)
 	{

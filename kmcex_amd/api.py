@@ -833,182 +833,134 @@ class KModel:
         return (kmers[:, 0].copy() if W == 1 else kmers), counts
 
     # ---- unitigs: the compacted de Bruijn graph of a counted listing (the rule: include/kmx.h)
-    def _unitigs_host(self, call):
-        """the sizing call, then the call with exact room -> (uint8 bases, uint64 offsets [n + 1], UNITIG_DTYPE records [n]).
-        Both calls rank the whole graph, so this costs the construction twice; tools/bench_unitigs.py times the bare C call."""
-        nu, nb = C.c_uint64(0), C.c_uint64(0)
-        _chk(call(None, 0, None, None, 0, C.byref(nu), C.byref(nb)))
-        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
-        off = np.zeros(nu.value + 1, dtype=np.uint64)
-        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
-        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, C.byref(nu), C.byref(nb)))
-        return buf[:nb.value], off, rec
+    def _unitig_call(self, call, dev: bool, links: bool = False, n=None):
+        """the sizing call, then the call with exact room, of any of the twelve unitig entry points: call takes what follows thr
+        (and params) in the C prototype.  -> (uint8 bases, uint64 offsets [n_unitigs + 1], UNITIG_DTYPE records [n_unitigs]); with
+        links + (uint64 link_offsets [2 n_unitigs + 1], uint32 links [n_links]); with n, the listing's size (the cleaning calls),
+        + (uint8 removed [n], stats dict).  dev: torch tensors on the model's device instead (int64 offsets and link_offsets, uint8
+        records [n_unitigs, 40], int32 links: the bits of the uint32 targets).  Both calls rank the whole graph, so this costs the
+        construction twice; tools/bench_unitigs.py times the bare C call."""
+        clean = n is not None
+        ctr = [C.c_uint64(0) for _ in range(3 if links else 2)]
+        tail = [C.byref(c) for c in ctr] + ([None, None] if clean else [])
+        _chk(call(None, 0, None, None, 0, *([None, None, 0] if links else []), *tail))
+        nu, nb, nl = ctr[0].value, ctr[1].value, ctr[2].value if links else 0
+        if dev:
+            import torch
+            where = torch.device("cuda", self.stats().device)
+            u8, w64, w32, rec_shape = torch.uint8, torch.int64, torch.int32, ((nu, C.sizeof(Unitig)), torch.uint8)
 
-    def _unitigs_dev(self, call):
-        """the same on the model's device -> torch tensors (uint8 bases, int64 offsets [n + 1], uint8 records [n, 40]); twice the
-        construction as well"""
-        import torch
-        nu, nb = C.c_uint64(0), C.c_uint64(0)
-        _chk(call(None, 0, None, None, 0, C.byref(nu), C.byref(nb)))
-        dev = torch.device("cuda", self.stats().device)
-        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
-        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
-        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, C.byref(nu), C.byref(nb)))
-        return buf[:nb.value], off, rec
+            def new(shape, dtype):
+                return torch.zeros(shape, dtype=dtype, device=where)
+
+            def ptr(a):
+                return a.data_ptr()
+        else:
+            u8, w64, w32, rec_shape, new = np.uint8, np.uint64, np.uint32, (nu, UNITIG_DTYPE), np.zeros
+
+            def ptr(a):
+                return a.ctypes.data
+        buf, off, rec = new(max(nb, 1), u8), new(nu + 1, w64), new(*rec_shape)
+        out, args = [buf[:nb], off, rec], [ptr(buf), nb, ptr(off), ptr(rec), nu]
+        if links:
+            loff, lk = new(2 * nu + 1, w64), new(max(nl, 1), w32)
+            out += [loff, lk[:nl]]
+            args += [ptr(loff), ptr(lk), nl]
+        if clean:
+            removed, st = new(max(n, 1), u8), CleanStats()
+            tail[-2:] = [ptr(removed), C.addressof(st)]
+        _chk(call(*args, *tail))
+        if clean:
+            out += [removed[:n], {f: int(getattr(st, f)) for f, _ in CleanStats._fields_}]
+        return tuple(out)
+
+    @staticmethod
+    def _host_listing(kmers, counts, k):
+        """a caller's listing as the host routes take it -> (contiguous uint64 words, uint32 counts, n)"""
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+        if kmers.size != counts.size * ((int(k) + 31) // 32):
+            raise KmxError(-1, f"{kmers.size} words for {counts.size} counts at k = {k}")
+        return kmers, counts, counts.size
+
+    @staticmethod
+    def _dev_listing(d_kmers, d_counts, k):
+        """a caller's listing as the _dev routes take it (int64 / uint64 words, int32 / uint32 counts) -> (contiguous words, counts, n)"""
+        n = d_counts.numel()
+        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
+            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
+        return d_kmers.contiguous(), d_counts.contiguous(), n
 
     def unitigs(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1):
         """kmx_unitigs: the unitigs of a listing (packed canonical k-mers, strictly ascending; uint32 counts; odd k in [5, 63])
         whose nodes are the k-mers with count >= thr -> (buf, offsets, rec) in seq_to_occ_flat's layout.  Needs no built model."""
-        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
-        n = counts.size
-        if kmers.size != n * ((int(k) + 31) // 32):
-            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
-        return self._unitigs_host(lambda *a: self.L.kmx_unitigs(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a))
+        kmers, counts, n = self._host_listing(kmers, counts, k)
+        return self._unitig_call(lambda *a: self.L.kmx_unitigs(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a), False)
 
     def unitigs_dev(self, d_kmers, d_counts, k: int, thr: int = 1):
         """kmx_unitigs_dev on torch tensors of the model's device (int64 / uint64 words, int32 / uint32 counts) -> torch tensors"""
-        n = d_counts.numel()
-        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
-            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
-        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
-        return self._unitigs_dev(lambda *a: self.L.kmx_unitigs_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a))
+        d_kmers, d_counts, n = self._dev_listing(d_kmers, d_counts, k)
+        return self._unitig_call(lambda *a: self.L.kmx_unitigs_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a), True)
 
     def count_unitigs(self, thr: int = 1):
         """kmx_count_unitigs: the unitigs of the listing the last count_finish / init_reads kept, read where it lies"""
-        return self._unitigs_host(lambda *a: self.L.kmx_count_unitigs(self.h, int(thr), *a))
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitigs(self.h, int(thr), *a), False)
 
     def count_unitigs_dev(self, thr: int = 1):
         """kmx_count_unitigs_dev: the same, the output as torch tensors on the model's device"""
-        return self._unitigs_dev(lambda *a: self.L.kmx_count_unitigs_dev(self.h, int(thr), *a))
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitigs_dev(self.h, int(thr), *a), True)
+
+    def _unitig_phases(self, call, names) -> dict:
+        sec, rounds = (C.c_double * len(names))(), C.c_uint64(0)
+        _chk(call(self.h, sec, C.byref(rounds)))
+        return {**{n: sec[i] for i, n in enumerate(names)}, "rounds": int(rounds.value)}
 
     def unitigs_phases(self) -> dict:
         """kmx_unitigs_last_phases: seconds per phase of the last unitig call (measured under set_profile(1)) and its rounds"""
-        sec, rounds = (C.c_double * 4)(), C.c_uint64(0)
-        _chk(self.L.kmx_unitigs_last_phases(self.h, sec, C.byref(rounds)))
-        return {**{n: sec[i] for i, n in enumerate(UNITIG_PHASES)}, "rounds": int(rounds.value)}
+        return self._unitig_phases(self.L.kmx_unitigs_last_phases, UNITIG_PHASES)
 
     # ---- the unitig graph: the unitigs and the edges between them as CSR over the 2 U oriented unitigs (the rule: include/kmx.h)
-    def _unitig_graph_host(self, call):
-        """the sizing call, then the call with exact room -> the tuple of _unitigs_host + (uint64 link_offsets [2 n + 1], uint32
-        links [n_links])"""
-        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl)))
-        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
-        off = np.zeros(nu.value + 1, dtype=np.uint64)
-        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
-        loff = np.zeros(2 * nu.value + 1, dtype=np.uint64)
-        links = np.empty(max(nl.value, 1), dtype=np.uint32)
-        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, loff.ctypes.data, links.ctypes.data, nl.value,
-                  C.byref(nu), C.byref(nb), C.byref(nl)))
-        return buf[:nb.value], off, rec, loff, links[:nl.value]
-
-    def _unitig_graph_dev(self, call):
-        """the same on the model's device -> torch tensors: those of _unitigs_dev + (int64 link_offsets [2 n + 1], int32 links
-        [n_links], the bits of the uint32 targets)"""
-        import torch
-        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl)))
-        dev = torch.device("cuda", self.stats().device)
-        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
-        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
-        loff = torch.zeros(2 * nu.value + 1, dtype=torch.int64, device=dev)
-        links = torch.empty(max(nl.value, 1), dtype=torch.int32, device=dev)
-        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, loff.data_ptr(), links.data_ptr(), nl.value,
-                  C.byref(nu), C.byref(nb), C.byref(nl)))
-        return buf[:nb.value], off, rec, loff, links[:nl.value]
-
     def unitig_graph(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1):
         """kmx_unitig_graph: unitigs() and the edges between the oriented unitigs o = 2 u + d (d = 1: the reverse complement) ->
         (buf, offsets, rec, link_offsets, links); the edges of o are links[link_offsets[o]:link_offsets[o + 1]]"""
-        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
-        n = counts.size
-        if kmers.size != n * ((int(k) + 31) // 32):
-            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
-        return self._unitig_graph_host(lambda *a: self.L.kmx_unitig_graph(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a))
+        kmers, counts, n = self._host_listing(kmers, counts, k)
+        return self._unitig_call(lambda *a: self.L.kmx_unitig_graph(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), *a), False, links=True)
 
     def unitig_graph_dev(self, d_kmers, d_counts, k: int, thr: int = 1):
         """kmx_unitig_graph_dev on torch tensors of the model's device (as unitigs_dev) -> torch tensors"""
-        n = d_counts.numel()
-        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
-            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
-        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
-        return self._unitig_graph_dev(lambda *a: self.L.kmx_unitig_graph_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a))
+        d_kmers, d_counts, n = self._dev_listing(d_kmers, d_counts, k)
+        return self._unitig_call(lambda *a: self.L.kmx_unitig_graph_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), *a), True, links=True)
 
     def count_unitig_graph(self, thr: int = 1):
         """kmx_count_unitig_graph: the unitig graph of the listing the last count_finish / init_reads kept"""
-        return self._unitig_graph_host(lambda *a: self.L.kmx_count_unitig_graph(self.h, int(thr), *a))
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitig_graph(self.h, int(thr), *a), False, links=True)
 
     def count_unitig_graph_dev(self, thr: int = 1):
         """kmx_count_unitig_graph_dev: the same, the output as torch tensors on the model's device"""
-        return self._unitig_graph_dev(lambda *a: self.L.kmx_count_unitig_graph_dev(self.h, int(thr), *a))
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitig_graph_dev(self.h, int(thr), *a), True, links=True)
 
     def unitig_graph_phases(self) -> dict:
         """kmx_unitig_graph_last_phases: unitigs_phases() plus "unitig_links", the seconds spent on the edges between unitigs"""
-        sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
-        _chk(self.L.kmx_unitig_graph_last_phases(self.h, sec, C.byref(rounds)))
-        return {**{n: sec[i] for i, n in enumerate(UNITIG_GRAPH_PHASES)}, "rounds": int(rounds.value)}
+        return self._unitig_phases(self.L.kmx_unitig_graph_last_phases, UNITIG_GRAPH_PHASES)
 
     # ---- cleaning the unitig graph: tips, islands and bubbles removed round by round (the rule: include/kmx.h)
     @staticmethod
     def _clean_params(k, ops, max_tip, max_bubble, max_rounds):
         return CleanParams(int(ops), int(2 * k if max_tip is None else max_tip), int(2 * k if max_bubble is None else max_bubble), int(max_rounds))
 
-    def _unitig_clean_host(self, call, n):
-        """the sizing call, then the call with exact room -> the tuple of _unitig_graph_host + (uint8 removed [n], stats dict)"""
-        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        st = CleanStats()
-        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl), None, None))
-        buf = np.empty(max(nb.value, 1), dtype=np.uint8)
-        off = np.zeros(nu.value + 1, dtype=np.uint64)
-        rec = np.zeros(nu.value, dtype=UNITIG_DTYPE)
-        loff = np.zeros(2 * nu.value + 1, dtype=np.uint64)
-        links = np.empty(max(nl.value, 1), dtype=np.uint32)
-        removed = np.zeros(max(n, 1), dtype=np.uint8)
-        _chk(call(buf.ctypes.data, nb.value, off.ctypes.data, rec.ctypes.data, nu.value, loff.ctypes.data, links.ctypes.data, nl.value,
-                  C.byref(nu), C.byref(nb), C.byref(nl), removed.ctypes.data, C.addressof(st)))
-        return buf[:nb.value], off, rec, loff, links[:nl.value], removed[:n], {f: int(getattr(st, f)) for f, _ in CleanStats._fields_}
-
-    def _unitig_clean_dev(self, call, n):
-        """the same on the model's device -> the torch tensors of _unitig_graph_dev + (uint8 removed [n], stats dict)"""
-        import torch
-        nu, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
-        st = CleanStats()
-        _chk(call(None, 0, None, None, 0, None, None, 0, C.byref(nu), C.byref(nb), C.byref(nl), None, None))
-        dev = torch.device("cuda", self.stats().device)
-        buf = torch.empty(max(nb.value, 1), dtype=torch.uint8, device=dev)
-        off = torch.zeros(nu.value + 1, dtype=torch.int64, device=dev)
-        rec = torch.zeros((nu.value, C.sizeof(Unitig)), dtype=torch.uint8, device=dev)
-        loff = torch.zeros(2 * nu.value + 1, dtype=torch.int64, device=dev)
-        links = torch.empty(max(nl.value, 1), dtype=torch.int32, device=dev)
-        removed = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
-        _chk(call(buf.data_ptr(), nb.value, off.data_ptr(), rec.data_ptr(), nu.value, loff.data_ptr(), links.data_ptr(), nl.value,
-                  C.byref(nu), C.byref(nb), C.byref(nl), removed.data_ptr(), C.addressof(st)))
-        return buf[:nb.value], off, rec, loff, links[:nl.value], removed[:n], {f: int(getattr(st, f)) for f, _ in CleanStats._fields_}
-
     def unitig_graph_clean(self, kmers: np.ndarray, counts: np.ndarray, k: int, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
         """kmx_unitig_graph_clean: unitig_graph() after tips (CLEAN_TIPS), islands (CLEAN_ISLANDS) and bubbles (CLEAN_BUBBLES) of at
         most max_tip / max_bubble k-mers (2 k when None) have been removed round by round -> (buf, offsets, rec, link_offsets,
         links, removed, stats): removed[i] is the round that removed listing entry i (0: it stays), stats a dict of kmx_clean_stats"""
-        kmers = np.ascontiguousarray(kmers, dtype=np.uint64)
-        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
-        n = counts.size
-        if kmers.size != n * ((int(k) + 31) // 32):
-            raise KmxError(-1, f"{kmers.size} words for {n} counts at k = {k}")
+        kmers, counts, n = self._host_listing(kmers, counts, k)
         P = self._clean_params(int(k), ops, max_tip, max_bubble, max_rounds)
-        return self._unitig_clean_host(lambda *a: self.L.kmx_unitig_graph_clean(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), C.addressof(P), *a), n)
+        return self._unitig_call(lambda *a: self.L.kmx_unitig_graph_clean(self.h, int(k), kmers.ctypes.data, counts.ctypes.data, n, int(thr), C.addressof(P), *a), False, links=True, n=n)
 
     def unitig_graph_clean_dev(self, d_kmers, d_counts, k: int, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
         """kmx_unitig_graph_clean_dev on torch tensors of the model's device (as unitigs_dev) -> torch tensors and the stats dict"""
-        n = d_counts.numel()
-        if d_kmers.numel() != n * ((int(k) + 31) // 32) or d_kmers.element_size() != 8 or d_counts.element_size() != 4:
-            raise KmxError(-1, f"{d_kmers.numel()} words for {n} counts at k = {k}")
-        d_kmers, d_counts = d_kmers.contiguous(), d_counts.contiguous()
+        d_kmers, d_counts, n = self._dev_listing(d_kmers, d_counts, k)
         P = self._clean_params(int(k), ops, max_tip, max_bubble, max_rounds)
-        return self._unitig_clean_dev(lambda *a: self.L.kmx_unitig_graph_clean_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), C.addressof(P), *a), n)
+        return self._unitig_call(lambda *a: self.L.kmx_unitig_graph_clean_dev(self.h, int(k), d_kmers.data_ptr(), d_counts.data_ptr(), n, int(thr), C.addressof(P), *a), True, links=True, n=n)
 
     def _count_listing_size(self):
         n = C.c_uint64(0)
@@ -1017,22 +969,18 @@ class KModel:
 
     def count_unitig_graph_clean(self, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
         """kmx_count_unitig_graph_clean: the cleaned unitig graph of the listing the last count_finish / init_reads kept"""
-        k = getattr(self, "_count_k", 0) or self.stats().k
-        P = self._clean_params(k, ops, max_tip, max_bubble, max_rounds)
-        return self._unitig_clean_host(lambda *a: self.L.kmx_count_unitig_graph_clean(self.h, int(thr), C.addressof(P), *a), self._count_listing_size())
+        P = self._clean_params(getattr(self, "_count_k", 0) or self.stats().k, ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitig_graph_clean(self.h, int(thr), C.addressof(P), *a), False, links=True, n=self._count_listing_size())
 
     def count_unitig_graph_clean_dev(self, thr: int = 1, ops: int = 7, max_tip=None, max_bubble=None, max_rounds: int = 16):
         """kmx_count_unitig_graph_clean_dev: the same, the output as torch tensors on the model's device"""
-        k = getattr(self, "_count_k", 0) or self.stats().k
-        P = self._clean_params(k, ops, max_tip, max_bubble, max_rounds)
-        return self._unitig_clean_dev(lambda *a: self.L.kmx_count_unitig_graph_clean_dev(self.h, int(thr), C.addressof(P), *a), self._count_listing_size())
+        P = self._clean_params(getattr(self, "_count_k", 0) or self.stats().k, ops, max_tip, max_bubble, max_rounds)
+        return self._unitig_call(lambda *a: self.L.kmx_count_unitig_graph_clean_dev(self.h, int(thr), C.addressof(P), *a), True, links=True, n=self._count_listing_size())
 
     def unitig_clean_phases(self) -> dict:
         """kmx_unitig_clean_last_phases: unitig_graph_phases() summed over the rounds of the last cleaning call, plus "clean", the
         seconds spent on the decisions and the removal"""
-        sec, rounds = (C.c_double * 6)(), C.c_uint64(0)
-        _chk(self.L.kmx_unitig_clean_last_phases(self.h, sec, C.byref(rounds)))
-        return {**{n: sec[i] for i, n in enumerate(UNITIG_CLEAN_PHASES)}, "rounds": int(rounds.value)}
+        return self._unitig_phases(self.L.kmx_unitig_clean_last_phases, UNITIG_CLEAN_PHASES)
 
     # ---- persistence
     # ---- mapping reads onto the unitigs (the rule: include/kmx.h): a session on the handle, begin .. seq_to_unitigs .. end

@@ -119,3 +119,21 @@ def test_entry_points_refuse_a_null_handle():
     assert b"null" in L.kmx_last_error()
     assert api.UNITIG_CLEAN_PHASES[:5] == api.UNITIG_GRAPH_PHASES and len(api.UNITIG_CLEAN_PHASES) == 6
     assert (api.CLEAN_TIPS, api.CLEAN_ISLANDS, api.CLEAN_BUBBLES, api.CLEAN_MAX_ROUNDS) == (1, 2, 4, 64)
+
+
+def test_all_twelve_unitig_entry_points_refuse_a_null_handle():
+    """one table over the three tiers and their four routes: a null handle is KMX_E_ARG whatever else is given, and neither
+    the counters nor the stats are written"""
+    L = api.load_library()
+    P = api.CleanParams(7, 42, 42, 16)
+    for tier, base in enumerate(("unitigs", "unitig_graph", "unitig_graph_clean")):
+        for counted in (False, True):
+            for dev in (False, True):
+                ctr = [C.c_uint64(7) for _ in range(3 if tier else 2)]
+                st = api.CleanStats(*[9] * 8)
+                args = [None] + ([] if counted else [31, None, None, 0]) + [1] + ([C.addressof(P)] if tier == 2 else []) + [None, 0, None, None, 0]
+                args += ([None, None, 0] if tier else []) + [C.byref(c) for c in ctr] + ([None, C.addressof(st)] if tier == 2 else [])
+                name = "kmx_" + ("count_" if counted else "") + base + ("_dev" if dev else "")
+                assert getattr(L, name)(*args) == -1, name
+                assert b"null" in L.kmx_last_error(), name
+                assert [c.value for c in ctr] == [7] * len(ctr) and all(getattr(st, f) == 9 for f, _ in api.CleanStats._fields_), name
