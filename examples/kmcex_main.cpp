@@ -12,6 +12,10 @@
 //     -M   with -u<thr>: read the input a second time (plain FASTA / FASTQ, not gzip, not @list) and map its reads onto the
 //          unitigs written (KModel::count_unitig_map_begin, seq_to_unitigs): reads.paths.tsv (read, start in read, windows,
 //          unitig, strand, offset) and unitigs.hits.tsv (unitig, mapped windows) beside unitigs.fa
+//     -W<max_gap>  with -M: also thread every read's segments through the graph (KModel::seq_walks; gaps of at most max_gap
+//          unmapped windows are bridged, k when omitted, with at most one base lost or gained per bridge): reads.gaf (one line
+//          per walk) and unitigs.links.tsv (link index, source, target, reads that cross it).  Implies the graph, as -G does;
+//          unitigs.gfa is still written only with -G
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -29,6 +33,7 @@ struct Params {
 	bool gpu_count = false, gfa = false, map = false;
 	long unitig_thr = -1;                                          // -u: the threshold, -1 = no unitigs
 	long clean_len = -1;                                           // -C: the cap of tips and bubbles in k-mers, 0 = 2 k, -1 = no cleaning
+	long walk_gap = -2;                                            // -W: max_gap, -1 = k, -2 = no walks
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -47,6 +52,11 @@ static bool parse(int argc, char **argv, Params &p)
 		else if (!strcmp(a, "-g")) p.gpu_count = true;
 		else if (!strcmp(a, "-G")) p.gfa = true;
 		else if (!strcmp(a, "-M")) p.map = true;
+		else if (!strncmp(a, "-W", 2)) {
+			char *end = nullptr;
+			p.walk_gap = a[2] ? strtol(a + 2, &end, 10) : -1;
+			if (a[2] && (*end || p.walk_gap < 0 || p.walk_gap > 0xFFFFFFFFL)) return false;   // not a number of windows
+		}
 		else if (!strncmp(a, "-C", 2)) {
 			char *end = nullptr;
 			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
@@ -66,6 +76,7 @@ static bool parse(int argc, char **argv, Params &p)
 	if (p.gfa && p.unitig_thr < 0) return false;                   // the graph is the unitigs' own
 	if (p.clean_len >= 0 && p.unitig_thr < 1) return false;        // cleaning removes nodes by "count below thr"
 	if (p.map && p.unitig_thr < 0) return false;                   // the reads are mapped onto the unitigs written
+	if (p.walk_gap > -2 && !p.map) return false;                   // the walks are built from the map's segments
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -109,7 +120,9 @@ int main(int argc, char **argv)
 		             "       -u<thr>  with -g and an odd k: write the unitigs of the k-mers with count >= thr (1) to <saved model>/unitigs.fa\n"
 		             "       -G  with -u<thr>: also write the unitigs and the edges between them as GFA 1 to <saved model>/unitigs.gfa\n"
 		             "       -C<len>  with -u<thr>, thr >= 1: clip tips, pop bubbles and drop islands of at most len k-mers (2 k) first\n"
-		             "       -M  with -u<thr>: map the reads of the (plain FASTA / FASTQ) input onto the unitigs: reads.paths.tsv, unitigs.hits.tsv\n";
+		             "       -M  with -u<thr>: map the reads of the (plain FASTA / FASTQ) input onto the unitigs: reads.paths.tsv, unitigs.hits.tsv\n"
+		             "       -W<max_gap>  with -M: join every read's segments into walks through the graph, bridging at most max_gap (k) unmapped windows:\n"
+		             "           reads.gaf, unitigs.links.tsv (link index, source, target, reads)\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -138,10 +151,11 @@ int main(int argc, char **argv)
 		std::vector<uint64_t> link_offsets;
 		std::vector<uint32_t> links;
 		kmx_clean_stats cs;
+		const bool walks = p.walk_gap > -2;
 		const uint32_t cap = (uint32_t)(p.clean_len > 0 ? p.clean_len : 2 * p.k);
 		const kmx_clean_params cp = {KMX_CLEAN_TIPS | KMX_CLEAN_ISLANDS | KMX_CLEAN_BUBBLES, cap, cap, 16};
 		const std::vector<std::string> strs = p.clean_len >= 0 ? km->count_unitig_graph_clean((uint32_t)p.unitig_thr, cp, &rec, &link_offsets, &links, &cs)
-		                                      : p.gfa          ? km->count_unitig_graph((uint32_t)p.unitig_thr, &rec, &link_offsets, &links)
+		                                      : p.gfa || walks ? km->count_unitig_graph((uint32_t)p.unitig_thr, &rec, &link_offsets, &links)
 		                                                       : km->count_unitigs((uint32_t)p.unitig_thr, &rec);
 		if (p.clean_len >= 0)
 			std::cout << "   cleaning (at most " << cap << " k-mers)        :     " << cs.rounds_run << " rounds" << (cs.converged ? "" : " (not converged)") << ", " << cs.n_tips << " tips, "
@@ -163,6 +177,12 @@ int main(int argc, char **argv)
 			const int c0 = in.peek();
 			if (!in || p.input[0] == '@' || (c0 != '>' && c0 != '@')) { std::cout << "-M reads a plain FASTA / FASTQ file, which " << p.input << " is not" << std::endl; return 1; }
 			std::ofstream paths((dir + "/reads.paths.tsv").c_str());
+			std::ofstream gaf;
+			if (walks) gaf.open((dir + "/reads.gaf").c_str());
+			const kmx_walk_params wp = {(uint32_t)(p.walk_gap >= 0 ? p.walk_gap : p.k), 1, {0, 0}};
+			std::vector<uint64_t> link_hits(links.size(), 0), walk_offsets;
+			std::vector<uint32_t> steps;
+			kmx_walk_stats wt = kmx_walk_stats();
 			std::vector<uint64_t> hits(strs.size(), 0), seg_offsets;
 			std::vector<std::string> reads;
 			uint64_t n_reads = 0, n_segs = 0, n_win = 0, n_mapped = 0;
@@ -175,6 +195,13 @@ int main(int argc, char **argv)
 				std::vector<uint64_t> off(reads.size() + 1, 0);
 				for (size_t i = 0; i < reads.size(); i++) { off[i + 1] = off[i] + reads[i].size(); n_win += rec_m[i].n_windows; n_mapped += rec_m[i].n_mapped; }
 				KModel::write_paths_tsv(paths, segs, seg_offsets, off, n_reads);
+				if (walks) {
+					kmx_walk_stats ws;
+					const std::vector<kmx_walk> wk = km->seq_walks(segs, seg_offsets, link_offsets, links, wp, &walk_offsets, &steps, &link_hits, &ws);
+					KModel::write_walks_gaf(gaf, wk, walk_offsets, steps, off, strs, p.k, n_reads);
+					wt.n_walks += ws.n_walks; wt.n_steps += ws.n_steps; wt.n_edge += ws.n_edge; wt.n_inside += ws.n_inside; wt.n_across += ws.n_across;
+					wt.n_unlinked += ws.n_unlinked; wt.n_breaks += ws.n_breaks;
+				}
 				n_reads += reads.size();
 				n_segs += segs.size();
 			}
@@ -185,6 +212,15 @@ int main(int argc, char **argv)
 			ht.close();
 			if (!paths || !ht) { std::cout << "could not write " << dir << "/reads.paths.tsv or unitigs.hits.tsv" << std::endl; return 1; }
 			std::cout << "   reads mapped onto the unitigs        :     " << n_reads << " reads, " << n_segs << " segments, " << n_mapped << " of " << n_win << " windows" << std::endl;
+			if (walks) {
+				gaf.close();
+				std::ofstream lt((dir + "/unitigs.links.tsv").c_str());
+				KModel::write_link_hits_tsv(lt, link_offsets, links, link_hits);
+				lt.close();
+				if (!gaf || !lt) { std::cout << "could not write " << dir << "/reads.gaf or unitigs.links.tsv" << std::endl; return 1; }
+				std::cout << "   walks (gaps of at most " << wp.max_gap << " windows)    :     " << wt.n_walks << " walks, " << wt.n_steps << " steps, " << wt.n_edge << " edges crossed, " << wt.n_inside + wt.n_across
+				          << " gaps bridged (" << wt.n_across << " across an edge), " << wt.n_breaks << " breaks" << std::endl;
+			}
 		}
 	}
 	delete km;

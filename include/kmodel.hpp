@@ -417,6 +417,65 @@ public:
 		for (size_t u = 0; u < hits.size(); u++) out << "u" << u << "\t" << hits[u] << "\n";
 	}
 
+	// The walks of mapped reads (the rule: kmx.h), inside the map session: seq_walks takes the vectors seq_to_unitigs returned and
+	// the CSR of the graph the session's unitigs came from, and returns one kmx_walk per walk in ascending position; walk_offsets
+	// [n + 1] is their CSR by read, steps the oriented unitigs of every walk back to back, and link_hits, which it ADDS the reads
+	// per traversed link to (the caller sizes it to links and zeroes it).  It gives room for every segment, so it never comes back
+	// short.
+	std::vector<kmx_walk> seq_walks(const std::vector<kmx_map_segment> &segs, const std::vector<uint64_t> &seg_offsets, const std::vector<uint64_t> &link_offsets,
+	                                const std::vector<uint32_t> &links, const kmx_walk_params &params, std::vector<uint64_t> *walk_offsets = 0, std::vector<uint32_t> *steps = 0,
+	                                std::vector<uint64_t> *link_hits = 0, kmx_walk_stats *stats = 0)
+	{
+		std::vector<kmx_walk> walks(segs.size() + 1);
+		std::vector<uint32_t> st(segs.size() + 1);
+		std::vector<uint64_t> wo(seg_offsets.empty() ? 1 : seg_offsets.size(), 0);
+		kmx_walk_stats ws = kmx_walk_stats();
+		if (seg_offsets.size() > 1)
+			check(kmx_unitig_walk_segs(h_, segs.empty() ? 0 : &segs[0], segs.size(), &seg_offsets[0], seg_offsets.size() - 1, link_offsets.empty() ? 0 : &link_offsets[0],
+			                           links.empty() ? 0 : &links[0], links.size(), &params, &walks[0], segs.size(), &wo[0], &st[0], segs.size(),
+			                           link_hits && !link_hits->empty() ? &(*link_hits)[0] : 0, &ws));
+		walks.resize((size_t)ws.n_walks);
+		st.resize((size_t)ws.n_steps);
+		if (walk_offsets) walk_offsets->swap(wo);
+		if (steps) steps->swap(st);
+		if (stats) *stats = ws;
+		return walks;
+	}
+	// the walks as GAF, one line per walk: the read (first_read + its index in the batch, as write_paths_tsv names it), its length,
+	// query start and end, '+', the path (">u<N>" / "<u<N>" per step, the names of write_unitigs_gfa), the path's length (the m of
+	// its steps + k - 1), start (off_first) and end (the m of all steps but the last + off_last + k), matches (n_covered: a lower
+	// bound), block length (the larger of the two spans), MAPQ 255, id:i:<indel> and bg:i:<bridges>.  offsets [n + 1] are the
+	// batch's own, strs the unitigs of the session.
+	static void write_walks_gaf(std::ostream &out, const std::vector<kmx_walk> &walks, const std::vector<uint64_t> &walk_offsets, const std::vector<uint32_t> &steps,
+	                            const std::vector<uint64_t> &offsets, const std::vector<std::string> &strs, int k, uint64_t first_read = 0)
+	{
+		for (size_t i = 0; i + 1 < walk_offsets.size() && i + 1 < offsets.size(); i++)
+			for (uint64_t e = walk_offsets[i]; e < walk_offsets[i + 1] && e < walks.size(); e++) {
+				const kmx_walk &w = walks[(size_t)e];
+				const uint64_t q0 = w.pos - offsets[i], q1 = q0 + w.n_span + (uint64_t)k - 1;
+				uint64_t sum_m = 0, m_last = 0;
+				out << first_read + i << "\t" << offsets[i + 1] - offsets[i] << "\t" << q0 << "\t" << q1 << "\t+\t";
+				for (uint64_t s = w.first_step; s < w.first_step + w.n_steps && s < steps.size(); s++) {
+					const uint32_t o = steps[(size_t)s];
+					m_last = (o >> 1) < strs.size() ? (uint64_t)strs[o >> 1].size() - (uint64_t)k + 1 : 0;
+					sum_m += m_last;
+					out << ((o & 1) ? '<' : '>') << "u" << (o >> 1);
+				}
+				const uint64_t p0 = w.off_first, p1 = sum_m - m_last + w.off_last + (uint64_t)k;
+				out << "\t" << sum_m + (uint64_t)k - 1 << "\t" << p0 << "\t" << p1 << "\t" << w.n_covered << "\t" << (q1 - q0 > p1 - p0 ? q1 - q0 : p1 - p0) << "\t255\tid:i:" << w.indel
+				    << "\tbg:i:" << w.n_inside + w.n_across << "\n";
+			}
+	}
+	// ... and the reads per link, one "<link index>\tu<source><+|->\tu<target><+|->\t<reads>" per link of the CSR
+	static void write_link_hits_tsv(std::ostream &out, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links, const std::vector<uint64_t> &link_hits)
+	{
+		for (uint64_t a = 0; a + 1 < link_offsets.size(); a++)
+			for (uint64_t e = link_offsets[a]; e < link_offsets[a + 1] && e < links.size() && e < link_hits.size(); e++) {
+				const uint32_t b = links[(size_t)e];
+				out << e << "\tu" << (a >> 1) << ((a & 1) ? '-' : '+') << "\tu" << (b >> 1) << ((b & 1) ? '-' : '+') << "\t" << link_hits[(size_t)e] << "\n";
+			}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -688,7 +688,7 @@ int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds /* [5] */, uint64
  *   4. A no-op is exact: with nothing to remove the output is byte for byte that of kmx_unitig_graph, rounds_run = 1,
  *      converged = 1.
  * Out of scope: bubbles whose arms hold more than one unitig; coverage-ratio or mean-coverage criteria and low-coverage edge
- * removal; P / W lines; several GPUs; choosing thr and the caps.                                                          */
+ * removal (the reads per link that it starts from: kmx_unitig_walk_segs); several GPUs; choosing thr and the caps.        */
 #define KMX_CLEAN_TIPS        1
 #define KMX_CLEAN_ISLANDS     2
 #define KMX_CLEAN_BUBBLES     4
@@ -760,8 +760,8 @@ int kmx_unitig_clean_last_phases(kmx_model *m, double *seconds /* [6] */, uint64
  *   (c) on a cleaned graph, a window whose k-mer is listed is unmapped exactly when its entry has removed[i] != 0 or a count
  *       below thr.
  * Out of scope: even k; mismatches or indels between read and graph (a read with an error maps on both sides of it, with a
- * gap of unmapped windows between: polish first); joining segments across gaps; GFA P / W lines (a read starts and ends
- * mid-unitig, which those lines cannot say); paired reads; several GPUs.                                                  */
+ * gap of unmapped windows between: polish first, or let kmx_unitig_walk_segs below bridge the gap); paired reads; several
+ * GPUs.                                                                                                                   */
 typedef struct kmx_map_segment {         /* 24 bytes, no padding */
 	uint64_t pos;                        /* flat position of its first window */
 	uint32_t n_windows;
@@ -810,6 +810,76 @@ int kmx_unitig_map_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_o
                             uint64_t *n_segs /* HOST */, uint64_t *d_seg_offsets /* [n_seqs + 1] */, kmx_seq_map *d_rec /* or NULL */, uint64_t *d_hits /* [n_unitigs] or NULL */);
 /* ends the session and frees its index; KMX_E_STATE outside one */
 int kmx_unitig_map_end(kmx_model *m);
+
+/* ---- walks: the segments of every read threaded through the unitig graph.  A post-pass on what kmx_unitig_map_seqs[_dev]
+ * wrote, inside the map session, which holds k, U and m_u; it reads no bases.
+ * Input: the segments of a batch (segs[n_segs], seg_offsets[n_seqs + 1]) exactly as the map call wrote them; the CSR of the graph
+ *   the session's unitig set came from (link_offsets[2 U + 1], links[n_links]; out[o] is the row of oriented unitig o); and
+ *   kmx_walk_params, with max_indel in [0, 255] and reserved = 0 (KMX_E_ARG otherwise).
+ * Joins.  For two consecutive segments A, B of one read, in signed 64-bit arithmetic: mA = m_(A.o >> 1),
+ *   endA = A.off + A.n_windows - 1, g = B.pos - A.pos - A.n_windows (the unmapped windows between them), row = out[A.o].
+ *   g == 0: the join is an EDGE iff endA == mA - 1, B.off == 0 and B.o occurs in row, at link index e; otherwise there is no join
+ *     and n_unlinked counts it.
+ *   1 <= g <= max_gap: it is INSIDE iff B.o == A.o, B.off > endA and |d| <= max_indel with d = (B.off - endA - 1) - g; else
+ *     ACROSS iff B.o occurs in row, at link index e, and |d| <= max_indel with d = (mA - 1 - endA) + B.off - g; else there is no
+ *     join and n_breaks counts it.  d is the number of path windows in the gap minus the number of read windows: a base the read
+ *     lost gives d = +1, a surplus base d = -1, a substitution d = 0.
+ *   g > max_gap or g < 0: no join, counted by n_breaks.
+ * A WALK is a maximal chain of joined segments of one read.  A STEP is an oriented unitig of its path: one for the walk's first
+ *   segment and one more for every EDGE or ACROSS join; INSIDE adds none.  Going round a circular unitig is an EDGE join o -> o.
+ *   With max_gap = 0 only exact traversals join.
+ * Every decision looks at one segment, its predecessor and one row of at most 4 entries, and all outputs are integer sums: a
+ * function of (segments, CSR, m_u, parameters) alone, byte-identical across runs and variants.  Consequences:
+ *   (a) with the CSR of the session's own graph n_unlinked is 0: two segments with g == 0 are neighbouring mapped windows, so
+ *       their k-mers are joined by an oriented edge of the node graph, and "the oriented edges of the node graph are exactly the
+ *       links inside unitigs plus the edges reported here" (the unitig graph above); a link inside a unitig does not start a
+ *       segment, so the edge is a reported one, leaving the last window of A.o for the first of B.o;
+ *   (b) a walk without INSIDE or ACROSS joins spells its read: the steps' oriented strings, concatenated with k - 1 bytes of
+ *       overlap, hold the read's bytes [pos, pos + n_span + k - 1), upper-cased, from off_first on, and n_covered is that length;
+ *   (c) the walks of the reverse complement of a read are the read's own, mirrored: in reverse order, steps reversed with o ^ 1,
+ *       and every +1 of link_hits on the mirror edge (b ^ 1) -> (a ^ 1) of a -> b; link_hits counts the traversed edge only, the
+ *       mirror edge is the caller's to add.
+ * Out of scope: gaps that span a whole unitig (a bridge crosses at most one edge); comparing the bases inside a gap (a bridge
+ * is accepted on its geometry alone); paired reads; several GPUs.                                                          */
+typedef struct kmx_walk_params { uint32_t max_gap, max_indel, reserved[2]; } kmx_walk_params;                  /* 16 bytes */
+typedef struct kmx_walk {                /* one per walk, in ascending pos; 80 bytes */
+	uint64_t pos;                        /* flat position of its first window */
+	uint64_t n_span;                     /* windows from its first to its last mapped window, inclusive */
+	uint64_t n_mapped;                   /* the sum of its segments' n_windows */
+	uint64_t n_covered;                  /* sum of (n_windows + k - 1) minus, per join, max(0, k - 1 - g): the read bases inside a mapped
+	                                        window, which match the path by consequence (a) of the map; a lower bound of the matches */
+	uint64_t first_seg, first_step;      /* its segments are segs[first_seg .. first_seg + n_segs), its steps steps[first_step .. + n_steps) */
+	uint32_t n_segs, n_steps;
+	uint32_t off_first;                  /* the offset of its first window in its first step */
+	uint32_t off_last;                   /* the offset of its last window in its last step */
+	uint32_t n_inside, n_across;
+	int32_t indel;                       /* the sum of d over its joins */
+	uint32_t reserved;                   /* 0 */
+} kmx_walk;
+typedef struct kmx_walk_stats { uint64_t n_walks, n_steps, n_edge, n_inside, n_across, n_unlinked, n_breaks, reserved; } kmx_walk_stats;   /* 64 bytes */
+/* walks[walk_capacity] receives the walks, walk_offsets[n_seqs + 1] their CSR by read (walk_offsets[r] is the number of the walk
+ * that starts at seg_offsets[r]), steps[step_capacity] the steps (the o of each), back to back in walk order, and link_hits
+ * [n_links] (or NULL) is ADDED to: +1 at e for every EDGE and ACROSS join, so a caller accumulates over batches and zeroes the
+ * array itself.  stats (HOST in both forms, required) receives the counts.  walks == NULL: the sizing call (steps is not read).
+ * More walks than walk_capacity or more steps than step_capacity: KMX_E_RANGE; stats, walk_offsets and link_hits are complete,
+ * the content of walks and steps is unspecified and nothing is written at or behind either capacity; n_segs always suffices for
+ * both.  Outside a session: KMX_E_STATE.  KMX_E_NOMEM leaves the handle and the session usable.  n_seqs == 0: KMX_OK, all-zero
+ * stats, nothing else written.  The host form checks seg_offsets (first 0, non-decreasing, last n_segs) and the CSR
+ * (link_offsets[0] == 0, non-decreasing, link_offsets[2 U] == n_links, every links[e] < 2 U): KMX_E_ARG.  The _dev form reads
+ * d_segs and d_seg_offsets where the map call left them and d_link_offsets and d_links where the graph call left them, and
+ * clamps instead: seg_offsets into [0, n_segs], row bounds into [0, n_links], at most 4 entries of a row are read, and a segment
+ * with o >= 2 U joins nothing and has no m_u looked up; bad input gives wrong walks, never an access outside the buffers.  It
+ * enqueues everything on the model's stream and waits once, for the counts.  Device memory: 21 bytes per segment (a flag byte,
+ * the join's d and overlap, the scanned pair of walk and step starts) plus the scan's scratch, kept on the handle between calls
+ * until the session ends; the host form also stages its input and output there.                                           */
+int kmx_unitig_walk_segs(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets /* [n_seqs + 1] */, uint64_t n_seqs,
+                         const uint64_t *link_offsets /* [2 U + 1] */, const uint32_t *links, uint64_t n_links, const kmx_walk_params *params,
+                         kmx_walk *walks /* or NULL */, uint64_t walk_capacity, uint64_t *walk_offsets /* [n_seqs + 1] */, uint32_t *steps, uint64_t step_capacity,
+                         uint64_t *link_hits /* [n_links] or NULL */, kmx_walk_stats *stats);
+int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets /* [n_seqs + 1] */, uint64_t n_seqs,
+                             const uint64_t *d_link_offsets /* [2 U + 1] */, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params /* HOST */,
+                             kmx_walk *d_walks /* or NULL */, uint64_t walk_capacity, uint64_t *d_walk_offsets /* [n_seqs + 1] */, uint32_t *d_steps, uint64_t step_capacity,
+                             uint64_t *d_link_hits /* [n_links] or NULL */, kmx_walk_stats *stats /* HOST */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

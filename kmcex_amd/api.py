@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_graph", "kmx_unitig_graph_dev", "kmx_count_unitig_graph", "kmx_count_unitig_graph_dev", "kmx_unitig_graph_last_phases",
     "kmx_unitig_graph_clean", "kmx_unitig_graph_clean_dev", "kmx_count_unitig_graph_clean", "kmx_count_unitig_graph_clean_dev", "kmx_unitig_clean_last_phases",
     "kmx_unitig_map_begin", "kmx_unitig_map_begin_dev", "kmx_count_unitig_map_begin", "kmx_count_unitig_map_begin_dev", "kmx_unitig_map_seqs", "kmx_unitig_map_seqs_dev", "kmx_unitig_map_end",
+    "kmx_unitig_walk_segs", "kmx_unitig_walk_segs_dev",
 ]
 
 
@@ -126,6 +127,30 @@ class SeqMap(C.Structure):
 # the same two as NumPy structured dtypes (what KModel.seq_to_unitigs returns)
 SEQ_SEGMENT_DTYPE = np.dtype([("pos", "<u8"), ("n_windows", "<u4"), ("o", "<u4"), ("off", "<u4"), ("reserved", "<u4")])
 SEQ_MAP_DTYPE = np.dtype([(f, "<u8") for f in ("n_windows", "n_mapped", "n_segments", "n_gaps", "first_mapped", "last_mapped", "longest", "reserved")])
+
+
+class WalkParams(C.Structure):
+    """kmx_walk_params of include/kmx.h: 16 bytes"""
+    _fields_ = [("max_gap", C.c_uint32), ("max_indel", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class Walk(C.Structure):
+    """kmx_walk of include/kmx.h: a maximal chain of joined segments of one read, 80 bytes"""
+    _fields_ = ([(f, C.c_uint64) for f in ("pos", "n_span", "n_mapped", "n_covered", "first_seg", "first_step")] +
+                [(f, C.c_uint32) for f in ("n_segs", "n_steps", "off_first", "off_last", "n_inside", "n_across")] + [("indel", C.c_int32), ("reserved", C.c_uint32)])
+
+
+class WalkStats(C.Structure):
+    """kmx_walk_stats of include/kmx.h: 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_walks", "n_steps", "n_edge", "n_inside", "n_across", "n_unlinked", "n_breaks", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_walk as a NumPy structured dtype (what KModel.unitig_walks_flat returns)
+WALK_DTYPE = np.dtype([(f, "<u8") for f in ("pos", "n_span", "n_mapped", "n_covered", "first_seg", "first_step")] +
+                      [(f, "<u4") for f in ("n_segs", "n_steps", "off_first", "off_last", "n_inside", "n_across")] + [("indel", "<i4"), ("reserved", "<u4")])
 
 
 class RingList(C.Structure):
@@ -269,6 +294,8 @@ def load_library():
     _sig(L, "kmx_unitig_map_seqs", [vp, vp, vp, u64, vp, u64, C.POINTER(u64), vp, vp, vp])
     _sig(L, "kmx_unitig_map_seqs_dev", [vp, vp, vp, u64, u64, vp, u64, C.POINTER(u64), vp, vp, vp])
     _sig(L, "kmx_unitig_map_end", [vp])
+    _sig(L, "kmx_unitig_walk_segs", [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(WalkParams), vp, u64, vp, vp, u64, vp, C.POINTER(WalkStats)])
+    _sig(L, "kmx_unitig_walk_segs_dev", [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(WalkParams), vp, u64, vp, vp, u64, vp, C.POINTER(WalkStats)])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -1053,6 +1080,52 @@ class KModel:
                                             d_seg_offsets.data_ptr(), d_rec.data_ptr() if d_rec is not None else None, d_hits.data_ptr() if d_hits is not None else None))
         return ns.value, d_seg_offsets
 
+    # ---- walks: the segments of a batch threaded through the unitig graph (the rule: include/kmx.h), inside the map session
+    def unitig_walks_flat(self, segs: np.ndarray, seg_offsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, max_gap: int, max_indel: int = 1,
+                          walk_capacity=None, step_capacity=None, link_hits=None):
+        """kmx_unitig_walk_segs on what seq_to_unitigs_flat returned and the CSR of the graph the session's unitigs came from ->
+        (WALK_DTYPE walks, uint64 walk_offsets [n_seqs + 1], uint32 steps, stats as a dict).  link_hits (uint64 [n_links], optional)
+        is ADDED to.  Capacities None: room for every segment, so the call never comes back short."""
+        segs = np.ascontiguousarray(segs, dtype=SEQ_SEGMENT_DTYPE)
+        seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        n_seqs = seg_offsets.size - 1
+        wcap = segs.size if walk_capacity is None else int(walk_capacity)
+        scap = segs.size if step_capacity is None else int(step_capacity)
+        walks = np.zeros(wcap, dtype=WALK_DTYPE)
+        steps = np.zeros(scap, dtype=np.uint32)
+        wo = np.zeros(n_seqs + 1, dtype=np.uint64)
+        if link_hits is not None and (link_hits.dtype != np.uint64 or not link_hits.flags.c_contiguous or link_hits.size < links.size):
+            raise KmxError(-1, "link_hits must be a contiguous uint64 array with one entry per link")
+        par, st = WalkParams(int(max_gap), int(max_indel)), WalkStats()
+        _chk(self.L.kmx_unitig_walk_segs(self.h, segs.ctypes.data, segs.size, seg_offsets.ctypes.data, n_seqs, link_offsets.ctypes.data, links.ctypes.data, links.size, C.byref(par),
+                                         walks.ctypes.data, wcap, wo.ctypes.data, steps.ctypes.data, scap, link_hits.ctypes.data if link_hits is not None else None, C.byref(st)))
+        return walks[:st.n_walks].copy(), wo, steps[:st.n_steps].copy(), st.as_dict()
+
+    def unitig_walks_dev(self, d_segs, n_segs: int, d_seg_offsets, d_link_offsets, d_links, max_gap: int, max_indel: int = 1, d_walks=None, d_steps=None, d_walk_offsets=None,
+                         d_link_hits=None):
+        """kmx_unitig_walk_segs_dev on torch tensors of the model's device, read where seq_to_unitigs_dev and the graph call left
+        them: d_segs uint8 [capacity, 24] holding n_segs segments, d_seg_offsets int64 [n_seqs + 1], d_link_offsets int64
+        [2 U + 1], d_links int32 [n_links]; d_walks uint8 [walk_capacity, 80] (None: the sizing call) with d_steps int32
+        [step_capacity], d_walk_offsets int64 [n_seqs + 1] (None: allocated), d_link_hits int64 [n_links] or None (added to)
+        -> (stats as a dict, d_walk_offsets)."""
+        import torch
+        n_seqs = d_seg_offsets.numel() - 1
+        if d_walk_offsets is None:
+            d_walk_offsets = torch.zeros(n_seqs + 1, dtype=torch.int64, device=d_seg_offsets.device)
+        par, st = WalkParams(int(max_gap), int(max_indel)), WalkStats()
+        _chk(self.L.kmx_unitig_walk_segs_dev(self.h, d_segs.data_ptr() if d_segs is not None else None, int(n_segs), d_seg_offsets.data_ptr(), n_seqs, d_link_offsets.data_ptr(),
+                                             d_links.data_ptr(), d_links.numel(), C.byref(par), d_walks.data_ptr() if d_walks is not None else None,
+                                             d_walks.shape[0] if d_walks is not None else 0, d_walk_offsets.data_ptr(), d_steps.data_ptr() if d_steps is not None else None,
+                                             d_steps.numel() if d_steps is not None else 0, d_link_hits.data_ptr() if d_link_hits is not None else None, C.byref(st)))
+        return st.as_dict(), d_walk_offsets
+
+    def seq_to_walks(self, reads, link_offsets: np.ndarray, links: np.ndarray, max_gap: int, max_indel: int = 1, link_hits=None):
+        """seq_to_unitigs, then unitig_walks_flat on its segments -> (walks, walk_offsets, steps, stats, segments, seg_offsets)"""
+        segs, so, _ = self.seq_to_unitigs(reads)
+        walks, wo, steps, st = self.unitig_walks_flat(segs, so, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
+        return walks, wo, steps, st, segs, so
 
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173
         _chk(self.L.kmx_save(self.h, save_dir.encode()))

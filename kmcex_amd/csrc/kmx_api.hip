@@ -374,6 +374,10 @@ struct kmx_model {
 		DevBuf<u64> d_code, d_spos, d_state;                       // per chunk: codes, segment starts; [2] segments so far, the open segment's start
 		DevBuf<u32> d_ex;                                          // the scanned start flags
 		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
+		DevBuf<unsigned char> d_wflag;                             // kmx_unitig_walk_segs*, per segment: the flag byte, ...
+		DevBuf<u32> d_wjoin;                                       // ... the join's overlap and d, ...
+		DevBuf<WalkTot> d_wsc;                                     // ... [n_segs + 1] the walk and step starts in front of it; ...
+		DevBuf<unsigned long long> d_wcnt;                         // ... [WALK_C_N] the call's counters
 	} map;
 };
 
@@ -384,6 +388,7 @@ static void map_drop(kmx_model *m)
 	if (S.d_start || S.d_place || S.d_code || S.d_km) hipStreamSynchronize(m->stream);
 	S.d_km.reset(); S.d_start.reset(); S.d_mu.reset(); S.d_err.reset(); S.d_place.reset();
 	S.d_code.reset(); S.d_spos.reset(); S.d_state.reset(); S.d_ex.reset(); S.d_tmp.reset();
+	S.d_wflag.reset(); S.d_wjoin.reset(); S.d_wsc.reset(); S.d_wcnt.reset();
 	S.dev = MapDev{};
 	S.on = S.from_count = false;
 }
@@ -3445,6 +3450,8 @@ extern "C" int kmx_count_unitig_map_begin(kmx_model *m, const char *useq, const 
 extern "C" int kmx_unitig_map_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, kmx_map_segment *d_segs, uint64_t capacity, uint64_t *n_segs, uint64_t *d_seg_offsets, kmx_seq_map *d_rec, uint64_t *d_hits) { return guarded([&] { return kmx_unitig_map_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_segs, capacity, n_segs, d_seg_offsets, d_rec, d_hits); }); }
 extern "C" int kmx_unitig_map_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, kmx_map_segment *segs, uint64_t capacity, uint64_t *n_segs, uint64_t *seg_offsets, kmx_seq_map *rec, uint64_t *hits) { return guarded([&] { return kmx_unitig_map_seqs_impl(m, seq, offsets, n_seqs, segs, capacity, n_segs, seg_offsets, rec, hits); }); }
 extern "C" int kmx_unitig_map_end(kmx_model *m) { return guarded([&] { return kmx_unitig_map_end_impl(m); }); }
+extern "C" int kmx_unitig_walk_segs(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets, uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_impl(m, segs, n_segs, seg_offsets, n_seqs, link_offsets, links, n_links, params, walks, walk_capacity, walk_offsets, steps, step_capacity, link_hits, stats); }); }
+extern "C" int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets, uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_dev_impl(m, d_segs, n_segs, d_seg_offsets, n_seqs, d_link_offsets, d_links, n_links, params, d_walks, walk_capacity, d_walk_offsets, d_steps, step_capacity, d_link_hits, stats); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

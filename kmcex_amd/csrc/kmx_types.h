@@ -390,6 +390,46 @@ struct MapOut {
 	u64 *so;
 	SeqMap *rec;
 };
+// kmx_unitig_walk_segs*: a walk, the layout of kmx_walk (include/kmx.h; map_host.h asserts it) ...
+struct Walk {
+	u64 pos, n_span, n_mapped, n_covered, first_seg, first_step;
+	u32 n_segs, n_steps, off_first, off_last, n_inside, n_across;
+	int indel;
+	u32 reserved;
+};
+// ... the scanned pair per segment: the walks and the steps that start in front of it ...
+struct WalkTot {
+	u64 w, s;
+};
+// ... what a segment's flag byte says of it and of the join with its predecessor ...
+enum { WALK_START = 1, WALK_STEP = 2, WALK_EDGE = 4, WALK_INSIDE = 8, WALK_ACROSS = 16 };
+// ... the counters of a call, in the order of kmx_walk_stats behind n_walks and n_steps ...
+enum { WALK_C_EDGE = 0, WALK_C_INSIDE, WALK_C_ACROSS, WALK_C_UNLINKED, WALK_C_BREAKS, WALK_C_N };
+// ... and the input, the work arrays (flag[n_segs], join[n_segs] = overlap << 16 | (d & 0xFFFF), sc[n_segs + 1], cnt[WALK_C_N])
+// and the output of one call (walk_kernels.h).  Every array of the caller is read and written under the bounds given here.
+struct WalkDev {
+	const MapSeg *segs;
+	u64 n_segs;
+	const u64 *so;               // [n_seqs + 1]
+	u64 n_seqs;
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	u64 n_links;
+	const u32 *mu;               // [U]
+	u64 U;
+	int k;
+	u32 max_gap, max_indel;
+	unsigned char *flag;
+	u32 *join;
+	WalkTot *sc;
+	unsigned long long *cnt;
+	Walk *walks;                 // [walk_cap], null with walk_cap = 0 in the sizing call
+	u64 walk_cap;
+	u64 *wo;                     // [n_seqs + 1]
+	u32 *steps;                  // [step_cap]
+	u64 step_cap;
+	unsigned long long *link_hits;   // [n_links] or null
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

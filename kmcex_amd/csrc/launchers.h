@@ -87,4 +87,6 @@ void map_index(const MapDev &, const unsigned char *, const u64 *, u64, hipStrea
 void map_rec_init(SeqMap *, u64, hipStream_t);
 hipError_t map_chunk(const MapDev &, const SeqView &, u64, u64, const MapChunk &, const MapOut &, unsigned long long *, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t map_finish(const MapOut &, const u64 *, u64, u64, int, DevBuf<unsigned char> &tmp, hipStream_t);
+// ... and kmx_unitig_walk_segs*: the walks of a batch's segments (walk_kernels.h); the totals land in D.sc[D.n_segs] and D.cnt
+hipError_t walk_segs(const WalkDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 }   // namespace kmxk

@@ -264,3 +264,126 @@ static int kmx_unitig_map_seqs_impl(kmx_model *m, const char *seq, const uint64_
 	HIPCHK(hipStreamSynchronize(st));
 	return KMX_OK;
 }
+
+// ---- kmx_unitig_walk_segs*: the walks of a batch's segments (the rule: include/kmx.h; the kernels: walk_kernels.h).  A post-pass
+// inside the session: the work arrays grow with n_segs and stay on the handle, everything is enqueued on the model's stream, and
+// one wait brings the two totals and the five counters to the host.
+static_assert(sizeof(kmx_walk) == 80 && sizeof(Walk) == 80 && sizeof(kmx_walk_stats) == 64 && sizeof(kmx_walk_params) == 16 && sizeof(WalkTot) == 16, "kmx_walk is 80 bytes, kmx_walk_stats 64, kmx_walk_params 16");
+static_assert(offsetof(kmx_walk, first_seg) == offsetof(Walk, first_seg) && offsetof(kmx_walk, n_segs) == offsetof(Walk, n_segs) && offsetof(kmx_walk, off_last) == offsetof(Walk, off_last) &&
+              offsetof(kmx_walk, n_across) == offsetof(Walk, n_across) && offsetof(kmx_walk, indel) == offsetof(Walk, indel), "Walk (kmx_types.h) is the layout of kmx_walk");
+
+static int walk_args(kmx_model *m, const char *who, const kmx_walk_params *p, kmx_walk_stats *stats)
+{
+	TRY(map_session(m, who));
+	if (!p || !stats) return fail(KMX_E_ARG, "null argument");
+	if (p->max_indel > 255) return fail(KMX_E_ARG, "max_indel = %u: at most 255", p->max_indel);
+	if (p->reserved[0] || p->reserved[1]) return fail(KMX_E_ARG, "kmx_walk_params.reserved is not 0");
+	*stats = kmx_walk_stats{0, 0, 0, 0, 0, 0, 0, 0};
+	return KMX_OK;
+}
+
+// the pass on device buffers (D: input, parameters and output; the session's part and the work arrays are filled in here)
+static int walk_core(kmx_model *m, WalkDev D, kmx_walk_stats *stats)
+{
+	auto &S = m->map;
+	const hipStream_t st = m->stream;
+	if (!D.n_segs) {
+		HIPCHK(hipMemsetAsync(D.wo, 0, (D.n_seqs + 1) * 8, st));
+		HIPCHK(hipStreamSynchronize(st));
+		return KMX_OK;
+	}
+	if (S.d_wflag.ensure(D.n_segs, st) != hipSuccess || S.d_wjoin.ensure(D.n_segs, st) != hipSuccess || S.d_wsc.ensure(D.n_segs + 1, st) != hipSuccess || S.d_wcnt.ensure(WALK_C_N, st) != hipSuccess)
+		return map_nomem();
+	D.mu = S.dev.mu; D.U = S.dev.U; D.k = S.dev.d.k;
+	D.flag = S.d_wflag; D.join = S.d_wjoin; D.sc = S.d_wsc; D.cnt = S.d_wcnt;
+	const hipError_t e = kmxk::walk_segs(D, S.d_tmp, st);
+	if (e != hipSuccess) return map_dev_fail(e);
+	WalkTot tot{0, 0};
+	unsigned long long c[WALK_C_N] = {0, 0, 0, 0, 0};
+	HIPCHK(hipMemcpyAsync(&tot, D.sc + D.n_segs, sizeof tot, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipMemcpyAsync(c, D.cnt, sizeof c, hipMemcpyDeviceToHost, st));
+	HIPCHK(hipStreamSynchronize(st));                              // the call's one wait
+	*stats = kmx_walk_stats{tot.w, tot.s, c[WALK_C_EDGE], c[WALK_C_INSIDE], c[WALK_C_ACROSS], c[WALK_C_UNLINKED], c[WALK_C_BREAKS], 0};
+	if (D.walks && (tot.w > D.walk_cap || tot.s > D.step_cap))
+		return fail(KMX_E_RANGE, "%llu walks and %llu steps, the buffers hold %llu and %llu", (unsigned long long)tot.w, (unsigned long long)tot.s, (unsigned long long)D.walk_cap, (unsigned long long)D.step_cap);
+	return KMX_OK;
+}
+
+static int kmx_unitig_walk_segs_dev_impl(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets,
+                                         const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets,
+                                         uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats)
+{
+	TRY(walk_args(m, "kmx_unitig_walk_segs_dev", params, stats));
+	if (!n_seqs) return KMX_OK;
+	if (!d_seg_offsets || !d_walk_offsets || (n_segs && !d_segs) || !d_link_offsets || (n_links && !d_links) || (d_walks && !d_steps)) return fail(KMX_E_ARG, "null argument");
+	HIPCHK(hipSetDevice(m->device));
+	WalkDev D{};
+	D.segs = (const MapSeg *)d_segs; D.n_segs = n_segs; D.so = (const u64 *)d_seg_offsets; D.n_seqs = n_seqs;
+	D.loffs = (const u64 *)d_link_offsets; D.links = d_links; D.n_links = n_links;
+	D.max_gap = params->max_gap; D.max_indel = params->max_indel;
+	D.walks = (Walk *)d_walks; D.walk_cap = d_walks ? walk_capacity : 0; D.wo = (u64 *)d_walk_offsets;
+	D.steps = d_walks ? d_steps : nullptr; D.step_cap = d_walks ? step_capacity : 0;
+	D.link_hits = (unsigned long long *)d_link_hits;
+	return walk_core(m, D, stats);
+}
+
+static int kmx_unitig_walk_segs_impl(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets,
+                                     const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets,
+                                     uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats)
+{
+	TRY(walk_args(m, "kmx_unitig_walk_segs", params, stats));
+	if (!n_seqs) return KMX_OK;
+	auto &S = m->map;
+	const u64 U = S.dev.U;
+	TRY(check_offsets(seg_offsets, n_seqs));
+	if (seg_offsets[n_seqs] != n_segs) return fail(KMX_E_ARG, "seg_offsets end at %llu, not at n_segs = %llu", (unsigned long long)seg_offsets[n_seqs], (unsigned long long)n_segs);
+	TRY(check_offsets(link_offsets, 2 * U));
+	if (link_offsets[2 * U] != n_links) return fail(KMX_E_ARG, "link_offsets end at %llu, not at n_links = %llu", (unsigned long long)link_offsets[2 * U], (unsigned long long)n_links);
+	if (!walk_offsets || (n_segs && !segs) || (n_links && !links) || (walks && !steps)) return fail(KMX_E_ARG, "null argument");
+	for (u64 e = 0; e < n_links; e++)
+		if ((u64)links[e] >= 2 * U) return fail(KMX_E_ARG, "links[%llu] = %u is no oriented unitig of the session's %llu", (unsigned long long)e, links[e], (unsigned long long)U);
+	HIPCHK(hipSetDevice(m->device));
+	const hipStream_t st = m->stream;
+	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
+		kmx_model *m;
+		DevBuf<MapSeg> segs;
+		DevBuf<u64> so, loffs, wo, hits;
+		DevBuf<u32> links, steps;
+		DevBuf<Walk> walks;
+		~Staged() { (void)hipStreamSynchronize(m->stream); }
+	} G{m};
+	const u64 wcap = walks ? std::min<u64>(walk_capacity, n_segs) : 0, scap = walks ? std::min<u64>(step_capacity, n_segs) : 0;
+	if (G.segs.alloc(n_segs) != hipSuccess || G.so.alloc(n_seqs + 1) != hipSuccess || G.loffs.alloc(2 * U + 1) != hipSuccess || G.links.alloc(n_links) != hipSuccess ||
+	    G.wo.alloc(n_seqs + 1) != hipSuccess || (walks && (G.walks.alloc(wcap) != hipSuccess || G.steps.alloc(scap) != hipSuccess)) || (link_hits && n_links && G.hits.alloc(n_links) != hipSuccess))
+		return map_nomem();
+	if (n_segs) HIPCHK(hipMemcpyAsync(G.segs, segs, n_segs * sizeof(MapSeg), hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(G.so, seg_offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
+	HIPCHK(hipMemcpyAsync(G.loffs, link_offsets, (2 * U + 1) * 8, hipMemcpyHostToDevice, st));
+	if (n_links) HIPCHK(hipMemcpyAsync(G.links, links, n_links * 4, hipMemcpyHostToDevice, st));
+	unsigned long long *d_hits = link_hits && n_links ? (unsigned long long *)G.hits.get() : nullptr;
+	if (d_hits) HIPCHK(hipMemsetAsync(d_hits, 0, n_links * 8, st));
+	WalkDev D{};
+	D.segs = G.segs; D.n_segs = n_segs; D.so = G.so; D.n_seqs = n_seqs;
+	D.loffs = G.loffs; D.links = G.links; D.n_links = n_links;
+	D.max_gap = params->max_gap; D.max_indel = params->max_indel;
+	D.walks = walks ? G.walks.get() : nullptr; D.walk_cap = wcap; D.wo = G.wo;
+	D.steps = walks ? G.steps.get() : nullptr; D.step_cap = scap;
+	D.link_hits = d_hits;
+	const int rc = walk_core(m, D, stats);
+	if (rc != KMX_OK && rc != KMX_E_RANGE) return rc;
+	const bool short_cap = walks && (stats->n_walks > walk_capacity || stats->n_steps > step_capacity);
+	std::vector<uint64_t> h;
+	if (d_hits) h.resize(n_links);
+	HIPCHK(hipMemcpyAsync(walk_offsets, G.wo, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, st));
+	if (d_hits) HIPCHK(hipMemcpyAsync(h.data(), d_hits, n_links * 8, hipMemcpyDeviceToHost, st));
+	if (walks && !short_cap) {
+		if (stats->n_walks) HIPCHK(hipMemcpyAsync(walks, G.walks, stats->n_walks * sizeof(Walk), hipMemcpyDeviceToHost, st));
+		if (stats->n_steps) HIPCHK(hipMemcpyAsync(steps, G.steps, stats->n_steps * 4, hipMemcpyDeviceToHost, st));
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	for (u64 e = 0; e < h.size(); e++) link_hits[e] += h[e];
+	if (short_cap)
+		return fail(KMX_E_RANGE, "%llu walks and %llu steps, the buffers hold %llu and %llu", (unsigned long long)stats->n_walks, (unsigned long long)stats->n_steps, (unsigned long long)walk_capacity,
+		            (unsigned long long)step_capacity);
+	return KMX_OK;
+}

@@ -1,10 +1,11 @@
 // unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*, kmx_*unitig_graph_clean*).  The host side that sizes the
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.  Behind them the launchers of map_kernels.h (kmx_unitig_map_*), which
-// search the same listing through the same bucket index; their host side is map_host.h.
+// search the same listing through the same bucket index, and the launcher of walk_kernels.h (kmx_unitig_walk_segs*); their host side is map_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
 #include "map_kernels.h"
+#include "walk_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -145,6 +146,25 @@ hipError_t map_finish(const MapOut &O, const u64 *offs, u64 n_seqs, u64 n_total,
 	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const u64 *)O.so, O.so, (u64)0, (size_t)(n_seqs + 1), rocprim::plus<u64>(), st));
 	RCHK(tmp.ensure(bytes, st));
 	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const u64 *)O.so, O.so, (u64)0, (size_t)(n_seqs + 1), rocprim::plus<u64>(), st));
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_walk_segs* (walk_kernels.h): flags, the scan of (walk starts, step starts), heads, sums.  D.sc[D.n_segs] holds
+// the two totals and D.cnt the five counters behind it; D.n_segs > 0
+hipError_t walk_segs(const WalkDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.flag, 0, D.n_segs, st));
+	RCHK(hipMemsetAsync(D.cnt, 0, WALK_C_N * sizeof(unsigned long long), st));
+	if (D.n_seqs) hipLaunchKernelGGL(k_walk_first, dim3(nblk(D.n_seqs)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_walk_join, dim3(nblk(D.n_segs)), dim3(256), 0, st, D);
+	auto tots = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), WalkFlagTot{D.flag, D.n_segs});
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, tots, D.sc, WalkTot{0, 0}, (size_t)(D.n_segs + 1), WalkPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, tots, D.sc, WalkTot{0, 0}, (size_t)(D.n_segs + 1), WalkPlus(), st));
+	const u64 n = D.n_segs > D.n_seqs + 1 ? D.n_segs : D.n_seqs + 1;
+	hipLaunchKernelGGL(k_walk_heads, dim3(nblk(n)), dim3(256), 0, st, D);
+	if (D.walks && D.walk_cap) hipLaunchKernelGGL(k_walk_sums, dim3(nblk(D.n_segs)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
