@@ -16,6 +16,10 @@
 //          unmapped windows are bridged, k when omitted, with at most one base lost or gained per bridge): reads.gaf (one line
 //          per walk) and unitigs.links.tsv (link index, source, target, reads that cross it).  Implies the graph, as -G does;
 //          unitigs.gfa is still written only with -G
+//     -X<min_reads>[,<ratio>]  with -M -W: drop the edges that fewer than min_reads reads cross (and, with ratio, those whose reads
+//          times ratio stay below the best edge at either end), merge the unitigs along what is left (KModel::unitig_contigs):
+//          contigs.fa and contigs.paths.tsv (contig, step, unitig, strand, k-mer offset); with -G also contigs.gfa (unitig and
+//          contig segments, the kept edges with their reads, one path line per contig)
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -34,6 +38,8 @@ struct Params {
 	long unitig_thr = -1;                                          // -u: the threshold, -1 = no unitigs
 	long clean_len = -1;                                           // -C: the cap of tips and bubbles in k-mers, 0 = 2 k, -1 = no cleaning
 	long walk_gap = -2;                                            // -W: max_gap, -1 = k, -2 = no walks
+	long long min_reads = -1;                                      // -X: min_reads, -1 = no contigs
+	long ratio = 0;                                                // -X<min_reads>,<ratio>
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -57,6 +63,18 @@ static bool parse(int argc, char **argv, Params &p)
 			p.walk_gap = a[2] ? strtol(a + 2, &end, 10) : -1;
 			if (a[2] && (*end || p.walk_gap < 0 || p.walk_gap > 0xFFFFFFFFL)) return false;   // not a number of windows
 		}
+		else if (!strncmp(a, "-X", 2)) {
+			char *end = nullptr;
+			if (!a[2]) return false;
+			p.min_reads = strtoll(a + 2, &end, 10);
+			if (end == a + 2 || p.min_reads < 0) return false;
+			if (*end == ',') {
+				const char *r = end + 1;
+				p.ratio = strtol(r, &end, 10);
+				if (end == r || p.ratio < 0 || p.ratio > 65536) return false;
+			}
+			if (*end) return false;
+		}
 		else if (!strncmp(a, "-C", 2)) {
 			char *end = nullptr;
 			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
@@ -77,6 +95,10 @@ static bool parse(int argc, char **argv, Params &p)
 	if (p.clean_len >= 0 && p.unitig_thr < 1) return false;        // cleaning removes nodes by "count below thr"
 	if (p.map && p.unitig_thr < 0) return false;                   // the reads are mapped onto the unitigs written
 	if (p.walk_gap > -2 && !p.map) return false;                   // the walks are built from the map's segments
+	if (p.min_reads >= 0 && (!p.map || p.walk_gap == -2)) {        // the contigs are built from the reads per link, which the walks count
+		std::cout << "-X needs -M -W: the contigs are built from the reads that cross every link, which the walks count\n";
+		return false;
+	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -122,7 +144,9 @@ int main(int argc, char **argv)
 		             "       -C<len>  with -u<thr>, thr >= 1: clip tips, pop bubbles and drop islands of at most len k-mers (2 k) first\n"
 		             "       -M  with -u<thr>: map the reads of the (plain FASTA / FASTQ) input onto the unitigs: reads.paths.tsv, unitigs.hits.tsv\n"
 		             "       -W<max_gap>  with -M: join every read's segments into walks through the graph, bridging at most max_gap (k) unmapped windows:\n"
-		             "           reads.gaf, unitigs.links.tsv (link index, source, target, reads)\n";
+		             "           reads.gaf, unitigs.links.tsv (link index, source, target, reads)\n"
+		             "       -X<min_reads>[,<ratio>]  with -M -W: merge the unitigs along the edges at least min_reads reads cross: contigs.fa,\n"
+		             "           contigs.paths.tsv (contig, step, unitig, strand, offset), and contigs.gfa with -G\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -220,6 +244,24 @@ int main(int argc, char **argv)
 				if (!gaf || !lt) { std::cout << "could not write " << dir << "/reads.gaf or unitigs.links.tsv" << std::endl; return 1; }
 				std::cout << "   walks (gaps of at most " << wp.max_gap << " windows)    :     " << wt.n_walks << " walks, " << wt.n_steps << " steps, " << wt.n_edge << " edges crossed, " << wt.n_inside + wt.n_across
 				          << " gaps bridged (" << wt.n_across << " across an edge), " << wt.n_breaks << " breaks" << std::endl;
+				if (p.min_reads >= 0) {
+					const kmx_contig_params xp = {(uint64_t)p.min_reads, (uint32_t)p.ratio, 0};
+					const KModel::Contigs ct = km->unitig_contigs(strs, &rec, link_offsets, links, link_hits, p.k, xp);
+					std::ofstream cf((dir + "/contigs.fa").c_str()), cp2((dir + "/contigs.paths.tsv").c_str());
+					KModel::write_contigs_fasta(cf, ct);
+					KModel::write_contig_paths_tsv(cp2, ct);
+					cf.close();
+					cp2.close();
+					if (!cf || !cp2) { std::cout << "could not write " << dir << "/contigs.fa or contigs.paths.tsv" << std::endl; return 1; }
+					if (p.gfa) {
+						std::ofstream cg((dir + "/contigs.gfa").c_str());
+						KModel::write_contigs_gfa(cg, ct, p.k, &strs, &rec);
+						cg.close();
+						if (!cg) { std::cout << "could not write " << dir << "/contigs.gfa" << std::endl; return 1; }
+					}
+					std::cout << "   contigs (links of >= " << p.min_reads << " reads" << (p.ratio ? ", ratio " : "") << (p.ratio ? std::to_string(p.ratio) : std::string()) << ")    :     " << ct.stats.n_contigs
+					          << " contigs (" << ct.stats.n_multi << " of several unitigs, " << ct.stats.n_circular << " circular), " << ct.stats.n_kept << " of " << ct.stats.n_links << " edges kept" << std::endl;
+				}
 			}
 		}
 	}

@@ -476,6 +476,82 @@ public:
 			}
 	}
 
+	// Contigs (the rule: kmx.h): the unitigs merged along the edges the reads support.  unitig_contigs takes the vectors a graph call
+	// returned (rec may be null: the contigs' counts are then 0) and the link_hits seq_walks accumulated; it needs no session.  The
+	// result holds the contigs, one kmx_contig each, steps (the oriented unitigs of every contig back to back), place (one per
+	// unitig: its contig, strand and k-mer offset there) and the contig graph as CSR with the reads behind every edge.
+	struct Contigs {
+		std::vector<std::string> strs;
+		std::vector<kmx_contig> rec;
+		std::vector<uint32_t> steps;
+		std::vector<kmx_contig_place> place;
+		std::vector<uint64_t> link_offsets;
+		std::vector<uint32_t> links;
+		std::vector<uint64_t> support;
+		kmx_contig_stats stats;
+	};
+	Contigs unitig_contigs(const std::vector<std::string> &unitigs, const std::vector<kmx_unitig> *rec, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links,
+	                       const std::vector<uint64_t> &link_hits, int k, const kmx_contig_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), nl = links.size();
+		if (link_offsets.size() != 2 * U + 1 || link_hits.size() != nl || (rec && rec->size() != U)) { std::cout << "unitig_contigs: the vectors are not those of one graph" << std::endl; exit(1); }
+		Contigs c;
+		std::string cseq(f.bases.size() + 1, '\0');
+		std::vector<uint64_t> coff(U + 1, 0);
+		c.rec.resize(U + 1); c.steps.resize(U + 1); c.place.resize(U + 1); c.link_offsets.resize(2 * U + 1); c.links.resize(nl + 1); c.support.resize(nl + 1);
+		uint64_t nc = 0, nb = 0, ncl = 0;
+		check(kmx_unitig_contigs(h_, k, f.bases.data(), f.off.data(), U, rec && U ? &(*rec)[0] : 0, &link_offsets[0], nl ? &links[0] : 0, nl, nl ? &link_hits[0] : 0, &params, &cseq[0], &coff[0],
+		                         &c.rec[0], &c.steps[0], &c.place[0], &c.link_offsets[0], &c.links[0], &c.support[0], &nc, &nb, &ncl, &c.stats));
+		coff.resize((size_t)nc + 1);
+		c.strs = split(cseq, coff);
+		c.rec.resize((size_t)nc); c.steps.resize(U); c.place.resize(U); c.link_offsets.resize(2 * (size_t)nc + 1); c.links.resize((size_t)ncl); c.support.resize((size_t)ncl);
+		return c;
+	}
+	// the contigs as FASTA, header ">c<index> n_kmers=<m> n_steps=<s> circular=<0|1>"
+	static void write_contigs_fasta(std::ostream &out, const Contigs &c)
+	{
+		for (size_t i = 0; i < c.strs.size(); i++)
+			out << ">c" << i << " n_kmers=" << c.rec[i].n_kmers << " n_steps=" << c.rec[i].n_steps << " circular=" << (int)c.rec[i].circular << "\n" << c.strs[i] << "\n";
+	}
+	// the contig graph as GFA 1: "S\tc<index>\t<string>\tLN:i:<len>\tKC:i:<sum_count>" per contig and, per mirror pair of edges (the
+	// choice of write_unitigs_gfa), "L\tc<a>\t<+|->\tc<b>\t<+|->\t<k-1>M\tRC:i:<support>".  With the unitigs (and their records, for
+	// KC) it first writes their segments as write_unitigs_gfa names them and, behind the links, one "P\tc<index>\t<u<N>+|-, ...>\t
+	// <k-1>M, ..." per contig ("*" for a single step): a path line must name segments of the same file.
+	static void write_contigs_gfa(std::ostream &out, const Contigs &c, int k, const std::vector<std::string> *unitigs = 0, const std::vector<kmx_unitig> *urec = 0)
+	{
+		out << "H\tVN:Z:1.0\n";
+		if (unitigs)
+			for (size_t u = 0; u < unitigs->size(); u++)
+				out << "S\tu" << u << "\t" << (*unitigs)[u] << "\tLN:i:" << (*unitigs)[u].size() << "\tKC:i:" << (urec && u < urec->size() ? (*urec)[u].sum_count : 0) << "\n";
+		for (size_t i = 0; i < c.strs.size(); i++) out << "S\tc" << i << "\t" << c.strs[i] << "\tLN:i:" << c.strs[i].size() << "\tKC:i:" << c.rec[i].sum_count << "\n";
+		for (uint64_t a = 0; a + 1 < c.link_offsets.size(); a++)
+			for (uint64_t e = c.link_offsets[a]; e < c.link_offsets[a + 1] && e < c.links.size(); e++) {
+				const uint64_t b = c.links[(size_t)e], mb = b ^ 1, ma = a ^ 1;
+				if (a < mb || (a == mb && b <= ma))
+					out << "L\tc" << (a >> 1) << "\t" << ((a & 1) ? '-' : '+') << "\tc" << (b >> 1) << "\t" << ((b & 1) ? '-' : '+') << "\t" << (k - 1) << "M\tRC:i:" << c.support[(size_t)e] << "\n";
+			}
+		if (!unitigs) return;
+		for (size_t i = 0; i < c.rec.size(); i++) {
+			out << "P\tc" << i << "\t";
+			for (uint64_t s = c.rec[i].first_step; s < c.rec[i].first_step + c.rec[i].n_steps && s < c.steps.size(); s++)
+				out << (s > c.rec[i].first_step ? "," : "") << "u" << (c.steps[(size_t)s] >> 1) << ((c.steps[(size_t)s] & 1) ? '-' : '+');
+			out << "\t";
+			if (c.rec[i].n_steps < 2) out << "*";
+			for (uint32_t s = 1; s < c.rec[i].n_steps; s++) out << (s > 1 ? "," : "") << (k - 1) << "M";
+			out << "\n";
+		}
+	}
+	// ... and every step as a table, one "c<contig>\t<step>\tu<unitig>\t<+|->\t<k-mer offset in the contig>" per step
+	static void write_contig_paths_tsv(std::ostream &out, const Contigs &c)
+	{
+		for (size_t i = 0; i < c.rec.size(); i++)
+			for (uint64_t s = 0; s < c.rec[i].n_steps && c.rec[i].first_step + s < c.steps.size(); s++) {
+				const uint32_t o = c.steps[(size_t)(c.rec[i].first_step + s)];
+				out << "c" << i << "\t" << s << "\tu" << (o >> 1) << "\t" << ((o & 1) ? '-' : '+') << "\t" << ((o >> 1) < c.place.size() ? c.place[o >> 1].off : 0) << "\n";
+			}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

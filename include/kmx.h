@@ -687,8 +687,8 @@ int kmx_unitig_graph_last_phases(kmx_model *m, double *seconds /* [5] */, uint64
  *      original counts.
  *   4. A no-op is exact: with nothing to remove the output is byte for byte that of kmx_unitig_graph, rounds_run = 1,
  *      converged = 1.
- * Out of scope: bubbles whose arms hold more than one unitig; coverage-ratio or mean-coverage criteria and low-coverage edge
- * removal (the reads per link that it starts from: kmx_unitig_walk_segs); several GPUs; choosing thr and the caps.        */
+ * Out of scope: bubbles whose arms hold more than one unitig; mean-coverage criteria; several GPUs; choosing thr and the caps.
+ * Low-coverage edge removal by the reads per link, with a coverage ratio: kmx_unitig_contigs below the walks.              */
 #define KMX_CLEAN_TIPS        1
 #define KMX_CLEAN_ISLANDS     2
 #define KMX_CLEAN_BUBBLES     4
@@ -840,7 +840,7 @@ int kmx_unitig_map_end(kmx_model *m);
  *       and every +1 of link_hits on the mirror edge (b ^ 1) -> (a ^ 1) of a -> b; link_hits counts the traversed edge only, the
  *       mirror edge is the caller's to add.
  * Out of scope: gaps that span a whole unitig (a bridge crosses at most one edge); comparing the bases inside a gap (a bridge
- * is accepted on its geometry alone); paired reads; several GPUs.                                                          */
+ * is accepted on its geometry alone); paired reads; several GPUs.  What consumes link_hits: kmx_unitig_contigs below.      */
 typedef struct kmx_walk_params { uint32_t max_gap, max_indel, reserved[2]; } kmx_walk_params;                  /* 16 bytes */
 typedef struct kmx_walk {                /* one per walk, in ascending pos; 80 bytes */
 	uint64_t pos;                        /* flat position of its first window */
@@ -880,6 +880,119 @@ int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64
                              const uint64_t *d_link_offsets /* [2 U + 1] */, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params /* HOST */,
                              kmx_walk *d_walks /* or NULL */, uint64_t walk_capacity, uint64_t *d_walk_offsets /* [n_seqs + 1] */, uint32_t *d_steps, uint64_t step_capacity,
                              uint64_t *d_link_hits /* [n_links] or NULL */, kmx_walk_stats *stats /* HOST */);
+
+/* ---- contigs: the unitigs merged along the edges the reads support.  A unitig ends at every branch of the k-mer graph; the
+ * reads per edge that kmx_unitig_walk_segs accumulated tell the branches that reads cross from those they do not.  This call
+ * drops the unsupported edges and merges unitigs along what has become the only way on.  The construction of the unitig rule one
+ * level up: the items are the 2 U oriented unitigs, not the 2 n oriented k-mers.
+ * Input: k, odd, in [5, 63]; a unitig set in the layout of kmx_query_seqs (useq, uoffsets[U + 1]; unitig u has
+ *   m_u = len_u - k + 1 >= 1 k-mers; U < 2^31; bytes of uppercase ACGT, what every kmx_*unitig* call writes: they are not checked,
+ *   a reverse step maps a byte b to b ^ 0x04 where b & 2 and to b ^ 0x15 otherwise, which complements ACGT); optionally its
+ *   records urec[U] (only sum_count, min_count and max_count are read); the CSR of its graph (link_offsets[2 U + 1],
+ *   links[n_links]; out[o] is the row of oriented unitig o = 2 u + d, at most 4 entries); link_hits[n_links] as
+ *   kmx_unitig_walk_segs accumulated it; and kmx_contig_params, ratio in [0, 65536], reserved = 0.
+ *   Support.  The mirror of edge e = (a -> b) is mir(e), the entry a ^ 1 of out[b ^ 1].  sup(e) = link_hits[e] + link_hits[mir(e)],
+ *     modulo 2^64 (hits below 2^63 are exact); a self-mirror edge (a hairpin a -> a ^ 1, mir(e) = e) has sup(e) = link_hits[e],
+ *     counted once.  sup is symmetric under mir by construction: the addition consequence (c) of the walks leaves to the caller.
+ *   Kept edges.  best(o) = the largest sup over ALL of out[o], 0 for an empty row.  e = (a -> b) is below_min iff
+ *     sup(e) < min_reads; otherwise below_ratio iff ratio > 0 and (sup(e) * ratio < best(a) or sup(e) * ratio < best(b ^ 1)), the
+ *     product taken in 128 bits; otherwise KEPT.  outK[o] is the kept part of out[o], in row order, and
+ *     inK[t] = { s ^ 1 : s in outK[t ^ 1] }.  best(b ^ 1) is the largest support of an edge INTO b, so both tests are the same
+ *     under mir and kept is symmetric.
+ *   Chain links.  o -> t is a chain link iff outK[o] = {t}, inK[t] = {o} and t != o ^ 1.  A kept hairpin is never one; a kept
+ *     self-loop o -> o with nothing else kept at either side IS one, a cycle of one step.  Every oriented unitig has at most one
+ *     chain link in and one out, and o -> t iff (t ^ 1) -> (o ^ 1), so the 2 U oriented unitigs fall into paths and cycles that
+ *     come in mirror pairs.  No component holds both orientations of a unitig: the mirror maps such a path onto itself end for
+ *     end, so its middle would be a link o -> o ^ 1 (excluded) or a unitig equal to its own mirror (o != o ^ 1); on a cycle the
+ *     mirror is a reflection, which fixes a step or a link, the same two impossibilities.
+ *   Contigs: one per mirror pair.  A path o_1 .. o_s: for s = 1 the representative is d = 0; otherwise, of P and its mirror, the
+ *     one whose first step has the smaller unitig index (the two first steps are the two ends: distinct unitigs).  A cycle: it
+ *     starts at its smallest unitig in orientation d = 0, follows the chain links once round and is spelled open with
+ *     circular = 1.  The string is the oriented string of o_1 followed by each later step's oriented string without its first
+ *     k - 1 bytes; a later step never rewrites the overlap, so the bytes are a function of the input even for a CSR whose
+ *     overlaps do not hold.  Contigs come in ascending unitig index of the first step; every unitig lies in exactly one, in one
+ *     orientation.
+ * Output.  The input's sizes always suffice, so there is no sizing call and no KMX_E_RANGE.  cseq[n_ubases] and coffsets[U + 1] in
+ *   the layout of kmx_query_seqs (C + 1 offsets are written); crec[U], the records below (C are written); steps[U], the o of
+ *   every step, back to back in contig order; place[U]: unitig u lies in contig oc >> 1, oc & 1 is 1 iff its step is 2 u + 1, and
+ *   off is the k-mer offset of that step's first window in the contig (modulo 2^32), which turns the map's segments and the
+ *   walks' steps into contig coordinates.  The contig graph: clink_offsets[2 U + 1] (2 C + 1 are written), clinks[n_links] and
+ *   csupport[n_links]: the edges out of oriented contig oc = 2 c + d are the kept edges of its LAST step (o_s for d = 0, o_1 ^ 1
+ *   for d = 1), in row order; the target is the oriented contig whose first step is that entry, and csupport[e] the edge's sup.
+ *   Such a contig exists: a kept edge o -> t that is no chain link has |outK[o]| > 1, |inK[t]| > 1 or t = o ^ 1, and in each case
+ *   t has no chain link in (for the first two because a chain link into t needs inK[t] to be its one source with that source's
+ *   one kept edge; for a hairpin because inK[o ^ 1] = {o} would make it the excluded link), so t starts its oriented path.  A
+ *   cycle has exactly 2c -> 2c and 2c+1 -> 2c+1: the unitig graph's convention.  On the HOST: *n_contigs, *n_cbases, *n_clinks and
+ *   kmx_contig_stats.  Everything is an integer sum, count, minimum or maximum and a function of the input alone: byte-identical
+ *   across runs and variants.
+ * Consequences:
+ *   (a) a no-op is exact: on a graph that kmx_*unitig_graph* returned, with min_reads = 0 and ratio = 0, every contig is one
+ *       unitig; cseq, coffsets, clink_offsets and clinks are byte for byte the input's; n_kmers, the counts, n_pred and n_succ
+ *       are the unitig record's, and so is circular except for an isolated unitig whose one edge is its own self-loop o -> o (a
+ *       run of one base that nothing else touches): no circular unitig, since a self-loop of the node graph is never a link, but
+ *       a cycle of one step here.  n_chain counts the closing links of these and of the circular unitigs, nothing else;
+ *   (b) a contig is a path of the node graph: when the overlaps hold, every window of a contig is a k-mer of exactly one unitig
+ *       and no k-mer appears twice, so the contig set is a valid set for kmx_unitig_map_begin on the same listing;
+ *   (c) mirror invariance: adding every edge's hits on its mirror instead changes nothing;
+ *   (d) place inverts steps; the n_steps sum to U, the n_kmers to the sum of m_u, and n_cbases = that sum + C (k - 1).
+ * Out of scope: repeat resolution from walks that span a unitig (only single edges are judged); iterating with a re-map;
+ * paired reads; even k; several GPUs; choosing min_reads and ratio.                                                        */
+typedef struct kmx_contig_params { uint64_t min_reads; uint32_t ratio; uint32_t reserved; } kmx_contig_params;          /* 16 bytes */
+typedef struct kmx_contig {              /* one per contig; 64 bytes, no padding */
+	uint64_t n_kmers;                    /* the sum of m_u over its steps; the string has n_kmers + k - 1 bytes */
+	uint64_t sum_count;                  /* from urec; 0 when urec is NULL */
+	uint32_t min_count, max_count;       /* from urec; 0 when urec is NULL */
+	uint64_t first_step;                 /* its steps are steps[first_step .. first_step + n_steps) */
+	uint32_t n_steps;
+	uint8_t  circular;
+	uint8_t  n_pred;                     /* |inK[o_1]|; 1 for a cycle */
+	uint8_t  n_succ;                     /* |outK[o_s]|; 1 for a cycle */
+	uint8_t  reserved;                   /* 0 */
+	uint64_t min_support, sum_support;   /* over its chain links, the closing link of a cycle included; 0 when it has none */
+	uint64_t reserved2;                  /* 0 */
+} kmx_contig;
+typedef struct kmx_contig_place { uint32_t oc; uint32_t off; } kmx_contig_place;                                         /* 8 bytes */
+typedef struct kmx_contig_stats { uint64_t n_links, n_kept, n_below_min, n_below_ratio, n_chain     /* oriented edges, each */,
+                                  n_contigs, n_circular, n_multi /* contigs of more than one step */; } kmx_contig_stats;    /* 64 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_apply_edits_dev); it runs on the model's stream and is a
+ * build-class call (see the threading note of kmx_query_packed).  urec may be NULL; every other buffer is required, also where a
+ * count is 0 (with U == 0 only the two offset arrays, the three counts and stats).  KMX_E_ARG before anything runs: an even or
+ * out-of-range k, U >= 2^31, ratio > 65536, reserved != 0, a NULL required buffer, an output that overlaps an input or another
+ * output; uoffsets whose first entry is not 0, that decrease, or that give a unitig fewer than k bytes; a CSR that
+ * kmx_unitig_walk_segs would refuse (link_offsets[0] != 0, decreasing, link_offsets[2 U] != n_links, a links[e] >= 2 U), a row
+ * longer than 4, an edge without its mirror.  U == 0: KMX_OK, coffsets[0] = clink_offsets[0] = 0, all counts zero.
+ * KMX_E_NOMEM leaves the handle usable.  The call returns when the output is complete.                                      */
+int kmx_unitig_contigs(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_unitig *urec /* or NULL */,
+                       const uint64_t *link_offsets /* [2 U + 1] */, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits /* [n_links] */,
+                       const kmx_contig_params *params, char *cseq /* [n_ubases] */, uint64_t *coffsets /* [U + 1] */, kmx_contig *crec /* [U] */,
+                       uint32_t *steps /* [U] */, kmx_contig_place *place /* [U] */, uint64_t *clink_offsets /* [2 U + 1] */, uint32_t *clinks /* [n_links] */,
+                       uint64_t *csupport /* [n_links] */, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats);
+/* The same on DEVICE buffers, read where the graph, map and walk calls left them; params, the three counts and stats are on the
+ * HOST.  It checks k, U, the parameters, NULL and overlap, and validates nothing else on the host; the kernels clamp instead:
+ * uoffsets into [0, n_ubases] (a unitig whose clamped bounds decrease has no bytes, one shorter than k no k-mers); row bounds
+ * into [0, n_links]; at most 4 entries of a row are read; a target >= 2 U is no edge and is not counted; an edge whose mirror is
+ * not found has sup = link_hits[e]; and a chain link o -> t additionally requires that the mirror side agrees
+ * (outK[t ^ 1] = {o ^ 1}), so the links are symmetric whatever the CSR and the argument above holds.  Every store is checked
+ * against U, n_ubases or n_links.  Bad device input gives wrong contigs; it never gives an access outside a buffer, and never
+ * more than the bounded number of launches: ceil(log2 2U) + 1 doubling rounds, the cut, and as many again.
+ * It waits for the stream once per doubling round (a word says whether anything moved; the rounds behind the cut run only when
+ * there is a cycle), as the unitig construction does, and once for the counts, and returns with nothing left in flight.  Device
+ * memory, kept on the handle between calls through the owning types of hip_owned.h: 195 bytes per unitig (2 x 32 for the two
+ * copies of pointer, step rank and k-mer rank of both orientations, whose spare copy the marks reuse; 2 x 8 for the two copies
+ * of the running minimum; 24 for the scanned marks; 2 x 21 for best, the only kept target, its support and the kept count of both
+ * orientations; 1 for the cycle flag; 8 for where a unitig's bytes go; 2 x 16 for the end counts and their scan; 2 x 4 for the
+ * last step of both oriented contigs) and 9 bytes per link (its support and its verdict), plus the scan's scratch.  The host
+ * form also stages its input and output there.                                                                             */
+int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, uint64_t n_ubases,
+                           const kmx_unitig *d_urec /* or NULL */, const uint64_t *d_link_offsets /* [2 U + 1] */, const uint32_t *d_links, uint64_t n_links,
+                           const uint64_t *d_link_hits /* [n_links] */, const kmx_contig_params *params /* HOST */, char *d_cseq /* [n_ubases] */,
+                           uint64_t *d_coffsets /* [U + 1] */, kmx_contig *d_crec /* [U] */, uint32_t *d_steps /* [U] */, kmx_contig_place *d_place /* [U] */,
+                           uint64_t *d_clink_offsets /* [2 U + 1] */, uint32_t *d_clinks /* [n_links] */, uint64_t *d_csupport /* [n_links] */,
+                           uint64_t *n_contigs /* HOST */, uint64_t *n_cbases /* HOST */, uint64_t *n_clinks /* HOST */, kmx_contig_stats *stats /* HOST */);
+/* where the last of these two calls on the handle spent its time, measured only under kmx_set_profile(m, 1) (every phase then
+ * waits for the stream): seconds[5] = supports and verdicts, ranking (links, rounds, cut), marks and their scan, records with
+ * steps, places and the contig graph, the bytes; *rounds = its doubling rounds (counted always)                              */
+int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

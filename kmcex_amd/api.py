@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_graph_clean", "kmx_unitig_graph_clean_dev", "kmx_count_unitig_graph_clean", "kmx_count_unitig_graph_clean_dev", "kmx_unitig_clean_last_phases",
     "kmx_unitig_map_begin", "kmx_unitig_map_begin_dev", "kmx_count_unitig_map_begin", "kmx_count_unitig_map_begin_dev", "kmx_unitig_map_seqs", "kmx_unitig_map_seqs_dev", "kmx_unitig_map_end",
     "kmx_unitig_walk_segs", "kmx_unitig_walk_segs_dev",
+    "kmx_unitig_contigs", "kmx_unitig_contigs_dev", "kmx_unitig_contigs_last_phases",
 ]
 
 
@@ -151,6 +152,25 @@ class WalkStats(C.Structure):
 # kmx_walk as a NumPy structured dtype (what KModel.unitig_walks_flat returns)
 WALK_DTYPE = np.dtype([(f, "<u8") for f in ("pos", "n_span", "n_mapped", "n_covered", "first_seg", "first_step")] +
                       [(f, "<u4") for f in ("n_segs", "n_steps", "off_first", "off_last", "n_inside", "n_across")] + [("indel", "<i4"), ("reserved", "<u4")])
+
+
+class ContigParams(C.Structure):
+    """kmx_contig_params of include/kmx.h: 16 bytes"""
+    _fields_ = [("min_reads", C.c_uint64), ("ratio", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class ContigStats(C.Structure):
+    """kmx_contig_stats of include/kmx.h: 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_links", "n_kept", "n_below_min", "n_below_ratio", "n_chain", "n_contigs", "n_circular", "n_multi")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_contig and kmx_contig_place as NumPy structured dtypes (what KModel.unitig_contigs_flat returns): 64 and 8 bytes
+CONTIG_DTYPE = np.dtype([("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count", "<u4"), ("max_count", "<u4"), ("first_step", "<u8"), ("n_steps", "<u4"),
+                         ("circular", "u1"), ("n_pred", "u1"), ("n_succ", "u1"), ("reserved", "u1"), ("min_support", "<u8"), ("sum_support", "<u8"), ("reserved2", "<u8")])
+CONTIG_PLACE_DTYPE = np.dtype([("oc", "<u4"), ("off", "<u4")])
 
 
 class RingList(C.Structure):
@@ -296,6 +316,10 @@ def load_library():
     _sig(L, "kmx_unitig_map_end", [vp])
     _sig(L, "kmx_unitig_walk_segs", [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(WalkParams), vp, u64, vp, vp, u64, vp, C.POINTER(WalkStats)])
     _sig(L, "kmx_unitig_walk_segs_dev", [vp, vp, u64, vp, u64, vp, vp, u64, C.POINTER(WalkParams), vp, u64, vp, vp, u64, vp, C.POINTER(WalkStats)])
+    p64 = C.POINTER(C.c_uint64)
+    _sig(L, "kmx_unitig_contigs", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(ContigParams), vp, vp, vp, vp, vp, vp, vp, vp, p64, p64, p64, C.POINTER(ContigStats)])
+    _sig(L, "kmx_unitig_contigs_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, C.POINTER(ContigParams), vp, vp, vp, vp, vp, vp, vp, vp, p64, p64, p64, C.POINTER(ContigStats)])
+    _sig(L, "kmx_unitig_contigs_last_phases", [vp, C.POINTER(C.c_double), p64])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -1126,6 +1150,73 @@ class KModel:
         segs, so, _ = self.seq_to_unitigs(reads)
         walks, wo, steps, st = self.unitig_walks_flat(segs, so, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
         return walks, wo, steps, st, segs, so
+
+    # ---- contigs: the unitigs merged along the edges the reads support (the rule: include/kmx.h); no model, no session
+    def unitig_contigs_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, link_hits: np.ndarray, min_reads: int = 1, ratio: int = 0,
+                            urec=None):
+        """kmx_unitig_contigs on what a graph call returned (uint8 bases, uint64 offsets [U + 1], optionally its UNITIG_DTYPE
+        records, uint64 link_offsets [2 U + 1], uint32 links) and the uint64 link_hits [n_links] the walks accumulated ->
+        (uint8 contig bases, uint64 coffsets [C + 1], CONTIG_DTYPE records [C], uint32 steps [U], CONTIG_PLACE_DTYPE place [U],
+        uint64 clink_offsets [2 C + 1], uint32 clinks, uint64 csupport, stats as a dict)."""
+        ubuf = np.ascontiguousarray(ubuf, dtype=np.uint8)
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        link_hits = np.ascontiguousarray(link_hits, dtype=np.uint64)
+        nu = uoffsets.size - 1
+        if link_offsets.size != 2 * nu + 1 or link_hits.size != links.size:
+            raise KmxError(-1, "link_offsets holds 2 U + 1 entries and link_hits one per link")
+        if urec is not None:
+            urec = np.ascontiguousarray(urec, dtype=UNITIG_DTYPE)
+            if urec.size != nu:
+                raise KmxError(-1, "urec holds one record per unitig")
+        cseq = np.zeros(max(ubuf.size, 1), dtype=np.uint8)
+        coffs = np.zeros(nu + 1, dtype=np.uint64)
+        crec = np.zeros(max(nu, 1), dtype=CONTIG_DTYPE)
+        steps = np.zeros(max(nu, 1), dtype=np.uint32)
+        place = np.zeros(max(nu, 1), dtype=CONTIG_PLACE_DTYPE)
+        cloffs = np.zeros(2 * nu + 1, dtype=np.uint64)
+        clinks = np.zeros(max(links.size, 1), dtype=np.uint32)
+        csup = np.zeros(max(links.size, 1), dtype=np.uint64)
+        par, st = ContigParams(int(min_reads), int(ratio), 0), ContigStats()
+        nc, nb, nl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_contigs(self.h, int(k), ubuf.ctypes.data, uoffsets.ctypes.data, nu, urec.ctypes.data if urec is not None else None, link_offsets.ctypes.data, links.ctypes.data,
+                                       links.size, link_hits.ctypes.data, C.byref(par), cseq.ctypes.data, coffs.ctypes.data, crec.ctypes.data, steps.ctypes.data, place.ctypes.data,
+                                       cloffs.ctypes.data, clinks.ctypes.data, csup.ctypes.data, C.byref(nc), C.byref(nb), C.byref(nl), C.byref(st)))
+        c, b, l = nc.value, nb.value, nl.value
+        return cseq[:b].copy(), coffs[:c + 1].copy(), crec[:c].copy(), steps[:nu].copy(), place[:nu].copy(), cloffs[:2 * c + 1].copy(), clinks[:l].copy(), csup[:l].copy(), st.as_dict()
+
+    def unitig_contigs_dev(self, k: int, d_ubuf, d_uoffsets, d_link_offsets, d_links, d_link_hits, min_reads: int = 1, ratio: int = 0, d_urec=None, out=None):
+        """kmx_unitig_contigs_dev on torch tensors of the model's device, read where the graph and walk calls left them: d_ubuf
+        uint8 [n_ubases], d_uoffsets int64 [U + 1], d_link_offsets int64 [2 U + 1], d_links int32 [n_links], d_link_hits int64
+        [n_links], d_urec uint8 [U, 40] or None.  out: the eight output tensors (d_cseq uint8 [n_ubases], d_coffsets int64 [U + 1],
+        d_crec uint8 [U, 64], d_steps int32 [U], d_place int32 [U, 2], d_clink_offsets int64 [2 U + 1], d_clinks int32 [n_links],
+        d_csupport int64 [n_links]), allocated when None -> (out, (n_contigs, n_cbases, n_clinks), stats as a dict)."""
+        import torch
+        nu, nb, nl, dev = d_uoffsets.numel() - 1, d_ubuf.numel(), d_links.numel(), d_uoffsets.device
+        if out is None:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            out = (z(max(nb, 1), torch.uint8), z(nu + 1, torch.int64), z((max(nu, 1), 64), torch.uint8), z(max(nu, 1), torch.int32), z((max(nu, 1), 2), torch.int32),
+                   z(2 * nu + 1, torch.int64), z(max(nl, 1), torch.int32), z(max(nl, 1), torch.int64))
+        par, st = ContigParams(int(min_reads), int(ratio), 0), ContigStats()
+        nc, ncb, ncl = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_contigs_dev(self.h, int(k), d_ubuf.data_ptr(), d_uoffsets.data_ptr(), nu, nb, d_urec.data_ptr() if d_urec is not None else None, d_link_offsets.data_ptr(),
+                                           d_links.data_ptr(), nl, d_link_hits.data_ptr(), C.byref(par), *[t.data_ptr() for t in out], C.byref(nc), C.byref(ncb), C.byref(ncl), C.byref(st)))
+        return out, (nc.value, ncb.value, ncl.value), st.as_dict()
+
+    def contigs_from_walks(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, reads, max_gap=None, max_indel: int = 1, min_reads: int = 1,
+                           ratio: int = 0, urec=None):
+        """inside a map session on these unitigs: seq_to_walks on the reads, then unitig_contigs_flat on the link hits they leave
+        -> what unitig_contigs_flat returns, with the link hits behind it"""
+        hits = np.zeros(np.asarray(links).size, dtype=np.uint64)
+        self.seq_to_walks(reads, link_offsets, links, int(k) if max_gap is None else int(max_gap), max_indel, link_hits=hits)
+        return self.unitig_contigs_flat(k, ubuf, uoffsets, link_offsets, links, hits, min_reads, ratio, urec) + (hits,)
+
+    def unitig_contigs_phases(self) -> dict:
+        """kmx_unitig_contigs_last_phases: seconds per phase of the last contig call (under set_profile(1)) and its doubling rounds"""
+        sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_contigs_last_phases(self.h, sec, C.byref(rounds)))
+        return dict(zip(("support", "ranking", "marks", "records", "bytes"), (float(x) for x in sec)), rounds=int(rounds.value))
 
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173
         _chk(self.L.kmx_save(self.h, save_dir.encode()))

@@ -379,6 +379,18 @@ struct kmx_model {
 		DevBuf<WalkTot> d_wsc;                                     // ... [n_segs + 1] the walk and step starts in front of it; ...
 		DevBuf<unsigned long long> d_wcnt;                         // ... [WALK_C_N] the call's counters
 	} map;
+	// kmx_unitig_contigs* (contig_host.h): the work arrays of a call, kept by capacity from call to call
+	struct CtgState {
+		DevBuf<u64> d_esup, d_best, d_supo, d_ubase;               // sup per link; best, the only kept edge's support per oriented unitig; where a unitig's bytes go
+		DevBuf<u64> d_clc;                                         // [2][2 U + 1] the kept edges at the contig ends, and their scan
+		DevBuf<unsigned char> d_ekeep, d_nk, d_circ, d_tmp;        // the verdict per link, the kept count per oriented unitig, the cycle flag per unitig; rocPRIM scratch
+		DevBuf<u32> d_only, d_mn, d_last, d_flag;                  // d_mn: [2][2 U] running minima; d_flag: [1 + t] round t moved
+		DevBuf<CtgRank> d_rank[2];                                 // [2 U + 2] each: the rank state and its copy, later the marks
+		DevBuf<CtgTot> d_sc;                                       // [U + 1] the scanned marks
+		DevBuf<unsigned long long> d_cnt;                          // [CTG_C_N]
+		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): supports and verdicts, ranking, marks, records and graph, bytes
+		u64 rounds = 0;
+	} ctg;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2921,6 +2933,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "count_host.h"
 #include "unitig_host.h"
 #include "map_host.h"
+#include "contig_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3452,6 +3465,9 @@ extern "C" int kmx_unitig_map_seqs(kmx_model *m, const char *seq, const uint64_t
 extern "C" int kmx_unitig_map_end(kmx_model *m) { return guarded([&] { return kmx_unitig_map_end_impl(m); }); }
 extern "C" int kmx_unitig_walk_segs(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets, uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_impl(m, segs, n_segs, seg_offsets, n_seqs, link_offsets, links, n_links, params, walks, walk_capacity, walk_offsets, steps, step_capacity, link_hits, stats); }); }
 extern "C" int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets, uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_dev_impl(m, d_segs, n_segs, d_seg_offsets, n_seqs, d_link_offsets, d_links, n_links, params, d_walks, walk_capacity, d_walk_offsets, d_steps, step_capacity, d_link_hits, stats); }); }
+extern "C" int kmx_unitig_contigs(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const kmx_contig_params *params, char *cseq, uint64_t *coffsets, kmx_contig *crec, uint32_t *steps, kmx_contig_place *place, uint64_t *clink_offsets, uint32_t *clinks, uint64_t *csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, params, cseq, coffsets, crec, steps, place, clink_offsets, clinks, csupport, n_contigs, n_cbases, n_clinks, stats); }); }
+extern "C" int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const kmx_contig_params *params, char *d_cseq, uint64_t *d_coffsets, kmx_contig *d_crec, uint32_t *d_steps, kmx_contig_place *d_place, uint64_t *d_clink_offsets, uint32_t *d_clinks, uint64_t *d_csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, params, d_cseq, d_coffsets, d_crec, d_steps, d_place, d_clink_offsets, d_clinks, d_csupport, n_contigs, n_cbases, n_clinks, stats); }); }
+extern "C" int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_contigs_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

@@ -430,6 +430,64 @@ struct WalkDev {
 	u64 step_cap;
 	unsigned long long *link_hits;   // [n_links] or null
 };
+// kmx_unitig_contigs*: a contig and a unitig's place, the layouts of kmx_contig and kmx_contig_place (include/kmx.h; contig_host.h
+// asserts them) ...
+struct Contig {
+	u64 n_kmers, sum_count;
+	u32 min_count, max_count;
+	u64 first_step;
+	u32 n_steps;
+	unsigned char circular, n_pred, n_succ, reserved;
+	u64 min_support, sum_support, reserved2;
+};
+struct CtgPlace {
+	u32 oc, off;
+};
+// ... the rank state of an oriented unitig (a head points at itself with steps == 0): the steps and the k-mers from ptr to here ...
+struct CtgRank {
+	u32 ptr, steps;
+	u64 kmers;
+};
+// ... what the scan of the marks adds up per unitig: the contigs that start there, their bytes, their steps ...
+struct CtgTot {
+	u64 n, len, steps;
+};
+// ... the counters of a call, the first five in the order of kmx_contig_stats ...
+enum { CTG_C_LINKS = 0, CTG_C_KEPT, CTG_C_BELOW_MIN, CTG_C_BELOW_RATIO, CTG_C_CHAIN, CTG_C_CIRCULAR, CTG_C_MULTI, CTG_C_N };
+// ... and the input, the work arrays and the output of one call (contig_kernels.h).  Every array of the caller is read and
+// written under the bounds given here: U, n_ubases, n_links.
+struct CtgDev {
+	int k;
+	u64 U, n_ubases, n_links;
+	const unsigned char *useq;   // [n_ubases]
+	const u64 *uoffs;            // [U + 1]
+	const Unitig *urec;          // [U] or null
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	const u64 *hits;             // [n_links]
+	u64 min_reads;
+	u32 ratio;
+	u64 *esup;                   // [n_links]: sup(e)
+	unsigned char *ekeep;        // [n_links]: 1 iff e is kept
+	u64 *best;                   // [2 U]
+	unsigned char *nk;           // [2 U]: |outK[o]|
+	u32 *only;                   // [2 U]: the one kept target, or CTG_NONE
+	u64 *supo;                   // [2 U]: its support
+	unsigned char *circ;         // [U]: the unitig lies on a cycle of chain links
+	CtgTot *sc;                  // [U + 1]: the scanned marks
+	u64 *ubase;                  // [U]: where the oriented string of u starts in cseq | CTG_REV | CTG_FIRST
+	u64 *clc, *clsc;             // [2 U + 1] each: the kept edges at the end of every oriented contig, and their scan
+	u32 *last;                   // [2 U]: the last step of every oriented contig
+	unsigned long long *cnt;     // [CTG_C_N]
+	unsigned char *cseq;         // [n_ubases]
+	u64 *coffs;                  // [U + 1]
+	Contig *crec;                // [U]
+	u32 *steps;                  // [U]
+	CtgPlace *place;             // [U]
+	u64 *cloffs;                 // [2 U + 1]
+	u32 *clinks;                 // [n_links]
+	u64 *csup;                   // [n_links]
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

@@ -89,4 +89,13 @@ hipError_t map_chunk(const MapDev &, const SeqView &, u64, u64, const MapChunk &
 hipError_t map_finish(const MapOut &, const u64 *, u64, u64, int, DevBuf<unsigned char> &tmp, hipStream_t);
 // ... and kmx_unitig_walk_segs*: the walks of a batch's segments (walk_kernels.h); the totals land in D.sc[D.n_segs] and D.cnt
 hipError_t walk_segs(const WalkDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+// ... and kmx_unitig_contigs* (contig_kernels.h): supports, verdicts and the rank state; a doubling round; the cut; marks + scan
+// (the totals land in D.sc[D.U]); steps, places, records, the scan of the end counts (its total in D.clsc[2 D.U]), the contig
+// graph and the bytes
+void contig_links(const CtgDev &, CtgRank *, u32 *, hipStream_t);
+void contig_round(const CtgRank *, const u32 *, CtgRank *, u32 *, u64, u32 *, hipStream_t);
+void contig_cut(const CtgDev &, const CtgRank *, const u32 *, CtgRank *, hipStream_t);
+hipError_t contig_mark(const CtgDev &, const CtgRank *, CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t contig_place(const CtgDev &, const CtgRank *, DevBuf<unsigned char> &tmp, hipStream_t);
+void contig_bytes(const CtgDev &, hipStream_t);
 }   // namespace kmxk

@@ -1,11 +1,13 @@
 // unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*, kmx_*unitig_graph_clean*).  The host side that sizes the
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.  Behind them the launchers of map_kernels.h (kmx_unitig_map_*), which
 // search the same listing through the same bucket index, and the launcher of walk_kernels.h (kmx_unitig_walk_segs*); their host side is map_host.h.
+// Last the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
 #include "map_kernels.h"
 #include "walk_kernels.h"
+#include "contig_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -15,6 +17,9 @@ inline unsigned nblk(u64 n) { return (unsigned)((n + 255) / 256); }
 
 struct TotPlus {
 	__host__ __device__ UniTot operator()(const UniTot &a, const UniTot &b) const { return UniTot{a.n + b.n, a.len + b.len}; }
+};
+struct CtgPlus {
+	__host__ __device__ CtgTot operator()(const CtgTot &a, const CtgTot &b) const { return CtgTot{a.n + b.n, a.len + b.len, a.steps + b.steps}; }
 };
 
 }   // namespace
@@ -166,6 +171,57 @@ hipError_t walk_segs(const WalkDev &D, DevBuf<unsigned char> &tmp, hipStream_t s
 	hipLaunchKernelGGL(k_walk_heads, dim3(nblk(n)), dim3(256), 0, st, D);
 	if (D.walks && D.walk_cap) hipLaunchKernelGGL(k_walk_sums, dim3(nblk(D.n_segs)), dim3(256), 0, st, D);
 	return hipGetLastError();
+}
+
+// ---- kmx_unitig_contigs* (contig_kernels.h); D.U > 0.  D.cnt is zero before contig_links, D.circ before contig_cut.
+
+// supports, verdicts with the four edge counters, the chain link in of every oriented unitig -> the rank state
+void contig_links(const CtgDev &D, CtgRank *rank, u32 *mn, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_ctg_sup, dim3(nblk(2 * D.U)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_ctg_keep, dim3(nblk(2 * D.U)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_ctg_init, dim3(nblk(2 * D.U)), dim3(256), 0, st, D, rank, mn);
+}
+
+void contig_round(const CtgRank *pin, const u32 *mnin, CtgRank *pout, u32 *mnout, u64 U, u32 *moved, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_ctg_round, dim3(nblk(2 * U)), dim3(256), 0, st, pin, mnin, pout, mnout, 2 * U, moved);
+}
+
+void contig_cut(const CtgDev &D, const CtgRank *pin, const u32 *mnin, CtgRank *pout, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_ctg_cut, dim3(nblk(2 * D.U)), dim3(256), 0, st, D, pin, mnin, pout);
+}
+
+// marks into tot[U + 1], then their exclusive scan into D.sc: D.sc[u] = (contigs, bytes, steps) in front of unitig u
+hipError_t contig_mark(const CtgDev &D, const CtgRank *rank, CtgTot *tot, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_ctg_mark, dim3(nblk(D.U + 1)), dim3(256), 0, st, D, rank, tot);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const CtgTot *)tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const CtgTot *)tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	return hipGetLastError();
+}
+
+// behind the marks: records, steps, places and coffsets, then the end counts, their scan and the contig graph
+hipError_t contig_place(const CtgDev &D, const CtgRank *rank, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.clc, 0, (2 * D.U + 1) * 8, st));
+	hipLaunchKernelGGL(k_ctg_rec_init, dim3(nblk(D.U)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_ctg_place, dim3(nblk(D.U + 1)), dim3(256), 0, st, D, rank);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const u64 *)D.clc, D.clsc, (u64)0, (size_t)(2 * D.U + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const u64 *)D.clc, D.clsc, (u64)0, (size_t)(2 * D.U + 1), rocprim::plus<u64>(), st));
+	hipLaunchKernelGGL(k_ctg_clinks, dim3(nblk(2 * D.U + 1)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the bytes: one block per tile of the flat input (D.ubase as contig_place left it)
+void contig_bytes(const CtgDev &D, hipStream_t st)
+{
+	if (D.n_ubases) hipLaunchKernelGGL(k_ctg_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
 }
 
 }   // namespace kmxk
