@@ -20,6 +20,11 @@
 //          times ratio stay below the best edge at either end), merge the unitigs along what is left (KModel::unitig_contigs):
 //          contigs.fa and contigs.paths.tsv (contig, step, unitig, strand, k-mer offset); with -G also contigs.gfa (unitig and
 //          contig segments, the kept edges with their reads, one path line per contig)
+//     -R<min_reads>[,<max_cross>]  with -M -W -X: first split every unitig whose reads pair its ways in with its ways out one to one
+//          (KModel::unitig_through per batch, then KModel::unitig_resolve: a pairing needs min_reads reads, every other pairing
+//          at most max_cross, 0 when omitted), so that repeats shorter than a read no longer end the contigs: contigs.* are built
+//          from the resolved graph, unitigs.resolved.tsv (new unitig, origin, copy) names its unitigs; unitigs.fa and unitigs.gfa
+//          stay the unresolved graph
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -40,6 +45,7 @@ struct Params {
 	long walk_gap = -2;                                            // -W: max_gap, -1 = k, -2 = no walks
 	long long min_reads = -1;                                      // -X: min_reads, -1 = no contigs
 	long ratio = 0;                                                // -X<min_reads>,<ratio>
+	long long res_min = -1, res_cross = 0;                         // -R<min_reads>[,<max_cross>], -1 = no resolution
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -75,6 +81,18 @@ static bool parse(int argc, char **argv, Params &p)
 			}
 			if (*end) return false;
 		}
+		else if (!strncmp(a, "-R", 2)) {
+			char *end = nullptr;
+			if (!a[2]) return false;
+			p.res_min = strtoll(a + 2, &end, 10);
+			if (end == a + 2 || p.res_min < 0) return false;
+			if (*end == ',') {
+				const char *r = end + 1;
+				p.res_cross = strtoll(r, &end, 10);
+				if (end == r || p.res_cross < 0) return false;
+			}
+			if (*end) return false;
+		}
 		else if (!strncmp(a, "-C", 2)) {
 			char *end = nullptr;
 			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
@@ -97,6 +115,10 @@ static bool parse(int argc, char **argv, Params &p)
 	if (p.walk_gap > -2 && !p.map) return false;                   // the walks are built from the map's segments
 	if (p.min_reads >= 0 && (!p.map || p.walk_gap == -2)) {        // the contigs are built from the reads per link, which the walks count
 		std::cout << "-X needs -M -W: the contigs are built from the reads that cross every link, which the walks count\n";
+		return false;
+	}
+	if (p.res_min >= 0 && p.min_reads < 0) {                       // the resolved graph is what the contigs are built from
+		std::cout << "-R needs -M -W -X: the repeats are resolved from the walks, and the contigs are built from the resolved graph\n";
 		return false;
 	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
@@ -146,7 +168,9 @@ int main(int argc, char **argv)
 		             "       -W<max_gap>  with -M: join every read's segments into walks through the graph, bridging at most max_gap (k) unmapped windows:\n"
 		             "           reads.gaf, unitigs.links.tsv (link index, source, target, reads)\n"
 		             "       -X<min_reads>[,<ratio>]  with -M -W: merge the unitigs along the edges at least min_reads reads cross: contigs.fa,\n"
-		             "           contigs.paths.tsv (contig, step, unitig, strand, offset), and contigs.gfa with -G\n";
+		             "           contigs.paths.tsv (contig, step, unitig, strand, offset), and contigs.gfa with -G\n"
+		             "       -R<min_reads>[,<max_cross>]  with -M -W -X: first resolve the repeats that reads span: unitigs.resolved.tsv (new unitig,\n"
+		             "           origin, copy); contigs.* are built from the resolved graph\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -204,7 +228,7 @@ int main(int argc, char **argv)
 			std::ofstream gaf;
 			if (walks) gaf.open((dir + "/reads.gaf").c_str());
 			const kmx_walk_params wp = {(uint32_t)(p.walk_gap >= 0 ? p.walk_gap : p.k), 1, {0, 0}};
-			std::vector<uint64_t> link_hits(links.size(), 0), walk_offsets;
+			std::vector<uint64_t> link_hits(links.size(), 0), walk_offsets, through;
 			std::vector<uint32_t> steps;
 			kmx_walk_stats wt = kmx_walk_stats();
 			std::vector<uint64_t> hits(strs.size(), 0), seg_offsets;
@@ -223,6 +247,7 @@ int main(int argc, char **argv)
 					kmx_walk_stats ws;
 					const std::vector<kmx_walk> wk = km->seq_walks(segs, seg_offsets, link_offsets, links, wp, &walk_offsets, &steps, &link_hits, &ws);
 					KModel::write_walks_gaf(gaf, wk, walk_offsets, steps, off, strs, p.k, n_reads);
+					if (p.res_min >= 0) km->unitig_through(wk, steps, link_offsets, links, through);
 					wt.n_walks += ws.n_walks; wt.n_steps += ws.n_steps; wt.n_edge += ws.n_edge; wt.n_inside += ws.n_inside; wt.n_across += ws.n_across;
 					wt.n_unlinked += ws.n_unlinked; wt.n_breaks += ws.n_breaks;
 				}
@@ -246,7 +271,24 @@ int main(int argc, char **argv)
 				          << " gaps bridged (" << wt.n_across << " across an edge), " << wt.n_breaks << " breaks" << std::endl;
 				if (p.min_reads >= 0) {
 					const kmx_contig_params xp = {(uint64_t)p.min_reads, (uint32_t)p.ratio, 0};
-					const KModel::Contigs ct = km->unitig_contigs(strs, &rec, link_offsets, links, link_hits, p.k, xp);
+					KModel::Resolved rs;
+					if (p.res_min >= 0) {
+						const kmx_resolve_params rp = {(uint64_t)p.res_min, (uint64_t)p.res_cross};
+						if (through.empty()) through.assign(16 * strs.size(), 0);
+						rs = km->unitig_resolve(strs, &rec, link_offsets, links, &link_hits, through, p.k, rp);
+						std::ofstream rt((dir + "/unitigs.resolved.tsv").c_str());
+						KModel::write_resolved_tsv(rt, rs);
+						rt.close();
+						if (!rt) { std::cout << "could not write " << dir << "/unitigs.resolved.tsv" << std::endl; return 1; }
+						std::cout << "   repeats resolved (>= " << p.res_min << " reads, <= " << p.res_cross << " across) :     " << rs.stats.n_resolved << " of " << rs.stats.n_candidates << " candidates ("
+						          << rs.stats.n_crossed << " crossed, " << rs.stats.n_unsupported << " unsupported, " << rs.stats.n_ambiguous << " ambiguous), " << rs.stats.n_unitigs_out << " unitigs"
+						          << std::endl;
+						if (links.empty()) rs.link_hits.clear();
+					}
+					const std::vector<std::string> &cstrs = p.res_min >= 0 ? rs.strs : strs;
+					const std::vector<kmx_unitig> &crec = p.res_min >= 0 ? rs.rec : rec;
+					const KModel::Contigs ct = p.res_min >= 0 ? km->unitig_contigs(rs.strs, &rs.rec, rs.link_offsets, rs.links, rs.link_hits, p.k, xp)
+					                                          : km->unitig_contigs(strs, &rec, link_offsets, links, link_hits, p.k, xp);
 					std::ofstream cf((dir + "/contigs.fa").c_str()), cp2((dir + "/contigs.paths.tsv").c_str());
 					KModel::write_contigs_fasta(cf, ct);
 					KModel::write_contig_paths_tsv(cp2, ct);
@@ -255,7 +297,7 @@ int main(int argc, char **argv)
 					if (!cf || !cp2) { std::cout << "could not write " << dir << "/contigs.fa or contigs.paths.tsv" << std::endl; return 1; }
 					if (p.gfa) {
 						std::ofstream cg((dir + "/contigs.gfa").c_str());
-						KModel::write_contigs_gfa(cg, ct, p.k, &strs, &rec);
+						KModel::write_contigs_gfa(cg, ct, p.k, &cstrs, &crec);
 						cg.close();
 						if (!cg) { std::cout << "could not write " << dir << "/contigs.gfa" << std::endl; return 1; }
 					}

@@ -552,6 +552,68 @@ public:
 			}
 	}
 
+	// Through hits and resolution (the rule: kmx.h).  unitig_through takes the walks and steps seq_walks returned and the CSR they
+	// were made with, and ADDS the reads per (way in, way out) of every unitig to through (16 per unitig; an empty vector is sized
+	// and zeroed).  unitig_resolve splits every unitig whose through hits pair its ways in with its ways out one to one; the result
+	// is an ordinary unitig graph (strings, records when rec is given, CSR, link_hits when given) that unitig_contigs takes as it
+	// is, with origin (the input unitig of every new one), place (per input unitig: its first copy and their number) and
+	// link_origin (the input edge of every new one).  Neither needs a session.
+	kmx_through_stats unitig_through(const std::vector<kmx_walk> &walks, const std::vector<uint32_t> &steps, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links,
+	                                 std::vector<uint64_t> &through)
+	{
+		const size_t U = link_offsets.empty() ? 0 : (link_offsets.size() - 1) / 2;
+		if (through.empty()) through.assign(16 * U, 0);
+		if (through.size() != 16 * U || link_offsets.empty()) { std::cout << "unitig_through: the vectors are not those of one graph" << std::endl; exit(1); }
+		kmx_through_stats st = kmx_through_stats();
+		check(kmx_unitig_walk_through(h_, walks.empty() ? 0 : &walks[0], walks.size(), steps.empty() ? 0 : &steps[0], steps.size(), &link_offsets[0], links.empty() ? 0 : &links[0], links.size(), U,
+		                              U ? &through[0] : 0, &st));
+		return st;
+	}
+	struct Resolved {
+		std::vector<std::string> strs;
+		std::vector<kmx_unitig> rec;                 // empty when no records were given
+		std::vector<uint32_t> origin;
+		std::vector<kmx_resolve_place> place;
+		std::vector<uint64_t> link_offsets;
+		std::vector<uint32_t> links;
+		std::vector<uint64_t> link_origin;
+		std::vector<uint64_t> link_hits;             // empty when no link hits were given
+		kmx_resolve_stats stats;
+	};
+	Resolved unitig_resolve(const std::vector<std::string> &unitigs, const std::vector<kmx_unitig> *rec, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links,
+	                        const std::vector<uint64_t> *link_hits, const std::vector<uint64_t> &through, int k, const kmx_resolve_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), nl = links.size();
+		if (link_offsets.size() != 2 * U + 1 || through.size() != 16 * U || (link_hits && link_hits->size() != nl) || (rec && rec->size() != U)) {
+			std::cout << "unitig_resolve: the vectors are not those of one graph" << std::endl;
+			exit(1);
+		}
+		const bool with_rec = rec && U, with_hits = link_hits && nl;
+		Resolved r;
+		uint64_t n = 0, nb = 0;
+		check(kmx_unitig_resolve(h_, k, f.bases.data(), f.off.data(), U, with_rec ? &(*rec)[0] : 0, &link_offsets[0], nl ? &links[0] : 0, nl, with_hits ? &(*link_hits)[0] : 0, U ? &through[0] : 0, &params,
+		                         0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, &n, &nb, &r.stats));                                     // the sizing call
+		std::string rseq((size_t)nb + 1, '\0');
+		std::vector<uint64_t> roff((size_t)n + 1, 0);
+		r.rec.resize(with_rec ? (size_t)n : 0); r.origin.resize((size_t)n + 1); r.place.resize(U + 1); r.link_offsets.resize(2 * (size_t)n + 1); r.links.resize(nl + 1); r.link_origin.resize(nl + 1);
+		r.link_hits.resize(with_hits ? nl : 0);
+		check(kmx_unitig_resolve(h_, k, f.bases.data(), f.off.data(), U, with_rec ? &(*rec)[0] : 0, &link_offsets[0], nl ? &links[0] : 0, nl, with_hits ? &(*link_hits)[0] : 0, U ? &through[0] : 0, &params,
+		                         &rseq[0], nb, &roff[0], n, with_rec ? &r.rec[0] : 0, &r.origin[0], &r.place[0], &r.link_offsets[0], &r.links[0], &r.link_origin[0], with_hits ? &r.link_hits[0] : 0, &n, &nb,
+		                         &r.stats));
+		r.strs = split(rseq, roff);
+		r.origin.resize((size_t)n); r.place.resize(U); r.links.resize(nl); r.link_origin.resize(nl);
+		return r;
+	}
+	// the resolved set as a table, one "u<new unitig>\tu<origin>\t<copy>" per new unitig
+	static void write_resolved_tsv(std::ostream &out, const Resolved &r)
+	{
+		for (size_t i = 0; i < r.origin.size(); i++) {
+			const uint32_t u = r.origin[i];
+			out << "u" << i << "\tu" << u << "\t" << (u < r.place.size() ? i - r.place[u].first : 0) << "\n";
+		}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

@@ -935,7 +935,8 @@ int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64
  *       and no k-mer appears twice, so the contig set is a valid set for kmx_unitig_map_begin on the same listing;
  *   (c) mirror invariance: adding every edge's hits on its mirror instead changes nothing;
  *   (d) place inverts steps; the n_steps sum to U, the n_kmers to the sum of m_u, and n_cbases = that sum + C (k - 1).
- * Out of scope: repeat resolution from walks that span a unitig (only single edges are judged); iterating with a re-map;
+ * Repeats shorter than a read: kmx_unitig_walk_through and kmx_unitig_resolve below, in front of this call.
+ * Out of scope: iterating with a re-map;
  * paired reads; even k; several GPUs; choosing min_reads and ratio.                                                        */
 typedef struct kmx_contig_params { uint64_t min_reads; uint32_t ratio; uint32_t reserved; } kmx_contig_params;          /* 16 bytes */
 typedef struct kmx_contig {              /* one per contig; 64 bytes, no padding */
@@ -993,6 +994,107 @@ int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64
  * waits for the stream): seconds[5] = supports and verdicts, ranking (links, rounds, cut), marks and their scan, records with
  * steps, places and the contig graph, the bytes; *rounds = its doubling rounds (counted always)                              */
 int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
+
+/* ---- through hits: the reads per (way in, way out) of every unitig.  link_hits judges single edges; a walk of three or more
+ * steps also says which way IN to a unitig goes with which way OUT, the evidence a repeat shorter than a read is resolved from.
+ * This call counts it; kmx_unitig_resolve below consumes it.
+ * Notation as above: U unitigs, oriented unitig o = 2 u + d, out[o] the CSR row (at most 4 entries).  For unitig u the RIGHT row
+ *   is R = out[2 u] and the LEFT row is L = out[2 u + 1]; entry a of L is "way in number a" when u is read forward: the edge
+ *   (L[a] ^ 1) -> 2 u.
+ * Input: the walks and steps exactly as kmx_unitig_walk_segs[_dev] wrote them, walks[n_walks] (only first_step and n_steps are
+ *   read) and steps[n_steps]; the CSR those walks were made with (link_offsets[2 U + 1], links[n_links]); and U.
+ * Output: through[16 U], which is ADDED to, like link_hits: the caller zeroes it and accumulates over batches.
+ * For every walk with steps s_0 .. s_(n-1) and every 0 < i < n - 1, let x = s_i, P = s_(i-1), N = s_(i+1).  Then i_in is the index
+ *   of P ^ 1 in out[x ^ 1] and i_out the index of N in out[x]; both take the first match among the first 4 entries.
+ *   (a, b) = (i_in, i_out) when x is even and (i_out, i_in) when x is odd, and through[16 (x >> 1) + 4 a + b] += 1.  If an index is
+ *   not found, or x, P or N >= 2 U, nothing is added and n_missing counts it.  n_interior counts every such i, n_added the
+ *   additions: n_interior = n_added + n_missing.  n_walks and n_steps are the call's arguments.
+ * Everything is an integer count and a function of (walks, steps, CSR) alone, byte-identical across runs and variants.
+ * Consequences:
+ *   (a) with the CSR the walks were made with n_missing is 0: every step after a walk's first came from an EDGE or ACROSS join
+ *       that found N in out[x], and the graph is mirror-symmetric, so P ^ 1 is in out[x ^ 1];
+ *   (b) the walk of a read's reverse complement adds to the SAME cells: it passes x ^ 1 between N ^ 1 and P ^ 1, which swaps the
+ *       two indices and the parity of x at once.  Unlike link_hits there is no mirror for the caller to add;
+ *   (c) when both arrays come from the same walk calls, the row sum of through[u][a][.] is at most link_hits[e] +
+ *       link_hits[mir(e)] for e = entry a of L (both terms also where mir(e) = e: a hairpin join is the way in of one step and
+ *       the way out of the step before, in the same row); the same holds for the columns and R;
+ *   (d) a circular unitig gone round twice adds to cell (0, 0) of itself.
+ * Out of scope: evidence from paired reads; several GPUs.                                                                   */
+typedef struct kmx_through_stats { uint64_t n_walks, n_steps, n_interior, n_added, n_missing, reserved[3]; } kmx_through_stats;   /* 64 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_unitig_contigs); it runs on the model's stream and is a
+ * build-class call.  stats is required; every buffer of a non-zero count is required, link_offsets always.  KMX_E_ARG before
+ * anything runs: a NULL required argument; U >= 2^31; walks whose first_step does not start at 0, with first_step[w + 1] !=
+ * first_step[w] + n_steps[w], or whose last sum is not n_steps; a CSR that kmx_unitig_walk_segs would refuse (link_offsets[0]
+ * != 0, decreasing, link_offsets[2 U] != n_links, a links[e] >= 2 U).  n_steps == 0 or U == 0: KMX_OK, nothing added.
+ * KMX_E_NOMEM leaves the handle usable.                                                                                   */
+int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets /* [2 U + 1] */,
+                            const uint32_t *links, uint64_t n_links, uint64_t n_unitigs, uint64_t *through /* [16 U] */, kmx_through_stats *stats);
+/* The same on DEVICE buffers, read where the walk and graph calls left them; stats is on the HOST.  It checks NULL and U and
+ * validates nothing else; the kernels clamp instead.  The records' n_steps is not used: walk boundaries are the first_step
+ * values, clamped into [0, n_steps]; row bounds are clamped into [0, n_links]; at most 4 entries of a row are read.  Bad input
+ * gives wrong counts and never an access outside a buffer.  It enqueues everything on the model's stream and waits once, for the
+ * stats.  Device memory, kept on the handle between calls: one byte per step plus the three counters.                       */
+int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets /* [2 U + 1] */,
+                                const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through /* [16 U] */, kmx_through_stats *stats /* HOST */);
+
+/* ---- resolution: a unitig whose through hits pair its ways in with its ways out one to one is split into one copy per way in.
+ * The output is an ordinary unitig graph, so kmx_unitig_contigs merges through the repeat unchanged.
+ * Input: as kmx_unitig_contigs (k, the unitig set, optionally urec, the CSR, optionally link_hits), through[16 U] as
+ *   kmx_unitig_walk_through accumulated it, and kmx_resolve_params.
+ * Unitig u, with R = out[2 u] of q entries and L = out[2 u + 1] of p entries, is a CANDIDATE iff p = q >= 2 and no entry of L or
+ *   R has unitig index u.  This excludes self-loops, hairpins and circular unitigs.  For a candidate, cell (a, b) with a, b < p is
+ *   SUPPORTED iff T = through[16 u + 4 a + b] >= min_reads and T >= 1.  The verdict is one of the following, in this order:
+ *   CROSSED: some unsupported cell has T > max_cross.  UNSUPPORTED: no cell is supported.  RESOLVED: every row a has exactly one
+ *   supported cell pi(a), and every column has exactly one.  AMBIGUOUS: otherwise.  Cells with a >= p or b >= p are ignored.
+ * The new graph.  An unresolved unitig has 1 copy.  A resolved one has p copies, and copy c belongs to way in c.  first[u] is the
+ *   exclusive sum of the copy counts, so new unitig first[u] + c is copy c of u; U' is the total.  Strings of copies are byte for
+ *   byte the origin's; the new offsets follow.  Every input edge e (entry j of out[o], o = 2 u + d, target t = 2 v + dt) becomes
+ *   exactly one new edge, so n_links does not change.  Its source: u unresolved: 2 first[u] + d; u resolved, d = 0 (j is a right
+ *   index): copy pi^-1(j); u resolved, d = 1 (j is a left index): copy j.  Its target: v unresolved: 2 first[v] + dt; v resolved:
+ *   with i = the index of o ^ 1 in out[t ^ 1], copy i for dt = 0 and copy pi_v^-1(i) for dt = 1.  Rows of an unresolved unitig
+ *   keep their order.  Copy c of a resolved unitig, u' = first[u] + c, has out'[2 u'] = {entry pi(c) of R} and
+ *   out'[2 u' + 1] = {entry c of L}.  Edges are numbered by (new oriented unitig, row order).
+ * Output: rseq[seq_capacity] and roffsets[rec_capacity + 1]; rrec[rec_capacity], NULL exactly when urec is: the origin's record
+ *   verbatim, with n_pred = n_succ = 1 for copies of a resolved unitig; origin[rec_capacity]; rplace[U]; rlink_offsets
+ *   [2 rec_capacity + 1]; rlinks[n_links]; link_origin[n_links], the input edge; rlink_hits[n_links] = link_hits[link_origin], NULL
+ *   exactly when link_hits is.  On the HOST: *n_unitigs_out, *n_bases_out and kmx_resolve_stats.  rseq == NULL is the sizing call:
+ *   the two counts and the stats, nothing else is written or needed of the outputs.  A capacity too small is KMX_E_RANGE, with
+ *   both counts set and nothing written.  4 U and 4 n_ubases always suffice; rec_capacity < 2^32, and a U' >= 2^31 is KMX_E_RANGE.
+ * Consequences:
+ *   (a) a no-op is exact: with through all zero, or with no resolved candidate, every output is byte for byte the input, and
+ *       origin and link_origin are the identity;
+ *   (b) the output is a valid input for kmx_unitig_contigs, whose host form accepts it: it is mirrored, has rows <= 4, has no edge
+ *       twice, and every overlap holds;
+ *   (c) a k-mer of a resolved unitig now appears p times, so the output is NOT a valid set for kmx_unitig_map_begin (it refuses
+ *       with KMX_E_ARG); through hits for a second round therefore cannot be had;
+ *   (d) everything is an integer count and a function of the input alone, byte-identical across runs and variants.
+ * Out of scope: iterating; p != q; repeats with a self edge; evidence from paired reads; choosing min_reads.                  */
+typedef struct kmx_resolve_params { uint64_t min_reads, max_cross; } kmx_resolve_params;                                 /* 16 bytes */
+typedef struct kmx_resolve_place { uint32_t first, n_copies; } kmx_resolve_place;                                        /* 8 bytes */
+typedef struct kmx_resolve_stats { uint64_t n_candidates, n_resolved, n_crossed, n_unsupported, n_ambiguous, n_copies_added, n_unitigs_out, reserved; } kmx_resolve_stats;   /* 64 bytes */
+/* On HOST buffers.  Needs no built model and no session; a build-class call on the model's stream.  KMX_E_ARG before anything
+ * runs, as kmx_unitig_contigs: an even or out-of-range k, U >= 2^31, a NULL required buffer (urec and rrec go together where
+ * U > 0, link_hits and rlink_hits where n_links > 0), an output that overlaps another buffer, bad uoffsets, a CSR that is not
+ * valid and mirrored with rows <= 4.
+ * U == 0: KMX_OK, roffsets[0] = rlink_offsets[0] = 0, all counts zero.  KMX_E_NOMEM leaves the handle usable.               */
+int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_unitig *urec /* or NULL */,
+                       const uint64_t *link_offsets /* [2 U + 1] */, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits /* or NULL */, const uint64_t *through /* [16 U] */,
+                       const kmx_resolve_params *params, char *rseq /* or NULL */, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin,
+                       kmx_resolve_place *rplace /* [U] */, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out,
+                       uint64_t *n_bases_out, kmx_resolve_stats *stats);
+/* The same on DEVICE buffers; params, the two counts and stats are on the HOST.  It checks k, U, NULL and overlap; the kernels
+ * clamp as those of kmx_unitig_contigs_dev do (uoffsets into [0, n_ubases], row bounds into [0, n_links], at most 4 entries of a
+ * row), and an edge whose target is >= 2 U or whose mirror is not found makes BOTH its ends unresolved, so the renaming is always
+ * defined.  Every store is checked against its capacity: bad input gives a wrong graph, never an access outside a buffer.  It
+ * waits for the stream once, for the counts and the stats, in front of the records, links and bytes, which it leaves enqueued on
+ * the model's stream.  Device memory, kept on the handle between calls: 53 bytes per unitig plus the scan's scratch.          */
+int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec /* or NULL */,
+                           const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits /* or NULL */, const uint64_t *d_through,
+                           const kmx_resolve_params *params /* HOST */, char *d_rseq /* or NULL */, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec,
+                           uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits,
+                           uint64_t *n_unitigs_out /* HOST */, uint64_t *n_bases_out /* HOST */, kmx_resolve_stats *stats /* HOST */);
+/* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): verdicts, scan and records, links, bytes */
+int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds /* [4] */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -58,6 +58,8 @@ ABI_SYMBOLS = [
     "kmx_unitig_map_begin", "kmx_unitig_map_begin_dev", "kmx_count_unitig_map_begin", "kmx_count_unitig_map_begin_dev", "kmx_unitig_map_seqs", "kmx_unitig_map_seqs_dev", "kmx_unitig_map_end",
     "kmx_unitig_walk_segs", "kmx_unitig_walk_segs_dev",
     "kmx_unitig_contigs", "kmx_unitig_contigs_dev", "kmx_unitig_contigs_last_phases",
+    "kmx_unitig_walk_through", "kmx_unitig_walk_through_dev",
+    "kmx_unitig_resolve", "kmx_unitig_resolve_dev", "kmx_unitig_resolve_last_phases",
 ]
 
 
@@ -171,6 +173,31 @@ class ContigStats(C.Structure):
 CONTIG_DTYPE = np.dtype([("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count", "<u4"), ("max_count", "<u4"), ("first_step", "<u8"), ("n_steps", "<u4"),
                          ("circular", "u1"), ("n_pred", "u1"), ("n_succ", "u1"), ("reserved", "u1"), ("min_support", "<u8"), ("sum_support", "<u8"), ("reserved2", "<u8")])
 CONTIG_PLACE_DTYPE = np.dtype([("oc", "<u4"), ("off", "<u4")])
+
+
+class ThroughStats(C.Structure):
+    """kmx_through_stats of include/kmx.h: 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_walks", "n_steps", "n_interior", "n_added", "n_missing")] + [("reserved", C.c_uint64 * 3)]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_ if f != "reserved"}
+
+
+class ResolveParams(C.Structure):
+    """kmx_resolve_params of include/kmx.h: 16 bytes"""
+    _fields_ = [("min_reads", C.c_uint64), ("max_cross", C.c_uint64)]
+
+
+class ResolveStats(C.Structure):
+    """kmx_resolve_stats of include/kmx.h: 64 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_candidates", "n_resolved", "n_crossed", "n_unsupported", "n_ambiguous", "n_copies_added", "n_unitigs_out", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_resolve_place as a NumPy structured dtype (what KModel.unitig_resolve_flat returns): 8 bytes
+RESOLVE_PLACE_DTYPE = np.dtype([("first", "<u4"), ("n_copies", "<u4")])
 
 
 class RingList(C.Structure):
@@ -320,6 +347,11 @@ def load_library():
     _sig(L, "kmx_unitig_contigs", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, C.POINTER(ContigParams), vp, vp, vp, vp, vp, vp, vp, vp, p64, p64, p64, C.POINTER(ContigStats)])
     _sig(L, "kmx_unitig_contigs_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, C.POINTER(ContigParams), vp, vp, vp, vp, vp, vp, vp, vp, p64, p64, p64, C.POINTER(ContigStats)])
     _sig(L, "kmx_unitig_contigs_last_phases", [vp, C.POINTER(C.c_double), p64])
+    _sig(L, "kmx_unitig_walk_through", [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, C.POINTER(ThroughStats)])
+    _sig(L, "kmx_unitig_walk_through_dev", [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, C.POINTER(ThroughStats)])
+    _sig(L, "kmx_unitig_resolve", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
+    _sig(L, "kmx_unitig_resolve_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
+    _sig(L, "kmx_unitig_resolve_last_phases", [vp, C.POINTER(C.c_double)])
     L.kmx_set_profile.argtypes = [vp, i32]
     L.kmx_get_kernel_times.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u64), i32]
     _lib = L
@@ -1217,6 +1249,129 @@ class KModel:
         sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
         _chk(self.L.kmx_unitig_contigs_last_phases(self.h, sec, C.byref(rounds)))
         return dict(zip(("support", "ranking", "marks", "records", "bytes"), (float(x) for x in sec)), rounds=int(rounds.value))
+
+    # ---- through hits: the reads per (way in, way out) of every unitig (the rule: include/kmx.h); no model, no session
+    def unitig_through_flat(self, walks: np.ndarray, steps: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, through=None):
+        """kmx_unitig_walk_through on what unitig_walks_flat returned (WALK_DTYPE walks, uint32 steps) and the CSR those walks were
+        made with -> (uint64 through [16 U], stats as a dict).  through (uint64 [16 U], optional) is ADDED to and returned; None: a
+        zeroed one."""
+        walks = np.ascontiguousarray(walks, dtype=WALK_DTYPE)
+        steps = np.ascontiguousarray(steps, dtype=np.uint32)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        nu = (link_offsets.size - 1) // 2
+        if through is None:
+            through = np.zeros(16 * nu, dtype=np.uint64)
+        if through.dtype != np.uint64 or not through.flags.c_contiguous or through.size < 16 * nu:
+            raise KmxError(-1, "through must be a contiguous uint64 array with 16 entries per unitig")
+        st = ThroughStats()
+        _chk(self.L.kmx_unitig_walk_through(self.h, walks.ctypes.data, walks.size, steps.ctypes.data, steps.size, link_offsets.ctypes.data, links.ctypes.data, links.size, nu,
+                                            through.ctypes.data, C.byref(st)))
+        return through, st.as_dict()
+
+    def unitig_through_dev(self, d_walks, n_walks: int, d_steps, n_steps: int, d_link_offsets, d_links, d_through=None):
+        """kmx_unitig_walk_through_dev on torch tensors of the model's device, read where unitig_walks_dev and the graph call left
+        them: d_walks uint8 [walk_capacity, 80] holding n_walks walks, d_steps int32 [step_capacity] holding n_steps steps,
+        d_link_offsets int64 [2 U + 1], d_links int32 [n_links]; d_through int64 [16 U] is ADDED to (None: a zeroed one is
+        allocated) -> (d_through, stats as a dict)."""
+        import torch
+        nu = (d_link_offsets.numel() - 1) // 2
+        if d_through is None:
+            d_through = torch.zeros(16 * nu, dtype=torch.int64, device=d_link_offsets.device)
+        st = ThroughStats()
+        _chk(self.L.kmx_unitig_walk_through_dev(self.h, d_walks.data_ptr() if n_walks else None, int(n_walks), d_steps.data_ptr() if n_steps else None, int(n_steps), d_link_offsets.data_ptr(),
+                                                d_links.data_ptr(), d_links.numel(), nu, d_through.data_ptr(), C.byref(st)))
+        return d_through, st.as_dict()
+
+    def through_from_walks(self, reads, link_offsets: np.ndarray, links: np.ndarray, max_gap: int, max_indel: int = 1, link_hits=None, through=None):
+        """inside a map session: seq_to_walks on the reads (link_hits, optional, is added to), then unitig_through_flat on the walks
+        they leave -> (through, stats as a dict)"""
+        walks, _, steps, _, _, _ = self.seq_to_walks(reads, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
+        return self.unitig_through_flat(walks, steps, link_offsets, links, through)
+
+    # ---- resolution: the unitigs whose through hits pair their ways in with their ways out are split (the rule: include/kmx.h)
+    def unitig_resolve_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, through: np.ndarray, min_reads: int = 2, max_cross: int = 0,
+                            urec=None, link_hits=None, capacity=None):
+        """kmx_unitig_resolve on what a graph call returned, the through hits and optionally the records and the link hits ->
+        (uint8 bases, uint64 roffsets [U' + 1], UNITIG_DTYPE records [U'] or None, uint32 origin [U'], RESOLVE_PLACE_DTYPE rplace [U],
+        uint64 rlink_offsets [2 U' + 1], uint32 rlinks, uint64 link_origin, uint64 rlink_hits or None, stats as a dict).  capacity None:
+        a sizing call first; (rec_capacity, seq_capacity): those (KmxError KMX_E_RANGE when short)."""
+        ubuf = np.ascontiguousarray(ubuf, dtype=np.uint8)
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        through = np.ascontiguousarray(through, dtype=np.uint64)
+        nu, nl = uoffsets.size - 1, links.size
+        if link_offsets.size != 2 * nu + 1 or through.size != 16 * nu or (link_hits is not None and np.asarray(link_hits).size != nl):
+            raise KmxError(-1, "link_offsets holds 2 U + 1 entries, through 16 per unitig and link_hits one per link")
+        if urec is not None:
+            urec = np.ascontiguousarray(urec, dtype=UNITIG_DTYPE)
+        if link_hits is not None:
+            link_hits = np.ascontiguousarray(link_hits, dtype=np.uint64)
+        par, st = ResolveParams(int(min_reads), int(max_cross)), ResolveStats()
+        n_out, b_out = C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        head = (self.h, int(k), ubuf.ctypes.data, uoffsets.ctypes.data, nu, ptr(urec), link_offsets.ctypes.data, links.ctypes.data, nl, ptr(link_hits), through.ctypes.data, C.byref(par))
+        if capacity is None:
+            _chk(self.L.kmx_unitig_resolve(*head, None, 0, None, 0, None, None, None, None, None, None, None, C.byref(n_out), C.byref(b_out), C.byref(st)))
+            capacity = (n_out.value, b_out.value)
+        rcap, scap = int(capacity[0]), int(capacity[1])
+        rseq = np.zeros(max(scap, 1), dtype=np.uint8)
+        roffs = np.zeros(rcap + 1, dtype=np.uint64)
+        rrec = np.zeros(max(rcap, 1), dtype=UNITIG_DTYPE) if urec is not None else None
+        origin = np.zeros(max(rcap, 1), dtype=np.uint32)
+        rplace = np.zeros(max(nu, 1), dtype=RESOLVE_PLACE_DTYPE)
+        rloffs = np.zeros(2 * rcap + 1, dtype=np.uint64)
+        rlinks = np.zeros(max(nl, 1), dtype=np.uint32)
+        lorigin = np.zeros(max(nl, 1), dtype=np.uint64)
+        rhits = np.zeros(max(nl, 1), dtype=np.uint64) if link_hits is not None else None
+        _chk(self.L.kmx_unitig_resolve(*head, rseq.ctypes.data, scap, roffs.ctypes.data, rcap, ptr(rrec), origin.ctypes.data, rplace.ctypes.data, rloffs.ctypes.data, rlinks.ctypes.data,
+                                       lorigin.ctypes.data, ptr(rhits), C.byref(n_out), C.byref(b_out), C.byref(st)))
+        n, b = n_out.value, b_out.value
+        return (rseq[:b].copy(), roffs[:n + 1].copy(), rrec[:n].copy() if rrec is not None else None, origin[:n].copy(), rplace[:nu].copy(), rloffs[:2 * n + 1].copy(), rlinks[:nl].copy(),
+                lorigin[:nl].copy(), rhits[:nl].copy() if rhits is not None else None, st.as_dict())
+
+    def unitig_resolve_dev(self, k: int, d_ubuf, d_uoffsets, d_link_offsets, d_links, d_through, min_reads: int = 2, max_cross: int = 0, d_urec=None, d_link_hits=None, capacity=None, out=None):
+        """kmx_unitig_resolve_dev on torch tensors of the model's device: d_ubuf uint8 [n_ubases], d_uoffsets int64 [U + 1],
+        d_link_offsets int64 [2 U + 1], d_links int32 [n_links], d_through int64 [16 U], d_urec uint8 [U, 40] or None, d_link_hits int64
+        [n_links] or None.  capacity None: a sizing call first; (rec_capacity, seq_capacity): those.  out: the nine output tensors
+        (d_rseq uint8, d_roffsets int64 [rec_capacity + 1], d_rrec uint8 [rec_capacity, 40] or None, d_origin int32, d_rplace int32 [U, 2],
+        d_rlink_offsets int64 [2 rec_capacity + 1], d_rlinks int32, d_link_origin int64, d_rlink_hits int64 or None), allocated when None
+        -> (out, (n_unitigs_out, n_bases_out), stats as a dict); the outputs are complete once the model's stream has drained."""
+        import torch
+        nu, nb, nl, dev = d_uoffsets.numel() - 1, d_ubuf.numel(), d_links.numel(), d_uoffsets.device
+        par, st = ResolveParams(int(min_reads), int(max_cross)), ResolveStats()
+        n_out, b_out = C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        head = (self.h, int(k), d_ubuf.data_ptr(), d_uoffsets.data_ptr(), nu, nb, ptr(d_urec), d_link_offsets.data_ptr(), d_links.data_ptr(), nl, ptr(d_link_hits), d_through.data_ptr(), C.byref(par))
+        if capacity is None and out is None:
+            _chk(self.L.kmx_unitig_resolve_dev(*head, None, 0, None, 0, None, None, None, None, None, None, None, C.byref(n_out), C.byref(b_out), C.byref(st)))
+            capacity = (n_out.value, b_out.value)
+        if out is None:
+            rcap, scap = int(capacity[0]), int(capacity[1])
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            out = (z(max(scap, 1), torch.uint8), z(rcap + 1, torch.int64), z((max(rcap, 1), 40), torch.uint8) if d_urec is not None else None, z(max(rcap, 1), torch.int32),
+                   z((max(nu, 1), 2), torch.int32), z(2 * rcap + 1, torch.int64), z(max(nl, 1), torch.int32), z(max(nl, 1), torch.int64), z(max(nl, 1), torch.int64) if d_link_hits is not None else None)
+        else:
+            rcap, scap = (out[1].numel() - 1, out[0].numel()) if capacity is None else (int(capacity[0]), int(capacity[1]))
+        _chk(self.L.kmx_unitig_resolve_dev(*head, out[0].data_ptr(), scap, out[1].data_ptr(), rcap, ptr(out[2]), out[3].data_ptr(), out[4].data_ptr(), out[5].data_ptr(), out[6].data_ptr(),
+                                           out[7].data_ptr(), ptr(out[8]), C.byref(n_out), C.byref(b_out), C.byref(st)))
+        return out, (n_out.value, b_out.value), st.as_dict()
+
+    def resolved_contigs_from_walks(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, reads, max_gap=None, max_indel: int = 1,
+                                    resolve_min_reads: int = 2, max_cross: int = 0, min_reads: int = 1, ratio: int = 0, urec=None):
+        """inside a map session on these unitigs: map -> walks with link_hits -> through -> resolve -> contigs on the resolved graph
+        -> (what unitig_contigs_flat returns on the resolved graph, what unitig_resolve_flat returned, the through hits)"""
+        hits = np.zeros(np.asarray(links).size, dtype=np.uint64)
+        through, _ = self.through_from_walks(reads, link_offsets, links, int(k) if max_gap is None else int(max_gap), max_indel, link_hits=hits)
+        res = self.unitig_resolve_flat(k, ubuf, uoffsets, link_offsets, links, through, resolve_min_reads, max_cross, urec, hits)
+        return self.unitig_contigs_flat(k, res[0], res[1], res[5], res[6], res[8], min_reads, ratio, res[2]), res, through
+
+    def unitig_resolve_phases(self) -> dict:
+        """kmx_unitig_resolve_last_phases: seconds per phase of the last resolve call (under set_profile(1))"""
+        sec = (C.c_double * 4)()
+        _chk(self.L.kmx_unitig_resolve_last_phases(self.h, sec))
+        return dict(zip(("verdicts", "records", "links", "bytes"), (float(x) for x in sec)))
 
     def save(self, save_dir: str) -> None:                    # kmodel.hpp:173
         _chk(self.L.kmx_save(self.h, save_dir.encode()))

@@ -391,6 +391,17 @@ struct kmx_model {
 		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): supports and verdicts, ranking, marks, records and graph, bytes
 		u64 rounds = 0;
 	} ctg;
+	// kmx_unitig_walk_through* and kmx_unitig_resolve* (resolve_host.h): the work arrays of a call, kept by capacity from call to call
+	struct ResState {
+		DevBuf<unsigned char> d_mark;                              // [n_steps + 1] 1 where a walk starts
+		DevBuf<unsigned long long> d_cnt;                          // [THR_C_N] the call's counters
+		// kmx_unitig_resolve*
+		DevBuf<unsigned char> d_bad, d_tmp;                        // [U] an edge at this unitig has no mirror; rocPRIM scratch
+		DevBuf<u32> d_ver;                                         // [U] the copies with pi packed above them
+		DevBuf<CtgTot> d_tot, d_sc;                                // [U + 1] each: (copies, bytes, edges) and their scan
+		DevBuf<unsigned long long> d_rcnt;                         // [RES_C_N]
+		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): verdicts, scan and records, links, bytes
+	} res;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2934,6 +2945,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "unitig_host.h"
 #include "map_host.h"
 #include "contig_host.h"
+#include "resolve_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3468,6 +3480,11 @@ extern "C" int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_s
 extern "C" int kmx_unitig_contigs(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const kmx_contig_params *params, char *cseq, uint64_t *coffsets, kmx_contig *crec, uint32_t *steps, kmx_contig_place *place, uint64_t *clink_offsets, uint32_t *clinks, uint64_t *csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, params, cseq, coffsets, crec, steps, place, clink_offsets, clinks, csupport, n_contigs, n_cbases, n_clinks, stats); }); }
 extern "C" int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const kmx_contig_params *params, char *d_cseq, uint64_t *d_coffsets, kmx_contig *d_crec, uint32_t *d_steps, kmx_contig_place *d_place, uint64_t *d_clink_offsets, uint32_t *d_clinks, uint64_t *d_csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, params, d_cseq, d_coffsets, d_crec, d_steps, d_place, d_clink_offsets, d_clinks, d_csupport, n_contigs, n_cbases, n_clinks, stats); }); }
 extern "C" int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_contigs_last_phases_impl(m, seconds, rounds); }); }
+extern "C" int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, uint64_t n_unitigs, uint64_t *through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_impl(m, walks, n_walks, steps, n_steps, link_offsets, links, n_links, n_unitigs, through, stats); }); }
+extern "C" int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_dev_impl(m, d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, n_unitigs, d_through, stats); }); }
+extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
+extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
+extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }
 extern "C" int kmx_save(kmx_model *m, const char *dir) { return guarded([&] { return kmx_save_impl(m, dir); }); }

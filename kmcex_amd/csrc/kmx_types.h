@@ -488,6 +488,58 @@ struct CtgDev {
 	u32 *clinks;                 // [n_links]
 	u64 *csup;                   // [n_links]
 };
+// kmx_unitig_walk_through*: the counters of a call, in the order of kmx_through_stats behind n_walks and n_steps ...
+enum { THR_C_INTERIOR = 0, THR_C_ADDED, THR_C_MISSING, THR_C_N };
+// ... and the input, the work arrays (mark[n_steps + 1]: 1 where a walk starts; cnt[THR_C_N]) and the output of one call
+// (resolve_kernels.h).  Every array of the caller is read and written under the bounds given here.
+struct ThroughDev {
+	const Walk *walks;           // [n_walks]: only first_step is read
+	u64 n_walks;
+	const u32 *steps;            // [n_steps]
+	u64 n_steps;
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	u64 n_links, U;
+	unsigned char *mark;
+	unsigned long long *cnt;
+	unsigned long long *through; // [16 U], added to
+};
+// kmx_unitig_resolve*: a unitig's place in the resolved set, the layout of kmx_resolve_place (include/kmx.h; resolve_host.h asserts it) ...
+struct ResPlace {
+	u32 first, n_copies;
+};
+// ... the counters of a call, in the order of kmx_resolve_stats ...
+enum { RES_C_CANDIDATES = 0, RES_C_RESOLVED, RES_C_CROSSED, RES_C_UNSUPPORTED, RES_C_AMBIGUOUS, RES_C_N };
+// ... and the input, the work arrays and the output of one call (resolve_kernels.h).  ver[u] = the copies of unitig u (1 to 4) with
+// pi packed above them: bits 8 + 2 a .. 9 + 2 a hold pi(a).  sc[u] = (new unitigs, bytes, edges) in front of unitig u, the scan of
+// (copies, copies x bytes, edges out of both orientations of all copies).  Every array of the caller is read and written under the
+// bounds given here: U, n_ubases, n_links, seq_cap, rec_cap.
+struct ResDev {
+	int k;
+	u64 U, n_ubases, n_links;
+	const unsigned char *useq;   // [n_ubases]
+	const u64 *uoffs;            // [U + 1]
+	const Unitig *urec;          // [U] or null
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	const u64 *hits;             // [n_links] or null
+	const u64 *through;          // [16 U]
+	u64 min_reads, max_cross;
+	unsigned char *bad;          // [U]: an edge at this unitig has no mirror
+	u32 *ver;                    // [U]
+	CtgTot *sc;                  // [U + 1]
+	unsigned long long *cnt;     // [RES_C_N]
+	unsigned char *rseq;         // [seq_cap]
+	u64 seq_cap, rec_cap;
+	u64 *roffs;                  // [rec_cap + 1]
+	Unitig *rrec;                // [rec_cap] or null
+	u32 *origin;                 // [rec_cap]
+	ResPlace *rplace;            // [U]
+	u64 *rloffs;                 // [2 rec_cap + 1]
+	u32 *rlinks;                 // [n_links]
+	u64 *lorigin;                // [n_links]
+	u64 *rhits;                  // [n_links] or null
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

@@ -98,4 +98,12 @@ void contig_cut(const CtgDev &, const CtgRank *, const u32 *, CtgRank *, hipStre
 hipError_t contig_mark(const CtgDev &, const CtgRank *, CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t contig_place(const CtgDev &, const CtgRank *, DevBuf<unsigned char> &tmp, hipStream_t);
 void contig_bytes(const CtgDev &, hipStream_t);
+// ... and kmx_unitig_walk_through* (resolve_kernels.h): the through hits of a batch's walks; the counters land in D.cnt
+hipError_t walk_through(const ThroughDev &, hipStream_t);
+// ... and kmx_unitig_resolve*: verdicts (the counters land in D.cnt), the scan (its totals in D.sc[D.U]), records, links, bytes
+hipError_t resolve_verdicts(const ResDev &, CtgTot *, hipStream_t);
+hipError_t resolve_scan(const ResDev &, const CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);
+void resolve_records(const ResDev &, hipStream_t);
+void resolve_links(const ResDev &, hipStream_t);
+void resolve_bytes(const ResDev &, hipStream_t);
 }   // namespace kmxk

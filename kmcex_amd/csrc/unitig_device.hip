@@ -1,13 +1,15 @@
 // unitig_device.hip -- the launchers of unitig_kernels.h (kmx_unitigs*, kmx_count_unitigs*, kmx_*unitig_graph*, kmx_*unitig_graph_clean*).  The host side that sizes the
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.  Behind them the launchers of map_kernels.h (kmx_unitig_map_*), which
 // search the same listing through the same bucket index, and the launcher of walk_kernels.h (kmx_unitig_walk_segs*); their host side is map_host.h.
-// Last the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.
+// Then the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.  Last the launcher of
+// resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
 #include "map_kernels.h"
 #include "walk_kernels.h"
 #include "contig_kernels.h"
+#include "resolve_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -222,6 +224,56 @@ hipError_t contig_place(const CtgDev &D, const CtgRank *rank, DevBuf<unsigned ch
 void contig_bytes(const CtgDev &D, hipStream_t st)
 {
 	if (D.n_ubases) hipLaunchKernelGGL(k_ctg_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
+}
+
+// ---- kmx_unitig_walk_through* (resolve_kernels.h): marks, then one lane per step.  D.cnt holds the three counters behind it;
+// D.n_steps > 0 and D.U > 0
+hipError_t walk_through(const ThroughDev &D, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.mark, 0, D.n_steps + 1, st));
+	RCHK(hipMemsetAsync(D.cnt, 0, THR_C_N * sizeof(unsigned long long), st));
+	if (D.n_walks) hipLaunchKernelGGL(k_thr_mark, dim3(nblk(D.n_walks)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_thr_count, dim3(nblk(D.n_steps)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_resolve* (resolve_kernels.h); D.U > 0
+
+// the edges without a mirror, then the verdict of every unitig and what the scan adds up (tot[U + 1])
+hipError_t resolve_verdicts(const ResDev &D, CtgTot *tot, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.bad, 0, D.U, st));
+	RCHK(hipMemsetAsync(D.cnt, 0, RES_C_N * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(k_res_bad, dim3(nblk(2 * D.U)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_res_verdict, dim3(nblk(D.U + 1)), dim3(256), 0, st, D, tot);
+	return hipGetLastError();
+}
+
+// the exclusive scan of the triples into D.sc: D.sc[u] = (new unitigs, bytes, edges) in front of unitig u, D.sc[U] the totals
+hipError_t resolve_scan(const ResDev &D, const CtgTot *tot, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	return hipGetLastError();
+}
+
+// rplace, origin, roffsets, records and row starts; the totals fit the capacities (the host has checked)
+void resolve_records(const ResDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_res_place, dim3(nblk(D.U + 1)), dim3(256), 0, st, D);
+}
+
+void resolve_links(const ResDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_res_rows, dim3(nblk(2 * D.U)), dim3(256), 0, st, D);
+}
+
+// the bytes: one block per tile of the flat input
+void resolve_bytes(const ResDev &D, hipStream_t st)
+{
+	if (D.n_ubases) hipLaunchKernelGGL(k_res_emit, dim3((unsigned)((D.n_ubases + RES_TILE - 1) / RES_TILE)), dim3(256), 0, st, D);
 }
 
 }   // namespace kmxk
