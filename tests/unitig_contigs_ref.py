@@ -1,7 +1,8 @@
 """The rule of kmx_unitig_contigs (include/kmx.h) restated in plain Python on top of unitig_walk_ref: the support of every edge
 between unitigs, the kept edges, the chain links, the contigs with their steps, places and records, and the contig graph.  With
 flat(), the check of the rule's consequences, the cases the tests share (those of the walks, ring2tips and the cut cases) and the
-text the facade and the driver must write.  Not a test."""
+text the facade and the driver must write; chain_case: the cut cases at chosen lengths, depths and forks, for tests/test_gpu_unitig_scale.py.
+Not a test."""
 import functools
 import hashlib
 import random
@@ -370,6 +371,80 @@ def cut_expected(n, k, ring):
         return text
     m0, total = len(strs[0]) - k + 1, len(text) - k + 1
     return U.rc((text[:total] * (3 + k // total))[m0:m0 + total + k - 1])
+
+
+@functools.lru_cache(maxsize=None)
+def chain_case(n, k, lens, ring, fork_every=0, seed=0):
+    """cut_case with the lengths given: unitig u < n has lens[u % len(lens)] bytes, so a tile of the flat input holds as many starts
+    as the lengths allow (4096 / 5 at k = 5) and n decides the depth of the doubling.  With fork_every = m > 0 the junction behind
+    every m-th unitig (behind unitigs m - 1, 2 m - 1, ...) gets a second successor, a tip of k bytes stored behind the n chain
+    unitigs, with its mirror edge: the chain breaks there and both edges stay in the contig graph
+    -> (k, strs, rows, hits, sequence); strs holds the n chain unitigs, then the tips"""
+    r = random.Random(seed * 1000003 + n * 1000 + k * 2 + int(ring))
+    ul = [lens[u % len(lens)] for u in range(n)]
+    assert min(ul) >= k
+    ms = [x - k + 1 for x in ul]
+    total = sum(ms)
+    seq = U.rand_seq(total if ring else total + k - 1, 8000 + seed * 131 + n * 64 + k + int(ring))
+    text = (seq * (2 + k // total))[:total + k - 1] if ring else seq
+    flip = set(r.sample(range(n), n // 2))
+    strs, at, ends = [], 0, []
+    for u in range(n):
+        s = text[at:at + ul[u]]
+        strs.append(U.rc(s) if u in flip else s)
+        at += ms[u]
+        ends.append(at)                                          # the next unitig along the sequence starts here
+    fwd = [2 * u + (1 if u in flip else 0) for u in range(n)]    # the orientation that reads along the sequence
+    forks = [j for j in range(n if ring else n - 1) if fork_every and (j + 1) % fork_every == 0]
+    rows = [[] for _ in range(2 * (n + len(forks)))]
+    for u in range(n if ring else n - 1):
+        a, b = fwd[u], fwd[(u + 1) % n]
+        rows[a].append(b)
+        if (b ^ 1, a ^ 1) != (a, b):
+            rows[b ^ 1].append(a ^ 1)
+    for i, j in enumerate(forks):                                # the tip: the k - 1 bytes both successors share, then a base the sequence does not go on with
+        e = ends[j]
+        follows = text[e + k - 1] if e + k - 1 < len(text) else text[e + k - 1 - total]      # (a ring goes on at its start)
+        tip = text[e:e + k - 1] + "ACGT"[("ACGT".index(follows) + 1 + r.randrange(3)) % 4]
+        back = r.random() < 0.5
+        strs.append(U.rc(tip) if back else tip)
+        t = 2 * (n + i) + int(back)
+        if r.random() < 0.5:
+            rows[fwd[j]].append(t)
+        else:
+            rows[fwd[j]].insert(0, t)
+        rows[t ^ 1].append(fwd[j] ^ 1)
+    hits = [1] * sum(map(len, rows))
+    return k, strs, rows, hits, text
+
+
+def chain_expected(n, k, lens, ring, seed=0):
+    """the one contig of a chain case without forks, by cut_expected's closed form"""
+    k, strs, rows, hits, text = chain_case(n, k, lens, ring, 0, seed)
+    if not ring or strs[0] == text[:len(strs[0])]:
+        return text
+    m0, total = len(strs[0]) - k + 1, len(text) - k + 1
+    return U.rc((text[:total] * (3 + k // total))[m0:m0 + total + k - 1])
+
+
+def fork_counts(n, m, ring):
+    """what a chain case with fork_every = m >= 2 must give, by arithmetic: F junctions fork (those behind unitigs m - 1, 2 m - 1, ...;
+    a line has n - 1 junctions, a ring n).  Every fork ends a piece of the chain and adds a tip, so a line falls into F + 1 pieces and
+    a ring into F (F >= 1), each a contig, beside F tips.  Every piece holds m unitigs or more, but a line's last one, which holds
+    n - F m >= 1.  At a fork two edges and their two mirrors are kept and are no chain links: 4 F edges of the contig graph
+    -> (n_contigs, n_multi, contig-graph edges)"""
+    assert m >= 2
+    f = n // m if ring else (n - 1) // m
+    assert f >= 1
+    if ring:
+        return 2 * f, f, 4 * f
+    return 2 * f + 1, f + int(n - f * m > 1), 4 * f
+
+
+@functools.lru_cache(maxsize=None)
+def want_chain(n, k, lens, ring, fork_every=0, seed=0):
+    k, strs, rows, hits, text = chain_case(n, k, lens, ring, fork_every, seed)
+    return contigs(k, strs, None, rows, hits, 1, 0)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,8 @@
 """The rules of kmx_unitig_walk_through and kmx_unitig_resolve (include/kmx.h) restated in plain Python on top of unitig_walk_ref and
 unitig_contigs_ref: the through hits of a batch's walks, the verdict per unitig, and the graph with every resolved unitig split into
 one copy per way in.  With flat(), the checks of the rules' consequences and the cases the tests share (the listed cases of the
-contigs with their real walks, planted repeats, synthetic through matrices on real graphs, the emit geometry).  Not a test."""
+contigs with their real walks, planted repeats, synthetic through matrices on real graphs, the emit geometry, and the gadgets and
+ladders by hand of tests/test_gpu_unitig_scale.py).  Not a test."""
 import functools
 import hashlib
 import random
@@ -281,6 +282,176 @@ def geometry_case(length, shift, k=21):
 
 
 GEOMETRY_LENGTHS = (21, 22, 4 * 16 + 15, 4 * 16 + 16, 4 * 16 + 17, 4095, 4096, 4097, 9000)
+
+
+def _stored(strs, rows, pairs, seed):
+    """the case as the library sees it: a seeded half of the unitigs reverse-complemented, their rows mirrored accordingly, and the
+    through hits of `pairs` (centre, oriented way in, oriented way out, count, all as built) counted by the rule of through()
+    -> (strs, rows, through)"""
+    n_u = len(strs)
+    r = random.Random(seed)
+    flip = [0] * n_u
+    for u in r.sample(range(n_u), n_u // 2):
+        flip[u] = 1
+    nm = lambda o: o ^ flip[o >> 1]
+    out_strs = [U.rc(s) if flip[u] else s for u, s in enumerate(strs)]
+    out_rows = [None] * (2 * n_u)
+    for o, row in enumerate(rows):
+        out_rows[nm(o)] = [nm(t) for t in row]
+    t = [0] * (16 * n_u)
+    for c, p, n, count in pairs:
+        x, p, n = nm(2 * c), nm(p), nm(n)
+        i_in, i_out = out_rows[x ^ 1].index(p ^ 1), out_rows[x].index(n)
+        a, b = (i_in, i_out) if not x & 1 else (i_out, i_in)
+        t[16 * c + 4 * a + b] += count
+    return out_strs, out_rows, t
+
+
+def _arms(k, centre, p, r):
+    """p ways in and p ways out of a centre, of k or k + 1 bytes each, whose overlaps with the centre hold"""
+    ins = [U.rand_seq(1 + r.randrange(2), r.randrange(1 << 30)) + centre[:k - 1] for _ in range(p)]
+    outs = [centre[len(centre) - (k - 1):] + U.rand_seq(1 + r.randrange(2), r.randrange(1 << 30)) for _ in range(p)]
+    return ins, outs
+
+
+def nth_permutation(p, index):
+    """permutation number `index` of range(p), in lexicographic order"""
+    left, out = list(range(p)), []
+    for i in range(p, 0, -1):
+        f = 1
+        for x in range(2, i):
+            f *= x
+        out.append(left.pop(index // f))
+        index %= f
+    return out
+
+
+GADGET_PIN = (3, 1)                                            # (min_reads, max_cross) at which a gadget's verdict is the planned one
+GADGET_GROUP = 192                                             # gadgets per group of the layout
+
+
+def gadget_plan(n_gadgets, spoil_every):
+    """per gadget (p, permutation number, None or the way it is spoiled); p = 2 + g % 3 and the number (g // 3) % p!, so all
+    2 + 6 + 24 pairs occur within 72 gadgets; every spoil_every-th one is spoiled, the three ways in rotation"""
+    fact = {2: 2, 3: 6, 4: 24}
+    return [(2 + g % 3, (g // 3) % fact[2 + g % 3], ("ambiguous", "crossed", "unsupported")[(g // spoil_every) % 3] if spoil_every and g % spoil_every == spoil_every - 1 else None)
+            for g in range(n_gadgets)]
+
+
+@functools.lru_cache(maxsize=None)
+def gadget_case(n_gadgets, k, lens, spoil_every, seed=0):
+    """disjoint gadgets: gadget g is a centre of lens[g % len(lens)] bytes with p ways in and p ways out (gadget_plan), arms of k or
+    k + 1 bytes.  Way in a is paired with way out perm[a] by a count of 3 to 5.  A spoiled gadget, at GADGET_PIN: one count moved to
+    another way out (ambiguous), one more cell of 2 (crossed: below min_reads, above max_cross), or every count 1 (unsupported).
+    The layout, in groups of GADGET_GROUP gadgets: the group's centres of fewer than 256 bytes, then all its arms, then its long
+    centres, so that one tile of the flat input holds hundreds of starts, resolved and unresolved, and long pieces begin in a dense
+    tile.  A seeded half of all unitigs is stored reverse-complemented -> (k, strs, rows, through), as geometry_case"""
+    r = random.Random(7700 + seed * 977 + n_gadgets * 31 + k)
+    plan = gadget_plan(n_gadgets, spoil_every)
+    strs, centre_of, arms_of = [], [None] * n_gadgets, [None] * n_gadgets
+    seqs = []
+    for g, (p, number, spoiled) in enumerate(plan):
+        centre = U.rand_seq(lens[g % len(lens)], r.randrange(1 << 30))
+        seqs.append((centre,) + _arms(k, centre, p, r))
+    for g0 in range(0, n_gadgets, GADGET_GROUP):
+        group = range(g0, min(g0 + GADGET_GROUP, n_gadgets))
+        for g in group:
+            if len(seqs[g][0]) < 256:
+                centre_of[g] = len(strs)
+                strs.append(seqs[g][0])
+        for g in group:
+            p = plan[g][0]
+            arms_of[g] = (list(range(len(strs), len(strs) + p)), list(range(len(strs) + p, len(strs) + 2 * p)))
+            strs += seqs[g][1] + seqs[g][2]
+        for g in group:
+            if centre_of[g] is None:
+                centre_of[g] = len(strs)
+                strs.append(seqs[g][0])
+    rows = [[] for _ in range(2 * len(strs))]
+    pairs = []
+    for g, (p, number, spoiled) in enumerate(plan):
+        c, (ins, outs) = centre_of[g], arms_of[g]
+        for i in range(p):                                       # way in i: ins[i] -> c; way out i: c -> outs[i]; each with its mirror
+            rows[2 * ins[i]].append(2 * c)
+            rows[2 * c + 1].append(2 * ins[i] + 1)
+            rows[2 * c].append(2 * outs[i])
+            rows[2 * outs[i] + 1].append(2 * c + 1)
+        perm = nth_permutation(p, number)
+        cell = {(a, perm[a]): (1 if spoiled == "unsupported" else r.randint(3, 5)) for a in range(p)}
+        if spoiled == "ambiguous":
+            a = r.randrange(p)
+            cell[(a, r.choice([b for b in range(p) if b != perm[a]]))] = cell.pop((a, perm[a]))
+        elif spoiled == "crossed":
+            a = r.randrange(p)
+            cell[(a, r.choice([b for b in range(p) if b != perm[a]]))] = 2
+        pairs += [(c, 2 * ins[a], 2 * outs[b], count) for (a, b), count in cell.items()]
+    return (k,) + _stored(strs, rows, pairs, 7800 + seed)
+
+
+@functools.lru_cache(maxsize=None)
+def ladder_case(n, k, seed=0):
+    """centres c_0 ... c_{n - 1} cut from one random sequence, each with two ways in and two ways out: c_i goes on to c_{i + 1} and to a
+    tip, c_{i + 1} is entered from c_i and from a tip (c_0 from two tips, c_{n - 1} goes on to two).  Through pairs centre with centre
+    and tip with tip, so every centre is resolved and both ends of every edge between centres are renamed.  The order within a row
+    is seeded; a seeded half is stored reverse-complemented -> (k, strs, rows, through)"""
+    r = random.Random(7900 + seed * 977 + n * 31 + k)
+    lens = [r.choice((k, k + 1, k + 3)) for _ in range(n)]
+    text = U.rand_seq(sum(x - k + 1 for x in lens) + k - 1, r.randrange(1 << 30))
+    strs, at, centres, tin, tout = [], 0, [], [], []
+    for i in range(n):
+        centre = text[at:at + lens[i]]
+        at += lens[i] - k + 1
+        ins, outs = _arms(k, centre, 2, r)
+        centres.append(len(strs))
+        strs.append(centre)
+        tin.append([len(strs) + j for j in range(2 if i == 0 else 1)])
+        strs += ins[:len(tin[-1])]
+        tout.append([len(strs) + j for j in range(2 if i == n - 1 else 1)])
+        strs += outs[:len(tout[-1])]
+    rows = [[] for _ in range(2 * len(strs))]
+    pairs = []
+
+    def edge(a, b):
+        for x, y in ((a, b), (b ^ 1, a ^ 1)):
+            if r.random() < 0.5:
+                rows[x].append(y)
+            else:
+                rows[x].insert(0, y)
+
+    for i in range(n):
+        c = centres[i]
+        ways_in = ([2 * centres[i - 1]] if i else []) + [2 * u for u in tin[i]]
+        ways_out = ([2 * centres[i + 1]] if i + 1 < n else []) + [2 * u for u in tout[i]]
+        for p in ways_in[1:] if i else ways_in:                  # (the edge from the centre in front was made as its way out)
+            edge(p, 2 * c)
+        for q in ways_out:
+            edge(2 * c, q)
+        pairs += [(c, ways_in[0], ways_out[0], r.randint(2, 4)), (c, ways_in[1], ways_out[1], r.randint(2, 4))]
+    return (k,) + _stored(strs, rows, pairs, 8000 + seed)
+
+
+def records_for(strs, rows, k, seed):
+    """unitig records and link hits for a case built by hand -> (recs as dicts, hits): seeded counts, n_pred and n_succ from the rows"""
+    r = random.Random(seed)
+    recs = []
+    for u, s in enumerate(strs):
+        m = len(s) - k + 1
+        lo = r.randint(1, 9)
+        hi = lo + r.randint(0, 40)
+        recs.append({"n_kmers": m, "sum_count": r.randint(lo * m, hi * m) if m > 1 else lo, "min_count": lo, "max_count": hi if m > 1 else lo, "first_node": r.randrange(1 << 40), "circular": 0,
+                     "n_pred": len(rows[2 * u + 1]), "n_succ": len(rows[2 * u]), "first_fwd": r.randrange(2)})
+    return recs, [r.randint(1, 1 << 40) for _ in range(sum(map(len, rows)))]
+
+
+def tile_starts(strs, marked=None, tile=4096):
+    """per aligned 4096-byte window of the flat input (a tile of the emit kernels): (unitigs that start in it, those of them in `marked`)"""
+    out, at = {}, 0
+    for u, s in enumerate(strs):
+        a = out.setdefault(at // tile, [0, 0])
+        a[0] += 1
+        a[1] += int(marked is not None and u in marked)
+        at += len(s)
+    return [tuple(out.get(i, (0, 0))) for i in range((at + tile - 1) // tile)]
 
 
 def resolved_tsv(res):
