@@ -25,6 +25,11 @@
 //          at most max_cross, 0 when omitted), so that repeats shorter than a read no longer end the contigs: contigs.* are built
 //          from the resolved graph, unitigs.resolved.tsv (new unitig, origin, copy) names its unitigs; unitigs.fa and unitigs.gfa
 //          stay the unresolved graph
+//     -P<max_dist>  with -M -W: the input is INTERLEAVED paired reads (reads 2 p and 2 p + 1 are the mates of pair p, forward-reverse);
+//          place the two mates of every pair in the graph (KModel::seq_pairs; a mate needs one mapped window, two unitigs are
+//          linked at a distance of at most max_dist windows, 1000 when omitted): pairs.insert.tsv (bin start, pairs; bins of 10
+//          bases up to 2000) and pairs.links.tsv (a, b, pairs, mean distance, min, max, link index or -).  A batch never splits a
+//          pair.  With -X the pairs per edge are added to the reads per edge before the contigs are built
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -32,6 +37,7 @@
 // <working_directory>/<basename(output_file_name)>.  Unlike the reference, main returns a proper status.
 #include "kmodel.hpp"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <sys/stat.h>
@@ -46,6 +52,7 @@ struct Params {
 	long long min_reads = -1;                                      // -X: min_reads, -1 = no contigs
 	long ratio = 0;                                                // -X<min_reads>,<ratio>
 	long long res_min = -1, res_cross = 0;                         // -R<min_reads>[,<max_cross>], -1 = no resolution
+	long pair_dist = -2;                                           // -P: max_dist, -1 = 1000, -2 = no pairs
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -93,6 +100,11 @@ static bool parse(int argc, char **argv, Params &p)
 			}
 			if (*end) return false;
 		}
+		else if (!strncmp(a, "-P", 2)) {
+			char *end = nullptr;
+			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
+			if (a[2] && (*end || p.pair_dist < 0 || p.pair_dist > 0xFFFFFFFFL)) return false;   // not a number of windows
+		}
 		else if (!strncmp(a, "-C", 2)) {
 			char *end = nullptr;
 			p.clean_len = a[2] ? strtol(a + 2, &end, 10) : 0;
@@ -119,6 +131,10 @@ static bool parse(int argc, char **argv, Params &p)
 	}
 	if (p.res_min >= 0 && p.min_reads < 0) {                       // the resolved graph is what the contigs are built from
 		std::cout << "-R needs -M -W -X: the repeats are resolved from the walks, and the contigs are built from the resolved graph\n";
+		return false;
+	}
+	if (p.pair_dist > -2 && (!p.map || p.walk_gap == -2)) {        // the pairs are placed by their walks
+		std::cout << "-P needs -M -W: the mates of a pair are placed by their walks\n";
 		return false;
 	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
@@ -170,7 +186,10 @@ int main(int argc, char **argv)
 		             "       -X<min_reads>[,<ratio>]  with -M -W: merge the unitigs along the edges at least min_reads reads cross: contigs.fa,\n"
 		             "           contigs.paths.tsv (contig, step, unitig, strand, offset), and contigs.gfa with -G\n"
 		             "       -R<min_reads>[,<max_cross>]  with -M -W -X: first resolve the repeats that reads span: unitigs.resolved.tsv (new unitig,\n"
-		             "           origin, copy); contigs.* are built from the resolved graph\n";
+		             "           origin, copy); contigs.* are built from the resolved graph\n"
+		             "       -P<max_dist>  with -M -W: the input is interleaved paired reads (forward-reverse); place the mates of every pair:\n"
+		             "           pairs.insert.tsv (insert sizes), pairs.links.tsv (unitigs linked at up to max_dist (1000) windows); with -X the\n"
+		             "           pairs per edge count as reads\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -234,10 +253,26 @@ int main(int argc, char **argv)
 			std::vector<uint64_t> hits(strs.size(), 0), seg_offsets;
 			std::vector<std::string> reads;
 			uint64_t n_reads = 0, n_segs = 0, n_win = 0, n_mapped = 0;
+			const bool pairs = p.pair_dist > -2;
+			const kmx_pair_params pp = {1, (uint32_t)(p.pair_dist >= 0 ? p.pair_dist : 1000), 10, 200};
+			std::vector<kmx_pair_link> plinks;
+			std::vector<uint64_t> insert_hist(pairs ? pp.n_bins : 0, 0), pair_hits(pairs ? links.size() : 0, 0);
+			std::vector<int64_t> frags;
+			kmx_pair_stats pt = kmx_pair_stats();
+			std::string carry;                                           // with -P: the first mate of a pair the last batch ended inside
+			bool carried = false;
 			km->count_unitig_map_begin(strs);
 			for (bool ok = true; in.peek() != EOF;) {
 				ok = next_reads(in, reads, size_t(1) << 26);
 				if (!ok) { std::cout << p.input << " is no FASTA / FASTQ file at read " << n_reads + reads.size() << std::endl; return 1; }
+				if (carried) { reads.insert(reads.begin(), carry); carried = false; }
+				if (pairs && reads.size() % 2) {
+					if (in.peek() == EOF) { std::cout << "-P reads interleaved pairs, and " << p.input << " holds an odd number of reads" << std::endl; return 1; }
+					carry = reads.back();
+					reads.pop_back();
+					carried = true;
+					if (reads.empty()) continue;
+				}
 				std::vector<kmx_seq_map> rec_m;
 				const std::vector<kmx_map_segment> segs = km->seq_to_unitigs(reads, &seg_offsets, &rec_m, &hits);
 				std::vector<uint64_t> off(reads.size() + 1, 0);
@@ -248,6 +283,14 @@ int main(int argc, char **argv)
 					const std::vector<kmx_walk> wk = km->seq_walks(segs, seg_offsets, link_offsets, links, wp, &walk_offsets, &steps, &link_hits, &ws);
 					KModel::write_walks_gaf(gaf, wk, walk_offsets, steps, off, strs, p.k, n_reads);
 					if (p.res_min >= 0) km->unitig_through(wk, steps, link_offsets, links, through);
+					if (pairs) {
+						kmx_pair_stats ps;
+						const std::vector<kmx_pair> pr = km->seq_pairs(wk, walk_offsets, steps, link_offsets, links, pp, &plinks, &insert_hist, &pair_hits, &ps);
+						for (size_t i = 0; i < pr.size(); i++)
+							if (pr[i].cls == KMX_PAIR_SAME && pr[i].frag >= 0) frags.push_back(pr[i].frag);
+						pt.n_pairs += ps.n_pairs; pt.n_none += ps.n_none; pt.n_single += ps.n_single; pt.n_same += ps.n_same; pt.n_negative += ps.n_negative;
+						pt.n_inverted += ps.n_inverted; pt.n_link += ps.n_link; pt.n_adjacent += ps.n_adjacent; pt.n_far += ps.n_far;
+					}
 					wt.n_walks += ws.n_walks; wt.n_steps += ws.n_steps; wt.n_edge += ws.n_edge; wt.n_inside += ws.n_inside; wt.n_across += ws.n_across;
 					wt.n_unlinked += ws.n_unlinked; wt.n_breaks += ws.n_breaks;
 				}
@@ -269,6 +312,19 @@ int main(int argc, char **argv)
 				if (!gaf || !lt) { std::cout << "could not write " << dir << "/reads.gaf or unitigs.links.tsv" << std::endl; return 1; }
 				std::cout << "   walks (gaps of at most " << wp.max_gap << " windows)    :     " << wt.n_walks << " walks, " << wt.n_steps << " steps, " << wt.n_edge << " edges crossed, " << wt.n_inside + wt.n_across
 				          << " gaps bridged (" << wt.n_across << " across an edge), " << wt.n_breaks << " breaks" << std::endl;
+				if (pairs) {
+					std::ofstream pl((dir + "/pairs.links.tsv").c_str()), pi((dir + "/pairs.insert.tsv").c_str());
+					KModel::write_pair_links_tsv(pl, plinks, link_offsets, links);
+					KModel::write_insert_hist_tsv(pi, insert_hist, pp.bin_width);
+					pl.close();
+					pi.close();
+					if (!pl || !pi) { std::cout << "could not write " << dir << "/pairs.links.tsv or pairs.insert.tsv" << std::endl; return 1; }
+					if (!frags.empty()) std::nth_element(frags.begin(), frags.begin() + frags.size() / 2, frags.end());
+					std::cout << "   pairs (links of at most " << pp.max_dist << " windows)  :     " << pt.n_pairs << " pairs: " << pt.n_same << " on one unitig (" << pt.n_negative << " negative, median fragment "
+					          << (frags.empty() ? 0 : frags[frags.size() / 2]) << "), " << pt.n_link << " links (" << pt.n_adjacent << " adjacent, " << plinks.size() << " distinct), " << pt.n_far << " far, "
+					          << pt.n_inverted << " inverted, " << pt.n_single << " single, " << pt.n_none << " unplaced" << std::endl;
+					for (size_t e = 0; e < link_hits.size() && e < pair_hits.size(); e++) link_hits[e] += pair_hits[e];   // what -X and -R judge the edges by
+				}
 				if (p.min_reads >= 0) {
 					const kmx_contig_params xp = {(uint64_t)p.min_reads, (uint32_t)p.ratio, 0};
 					KModel::Resolved rs;

@@ -614,6 +614,53 @@ public:
 		}
 	}
 
+	// Read pairs (the rule: kmx.h), inside the map session: seq_pairs takes the walks, walk_offsets and steps seq_walks returned for
+	// a batch of interleaved mates (reads 2 p and 2 p + 1 are pair p) and the CSR of the session's graph, and returns one kmx_pair
+	// per pair.  plinks is the list of pair links earlier batches left (empty at first) and becomes the merge with this batch;
+	// hist (params.n_bins entries) and pair_hits (one per link) are ADDED to; a shorter vector is grown with zeros first.  It gives
+	// the list room for every entry, so it never comes back short.
+	std::vector<kmx_pair> seq_pairs(const std::vector<kmx_walk> &walks, const std::vector<uint64_t> &walk_offsets, const std::vector<uint32_t> &steps, const std::vector<uint64_t> &link_offsets,
+	                                const std::vector<uint32_t> &links, const kmx_pair_params &params, std::vector<kmx_pair_link> *plinks = 0, std::vector<uint64_t> *hist = 0,
+	                                std::vector<uint64_t> *pair_hits = 0, kmx_pair_stats *stats = 0)
+	{
+		const size_t n_seqs = walk_offsets.empty() ? 0 : walk_offsets.size() - 1, np = n_seqs / 2;
+		std::vector<kmx_pair> pairs(np + 1);
+		kmx_pair_stats ps = kmx_pair_stats();
+		uint64_t n = plinks ? plinks->size() : 0;
+		if (plinks) plinks->resize((size_t)n + np + 1);
+		if (hist && hist->size() < params.n_bins) hist->resize(params.n_bins, 0);
+		if (pair_hits && pair_hits->size() < links.size()) pair_hits->resize(links.size(), 0);
+		check(kmx_unitig_pair_walks(h_, walks.empty() ? 0 : &walks[0], walks.size(), n_seqs ? &walk_offsets[0] : 0, n_seqs, steps.empty() ? 0 : &steps[0], steps.size(),
+		                            link_offsets.empty() ? 0 : &link_offsets[0], links.empty() ? 0 : &links[0], links.size(), &params, &pairs[0], hist && !hist->empty() ? &(*hist)[0] : 0,
+		                            pair_hits && !pair_hits->empty() ? &(*pair_hits)[0] : 0, plinks ? &(*plinks)[0] : 0, n + np, &n, &ps));
+		if (plinks) plinks->resize((size_t)n);
+		pairs.resize(np);
+		if (stats) *stats = ps;
+		return pairs;
+	}
+	// the pair links as a table, one "u<a><+|->\tu<b><+|->\t<pairs>\t<mean dist, one decimal>\t<min>\t<max>\t<link index or ->" per
+	// entry: the index is that of the edge a -> b in the CSR (the first match among the first 4 entries of its row), "-" when the
+	// two are not adjacent ...
+	static void write_pair_links_tsv(std::ostream &out, const std::vector<kmx_pair_link> &plinks, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links)
+	{
+		for (size_t i = 0; i < plinks.size(); i++) {
+			const kmx_pair_link &p = plinks[i];
+			const uint64_t q = p.n_pairs ? (p.sum_dist * 10 + p.n_pairs / 2) / p.n_pairs : 0;
+			out << "u" << (p.a >> 1) << ((p.a & 1) ? '-' : '+') << "\tu" << (p.b >> 1) << ((p.b & 1) ? '-' : '+') << "\t" << p.n_pairs << "\t" << q / 10 << "." << q % 10 << "\t" << p.min_dist << "\t"
+			    << p.max_dist << "\t";
+			uint64_t e = ~(uint64_t)0;
+			if ((uint64_t)p.a + 1 < link_offsets.size())
+				for (uint64_t t = link_offsets[p.a]; t < link_offsets[p.a + 1] && t < link_offsets[p.a] + 4 && t < links.size(); t++)
+					if (links[(size_t)t] == p.b) { e = t; break; }
+			if (e == ~(uint64_t)0) out << "-\n"; else out << e << "\n";
+		}
+	}
+	// ... and the insert-size histogram, one "<bin start>\t<pairs>" per bin (the last bin also holds everything beyond it)
+	static void write_insert_hist_tsv(std::ostream &out, const std::vector<uint64_t> &hist, uint32_t bin_width)
+	{
+		for (size_t i = 0; i < hist.size(); i++) out << (uint64_t)i * bin_width << "\t" << hist[i] << "\n";
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

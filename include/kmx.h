@@ -840,7 +840,8 @@ int kmx_unitig_map_end(kmx_model *m);
  *       and every +1 of link_hits on the mirror edge (b ^ 1) -> (a ^ 1) of a -> b; link_hits counts the traversed edge only, the
  *       mirror edge is the caller's to add.
  * Out of scope: gaps that span a whole unitig (a bridge crosses at most one edge); comparing the bases inside a gap (a bridge
- * is accepted on its geometry alone); paired reads; several GPUs.  What consumes link_hits: kmx_unitig_contigs below.      */
+ * is accepted on its geometry alone); paired reads (kmx_unitig_pair_walks below places the two mates of a pair from these walks);
+ * several GPUs.  What consumes link_hits: kmx_unitig_contigs below.                                                        */
 typedef struct kmx_walk_params { uint32_t max_gap, max_indel, reserved[2]; } kmx_walk_params;                  /* 16 bytes */
 typedef struct kmx_walk {                /* one per walk, in ascending pos; 80 bytes */
 	uint64_t pos;                        /* flat position of its first window */
@@ -937,7 +938,8 @@ int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64
  *   (d) place inverts steps; the n_steps sum to U, the n_kmers to the sum of m_u, and n_cbases = that sum + C (k - 1).
  * Repeats shorter than a read: kmx_unitig_walk_through and kmx_unitig_resolve below, in front of this call.
  * Out of scope: iterating with a re-map;
- * paired reads; even k; several GPUs; choosing min_reads and ratio.                                                        */
+ * paired reads, beyond adding the pair_hits of kmx_unitig_pair_walks to link_hits; even k; several GPUs; choosing min_reads and
+ * ratio.                                                                                                                   */
 typedef struct kmx_contig_params { uint64_t min_reads; uint32_t ratio; uint32_t reserved; } kmx_contig_params;          /* 16 bytes */
 typedef struct kmx_contig {              /* one per contig; 64 bytes, no padding */
 	uint64_t n_kmers;                    /* the sum of m_u over its steps; the string has n_kmers + k - 1 bytes */
@@ -1095,6 +1097,101 @@ int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64
                            uint64_t *n_unitigs_out /* HOST */, uint64_t *n_bases_out /* HOST */, kmx_resolve_stats *stats /* HOST */);
 /* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): verdicts, scan and records, links, bytes */
 int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds /* [4] */);
+
+/* ---- read pairs: where the two mates of a pair lie in the graph.  The repeats kmx_unitig_resolve leaves are longer than a read;
+ * a read cannot cross them, the fragment both mates were read from can.  A post-pass on what kmx_unitig_walk_segs[_dev] wrote for
+ * a batch in which reads 2 p and 2 p + 1 are the two mates of pair p (interleaved), inside the map session, which holds k, U and
+ * m_u; it reads no bases and no segments.  The library is forward-reverse (FR): mate 2 comes from the opposite strand and faces
+ * inward.  It gives the insert-size histogram of the library, the pairs per edge of the graph in the layout of link_hits (so
+ * that kmx_unitig_contigs consumes it unchanged), and the pairs between unitigs that are not adjacent, with a distance: the
+ * scaffold evidence.  The contigs of kmx_unitig_contigs are a valid unitig set for kmx_unitig_map_begin, so pairs mapped onto the
+ * contigs give links between contigs without a coordinate translation.
+ * Input: walks[n_walks], walk_offsets[n_seqs + 1] and steps[n_steps] as the walk call wrote them; n_seqs is even and
+ *   n_pairs = n_seqs / 2; the CSR of the session's graph (link_offsets[2 U + 1], links[n_links]; out[o] is the row of oriented
+ *   unitig o, at most 4 entries of a row are read); and kmx_pair_params, bin_width >= 1, n_bins in [1, 65536].
+ * Placing a read.  The candidates of read r are the walks w in [walk_offsets[r], walk_offsets[r + 1]) with n_mapped >= min_mapped,
+ *   n_steps >= 1, a last step o = steps[first_step + n_steps - 1] < 2 U and off_last < m_(o >> 1).  The ANCHOR is the candidate
+ *   with the largest n_mapped (compared as min(n_mapped, 2^32 - 1)); ties go to the lowest index (only the first 2^32 - 1 walks
+ *   of a read are looked at).  A read with no candidate is unplaced.  The INNER END of a placed read is (o, x) = (last step, off_last): the mapped window nearest to its mate.
+ * A pair.  A is read 2 p, B is read 2 p + 1.  With both placed, a = (oa, xa) is A's inner end, and B's inner end (oB, xB) is
+ *   mirrored onto A's strand: ob = oB ^ 1, xb = m_(oB >> 1) - 1 - xB.  All arithmetic is signed 64-bit.  The class of the pair:
+ *   KMX_PAIR_NONE      neither mate is placed;
+ *   KMX_PAIR_SINGLE    exactly one is;
+ *   KMX_PAIR_SAME      oa == ob.  d = xb - xa and frag = d + A.n_span + B.n_span + k - 2: the fragment's bases between the outer
+ *                      mapped windows, exact for reads without indels.  frag < 0: n_negative counts the pair; otherwise
+ *                      hist[min(frag / bin_width, n_bins - 1)] += 1;
+ *   KMX_PAIR_INVERTED  oa == ob ^ 1;
+ *   otherwise dist = (m_(oa >> 1) - 1 - xa) + xb, the windows left in oa behind A plus the windows of ob in front of B, and
+ *   KMX_PAIR_FAR       dist > max_dist;
+ *   KMX_PAIR_LINK      otherwise.  With e the index of the first entry equal to ob among the (at most 4) entries of out[oa], if
+ *                      there is one: pair_hits[e] += 1 and n_adjacent counts it -- the traversed direction only, exactly like
+ *                      link_hits; the mirror edge is the consumer's to add.  The pair contributes (key, dist) to the pair links:
+ *                      key = (oa, ob) when oa << 32 | ob is smaller than (ob ^ 1) << 32 | (oa ^ 1), and (ob ^ 1, oa ^ 1)
+ *                      otherwise; the two are equal only for an inverted pair.
+ * Output.  pairs[n_pairs] (or NULL), one record each.  hist[n_bins] and pair_hits[n_links] (either may be NULL) are ADDED to, as
+ *   hits and link_hits are.  plinks[capacity] with *n_plinks (HOST in both forms) is an IN/OUT list of kmx_pair_link, strictly
+ *   ascending by a << 32 | b: on entry what earlier batches left (a first call passes *n_plinks = 0), on return the merge with
+ *   this batch, equal keys folded by sum, sum, minimum and maximum; capacity >= *n_plinks + n_pairs always suffices.  If more
+ *   entries are needed the call returns KMX_E_RANGE with *n_plinks the number needed, the list exactly as it was and records,
+ *   stats, hist and pair_hits complete, so a caller that repeats the call passes hist = pair_hits = NULL: the convention of
+ *   kmx_unitig_map_seqs.  plinks == NULL: no list is built and *n_plinks is not used.  stats (HOST in both forms, required).
+ * Every decision looks at two anchors, two walks, two steps, two m_u and one row, and all outputs are integer sums, counts,
+ * minima and maxima: a function of (walks, steps, CSR, m_u, parameters, list) alone, byte-identical across runs, variants and
+ * batch splits.  Consequences:
+ *   (a) swapping the two mates of every pair leaves hist, the list, stats and every SAME d and frag unchanged, and moves each
+ *       pair_hits increment to the mirror edge: A' = B and B' = A give oa' = ob ^ 1 and ob' = oa ^ 1, which mirrors the same
+ *       position, swaps the two terms of dist and picks the same canonical key;
+ *   (b) n_none + n_single + n_same + n_inverted + n_link + n_far == n_pairs; the n_pairs added to the list sum to n_link, the
+ *       increments to hist to n_same - n_negative, those to pair_hits to n_adjacent;
+ *   (c) cutting a batch at any pair boundary and merging into the same list gives the same bytes as one call;
+ *   (d) for error-free pairs drawn from a genome that is one unitig every pair is SAME and frag is the true fragment length.
+ * Out of scope: RF and FF libraries; mates in two separate files; pairs on a resolved graph, where a k-mer lies on several
+ * copies; acting on the links (ordering and joining contigs, gap filling); choosing max_dist; several GPUs.                 */
+#define KMX_PAIR_NONE     0
+#define KMX_PAIR_SINGLE   1
+#define KMX_PAIR_SAME     2
+#define KMX_PAIR_INVERTED 3
+#define KMX_PAIR_LINK     4
+#define KMX_PAIR_FAR      5
+typedef struct kmx_pair_params { uint32_t min_mapped, max_dist, bin_width, n_bins; } kmx_pair_params;                    /* 16 bytes */
+typedef struct kmx_pair {                /* one per pair; 64 bytes, no padding */
+	uint64_t walk_a, walk_b;             /* the anchors' indices into walks; all ones for an unplaced mate */
+	uint32_t cls;                        /* KMX_PAIR_* */
+	uint32_t edge;                       /* e of a LINK between adjacent unitigs; 0xFFFFFFFF when there is none */
+	uint32_t oa, xa, ob, xb;             /* the inner ends, B's mirrored; 0 for an unplaced mate */
+	int64_t d;                           /* d for SAME, dist for LINK and FAR, 0 otherwise */
+	int64_t frag;                        /* SAME only, 0 otherwise */
+	uint64_t reserved;                   /* 0 */
+} kmx_pair;
+typedef struct kmx_pair_link {           /* 32 bytes, no padding */
+	uint32_t a, b;                       /* the canonical key: oriented unitig a, then b at the distance below */
+	uint64_t n_pairs, sum_dist;
+	uint32_t min_dist, max_dist;
+} kmx_pair_link;
+typedef struct kmx_pair_stats { uint64_t n_pairs, n_none, n_single, n_same, n_negative, n_inverted, n_link, n_adjacent, n_far, reserved; } kmx_pair_stats;   /* 80 bytes */
+/* On HOST buffers.  KMX_E_ARG before anything runs: an odd n_seqs, bin_width == 0, n_bins outside [1, 65536], a NULL required
+ * buffer (params, stats and walk_offsets; walks, steps and links where their count is not 0; link_offsets; n_plinks with
+ * plinks), *n_plinks > capacity, an output that overlaps an input; walk_offsets (first 0, non-decreasing, last n_walks) and the
+ * CSR checked as kmx_unitig_walk_segs checks seg_offsets and the CSR; an input list that is not strictly ascending.  Outside a
+ * session: KMX_E_STATE.  KMX_E_NOMEM leaves the handle and the session usable.  n_seqs == 0: KMX_OK, all-zero stats, the list
+ * untouched.  It stages its input and output on the device as the host form of the walk call does.                          */
+int kmx_unitig_pair_walks(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint64_t *walk_offsets /* [n_seqs + 1] */, uint64_t n_seqs, const uint32_t *steps, uint64_t n_steps,
+                          const uint64_t *link_offsets /* [2 U + 1] */, const uint32_t *links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *pairs /* [n_seqs / 2] or NULL */,
+                          uint64_t *hist /* [n_bins] or NULL */, uint64_t *pair_hits /* [n_links] or NULL */, kmx_pair_link *plinks /* or NULL */, uint64_t capacity, uint64_t *n_plinks,
+                          kmx_pair_stats *stats);
+/* The same on DEVICE buffers, read where the walk and graph calls left them; params, *n_plinks and stats are on the HOST.  It
+ * checks the parameters, NULL, *n_plinks <= capacity and overlap, and clamps instead of validating: walk_offsets into
+ * [0, n_walks]; a walk whose first_step + n_steps - 1 is not in [0, n_steps) is no candidate; row bounds into [0, n_links]; the
+ * input list is taken as it is (a list that is not ascending is merged all the same).  Every store is checked against its
+ * capacity: bad device input gives wrong pairs and never an access outside a buffer.  It enqueues everything on the model's
+ * stream and waits once, for the merged count and the stats; the list is written by a last launch only where the count fits.
+ * Device memory, kept on the session until kmx_unitig_map_end: 8 bytes per read for the anchors, 4 per pair for the distances,
+ * and 72 bytes per work item (a pair or an entry of the input list: key and index, both twice for the sort; the scanned key
+ * changes; the merged record) plus the scratch of the sort and the scan.                                                       */
+int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint64_t *d_walk_offsets /* [n_seqs + 1] */, uint64_t n_seqs, const uint32_t *d_steps,
+                              uint64_t n_steps, const uint64_t *d_link_offsets /* [2 U + 1] */, const uint32_t *d_links, uint64_t n_links, const kmx_pair_params *params /* HOST */,
+                              kmx_pair *d_pairs /* or NULL */, uint64_t *d_hist /* or NULL */, uint64_t *d_pair_hits /* or NULL */, kmx_pair_link *d_plinks /* or NULL */, uint64_t capacity,
+                              uint64_t *n_plinks /* HOST */, kmx_pair_stats *stats /* HOST */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_contigs", "kmx_unitig_contigs_dev", "kmx_unitig_contigs_last_phases",
     "kmx_unitig_walk_through", "kmx_unitig_walk_through_dev",
     "kmx_unitig_resolve", "kmx_unitig_resolve_dev", "kmx_unitig_resolve_last_phases",
+    "kmx_unitig_pair_walks", "kmx_unitig_pair_walks_dev",
 ]
 
 
@@ -198,6 +199,36 @@ class ResolveStats(C.Structure):
 
 # kmx_resolve_place as a NumPy structured dtype (what KModel.unitig_resolve_flat returns): 8 bytes
 RESOLVE_PLACE_DTYPE = np.dtype([("first", "<u4"), ("n_copies", "<u4")])
+
+
+class PairParams(C.Structure):
+    """kmx_pair_params of include/kmx.h: 16 bytes"""
+    _fields_ = [(f, C.c_uint32) for f in ("min_mapped", "max_dist", "bin_width", "n_bins")]
+
+
+class Pair(C.Structure):
+    """kmx_pair of include/kmx.h: where the two mates of a pair lie, 64 bytes"""
+    _fields_ = ([("walk_a", C.c_uint64), ("walk_b", C.c_uint64)] + [(f, C.c_uint32) for f in ("cls", "edge", "oa", "xa", "ob", "xb")] +
+                [("d", C.c_int64), ("frag", C.c_int64), ("reserved", C.c_uint64)])
+
+
+class PairLink(C.Structure):
+    """kmx_pair_link of include/kmx.h: the pairs between two oriented unitigs, 32 bytes"""
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("n_pairs", C.c_uint64), ("sum_dist", C.c_uint64), ("min_dist", C.c_uint32), ("max_dist", C.c_uint32)]
+
+
+class PairStats(C.Structure):
+    """kmx_pair_stats of include/kmx.h: 80 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_pairs", "n_none", "n_single", "n_same", "n_negative", "n_inverted", "n_link", "n_adjacent", "n_far", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_pair and kmx_pair_link as NumPy structured dtypes (what KModel.unitig_pairs_flat returns): 64 and 32 bytes
+PAIR_DTYPE = np.dtype([("walk_a", "<u8"), ("walk_b", "<u8")] + [(f, "<u4") for f in ("cls", "edge", "oa", "xa", "ob", "xb")] + [("d", "<i8"), ("frag", "<i8"), ("reserved", "<u8")])
+PAIR_LINK_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("n_pairs", "<u8"), ("sum_dist", "<u8"), ("min_dist", "<u4"), ("max_dist", "<u4")])
+PAIR_CLASSES = {0: "NONE", 1: "SINGLE", 2: "SAME", 3: "INVERTED", 4: "LINK", 5: "FAR"}
 
 
 class RingList(C.Structure):
@@ -349,6 +380,8 @@ def load_library():
     _sig(L, "kmx_unitig_contigs_last_phases", [vp, C.POINTER(C.c_double), p64])
     _sig(L, "kmx_unitig_walk_through", [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, C.POINTER(ThroughStats)])
     _sig(L, "kmx_unitig_walk_through_dev", [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, C.POINTER(ThroughStats)])
+    _sig(L, "kmx_unitig_pair_walks", [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, C.POINTER(PairParams), vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PairStats)])
+    _sig(L, "kmx_unitig_pair_walks_dev", [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, C.POINTER(PairParams), vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PairStats)])
     _sig(L, "kmx_unitig_resolve", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1182,6 +1215,71 @@ class KModel:
         segs, so, _ = self.seq_to_unitigs(reads)
         walks, wo, steps, st = self.unitig_walks_flat(segs, so, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
         return walks, wo, steps, st, segs, so
+
+    # ---- read pairs: the two mates of every pair placed in the graph (the rule: include/kmx.h), inside the map session
+    def unitig_pairs_flat(self, walks: np.ndarray, walk_offsets: np.ndarray, steps: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, max_dist: int, min_mapped: int = 1,
+                          bin_width: int = 10, n_bins: int = 200, plinks=None, capacity=None, hist=None, pair_hits=None, records: bool = True):
+        """kmx_unitig_pair_walks on what unitig_walks_flat returned for a batch of interleaved mates and the CSR of the session's
+        graph -> (PAIR_DTYPE records [n_pairs] or None, PAIR_LINK_DTYPE list, stats as a dict).  plinks: the list earlier batches
+        left (None: empty; False: no list is built and None comes back); the merged list is returned, the argument is not
+        changed.  capacity None: room for every entry, so the call never comes back short; a number: that many entries (KmxError
+        KMX_E_RANGE when short, its `needed` the number needed).  hist (uint64 [n_bins]) and pair_hits (uint64 [n_links]), both
+        optional, are ADDED to."""
+        walks = np.ascontiguousarray(walks, dtype=WALK_DTYPE)
+        walk_offsets = np.ascontiguousarray(walk_offsets, dtype=np.uint64)
+        steps = np.ascontiguousarray(steps, dtype=np.uint32)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        n_seqs = walk_offsets.size - 1
+        if hist is not None and (hist.dtype != np.uint64 or not hist.flags.c_contiguous or hist.size < int(n_bins)):
+            raise KmxError(-1, "hist must be a contiguous uint64 array with one entry per bin")
+        if pair_hits is not None and (pair_hits.dtype != np.uint64 or not pair_hits.flags.c_contiguous or pair_hits.size < links.size):
+            raise KmxError(-1, "pair_hits must be a contiguous uint64 array with one entry per link")
+        rec = np.zeros(n_seqs // 2, dtype=PAIR_DTYPE) if records else None
+        par, st, n = PairParams(int(min_mapped), int(max_dist), int(bin_width), int(n_bins)), PairStats(), C.c_uint64(0)
+        lst = None
+        if plinks is not False:
+            old = np.zeros(0, dtype=PAIR_LINK_DTYPE) if plinks is None else np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+            cap = old.size + n_seqs // 2 if capacity is None else int(capacity)
+            lst = np.zeros(max(cap, old.size), dtype=PAIR_LINK_DTYPE)
+            lst[:old.size] = old
+            n.value = old.size
+        try:
+            _chk(self.L.kmx_unitig_pair_walks(self.h, walks.ctypes.data, walks.size, walk_offsets.ctypes.data, n_seqs, steps.ctypes.data, steps.size, link_offsets.ctypes.data, links.ctypes.data,
+                                              links.size, C.byref(par), rec.ctypes.data if records else None, hist.ctypes.data if hist is not None else None,
+                                              pair_hits.ctypes.data if pair_hits is not None else None, lst.ctypes.data if lst is not None else None, cap if lst is not None else 0, C.byref(n),
+                                              C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            raise
+        return rec, (lst[:n.value].copy() if lst is not None else None), st.as_dict()
+
+    def unitig_pairs_dev(self, d_walks, n_walks: int, d_walk_offsets, d_steps, n_steps: int, d_link_offsets, d_links, max_dist: int, min_mapped: int = 1, bin_width: int = 10,
+                         n_bins: int = 200, d_pairs=None, d_hist=None, d_pair_hits=None, d_plinks=None, n_plinks: int = 0):
+        """kmx_unitig_pair_walks_dev on torch tensors of the model's device, read where unitig_walks_dev and the graph call left
+        them: d_walks uint8 [walk_capacity, 80] holding n_walks walks, d_walk_offsets int64 [n_seqs + 1], d_steps int32 holding
+        n_steps steps, d_link_offsets int64 [2 U + 1], d_links int32 [n_links]; d_pairs uint8 [n_pairs, 64] or None, d_hist int64
+        [n_bins] and d_pair_hits int64 [n_links] or None (added to), d_plinks uint8 [capacity, 32] holding n_plinks entries or
+        None -> (stats as a dict, the entries the list now holds).  KmxError KMX_E_RANGE carries the number needed in `needed`."""
+        n_seqs = d_walk_offsets.numel() - 1
+        par, st, n = PairParams(int(min_mapped), int(max_dist), int(bin_width), int(n_bins)), PairStats(), C.c_uint64(int(n_plinks))
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            _chk(self.L.kmx_unitig_pair_walks_dev(self.h, d_walks.data_ptr() if n_walks else None, int(n_walks), d_walk_offsets.data_ptr(), n_seqs, d_steps.data_ptr() if n_steps else None,
+                                                  int(n_steps), d_link_offsets.data_ptr(), d_links.data_ptr() if d_links.numel() else None, d_links.numel(), C.byref(par), ptr(d_pairs), ptr(d_hist),
+                                                  ptr(d_pair_hits), ptr(d_plinks), d_plinks.shape[0] if d_plinks is not None else 0, C.byref(n), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            raise
+        return st.as_dict(), int(n.value)
+
+    def seq_to_pairs(self, reads, link_offsets: np.ndarray, links: np.ndarray, max_dist: int, max_gap: int, max_indel: int = 1, min_mapped: int = 1, bin_width: int = 10, n_bins: int = 200,
+                     plinks=None, hist=None, pair_hits=None, link_hits=None):
+        """inside a map session, on interleaved reads (2 p and 2 p + 1 are the mates of pair p): seq_to_walks, then
+        unitig_pairs_flat on its walks -> (pair records, the merged list, pair stats, walks, walk_offsets, steps)"""
+        walks, wo, steps, _, _, _ = self.seq_to_walks(reads, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
+        rec, lst, st = self.unitig_pairs_flat(walks, wo, steps, link_offsets, links, max_dist, min_mapped, bin_width, n_bins, plinks=plinks, hist=hist, pair_hits=pair_hits)
+        return rec, lst, st, walks, wo, steps
 
     # ---- contigs: the unitigs merged along the edges the reads support (the rule: include/kmx.h); no model, no session
     def unitig_contigs_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, link_hits: np.ndarray, min_reads: int = 1, ratio: int = 0,

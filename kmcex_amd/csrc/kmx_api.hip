@@ -378,6 +378,10 @@ struct kmx_model {
 		DevBuf<u32> d_wjoin;                                       // ... the join's overlap and d, ...
 		DevBuf<WalkTot> d_wsc;                                     // ... [n_segs + 1] the walk and step starts in front of it; ...
 		DevBuf<unsigned long long> d_wcnt;                         // ... [WALK_C_N] the call's counters
+		DevBuf<unsigned long long> d_panchor, d_pcnt;              // kmx_unitig_pair_walks* (pair_host.h): [n_seqs] the anchor words, [PAIR_C_N] the call's counters, ...
+		DevBuf<u64> d_pkey, d_psc;                                 // ... [4][n_items] keys, indices and both sorted; [n_items + 1] the scanned key changes, ...
+		DevBuf<u32> d_pdist;                                       // ... [n_pairs] the distance of every pair that is a link, ...
+		DevBuf<PairLink> d_pmrg;                                   // ... [n_items] the merged list
 	} map;
 	// kmx_unitig_contigs* (contig_host.h): the work arrays of a call, kept by capacity from call to call
 	struct CtgState {
@@ -412,6 +416,7 @@ static void map_drop(kmx_model *m)
 	S.d_km.reset(); S.d_start.reset(); S.d_mu.reset(); S.d_err.reset(); S.d_place.reset();
 	S.d_code.reset(); S.d_spos.reset(); S.d_state.reset(); S.d_ex.reset(); S.d_tmp.reset();
 	S.d_wflag.reset(); S.d_wjoin.reset(); S.d_wsc.reset(); S.d_wcnt.reset();
+	S.d_panchor.reset(); S.d_pcnt.reset(); S.d_pkey.reset(); S.d_psc.reset(); S.d_pdist.reset(); S.d_pmrg.reset();
 	S.dev = MapDev{};
 	S.on = S.from_count = false;
 }
@@ -2946,6 +2951,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "map_host.h"
 #include "contig_host.h"
 #include "resolve_host.h"
+#include "pair_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3482,6 +3488,8 @@ extern "C" int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, c
 extern "C" int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_contigs_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, uint64_t n_unitigs, uint64_t *through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_impl(m, walks, n_walks, steps, n_steps, link_offsets, links, n_links, n_unitigs, through, stats); }); }
 extern "C" int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_dev_impl(m, d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, n_unitigs, d_through, stats); }); }
+extern "C" int kmx_unitig_pair_walks(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint64_t *walk_offsets, uint64_t n_seqs, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *pairs, uint64_t *hist, uint64_t *pair_hits, kmx_pair_link *plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_impl(m, PairArgs{walks, n_walks, walk_offsets, n_seqs, steps, n_steps, link_offsets, links, n_links, params, pairs, hist, pair_hits, plinks, capacity, n_plinks, stats}); }); }
+extern "C" int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint64_t *d_walk_offsets, uint64_t n_seqs, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *d_pairs, uint64_t *d_hist, uint64_t *d_pair_hits, kmx_pair_link *d_plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_dev_impl(m, PairArgs{d_walks, n_walks, d_walk_offsets, n_seqs, d_steps, n_steps, d_link_offsets, d_links, n_links, params, d_pairs, d_hist, d_pair_hits, d_plinks, capacity, n_plinks, stats}); }); }
 extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
 extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }

@@ -540,6 +540,53 @@ struct ResDev {
 	u64 *lorigin;                // [n_links]
 	u64 *rhits;                  // [n_links] or null
 };
+// kmx_unitig_pair_walks*: a pair's record and an entry of the pair links, the layouts of kmx_pair and kmx_pair_link (include/kmx.h;
+// pair_host.h asserts them) ...
+struct Pair {
+	u64 walk_a, walk_b;
+	u32 cls, edge, oa, xa, ob, xb;
+	long long d, frag;
+	u64 reserved;
+};
+struct PairLink {
+	u32 a, b;
+	u64 n_pairs, sum_dist;
+	u32 min_dist, max_dist;
+};
+// ... the classes (KMX_PAIR_* of include/kmx.h) and the counters of a call, in the order of kmx_pair_stats behind n_pairs ...
+enum { PAIR_NONE = 0, PAIR_SINGLE, PAIR_SAME, PAIR_INVERTED, PAIR_LINK, PAIR_FAR };
+enum { PAIR_C_NONE = 0, PAIR_C_SINGLE, PAIR_C_SAME, PAIR_C_NEGATIVE, PAIR_C_INVERTED, PAIR_C_LINK, PAIR_C_ADJACENT, PAIR_C_FAR, PAIR_C_N };
+// ... and the input, the work arrays and the output of one call (pair_kernels.h).  The work items of the fold are the n_in entries
+// of the input list, then one per pair: key[i] = a << 32 | b (PAIR_NO_KEY for a pair that is no link), idx[i] = i; skey, sidx: the
+// same sorted by key; sc[n_items + 1]: the key changes in front of a sorted item, sc[n_items] the merged count; mrg[n_items]: the
+// merged records, their min_dist inverted so that all zero is the neutral element.  Every array of the caller is read and
+// written under the bounds given here.
+struct PairDev {
+	const Walk *walks;           // [n_walks]
+	u64 n_walks;
+	const u64 *wo;               // [n_seqs + 1]
+	u64 n_seqs, n_pairs;
+	const u32 *steps;            // [n_steps]
+	u64 n_steps;
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	u64 n_links;
+	const u32 *mu;               // [U]
+	u64 U;
+	int k;
+	u32 min_mapped, max_dist, bin_width, n_bins;
+	unsigned long long *anchor;  // [n_seqs]: min(n_mapped, 2^32 - 1) << 32 | ~(index within the read), 0 for none
+	unsigned long long *cnt;     // [PAIR_C_N]
+	Pair *pairs;                 // [n_pairs] or null
+	unsigned long long *hist;    // [n_bins] or null, added to
+	unsigned long long *pair_hits;   // [n_links] or null, added to
+	PairLink *plinks;            // [cap] or null: the list, in and out
+	u64 cap, n_in, n_items;      // n_items = n_in + n_pairs, 0 without a list
+	u64 *key, *idx, *skey, *sidx;
+	u32 *dist;                   // [n_pairs]
+	u64 *sc;
+	PairLink *mrg;
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

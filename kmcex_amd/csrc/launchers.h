@@ -100,6 +100,9 @@ hipError_t contig_place(const CtgDev &, const CtgRank *, DevBuf<unsigned char> &
 void contig_bytes(const CtgDev &, hipStream_t);
 // ... and kmx_unitig_walk_through* (resolve_kernels.h): the through hits of a batch's walks; the counters land in D.cnt
 hipError_t walk_through(const ThroughDev &, hipStream_t);
+// ... and kmx_unitig_pair_walks* (pair_kernels.h): the pairs of a batch's walks; the counters land in D.cnt, the merged count of
+// the list in D.sc[D.n_items]
+hipError_t pair_walks(const PairDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 // ... and kmx_unitig_resolve*: verdicts (the counters land in D.cnt), the scan (its totals in D.sc[D.U]), records, links, bytes
 hipError_t resolve_verdicts(const ResDev &, CtgTot *, hipStream_t);
 hipError_t resolve_scan(const ResDev &, const CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);

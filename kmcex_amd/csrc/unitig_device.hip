@@ -2,7 +2,8 @@
 // buffers, waits for the round flags and the totals, and checks the capacities is unitig_host.h.  Behind them the launchers of map_kernels.h (kmx_unitig_map_*), which
 // search the same listing through the same bucket index, and the launcher of walk_kernels.h (kmx_unitig_walk_segs*); their host side is map_host.h.
 // Then the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.  Last the launcher of
-// resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.
+// resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
+// (kmx_unitig_pair_walks*); its host side is pair_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -10,6 +11,7 @@
 #include "walk_kernels.h"
 #include "contig_kernels.h"
 #include "resolve_kernels.h"
+#include "pair_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -274,6 +276,31 @@ void resolve_links(const ResDev &D, hipStream_t st)
 void resolve_bytes(const ResDev &D, hipStream_t st)
 {
 	if (D.n_ubases) hipLaunchKernelGGL(k_res_emit, dim3((unsigned)((D.n_ubases + RES_TILE - 1) / RES_TILE)), dim3(256), 0, st, D);
+}
+
+// ---- kmx_unitig_pair_walks* (pair_kernels.h): anchors, classes, then the fold of the work items into the list: sort by key,
+// scan of the key changes, fold, store.  D.cnt holds the eight counters behind it and, with a list, D.sc[D.n_items] the merged
+// count; D.n_pairs > 0
+hipError_t pair_walks(const PairDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.anchor, 0, D.n_seqs * 8, st));
+	RCHK(hipMemsetAsync(D.cnt, 0, PAIR_C_N * sizeof(unsigned long long), st));
+	if (D.n_walks) hipLaunchKernelGGL(k_pair_anchor, dim3(nblk(D.n_walks)), dim3(256), 0, st, D);
+	if (D.n_items && D.n_in) hipLaunchKernelGGL(k_pair_items, dim3(nblk(D.n_in)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_pair_classify, dim3(nblk(D.n_pairs)), dim3(256), 0, st, D);
+	if (!D.n_items) return hipGetLastError();
+	size_t b1 = 0, b2 = 0;
+	auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), PairKeyFlag{D.skey, D.n_items});
+	RCHK(rocprim::radix_sort_pairs(nullptr, b1, D.key, D.skey, D.idx, D.sidx, (size_t)D.n_items, 0, 64, st));
+	RCHK(rocprim::exclusive_scan(nullptr, b2, flags, D.sc, (u64)0, (size_t)(D.n_items + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(b1 > b2 ? b1 : b2, st));
+	RCHK(rocprim::radix_sort_pairs(tmp.get(), b1, D.key, D.skey, D.idx, D.sidx, (size_t)D.n_items, 0, 64, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), b2, flags, D.sc, (u64)0, (size_t)(D.n_items + 1), rocprim::plus<u64>(), st));
+	RCHK(hipMemsetAsync(D.mrg, 0, D.n_items * sizeof(PairLink), st));
+	hipLaunchKernelGGL(k_pair_fold, dim3(nblk(D.n_items)), dim3(256), 0, st, D);
+	const u64 n_store = D.n_items < D.cap ? D.n_items : D.cap;
+	if (n_store) hipLaunchKernelGGL(k_pair_store, dim3(nblk(n_store)), dim3(256), 0, st, D);
+	return hipGetLastError();
 }
 
 }   // namespace kmxk
