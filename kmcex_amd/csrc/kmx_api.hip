@@ -458,6 +458,7 @@ std::atomic<unsigned long long> kmx_malloc_ns{0};
 std::atomic<long long> kmx_fail_alloc{0};
 
 #define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+#include "graph_checks.h"                                      // check_offsets, the CSR and buffer checks: they need fail and TRY only
 
 // n elements, fresh (what the buffer held goes) / grown only when n exceeds what is there; `zero`: cleared on the stream
 template <typename T> static int dalloc(DevBuf<T> &b, u64 n, bool zero, hipStream_t st)
@@ -2220,16 +2221,6 @@ struct SeqChunks {
 	u64 seqs_of(u64 c) const { return n_bnd[c] - 1; }
 };
 
-// KMX_E_ARG when offsets[0] != 0 or the offsets decrease (before anything runs)
-static int check_offsets(const uint64_t *offsets, uint64_t n_seqs)
-{
-	if (!offsets) return fail(KMX_E_ARG, "null argument");
-	if (offsets[0] != 0) return fail(KMX_E_ARG, "offsets[0] = %llu, not 0", (unsigned long long)offsets[0]);
-	for (u64 i = 0; i < n_seqs; i++)
-		if (offsets[i + 1] < offsets[i]) return fail(KMX_E_ARG, "offsets decrease at sequence %llu", (unsigned long long)i);
-	return KMX_OK;
-}
-
 // Every device buffer a host variant of summarise, correct, edit or polish owns for the length of the call: the caller's
 // offsets, one record per sequence (want_rec), the bases when the call needs them whole (null: they stream through the
 // pinned slots instead), n_aux words of the call's own (the edit list; the offsets of the polished reads) and out (the
@@ -2370,12 +2361,6 @@ static_assert(sizeof(kmx_seq_correction) == 64 && sizeof(SeqCorrection) == 64, "
 static_assert(offsetof(kmx_seq_correction, n_weak) == offsetof(SeqCorrection, n_weak) && offsetof(kmx_seq_correction, n_unfixable) == offsetof(SeqCorrection, n_unfixable),
               "SeqCorrection (kmx_types.h) is the layout of kmx_seq_correction");
 
-static bool spans_overlap(const void *a, u64 na, const void *b, u64 nb)
-{
-	const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-	return na && nb && x < y + nb && y < x + na;
-}
-
 // the handle's buffers for pieces / chunks of `piece` windows: dirty list and weak bits with both halos, a flag per
 // workgroup (slot_bytes != 0: the pinned slots too, `answers` int32 words of output each).  Failing is KMX_E_NOMEM.
 static int ensure_correct_buffers(kmx_model *m, u64 piece, size_t slot_bytes, size_t answers, std::optional<SeqDirtyCursor> &dirty)
@@ -2394,7 +2379,7 @@ static int kmx_correct_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint
 	if (min_support < 1 || min_support > 64) return fail(KMX_E_ARG, "min_support = %d, not in [1, 64]", min_support);
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || (n_bases && (!d_seq || !d_seq_out))) return fail(KMX_E_ARG, "null argument");
-	if (spans_overlap(d_seq, n_bases, d_seq_out, n_bases)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
+	if (spans_share(Span{d_seq, n_bases, false}, Span{d_seq_out, n_bases, true})) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
 	HIPCHK(hipSetDevice(m->device));
 	const u64 piece = seq_piece(), H = KMX_CORR_HALO(m->k);
 	std::optional<SeqDirtyCursor> dirty;
@@ -2434,7 +2419,7 @@ static int kmx_correct_seqs_impl(kmx_model *m, const char *seq, const uint64_t *
 		return KMX_OK;
 	}
 	if (!seq || !seq_out) return fail(KMX_E_ARG, "null argument");
-	if (seq_out != seq && spans_overlap(seq, n_bases, seq_out, n_bases)) return fail(KMX_E_ARG, "seq_out overlaps seq (only seq_out == seq is allowed)");
+	if (seq_out != seq && spans_share(Span{seq, n_bases, false}, Span{seq_out, n_bases, true})) return fail(KMX_E_ARG, "seq_out overlaps seq (only seq_out == seq is allowed)");
 	HIPCHK(hipSetDevice(m->device));
 	SeqOnDevice<SeqCorrection> dev{m};
 	TRY(dev.upload(nullptr, offsets, n_seqs, rec != nullptr));
@@ -2774,7 +2759,7 @@ static int kmx_polish_seqs_dev_impl(kmx_model *m, const char *d_seq, const uint6
 	TRY(polish_args(min_support, ops, max_passes));
 	if (!n_seqs) return KMX_OK;
 	if (!d_offsets || !d_offsets_out || (n_bases && !d_seq) || (out_capacity && !d_seq_out)) return fail(KMX_E_ARG, "null argument");
-	if (spans_overlap(d_seq, n_bases, d_seq_out, out_capacity)) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
+	if (spans_share(Span{d_seq, n_bases, false}, Span{d_seq_out, out_capacity, true})) return fail(KMX_E_ARG, "d_seq_out overlaps d_seq");
 	HIPCHK(hipSetDevice(m->device));
 	if (passes_run) *passes_run = 1;
 	if (!n_bases) {
@@ -2806,7 +2791,7 @@ static int kmx_polish_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 	TRY(check_offsets(offsets, n_seqs));
 	const u64 n_bases = offsets[n_seqs];
 	if (!offsets_out || (n_bases && !seq) || (out_capacity && !seq_out)) return fail(KMX_E_ARG, "null argument");
-	if (spans_overlap(seq, n_bases, seq_out, out_capacity)) return fail(KMX_E_ARG, "seq_out overlaps seq");
+	if (spans_share(Span{seq, n_bases, false}, Span{seq_out, out_capacity, true})) return fail(KMX_E_ARG, "seq_out overlaps seq");
 	if (passes_run) *passes_run = 1;
 	if (!n_bases) {
 		for (u64 i = 0; i <= n_seqs; i++) offsets_out[i] = 0;
@@ -2947,6 +2932,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 }
 
 #include "count_host.h"
+#include "graph_host.h"
 #include "unitig_host.h"
 #include "map_host.h"
 #include "contig_host.h"
@@ -3481,17 +3467,17 @@ extern "C" int kmx_count_unitig_map_begin(kmx_model *m, const char *useq, const 
 extern "C" int kmx_unitig_map_seqs_dev(kmx_model *m, const char *d_seq, const uint64_t *d_offsets, uint64_t n_seqs, uint64_t n_bases, kmx_map_segment *d_segs, uint64_t capacity, uint64_t *n_segs, uint64_t *d_seg_offsets, kmx_seq_map *d_rec, uint64_t *d_hits) { return guarded([&] { return kmx_unitig_map_seqs_dev_impl(m, d_seq, d_offsets, n_seqs, n_bases, d_segs, capacity, n_segs, d_seg_offsets, d_rec, d_hits); }); }
 extern "C" int kmx_unitig_map_seqs(kmx_model *m, const char *seq, const uint64_t *offsets, uint64_t n_seqs, kmx_map_segment *segs, uint64_t capacity, uint64_t *n_segs, uint64_t *seg_offsets, kmx_seq_map *rec, uint64_t *hits) { return guarded([&] { return kmx_unitig_map_seqs_impl(m, seq, offsets, n_seqs, segs, capacity, n_segs, seg_offsets, rec, hits); }); }
 extern "C" int kmx_unitig_map_end(kmx_model *m) { return guarded([&] { return kmx_unitig_map_end_impl(m); }); }
-extern "C" int kmx_unitig_walk_segs(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets, uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_impl(m, segs, n_segs, seg_offsets, n_seqs, link_offsets, links, n_links, params, walks, walk_capacity, walk_offsets, steps, step_capacity, link_hits, stats); }); }
-extern "C" int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets, uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_dev_impl(m, d_segs, n_segs, d_seg_offsets, n_seqs, d_link_offsets, d_links, n_links, params, d_walks, walk_capacity, d_walk_offsets, d_steps, step_capacity, d_link_hits, stats); }); }
-extern "C" int kmx_unitig_contigs(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const kmx_contig_params *params, char *cseq, uint64_t *coffsets, kmx_contig *crec, uint32_t *steps, kmx_contig_place *place, uint64_t *clink_offsets, uint32_t *clinks, uint64_t *csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, params, cseq, coffsets, crec, steps, place, clink_offsets, clinks, csupport, n_contigs, n_cbases, n_clinks, stats); }); }
-extern "C" int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const kmx_contig_params *params, char *d_cseq, uint64_t *d_coffsets, kmx_contig *d_crec, uint32_t *d_steps, kmx_contig_place *d_place, uint64_t *d_clink_offsets, uint32_t *d_clinks, uint64_t *d_csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, params, d_cseq, d_coffsets, d_crec, d_steps, d_place, d_clink_offsets, d_clinks, d_csupport, n_contigs, n_cbases, n_clinks, stats); }); }
+extern "C" int kmx_unitig_walk_segs(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets, uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_impl(m, WalkArgs{segs, n_segs, seg_offsets, n_seqs, link_offsets, links, n_links, params, walks, walk_capacity, walk_offsets, steps, step_capacity, link_hits, stats}); }); }
+extern "C" int kmx_unitig_walk_segs_dev(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets, uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats) { return guarded([&] { return kmx_unitig_walk_segs_dev_impl(m, WalkArgs{d_segs, n_segs, d_seg_offsets, n_seqs, d_link_offsets, d_links, n_links, params, d_walks, walk_capacity, d_walk_offsets, d_steps, step_capacity, d_link_hits, stats}); }); }
+extern "C" int kmx_unitig_contigs(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const kmx_contig_params *params, char *cseq, uint64_t *coffsets, kmx_contig *crec, uint32_t *steps, kmx_contig_place *place, uint64_t *clink_offsets, uint32_t *clinks, uint64_t *csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_impl(m, CtgArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, params, cseq, coffsets, crec, steps, place, clink_offsets, clinks, csupport, n_contigs, n_cbases, n_clinks, stats}); }); }
+extern "C" int kmx_unitig_contigs_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const kmx_contig_params *params, char *d_cseq, uint64_t *d_coffsets, kmx_contig *d_crec, uint32_t *d_steps, kmx_contig_place *d_place, uint64_t *d_clink_offsets, uint32_t *d_clinks, uint64_t *d_csupport, uint64_t *n_contigs, uint64_t *n_cbases, uint64_t *n_clinks, kmx_contig_stats *stats) { return guarded([&] { return kmx_unitig_contigs_dev_impl(m, CtgArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, params, d_cseq, d_coffsets, d_crec, d_steps, d_place, d_clink_offsets, d_clinks, d_csupport, n_contigs, n_cbases, n_clinks, stats}); }); }
 extern "C" int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_contigs_last_phases_impl(m, seconds, rounds); }); }
-extern "C" int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, uint64_t n_unitigs, uint64_t *through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_impl(m, walks, n_walks, steps, n_steps, link_offsets, links, n_links, n_unitigs, through, stats); }); }
-extern "C" int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_dev_impl(m, d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, n_unitigs, d_through, stats); }); }
+extern "C" int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, uint64_t n_unitigs, uint64_t *through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_impl(m, ThroughArgs{walks, n_walks, steps, n_steps, link_offsets, links, n_links, n_unitigs, through, stats}); }); }
+extern "C" int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_dev_impl(m, ThroughArgs{d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, n_unitigs, d_through, stats}); }); }
 extern "C" int kmx_unitig_pair_walks(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint64_t *walk_offsets, uint64_t n_seqs, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *pairs, uint64_t *hist, uint64_t *pair_hits, kmx_pair_link *plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_impl(m, PairArgs{walks, n_walks, walk_offsets, n_seqs, steps, n_steps, link_offsets, links, n_links, params, pairs, hist, pair_hits, plinks, capacity, n_plinks, stats}); }); }
 extern "C" int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint64_t *d_walk_offsets, uint64_t n_seqs, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *d_pairs, uint64_t *d_hist, uint64_t *d_pair_hits, kmx_pair_link *d_plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_dev_impl(m, PairArgs{d_walks, n_walks, d_walk_offsets, n_seqs, d_steps, n_steps, d_link_offsets, d_links, n_links, params, d_pairs, d_hist, d_pair_hits, d_plinks, capacity, n_plinks, stats}); }); }
-extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, k, useq, uoffsets, n_unitigs, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
-extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats); }); }
+extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, ResArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
+extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, ResArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }
 extern "C" int kmx_build_from_reads(kmx_model *m, int k, const char *input) { return guarded([&] { return kmx_build_from_reads_impl(m, k, input); }); }
 extern "C" int kmx_download(kmx_model *m, int which, int index, uint8_t *dst, uint64_t capacity, uint64_t *written) { return guarded([&] { return kmx_download_impl(m, which, index, dst, capacity, written); }); }

@@ -1,5 +1,6 @@
 // map_host.h -- kmx_unitig_map_*: a session that maps the windows of reads onto the unitigs of a listing (the rule: include/kmx.h;
 // the kernels: map_kernels.h).  Included into kmx_api.hip after unitig_host.h, whose argument check and bucket index it shares.
+// The host forms stage their buffers in a Staging and validate offsets and CSR with graph_checks.h (both: graph_host.h).
 //
 // begin validates the listing and builds its bucket index (k_uni_index, into the session's own array: a kmx_unitigs call on the
 // handle rebuilds the other one), then the place table and m_u from the unitig set, and waits once for the two error words.
@@ -23,7 +24,8 @@ static u64 map_chunk_size()
 	return x > 0 ? std::min<u64>((u64)x, kMapChunk) : kMapChunk;
 }
 
-static int map_nomem() { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of the unitig map could not be allocated"); }
+static const char *const kMapWhat = "the unitig map";
+static int map_nomem() { return graph_nomem(kMapWhat); }
 
 static int map_session(kmx_model *m, const char *who)
 {
@@ -37,7 +39,7 @@ static int map_begin_core(kmx_model *m, int k, const u64 *d_km, u64 n, const uns
 {
 	auto &S = m->map;
 	const hipStream_t st = m->stream;
-	if (U >> 31) return fail(KMX_E_ARG, "%llu unitigs: a map takes fewer than 2^31", (unsigned long long)U);
+	TRY(check_unitig_count(U));
 	int lg = 0;
 	while ((u64(1) << lg) < n) lg++;
 	UniDev d{};
@@ -87,35 +89,31 @@ static int kmx_unitig_map_begin_dev_impl(kmx_model *m, int k, const uint64_t *d_
 	return map_begin_core(m, k, (const u64 *)d_kmers, n, (const unsigned char *)d_useq, (const u64 *)d_uoffsets, U, n_ubases, false);
 }
 
-// the unitig set of a host variant, on the device for the length of begin
-struct MapSetOnDevice {
-	kmx_model *m;
-	DevBuf<unsigned char> seq;
-	DevBuf<u64> offs;
-	~MapSetOnDevice() { (void)hipStreamSynchronize(m->stream); }
-	int upload(const char *useq, const uint64_t *uoffsets, u64 U)
-	{
-		if (!U) return KMX_OK;
-		TRY(check_offsets(uoffsets, U));
-		if (seq.alloc(uoffsets[U]) != hipSuccess || offs.alloc(U + 1) != hipSuccess) return map_nomem();
-		if (uoffsets[U]) HIPCHK(hipMemcpyAsync(seq, useq, uoffsets[U], hipMemcpyHostToDevice, m->stream));
-		HIPCHK(hipMemcpyAsync(offs, uoffsets, (U + 1) * 8, hipMemcpyHostToDevice, m->stream));
-		return KMX_OK;
-	}
-};
+// the unitig set of a host variant, staged for the length of begin
+static int map_set_upload(Staging &G, const char *useq, const uint64_t *uoffsets, u64 U, const unsigned char **d_useq, const u64 **d_uoffs)
+{
+	*d_useq = nullptr; *d_uoffs = nullptr;
+	if (!U) return KMX_OK;
+	TRY(check_offsets(uoffsets, U));
+	*d_useq = G.in<unsigned char>(useq, uoffsets[U]);
+	*d_uoffs = G.in<u64>(uoffsets, U + 1);
+	return G.status();
+}
 
 static int kmx_unitig_map_begin_impl(kmx_model *m, int k, const uint64_t *kmers, uint64_t n, const char *useq, const uint64_t *uoffsets, uint64_t U)
 {
 	TRY(map_begin_args(m, k, n, kmers, useq, uoffsets, U));
-	MapSetOnDevice set{m};
-	TRY(set.upload(useq, uoffsets, U));
+	Staging G(m, kMapWhat);
+	const unsigned char *d_useq;
+	const u64 *d_uoffs;
+	TRY(map_set_upload(G, useq, uoffsets, U, &d_useq, &d_uoffs));
 	auto &S = m->map;
 	const u64 W = (u64)(k + 31) / 32;
 	if (n) {
 		if (S.d_km.ensure(n * W, m->stream) != hipSuccess) { map_drop(m); return map_nomem(); }
 		HIPCHK(hipMemcpyAsync(S.d_km, kmers, n * W * 8, hipMemcpyHostToDevice, m->stream));
 	}
-	return map_begin_core(m, k, S.d_km, n, set.seq, set.offs, U, U ? uoffsets[U] : 0, false);
+	return map_begin_core(m, k, S.d_km, n, d_useq, d_uoffs, U, U ? uoffsets[U] : 0, false);
 }
 
 static int kmx_count_unitig_map_begin_dev_impl(kmx_model *m, const char *d_useq, const uint64_t *d_uoffsets, uint64_t U, uint64_t n_ubases)
@@ -131,9 +129,11 @@ static int kmx_count_unitig_map_begin_impl(kmx_model *m, const char *useq, const
 	TRY(count_unitigs_listing(m, "kmx_count_unitig_map_begin"));
 	auto &C = m->cnt;
 	TRY(map_begin_args(m, C.k, C.n_list, C.d_run[1].get(), useq, uoffsets, U));
-	MapSetOnDevice set{m};
-	TRY(set.upload(useq, uoffsets, U));
-	return map_begin_core(m, C.k, C.d_run[1], C.n_list, set.seq, set.offs, U, U ? uoffsets[U] : 0, true);
+	Staging G(m, kMapWhat);
+	const unsigned char *d_useq;
+	const u64 *d_uoffs;
+	TRY(map_set_upload(G, useq, uoffsets, U, &d_useq, &d_uoffs));
+	return map_begin_core(m, C.k, C.d_run[1], C.n_list, d_useq, d_uoffs, U, U ? uoffsets[U] : 0, true);
 }
 
 static int kmx_unitig_map_end_impl(kmx_model *m)
@@ -217,23 +217,14 @@ static int kmx_unitig_map_seqs_impl(kmx_model *m, const char *seq, const uint64_
 	auto &S = m->map;
 	const hipStream_t st = m->stream;
 	std::lock_guard<std::mutex> lk(m->query_mu);                  // the pinned slots of m->qfeed
-	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
-		kmx_model *m;
-		DevBuf<u64> offs, so, hits;
-		DevBuf<MapSeg> segs;
-		DevBuf<SeqMap> rec;
-		~Staged() { (void)hipStreamSynchronize(m->stream); }
-	} D{m};
+	Staging G(m, kMapWhat);
 	const u64 U = S.dev.U, seg_cap = segs ? std::min<u64>(capacity, n_bases) : 0;
-	if (D.offs.alloc(n_seqs + 1) != hipSuccess || D.so.alloc(n_seqs + 1) != hipSuccess || (rec && D.rec.alloc(n_seqs) != hipSuccess) || (segs && D.segs.alloc(seg_cap) != hipSuccess) ||
-	    (hits && U && D.hits.alloc(U) != hipSuccess))
-		return map_nomem();
-	HIPCHK(hipMemcpyAsync(D.offs, offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-	unsigned long long *d_hits = hits && U ? (unsigned long long *)D.hits.get() : nullptr;
-	if (d_hits) HIPCHK(hipMemsetAsync(d_hits, 0, U * 8, st));
+	const u64 *d_offs = G.in<u64>(offsets, n_seqs + 1);
+	const MapOut O{segs ? G.out<MapSeg>(seg_cap) : nullptr, seg_cap, G.out<u64>(n_seqs + 1), rec ? G.out<SeqMap>(n_seqs) : nullptr};
+	unsigned long long *d_hits = hits && U ? G.zeroed<unsigned long long>(U) : nullptr;
+	TRY(G.status());
 	SeqChunks sc(seq, offsets, n_seqs, (u64)S.dev.d.k, map_chunk_size());
 	const SlotShape shape = sc.bases_shape();
-	const MapOut O{segs ? D.segs.get() : nullptr, seg_cap, D.so, rec ? D.rec.get() : nullptr};
 	MapChunk C{};
 	TRY(map_batch_begin(m, sc.C, &C, O, n_seqs));
 	if (ensure_query_feed(m, shape.slot_bytes, 0) != KMX_OK) return map_nomem();
@@ -243,43 +234,59 @@ static int kmx_unitig_map_seqs_impl(kmx_model *m, const char *seq, const uint64_
 		[&](int, u64 lo, u64 hi, unsigned char *dst) { sc.stage_bases(lo, hi, dst); },
 		[&](int s, u64 cn, u64 c) {
 			if (le != hipSuccess) return;
-			le = kmxk::map_chunk(S.dev, SeqView{F.d_in[s], c * sc.C, c * sc.C + sc.nbytes_of(c), n_bases, D.offs, n_seqs}, c * sc.C, cn, C, O, d_hits, S.d_tmp, st);
+			le = kmxk::map_chunk(S.dev, SeqView{F.d_in[s], c * sc.C, c * sc.C + sc.nbytes_of(c), n_bases, d_offs, n_seqs}, c * sc.C, cn, C, O, d_hits, S.d_tmp, st);
 		}, (int32_t *)nullptr, &shape));
 	if (le != hipSuccess) return map_dev_fail(le);
-	const hipError_t e = kmxk::map_finish(O, D.offs, n_seqs, n_bases, S.dev.d.k, S.d_tmp, st);
+	const hipError_t e = kmxk::map_finish(O, d_offs, n_seqs, n_bases, S.dev.d.k, S.d_tmp, st);
 	if (e != hipSuccess) return map_dev_fail(e);
 	u64 ns = 0;
-	std::vector<uint64_t> h;
-	if (d_hits) h.resize(U);
-	HIPCHK(hipMemcpyAsync(&ns, S.d_state, 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(seg_offsets, D.so, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, st));
-	if (rec) HIPCHK(hipMemcpyAsync(rec, D.rec, n_seqs * sizeof(SeqMap), hipMemcpyDeviceToHost, st));
-	if (d_hits) HIPCHK(hipMemcpyAsync(h.data(), d_hits, U * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (u64 u = 0; u < h.size(); u++) hits[u] += h[u];
+	G.down(&ns, S.d_state.get(), 1);
+	G.down(seg_offsets, O.so, n_seqs + 1);
+	if (rec) G.down(rec, O.rec, n_seqs);
+	if (d_hits) G.down_add(hits, d_hits, U);
+	TRY(G.finish());
 	*n_segs = ns;
 	if (!segs) return KMX_OK;
 	if (ns > capacity) return map_range(ns, capacity);
-	if (ns) HIPCHK(hipMemcpyAsync(segs, D.segs, ns * sizeof(MapSeg), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	return KMX_OK;
+	G.down(segs, O.segs, ns);
+	return G.finish();
 }
 
 // ---- kmx_unitig_walk_segs*: the walks of a batch's segments (the rule: include/kmx.h; the kernels: walk_kernels.h).  A post-pass
 // inside the session: the work arrays grow with n_segs and stay on the handle, everything is enqueued on the model's stream, and
-// one wait brings the two totals and the five counters to the host.
+// one wait brings the two totals and the five counters to the host.  The entry point fills a WalkArgs, walk_args checks it for both
+// forms and walk_dev_of fills the kernel block's sizes: the forms differ in what the host one validates, stages and downloads.
 static_assert(sizeof(kmx_walk) == 80 && sizeof(Walk) == 80 && sizeof(kmx_walk_stats) == 64 && sizeof(kmx_walk_params) == 16 && sizeof(WalkTot) == 16, "kmx_walk is 80 bytes, kmx_walk_stats 64, kmx_walk_params 16");
 static_assert(offsetof(kmx_walk, first_seg) == offsetof(Walk, first_seg) && offsetof(kmx_walk, n_segs) == offsetof(Walk, n_segs) && offsetof(kmx_walk, off_last) == offsetof(Walk, off_last) &&
               offsetof(kmx_walk, n_across) == offsetof(Walk, n_across) && offsetof(kmx_walk, indel) == offsetof(Walk, indel), "Walk (kmx_types.h) is the layout of kmx_walk");
 
-static int walk_args(kmx_model *m, const char *who, const kmx_walk_params *p, kmx_walk_stats *stats)
+// the buffers of one call: what both forms check before anything runs
+struct WalkArgs {
+	const kmx_map_segment *segs; u64 n_segs;
+	const uint64_t *so; u64 n_seqs;
+	const uint64_t *loffs; const uint32_t *links; u64 n_links;
+	const kmx_walk_params *params;
+	kmx_walk *walks; u64 walk_cap; uint64_t *wo; uint32_t *steps; u64 step_cap;
+	uint64_t *link_hits;
+	kmx_walk_stats *stats;
+};
+
+static int walk_args(kmx_model *m, const char *who, const WalkArgs &A)
 {
 	TRY(map_session(m, who));
-	if (!p || !stats) return fail(KMX_E_ARG, "null argument");
+	const kmx_walk_params *p = A.params;
+	if (!p || !A.stats) return fail(KMX_E_ARG, "null argument");
 	if (p->max_indel > 255) return fail(KMX_E_ARG, "max_indel = %u: at most 255", p->max_indel);
 	if (p->reserved[0] || p->reserved[1]) return fail(KMX_E_ARG, "kmx_walk_params.reserved is not 0");
-	*stats = kmx_walk_stats{0, 0, 0, 0, 0, 0, 0, 0};
+	*A.stats = kmx_walk_stats{0, 0, 0, 0, 0, 0, 0, 0};
+	if (!A.n_seqs) return KMX_OK;
+	if (!A.so || !A.wo || (A.n_segs && !A.segs) || !A.loffs || (A.n_links && !A.links) || (A.walks && !A.steps)) return fail(KMX_E_ARG, "null argument");
 	return KMX_OK;
+}
+
+static int walk_range(const kmx_walk_stats &s, u64 walk_cap, u64 step_cap)
+{
+	return fail(KMX_E_RANGE, "%llu walks and %llu steps, the buffers hold %llu and %llu", (unsigned long long)s.n_walks, (unsigned long long)s.n_steps, (unsigned long long)walk_cap, (unsigned long long)step_cap);
 }
 
 // the pass on device buffers (D: input, parameters and output; the session's part and the work arrays are filled in here)
@@ -304,86 +311,54 @@ static int walk_core(kmx_model *m, WalkDev D, kmx_walk_stats *stats)
 	HIPCHK(hipMemcpyAsync(c, D.cnt, sizeof c, hipMemcpyDeviceToHost, st));
 	HIPCHK(hipStreamSynchronize(st));                              // the call's one wait
 	*stats = kmx_walk_stats{tot.w, tot.s, c[WALK_C_EDGE], c[WALK_C_INSIDE], c[WALK_C_ACROSS], c[WALK_C_UNLINKED], c[WALK_C_BREAKS], 0};
-	if (D.walks && (tot.w > D.walk_cap || tot.s > D.step_cap))
-		return fail(KMX_E_RANGE, "%llu walks and %llu steps, the buffers hold %llu and %llu", (unsigned long long)tot.w, (unsigned long long)tot.s, (unsigned long long)D.walk_cap, (unsigned long long)D.step_cap);
-	return KMX_OK;
+	return D.walks && (tot.w > D.walk_cap || tot.s > D.step_cap) ? walk_range(*stats, D.walk_cap, D.step_cap) : KMX_OK;
 }
 
-static int kmx_unitig_walk_segs_dev_impl(kmx_model *m, const kmx_map_segment *d_segs, uint64_t n_segs, const uint64_t *d_seg_offsets, uint64_t n_seqs, const uint64_t *d_link_offsets,
-                                         const uint32_t *d_links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *d_walks, uint64_t walk_capacity, uint64_t *d_walk_offsets,
-                                         uint32_t *d_steps, uint64_t step_capacity, uint64_t *d_link_hits, kmx_walk_stats *stats)
+// the sizes and parameters of the kernel block; the pointers are the form's own
+static WalkDev walk_dev_of(const WalkArgs &A)
 {
-	TRY(walk_args(m, "kmx_unitig_walk_segs_dev", params, stats));
-	if (!n_seqs) return KMX_OK;
-	if (!d_seg_offsets || !d_walk_offsets || (n_segs && !d_segs) || !d_link_offsets || (n_links && !d_links) || (d_walks && !d_steps)) return fail(KMX_E_ARG, "null argument");
-	HIPCHK(hipSetDevice(m->device));
 	WalkDev D{};
-	D.segs = (const MapSeg *)d_segs; D.n_segs = n_segs; D.so = (const u64 *)d_seg_offsets; D.n_seqs = n_seqs;
-	D.loffs = (const u64 *)d_link_offsets; D.links = d_links; D.n_links = n_links;
-	D.max_gap = params->max_gap; D.max_indel = params->max_indel;
-	D.walks = (Walk *)d_walks; D.walk_cap = d_walks ? walk_capacity : 0; D.wo = (u64 *)d_walk_offsets;
-	D.steps = d_walks ? d_steps : nullptr; D.step_cap = d_walks ? step_capacity : 0;
-	D.link_hits = (unsigned long long *)d_link_hits;
-	return walk_core(m, D, stats);
+	D.n_segs = A.n_segs; D.n_seqs = A.n_seqs; D.n_links = A.n_links;
+	D.max_gap = A.params->max_gap; D.max_indel = A.params->max_indel;
+	D.walk_cap = A.walks ? A.walk_cap : 0; D.step_cap = A.walks ? A.step_cap : 0;
+	return D;
 }
 
-static int kmx_unitig_walk_segs_impl(kmx_model *m, const kmx_map_segment *segs, uint64_t n_segs, const uint64_t *seg_offsets, uint64_t n_seqs, const uint64_t *link_offsets,
-                                     const uint32_t *links, uint64_t n_links, const kmx_walk_params *params, kmx_walk *walks, uint64_t walk_capacity, uint64_t *walk_offsets,
-                                     uint32_t *steps, uint64_t step_capacity, uint64_t *link_hits, kmx_walk_stats *stats)
+static int kmx_unitig_walk_segs_dev_impl(kmx_model *m, const WalkArgs &A)
 {
-	TRY(walk_args(m, "kmx_unitig_walk_segs", params, stats));
-	if (!n_seqs) return KMX_OK;
-	auto &S = m->map;
-	const u64 U = S.dev.U;
-	TRY(check_offsets(seg_offsets, n_seqs));
-	if (seg_offsets[n_seqs] != n_segs) return fail(KMX_E_ARG, "seg_offsets end at %llu, not at n_segs = %llu", (unsigned long long)seg_offsets[n_seqs], (unsigned long long)n_segs);
-	TRY(check_offsets(link_offsets, 2 * U));
-	if (link_offsets[2 * U] != n_links) return fail(KMX_E_ARG, "link_offsets end at %llu, not at n_links = %llu", (unsigned long long)link_offsets[2 * U], (unsigned long long)n_links);
-	if (!walk_offsets || (n_segs && !segs) || (n_links && !links) || (walks && !steps)) return fail(KMX_E_ARG, "null argument");
-	for (u64 e = 0; e < n_links; e++)
-		if ((u64)links[e] >= 2 * U) return fail(KMX_E_ARG, "links[%llu] = %u is no oriented unitig of the session's %llu", (unsigned long long)e, links[e], (unsigned long long)U);
+	TRY(walk_args(m, "kmx_unitig_walk_segs_dev", A));
+	if (!A.n_seqs) return KMX_OK;
 	HIPCHK(hipSetDevice(m->device));
-	const hipStream_t st = m->stream;
-	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
-		kmx_model *m;
-		DevBuf<MapSeg> segs;
-		DevBuf<u64> so, loffs, wo, hits;
-		DevBuf<u32> links, steps;
-		DevBuf<Walk> walks;
-		~Staged() { (void)hipStreamSynchronize(m->stream); }
-	} G{m};
-	const u64 wcap = walks ? std::min<u64>(walk_capacity, n_segs) : 0, scap = walks ? std::min<u64>(step_capacity, n_segs) : 0;
-	if (G.segs.alloc(n_segs) != hipSuccess || G.so.alloc(n_seqs + 1) != hipSuccess || G.loffs.alloc(2 * U + 1) != hipSuccess || G.links.alloc(n_links) != hipSuccess ||
-	    G.wo.alloc(n_seqs + 1) != hipSuccess || (walks && (G.walks.alloc(wcap) != hipSuccess || G.steps.alloc(scap) != hipSuccess)) || (link_hits && n_links && G.hits.alloc(n_links) != hipSuccess))
-		return map_nomem();
-	if (n_segs) HIPCHK(hipMemcpyAsync(G.segs, segs, n_segs * sizeof(MapSeg), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.so, seg_offsets, (n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.loffs, link_offsets, (2 * U + 1) * 8, hipMemcpyHostToDevice, st));
-	if (n_links) HIPCHK(hipMemcpyAsync(G.links, links, n_links * 4, hipMemcpyHostToDevice, st));
-	unsigned long long *d_hits = link_hits && n_links ? (unsigned long long *)G.hits.get() : nullptr;
-	if (d_hits) HIPCHK(hipMemsetAsync(d_hits, 0, n_links * 8, st));
-	WalkDev D{};
-	D.segs = G.segs; D.n_segs = n_segs; D.so = G.so; D.n_seqs = n_seqs;
-	D.loffs = G.loffs; D.links = G.links; D.n_links = n_links;
-	D.max_gap = params->max_gap; D.max_indel = params->max_indel;
-	D.walks = walks ? G.walks.get() : nullptr; D.walk_cap = wcap; D.wo = G.wo;
-	D.steps = walks ? G.steps.get() : nullptr; D.step_cap = scap;
-	D.link_hits = d_hits;
-	const int rc = walk_core(m, D, stats);
+	WalkDev D = walk_dev_of(A);
+	D.segs = (const MapSeg *)A.segs; D.so = (const u64 *)A.so; D.loffs = (const u64 *)A.loffs; D.links = A.links;
+	D.walks = (Walk *)A.walks; D.wo = (u64 *)A.wo; D.steps = A.walks ? A.steps : nullptr; D.link_hits = (unsigned long long *)A.link_hits;
+	return walk_core(m, D, A.stats);
+}
+
+static int kmx_unitig_walk_segs_impl(kmx_model *m, const WalkArgs &A)
+{
+	TRY(walk_args(m, "kmx_unitig_walk_segs", A));
+	if (!A.n_seqs) return KMX_OK;
+	const u64 n_segs = A.n_segs, n_seqs = A.n_seqs, n_links = A.n_links;
+	TRY(check_offsets(A.so, n_seqs));
+	if (A.so[n_seqs] != n_segs) return fail(KMX_E_ARG, "seg_offsets end at %llu, not at n_segs = %llu", (unsigned long long)A.so[n_seqs], (unsigned long long)n_segs);
+	TRY(check_link_csr(A.loffs, A.links, n_links, m->map.dev.U, false));
+	HIPCHK(hipSetDevice(m->device));
+	Staging G(m, kMapWhat);
+	WalkDev D = walk_dev_of(A);
+	D.walk_cap = std::min<u64>(D.walk_cap, n_segs); D.step_cap = std::min<u64>(D.step_cap, n_segs);   // a segment starts at most one walk and one step
+	D.segs = G.in<MapSeg>(A.segs, n_segs); D.so = G.in<u64>(A.so, n_seqs + 1); D.loffs = G.in<u64>(A.loffs, 2 * m->map.dev.U + 1); D.links = G.in<u32>(A.links, n_links);
+	D.wo = G.out<u64>(n_seqs + 1);
+	if (A.walks) { D.walks = G.out<Walk>(D.walk_cap); D.steps = G.out<u32>(D.step_cap); }
+	if (A.link_hits && n_links) D.link_hits = G.zeroed<unsigned long long>(n_links);
+	TRY(G.status());
+	const int rc = walk_core(m, D, A.stats);
 	if (rc != KMX_OK && rc != KMX_E_RANGE) return rc;
-	const bool short_cap = walks && (stats->n_walks > walk_capacity || stats->n_steps > step_capacity);
-	std::vector<uint64_t> h;
-	if (d_hits) h.resize(n_links);
-	HIPCHK(hipMemcpyAsync(walk_offsets, G.wo, (n_seqs + 1) * 8, hipMemcpyDeviceToHost, st));
-	if (d_hits) HIPCHK(hipMemcpyAsync(h.data(), d_hits, n_links * 8, hipMemcpyDeviceToHost, st));
-	if (walks && !short_cap) {
-		if (stats->n_walks) HIPCHK(hipMemcpyAsync(walks, G.walks, stats->n_walks * sizeof(Walk), hipMemcpyDeviceToHost, st));
-		if (stats->n_steps) HIPCHK(hipMemcpyAsync(steps, G.steps, stats->n_steps * 4, hipMemcpyDeviceToHost, st));
-	}
-	HIPCHK(hipStreamSynchronize(st));
-	for (u64 e = 0; e < h.size(); e++) link_hits[e] += h[e];
-	if (short_cap)
-		return fail(KMX_E_RANGE, "%llu walks and %llu steps, the buffers hold %llu and %llu", (unsigned long long)stats->n_walks, (unsigned long long)stats->n_steps, (unsigned long long)walk_capacity,
-		            (unsigned long long)step_capacity);
-	return KMX_OK;
+	const kmx_walk_stats &s = *A.stats;
+	const bool short_cap = A.walks && (s.n_walks > A.walk_cap || s.n_steps > A.step_cap);
+	G.down(A.wo, D.wo, n_seqs + 1);
+	G.down_add(A.link_hits, D.link_hits, D.link_hits ? n_links : 0);
+	if (A.walks && !short_cap) { G.down(A.walks, D.walks, s.n_walks); G.down(A.steps, D.steps, s.n_steps); }
+	TRY(G.finish());
+	return short_cap ? walk_range(s, A.walk_cap, A.step_cap) : KMX_OK;
 }

@@ -6,7 +6,8 @@
 // stream, and ONE wait brings the counters and the merged count to the host.  The merged list reaches the caller's buffer by a
 // launch that reads the count on the device, so a list that does not fit is never touched.  The _dev form checks what can be
 // checked without reading a buffer; the host form validates walk_offsets, the CSR and the input list, stages its input and
-// zeroed copies of hist and pair_hits for the length of the call, downloads and adds.
+// zeroed copies of hist and pair_hits for the length of the call, downloads and adds.  The CSR and buffer checks and the staging
+// owner (Staging) are shared: graph_host.h.
 static_assert(sizeof(kmx_pair_params) == 16 && sizeof(kmx_pair) == 64 && sizeof(Pair) == 64 && sizeof(kmx_pair_link) == 32 && sizeof(PairLink) == 32 && sizeof(kmx_pair_stats) == 80,
               "kmx_pair_params is 16 bytes, kmx_pair 64, kmx_pair_link 32, kmx_pair_stats 80");
 static_assert(offsetof(kmx_pair, walk_b) == offsetof(Pair, walk_b) && offsetof(kmx_pair, cls) == offsetof(Pair, cls) && offsetof(kmx_pair, edge) == offsetof(Pair, edge) &&
@@ -45,11 +46,12 @@ static int pair_args(kmx_model *m, const char *who, const PairArgs &A)
 	if (!A.n_seqs) return KMX_OK;
 	if (!A.wo || !A.loffs || (A.n_walks && !A.walks) || (A.n_steps && !A.steps) || (A.n_links && !A.links)) return fail(KMX_E_ARG, "null argument");
 	const u64 U = m->map.dev.U, np = A.n_seqs / 2;
-	const CtgSpan in[5] = {{A.walks, A.n_walks * sizeof(kmx_walk), false}, {A.wo, (A.n_seqs + 1) * 8, false}, {A.steps, A.n_steps * 4, false}, {A.loffs, (2 * U + 1) * 8, false}, {A.links, A.n_links * 4, false}};
-	const CtgSpan out[4] = {{A.pairs, np * sizeof(kmx_pair), true}, {A.hist, (u64)p->n_bins * 8, true}, {A.pair_hits, A.n_links * 8, true}, {A.plinks, A.capacity * sizeof(kmx_pair_link), true}};
-	for (int i = 0; i < 4; i++)
-		for (int j = 0; j < 5; j++)
-			if (ctg_overlap(out[i].p, out[i].bytes, in[j].p, in[j].bytes)) return fail(KMX_E_ARG, "an output buffer overlaps an input of the call (output %d, input %d)", i, j);
+	Span s[6] = {{A.walks, A.n_walks * sizeof(kmx_walk), false}, {A.wo, (A.n_seqs + 1) * 8, false}, {A.steps, A.n_steps * 4, false}, {A.loffs, (2 * U + 1) * 8, false}, {A.links, A.n_links * 4, false}, {}};
+	const Span out[4] = {opt_span(A.pairs, np * sizeof(kmx_pair), true), opt_span(A.hist, (u64)p->n_bins * 8, true), opt_span(A.pair_hits, A.n_links * 8, true), opt_span(A.plinks, A.capacity * sizeof(kmx_pair_link), true)};
+	for (const Span &o : out) {                                    // every output against the inputs: two outputs are not compared
+		s[5] = o;
+		TRY(check_spans(s, 6));
+	}
 	return KMX_OK;
 }
 
@@ -116,55 +118,29 @@ static int kmx_unitig_pair_walks_impl(kmx_model *m, const PairArgs &A)
 	const u64 U = m->map.dev.U, np = A.n_seqs / 2, n_in = A.plinks ? *A.n_plinks : 0, nb = A.params->n_bins;
 	TRY(check_offsets(A.wo, A.n_seqs));
 	if (A.wo[A.n_seqs] != A.n_walks) return fail(KMX_E_ARG, "walk_offsets end at %llu, not at n_walks = %llu", (unsigned long long)A.wo[A.n_seqs], (unsigned long long)A.n_walks);
-	TRY(check_offsets(A.loffs, 2 * U));
-	if (A.loffs[2 * U] != A.n_links) return fail(KMX_E_ARG, "link_offsets end at %llu, not at n_links = %llu", (unsigned long long)A.loffs[2 * U], (unsigned long long)A.n_links);
-	for (u64 e = 0; e < A.n_links; e++)
-		if ((u64)A.links[e] >= 2 * U) return fail(KMX_E_ARG, "links[%llu] = %u is no oriented unitig of the session's %llu", (unsigned long long)e, A.links[e], (unsigned long long)U);
+	TRY(check_link_csr(A.loffs, A.links, A.n_links, U, false));
 	for (u64 i = 1; i < n_in; i++)
 		if (((u64)A.plinks[i - 1].a << 32 | A.plinks[i - 1].b) >= ((u64)A.plinks[i].a << 32 | A.plinks[i].b))
 			return fail(KMX_E_ARG, "the list of pair links is not strictly ascending at entry %llu", (unsigned long long)i);
 	HIPCHK(hipSetDevice(m->device));
-	const hipStream_t st = m->stream;
-	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
-		kmx_model *m;
-		DevBuf<Walk> walks;
-		DevBuf<u64> wo, loffs, hist, hits;
-		DevBuf<u32> steps, links;
-		DevBuf<Pair> pairs;
-		DevBuf<PairLink> plinks;
-		~Staged() { (void)hipStreamSynchronize(m->stream); }
-	} G{m};
-	const u64 cap = A.plinks ? std::min<u64>(A.capacity, n_in + np) : 0;   // the merge never needs more
-	const bool want_hits = A.pair_hits && A.n_links;
-	if (G.walks.alloc(A.n_walks) != hipSuccess || G.wo.alloc(A.n_seqs + 1) != hipSuccess || G.steps.alloc(A.n_steps) != hipSuccess || G.loffs.alloc(2 * U + 1) != hipSuccess ||
-	    G.links.alloc(A.n_links) != hipSuccess || (A.pairs && G.pairs.alloc(np) != hipSuccess) || (A.hist && G.hist.alloc(nb) != hipSuccess) || (want_hits && G.hits.alloc(A.n_links) != hipSuccess) ||
-	    (A.plinks && G.plinks.alloc(cap) != hipSuccess))
-		return map_nomem();
-	if (A.n_walks) HIPCHK(hipMemcpyAsync(G.walks, A.walks, A.n_walks * sizeof(Walk), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.wo, A.wo, (A.n_seqs + 1) * 8, hipMemcpyHostToDevice, st));
-	if (A.n_steps) HIPCHK(hipMemcpyAsync(G.steps, A.steps, A.n_steps * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.loffs, A.loffs, (2 * U + 1) * 8, hipMemcpyHostToDevice, st));
-	if (A.n_links) HIPCHK(hipMemcpyAsync(G.links, A.links, A.n_links * 4, hipMemcpyHostToDevice, st));
-	if (n_in) HIPCHK(hipMemcpyAsync(G.plinks, A.plinks, n_in * sizeof(PairLink), hipMemcpyHostToDevice, st));
-	if (A.hist) HIPCHK(hipMemsetAsync(G.hist, 0, nb * 8, st));
-	if (want_hits) HIPCHK(hipMemsetAsync(G.hits, 0, A.n_links * 8, st));
+	Staging G(m, kMapWhat);
 	PairDev D = pair_dev_of(A);
-	D.walks = G.walks; D.wo = G.wo; D.steps = G.steps; D.loffs = G.loffs; D.links = G.links;
-	D.pairs = A.pairs ? G.pairs.get() : nullptr; D.hist = A.hist ? (unsigned long long *)G.hist.get() : nullptr; D.pair_hits = want_hits ? (unsigned long long *)G.hits.get() : nullptr;
-	D.plinks = A.plinks ? G.plinks.get() : nullptr; D.cap = cap;
+	D.cap = A.plinks ? std::min<u64>(A.capacity, n_in + np) : 0;      // the merge never needs more
+	D.walks = G.in<Walk>(A.walks, A.n_walks); D.wo = G.in<u64>(A.wo, A.n_seqs + 1); D.steps = G.in<u32>(A.steps, A.n_steps); D.loffs = G.in<u64>(A.loffs, 2 * U + 1);
+	D.links = G.in<u32>(A.links, A.n_links);
+	if (A.pairs) D.pairs = G.out<Pair>(np);
+	if (A.hist) D.hist = G.zeroed<unsigned long long>(nb);
+	if (A.pair_hits && A.n_links) D.pair_hits = G.zeroed<unsigned long long>(A.n_links);
+	if (A.plinks) D.plinks = G.in<PairLink>(A.plinks, n_in, D.cap);
+	TRY(G.status());
 	u64 merged = 0;
 	TRY(pair_core(m, D, A.stats, &merged));
-	std::vector<uint64_t> hh, hl;
-	if (A.hist) hh.resize(nb);
-	if (want_hits) hl.resize(A.n_links);
-	if (A.pairs) HIPCHK(hipMemcpyAsync(A.pairs, G.pairs, np * sizeof(Pair), hipMemcpyDeviceToHost, st));
-	if (A.hist) HIPCHK(hipMemcpyAsync(hh.data(), G.hist, nb * 8, hipMemcpyDeviceToHost, st));
-	if (want_hits) HIPCHK(hipMemcpyAsync(hl.data(), G.hits, A.n_links * 8, hipMemcpyDeviceToHost, st));
-	const bool fits = A.plinks && merged <= A.capacity;               // merged <= n_in + np always, so then it also fits cap
-	if (fits && merged) HIPCHK(hipMemcpyAsync(A.plinks, G.plinks, merged * sizeof(PairLink), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (u64 i = 0; i < hh.size(); i++) A.hist[i] += hh[i];
-	for (u64 e = 0; e < hl.size(); e++) A.pair_hits[e] += hl[e];
+	G.down(A.pairs, D.pairs, D.pairs ? np : 0);
+	G.down_add(A.hist, D.hist, D.hist ? nb : 0);
+	G.down_add(A.pair_hits, D.pair_hits, D.pair_hits ? A.n_links : 0);
+	const bool fits = A.plinks && merged <= A.capacity;               // merged <= n_in + np always, so then it also fits D.cap
+	if (fits) G.down(A.plinks, D.plinks, merged);
+	TRY(G.finish());
 	if (!A.plinks) return KMX_OK;
 	*A.n_plinks = merged;
 	return fits ? KMX_OK : pair_range(merged, A.capacity);

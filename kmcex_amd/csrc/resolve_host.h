@@ -4,19 +4,29 @@
 // through_core runs the count on device buffers: the marks and the three counters stay on the handle by capacity
 // (kmx_model::res), everything is enqueued on the model's stream, and ONE wait brings the counters to the host.  The _dev form
 // checks what can be checked without reading a buffer and hands the caller's pointers over; the host form validates the walks and
-// the CSR, stages its input and a zeroed through of its own for the length of the call, downloads it and adds.
+// the CSR, stages its input and a zeroed through of its own for the length of the call, downloads it and adds.  Both calls of this
+// file take their arguments as a struct (ThroughArgs, ResArgs) that one *_args function checks for both forms; the checks of k,
+// offsets, unitig lengths, CSR and buffers, the staging owner (Staging) and the phase clock are shared: graph_host.h.
 static_assert(sizeof(kmx_through_stats) == 64, "kmx_through_stats is 64 bytes");
 
-static int thr_nomem() { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of the through hits could not be allocated"); }
+static const char *const kThrWhat = "the through hits";
+static int thr_nomem() { return graph_nomem(kThrWhat); }
 
-// what both forms check before anything runs
-static int through_args(kmx_model *m, const void *walks, u64 n_walks, const void *steps, u64 n_steps, const void *link_offsets, const void *links, u64 n_links, u64 U, const void *through,
-                        kmx_through_stats *stats)
+// the buffers of one call: what both forms check before anything runs
+struct ThroughArgs {
+	const kmx_walk *walks; u64 n_walks;
+	const uint32_t *steps; u64 n_steps;
+	const uint64_t *loffs; const uint32_t *links; u64 n_links, U;
+	uint64_t *through;
+	kmx_through_stats *stats;
+};
+
+static int through_args(kmx_model *m, const ThroughArgs &A)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (!stats || !link_offsets || (n_walks && !walks) || (n_steps && !steps) || (n_links && !links) || (U && !through)) return fail(KMX_E_ARG, "null argument");
-	if (U >> 31) return fail(KMX_E_ARG, "%llu unitigs: the through hits take fewer than 2^31", (unsigned long long)U);
-	*stats = kmx_through_stats{n_walks, n_steps, 0, 0, 0, {0, 0, 0}};
+	if (!A.stats || !A.loffs || (A.n_walks && !A.walks) || (A.n_steps && !A.steps) || (A.n_links && !A.links) || (A.U && !A.through)) return fail(KMX_E_ARG, "null argument");
+	TRY(check_unitig_count(A.U));
+	*A.stats = kmx_through_stats{A.n_walks, A.n_steps, 0, 0, 0, {0, 0, 0}};
 	return KMX_OK;
 }
 
@@ -38,62 +48,43 @@ static int through_core(kmx_model *m, ThroughDev D, kmx_through_stats *stats)
 	return KMX_OK;
 }
 
-static int kmx_unitig_walk_through_dev_impl(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links,
-                                            uint64_t n_links, uint64_t U, uint64_t *d_through, kmx_through_stats *stats)
+static ThroughDev through_dev_of(const ThroughArgs &A)
 {
-	TRY(through_args(m, d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, U, d_through, stats));
-	if (!n_steps || !U) return KMX_OK;
-	HIPCHK(hipSetDevice(m->device));
 	ThroughDev D{};
-	D.walks = (const Walk *)d_walks; D.n_walks = n_walks; D.steps = d_steps; D.n_steps = n_steps;
-	D.loffs = (const u64 *)d_link_offsets; D.links = d_links; D.n_links = n_links; D.U = U;
-	D.through = (unsigned long long *)d_through;
-	return through_core(m, D, stats);
+	D.n_walks = A.n_walks; D.n_steps = A.n_steps; D.n_links = A.n_links; D.U = A.U;
+	return D;
 }
 
-static int kmx_unitig_walk_through_impl(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links,
-                                        uint64_t n_links, uint64_t U, uint64_t *through, kmx_through_stats *stats)
+static int kmx_unitig_walk_through_dev_impl(kmx_model *m, const ThroughArgs &A)
 {
-	TRY(through_args(m, walks, n_walks, steps, n_steps, link_offsets, links, n_links, U, through, stats));
-	u64 at = 0;
-	for (u64 w = 0; w < n_walks; w++) {
-		if (walks[w].first_step != at) return fail(KMX_E_ARG, "walk %llu starts at step %llu, not at %llu", (unsigned long long)w, (unsigned long long)walks[w].first_step, (unsigned long long)at);
-		at += walks[w].n_steps;
-	}
-	if (at != n_steps) return fail(KMX_E_ARG, "the walks hold %llu steps, not n_steps = %llu", (unsigned long long)at, (unsigned long long)n_steps);
-	TRY(check_offsets(link_offsets, 2 * U));
-	if (link_offsets[2 * U] != n_links) return fail(KMX_E_ARG, "link_offsets end at %llu, not at n_links = %llu", (unsigned long long)link_offsets[2 * U], (unsigned long long)n_links);
-	for (u64 e = 0; e < n_links; e++)
-		if ((u64)links[e] >= 2 * U) return fail(KMX_E_ARG, "links[%llu] = %u is no oriented unitig of %llu", (unsigned long long)e, links[e], (unsigned long long)U);
-	if (!n_steps || !U) return KMX_OK;
+	TRY(through_args(m, A));
+	if (!A.n_steps || !A.U) return KMX_OK;
 	HIPCHK(hipSetDevice(m->device));
-	const hipStream_t st = m->stream;
-	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
-		kmx_model *m;
-		DevBuf<Walk> walks;
-		DevBuf<u32> steps, links;
-		DevBuf<u64> loffs;
-		DevBuf<unsigned long long> through;
-		~Staged() { (void)hipStreamSynchronize(m->stream); }
-	} G{m};
-	if (G.walks.alloc(n_walks) != hipSuccess || G.steps.alloc(n_steps) != hipSuccess || G.links.alloc(n_links) != hipSuccess || G.loffs.alloc(2 * U + 1) != hipSuccess ||
-	    G.through.alloc(16 * U) != hipSuccess)
-		return thr_nomem();
-	HIPCHK(hipMemcpyAsync(G.walks, walks, n_walks * sizeof(Walk), hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.steps, steps, n_steps * 4, hipMemcpyHostToDevice, st));
-	if (n_links) HIPCHK(hipMemcpyAsync(G.links, links, n_links * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.loffs, link_offsets, (2 * U + 1) * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemsetAsync(G.through, 0, 16 * U * 8, st));
-	ThroughDev D{};
-	D.walks = G.walks; D.n_walks = n_walks; D.steps = G.steps; D.n_steps = n_steps;
-	D.loffs = G.loffs; D.links = G.links; D.n_links = n_links; D.U = U;
-	D.through = G.through;
-	TRY(through_core(m, D, stats));
-	std::vector<uint64_t> h(16 * U);
-	HIPCHK(hipMemcpyAsync(h.data(), G.through, 16 * U * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	for (u64 i = 0; i < h.size(); i++) through[i] += h[i];
-	return KMX_OK;
+	ThroughDev D = through_dev_of(A);
+	D.walks = (const Walk *)A.walks; D.steps = A.steps; D.loffs = (const u64 *)A.loffs; D.links = A.links; D.through = (unsigned long long *)A.through;
+	return through_core(m, D, A.stats);
+}
+
+static int kmx_unitig_walk_through_impl(kmx_model *m, const ThroughArgs &A)
+{
+	TRY(through_args(m, A));
+	u64 at = 0;
+	for (u64 w = 0; w < A.n_walks; w++) {
+		if (A.walks[w].first_step != at) return fail(KMX_E_ARG, "walk %llu starts at step %llu, not at %llu", (unsigned long long)w, (unsigned long long)A.walks[w].first_step, (unsigned long long)at);
+		at += A.walks[w].n_steps;
+	}
+	if (at != A.n_steps) return fail(KMX_E_ARG, "the walks hold %llu steps, not n_steps = %llu", (unsigned long long)at, (unsigned long long)A.n_steps);
+	TRY(check_link_csr(A.loffs, A.links, A.n_links, A.U, false));
+	if (!A.n_steps || !A.U) return KMX_OK;
+	HIPCHK(hipSetDevice(m->device));
+	Staging G(m, kThrWhat);
+	ThroughDev D = through_dev_of(A);
+	D.walks = G.in<Walk>(A.walks, A.n_walks); D.steps = G.in<u32>(A.steps, A.n_steps); D.links = G.in<u32>(A.links, A.n_links); D.loffs = G.in<u64>(A.loffs, 2 * A.U + 1);
+	D.through = G.zeroed<unsigned long long>(16 * A.U);
+	TRY(G.status());
+	TRY(through_core(m, D, A.stats));
+	G.down_add(A.through, D.through, 16 * A.U);
+	return G.finish();
 }
 
 // ---- kmx_unitig_resolve[_dev]: the graph with every resolved unitig split into one copy per way in.  resolve_core runs the
@@ -102,39 +93,41 @@ static int kmx_unitig_walk_through_impl(kmx_model *m, const kmx_walk *walks, uin
 static_assert(sizeof(kmx_resolve_params) == 16 && sizeof(kmx_resolve_place) == 8 && sizeof(ResPlace) == 8 && sizeof(kmx_resolve_stats) == 64,
               "kmx_resolve_params is 16 bytes, kmx_resolve_place 8, kmx_resolve_stats 64");
 
-static int res_nomem() { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of the resolution could not be allocated"); }
+static const char *const kResWhat = "the resolution";
+static int res_nomem() { return graph_nomem(kResWhat); }
 
-// what both forms check before anything runs
-static int resolve_args(kmx_model *m, int k, u64 U, const kmx_resolve_params *p, const CtgSpan *spans, int n_spans, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats)
+// the buffers of one call (n_ubases: the host form fills it in from uoffsets; rseq == null: the sizing call): what both forms
+// check before anything runs
+struct ResArgs {
+	int k;
+	const char *useq; const uint64_t *uoffs; u64 U, n_ubases; const kmx_unitig *urec;
+	const uint64_t *loffs; const uint32_t *links; u64 n_links; const uint64_t *hits, *through;
+	const kmx_resolve_params *params;
+	char *rseq; u64 seq_cap; uint64_t *roffs; u64 rec_cap; kmx_unitig *rrec; uint32_t *origin; kmx_resolve_place *rplace;
+	uint64_t *rloffs; uint32_t *rlinks; uint64_t *lorigin, *rhits;
+	uint64_t *n_out, *n_bases_out;
+	kmx_resolve_stats *stats;
+};
+
+static int resolve_args(kmx_model *m, const ResArgs &A)
 {
 	if (!m) return fail(KMX_E_ARG, "null model");
-	if (k < 5 || k > 63 || !(k & 1)) return fail(KMX_E_ARG, "the resolution needs an odd k in [5, 63], not %d", k);
-	if (U >> 31) return fail(KMX_E_ARG, "%llu unitigs: the resolution takes fewer than 2^31", (unsigned long long)U);
-	if (!p || !n_unitigs_out || !n_bases_out || !stats) return fail(KMX_E_ARG, "null argument");
-	for (int i = 0; i < n_spans; i++)
-		if (!spans[i].p && spans[i].bytes) return fail(KMX_E_ARG, "null argument (buffer %d of the call)", i);
-	for (int i = 0; i < n_spans; i++)
-		for (int j = i + 1; j < n_spans; j++)
-			if ((spans[i].out || spans[j].out) && ctg_overlap(spans[i].p, spans[i].bytes, spans[j].p, spans[j].bytes))
-				return fail(KMX_E_ARG, "an output buffer overlaps another buffer of the call (buffers %d and %d)", i, j);
-	*n_unitigs_out = *n_bases_out = 0;
-	*stats = kmx_resolve_stats{0, 0, 0, 0, 0, 0, 0, 0};
+	TRY(check_odd_k(A.k));
+	TRY(check_unitig_count(A.U));
+	if (!A.params || !A.n_out || !A.n_bases_out || !A.stats) return fail(KMX_E_ARG, "null argument");
+	if (A.rseq && A.U && !!A.urec != !!A.rrec) return fail(KMX_E_ARG, "rrec is NULL exactly when urec is");
+	if (A.rseq && A.n_links && !!A.hits != !!A.rhits) return fail(KMX_E_ARG, "rlink_hits is NULL exactly when link_hits is");
+	if (A.rseq && (A.rec_cap >> 32)) return fail(KMX_E_ARG, "rec_capacity = %llu: at most 2^32 - 1", (unsigned long long)A.rec_cap);
+	const u64 U = A.U, rc = A.rseq ? A.rec_cap : 0, nl = A.rseq ? A.n_links : 0;   // the sizing call takes no output buffer
+	const Span spans[] = {{A.useq, A.n_ubases, false}, {A.uoffs, (U + 1) * 8, false}, {A.loffs, (2 * U + 1) * 8, false}, {A.links, A.n_links * 4, false}, {A.through, 16 * U * 8, false},
+	                      opt_span(A.urec, U * sizeof(Unitig), false), opt_span(A.hits, A.n_links * 8, false),
+	                      {A.rseq, A.rseq ? A.seq_cap : 0, true}, {A.roffs, A.rseq ? (rc + 1) * 8 : 0, true}, opt_span(A.rrec, rc * sizeof(Unitig), true), {A.origin, rc * 4, true},
+	                      {A.rplace, A.rseq ? U * 8 : 0, true}, {A.rloffs, A.rseq ? (2 * rc + 1) * 8 : 0, true}, {A.rlinks, nl * 4, true}, {A.lorigin, nl * 8, true}, opt_span(A.rhits, nl * 8, true)};
+	TRY(check_spans(spans, 16));
+	*A.n_out = *A.n_bases_out = 0;
+	*A.stats = kmx_resolve_stats{0, 0, 0, 0, 0, 0, 0, 0};
 	return KMX_OK;
 }
-
-struct ResClock {
-	kmx_model *m;
-	std::chrono::steady_clock::time_point t0;
-	explicit ResClock(kmx_model *mm) : m(mm) { if (m->prof.on) { hipStreamSynchronize(m->stream); t0 = std::chrono::steady_clock::now(); } }
-	void lap(int phase)
-	{
-		if (!m->prof.on) return;
-		hipStreamSynchronize(m->stream);
-		const auto t1 = std::chrono::steady_clock::now();
-		m->res.phase_s[phase] += std::chrono::duration<double>(t1 - t0).count();
-		t0 = t1;
-	}
-};
 
 // the transform on device buffers (D: input, parameters and output; the work arrays are filled in here); D.U > 0.  D.rseq == null:
 // the sizing call
@@ -148,7 +141,7 @@ static int resolve_core(kmx_model *m, ResDev D, uint64_t *n_unitigs_out, uint64_
 	    S.d_rcnt.ensure(RES_C_N, st) != hipSuccess)
 		return res_nomem();
 	D.bad = S.d_bad; D.ver = S.d_ver; D.sc = S.d_sc; D.cnt = S.d_rcnt;
-	ResClock clk(m);
+	PhaseClock clk(m, S.phase_s);
 	HIPCHK(kmxk::resolve_verdicts(D, S.d_tot, st));
 	clk.lap(0);
 	const hipError_t e = kmxk::resolve_scan(D, S.d_tot, S.d_tmp, st);
@@ -177,124 +170,74 @@ static int resolve_core(kmx_model *m, ResDev D, uint64_t *n_unitigs_out, uint64_
 	return KMX_OK;
 }
 
-static int kmx_unitig_resolve_dev_impl(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t U, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets,
-                                       const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq,
-                                       uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets,
-                                       uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats)
+// the sizes and parameters of the kernel block; the pointers and the capacities are the form's own
+static ResDev resolve_dev_of(const ResArgs &A)
 {
-	const u64 U1 = (U >> 31) ? 0 : U, rc = d_rseq ? rec_capacity : 0, sc = d_rseq ? seq_capacity : 0, nl = d_rseq ? n_links : 0, up = d_rseq ? U1 : 0;
-	if (d_rseq && U && !!d_urec != !!d_rrec) return fail(KMX_E_ARG, "rrec is NULL exactly when urec is");
-	if (d_rseq && n_links && !!d_link_hits != !!d_rlink_hits) return fail(KMX_E_ARG, "rlink_hits is NULL exactly when link_hits is");
-	if (d_rseq && (rec_capacity >> 32)) return fail(KMX_E_ARG, "rec_capacity = %llu: at most 2^32 - 1", (unsigned long long)rec_capacity);
-	const CtgSpan spans[] = {{d_useq, n_ubases, false}, {d_uoffsets, (U1 + 1) * 8, false}, {d_link_offsets, (2 * U1 + 1) * 8, false}, {d_links, n_links * 4, false}, {d_through, 16 * U1 * 8, false},
-	                         {d_urec, d_urec ? U1 * sizeof(Unitig) : 0, false}, {d_link_hits, d_link_hits ? n_links * 8 : 0, false},
-	                         {d_rseq, sc, true}, {d_roffsets, d_rseq ? (rc + 1) * 8 : 0, true}, {d_rrec, d_rrec ? rc * sizeof(Unitig) : 0, true}, {d_origin, rc * 4, true}, {d_rplace, up * 8, true},
-	                         {d_rlink_offsets, d_rseq ? (2 * rc + 1) * 8 : 0, true}, {d_rlinks, nl * 4, true}, {d_link_origin, nl * 8, true}, {d_rlink_hits, d_rlink_hits ? nl * 8 : 0, true}};
-	TRY(resolve_args(m, k, U, params, spans, 16, n_unitigs_out, n_bases_out, stats));
+	ResDev D{};
+	D.k = A.k; D.U = A.U; D.n_ubases = A.n_ubases; D.n_links = A.n_links;
+	D.min_reads = A.params->min_reads; D.max_cross = A.params->max_cross;
+	return D;
+}
+
+static int kmx_unitig_resolve_dev_impl(kmx_model *m, const ResArgs &A)
+{
+	TRY(resolve_args(m, A));
 	HIPCHK(hipSetDevice(m->device));
 	const hipStream_t st = m->stream;
-	if (!U) {
-		if (d_rseq) {
-			HIPCHK(hipMemsetAsync(d_roffsets, 0, 8, st));
-			HIPCHK(hipMemsetAsync(d_rlink_offsets, 0, 8, st));
+	if (!A.U) {
+		if (A.rseq) {
+			HIPCHK(hipMemsetAsync(A.roffs, 0, 8, st));
+			HIPCHK(hipMemsetAsync(A.rloffs, 0, 8, st));
 			HIPCHK(hipStreamSynchronize(st));
 		}
 		return KMX_OK;
 	}
-	ResDev D{};
-	D.k = k; D.U = U; D.n_ubases = n_ubases; D.n_links = n_links;
-	D.useq = (const unsigned char *)d_useq; D.uoffs = (const u64 *)d_uoffsets; D.urec = (const Unitig *)d_urec; D.loffs = (const u64 *)d_link_offsets; D.links = d_links; D.hits = (const u64 *)d_link_hits;
-	D.through = (const u64 *)d_through; D.min_reads = params->min_reads; D.max_cross = params->max_cross;
-	D.rseq = (unsigned char *)d_rseq; D.seq_cap = seq_capacity; D.rec_cap = rec_capacity; D.roffs = (u64 *)d_roffsets; D.rrec = (Unitig *)d_rrec; D.origin = d_origin; D.rplace = (ResPlace *)d_rplace;
-	D.rloffs = (u64 *)d_rlink_offsets; D.rlinks = d_rlinks; D.lorigin = (u64 *)d_link_origin; D.rhits = (u64 *)d_rlink_hits;
-	return resolve_core(m, D, n_unitigs_out, n_bases_out, stats);
+	ResDev D = resolve_dev_of(A);
+	D.useq = (const unsigned char *)A.useq; D.uoffs = (const u64 *)A.uoffs; D.urec = (const Unitig *)A.urec; D.loffs = (const u64 *)A.loffs; D.links = A.links; D.hits = (const u64 *)A.hits;
+	D.through = (const u64 *)A.through;
+	D.rseq = (unsigned char *)A.rseq; D.seq_cap = A.seq_cap; D.rec_cap = A.rec_cap; D.roffs = (u64 *)A.roffs; D.rrec = (Unitig *)A.rrec; D.origin = A.origin; D.rplace = (ResPlace *)A.rplace;
+	D.rloffs = (u64 *)A.rloffs; D.rlinks = A.rlinks; D.lorigin = (u64 *)A.lorigin; D.rhits = (u64 *)A.rhits;
+	return resolve_core(m, D, A.n_out, A.n_bases_out, A.stats);
 }
 
-static int kmx_unitig_resolve_impl(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t U, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links,
-                                   const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity,
-                                   kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits,
-                                   uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats)
+static int kmx_unitig_resolve_impl(kmx_model *m, ResArgs A)
 {
-	if (!uoffsets || !link_offsets) return fail(KMX_E_ARG, "null argument");
-	if (U >> 31) return fail(KMX_E_ARG, "%llu unitigs: the resolution takes fewer than 2^31", (unsigned long long)U);
-	if (k < 5 || k > 63 || !(k & 1)) return fail(KMX_E_ARG, "the resolution needs an odd k in [5, 63], not %d", k);
-	if (rseq && U && !!urec != !!rrec) return fail(KMX_E_ARG, "rrec is NULL exactly when urec is");
-	if (rseq && n_links && !!link_hits != !!rlink_hits) return fail(KMX_E_ARG, "rlink_hits is NULL exactly when link_hits is");
-	if (rseq && (rec_capacity >> 32)) return fail(KMX_E_ARG, "rec_capacity = %llu: at most 2^32 - 1", (unsigned long long)rec_capacity);
-	TRY(check_offsets(uoffsets, U));
-	const u64 n_ubases = uoffsets[U];
-	const u64 rc = rseq ? rec_capacity : 0, sc = rseq ? seq_capacity : 0, nl = rseq ? n_links : 0, up = rseq ? U : 0;
-	const CtgSpan spans[] = {{useq, n_ubases, false}, {uoffsets, (U + 1) * 8, false}, {link_offsets, (2 * U + 1) * 8, false}, {links, n_links * 4, false}, {through, 16 * U * 8, false},
-	                         {urec, urec ? U * sizeof(Unitig) : 0, false}, {link_hits, link_hits ? n_links * 8 : 0, false},
-	                         {rseq, sc, true}, {roffsets, rseq ? (rc + 1) * 8 : 0, true}, {rrec, rrec ? rc * sizeof(Unitig) : 0, true}, {origin, rc * 4, true}, {rplace, up * 8, true},
-	                         {rlink_offsets, rseq ? (2 * rc + 1) * 8 : 0, true}, {rlinks, nl * 4, true}, {link_origin, nl * 8, true}, {rlink_hits, rlink_hits ? nl * 8 : 0, true}};
-	TRY(resolve_args(m, k, U, params, spans, 16, n_unitigs_out, n_bases_out, stats));
-	for (u64 u = 0; u < U; u++)
-		if (uoffsets[u + 1] - uoffsets[u] < (u64)k) return fail(KMX_E_ARG, "unitig %llu has %llu bytes, fewer than k = %d", (unsigned long long)u, (unsigned long long)(uoffsets[u + 1] - uoffsets[u]), k);
-	TRY(check_offsets(link_offsets, 2 * U));
-	if (link_offsets[2 * U] != n_links) return fail(KMX_E_ARG, "link_offsets end at %llu, not at n_links = %llu", (unsigned long long)link_offsets[2 * U], (unsigned long long)n_links);
-	for (u64 o = 0; o < 2 * U; o++)
-		if (link_offsets[o + 1] - link_offsets[o] > 4) return fail(KMX_E_ARG, "the row of oriented unitig %llu has %llu entries, more than 4", (unsigned long long)o, (unsigned long long)(link_offsets[o + 1] - link_offsets[o]));
-	for (u64 e = 0; e < n_links; e++)
-		if ((u64)links[e] >= 2 * U) return fail(KMX_E_ARG, "links[%llu] = %u is no oriented unitig of %llu", (unsigned long long)e, links[e], (unsigned long long)U);
-	for (u64 a = 0; a < 2 * U; a++)
-		for (u64 e = link_offsets[a]; e < link_offsets[a + 1]; e++) {
-			const u64 b1 = (u64)links[e] ^ 1;
-			bool found = false;
-			for (u64 f = link_offsets[b1]; f < link_offsets[b1 + 1]; f++) found = found || links[f] == (u32)(a ^ 1);
-			if (!found) return fail(KMX_E_ARG, "the edge %llu -> %u has no mirror %llu -> %llu", (unsigned long long)a, links[e], (unsigned long long)b1, (unsigned long long)(a ^ 1));
-		}
+	TRY(check_unitig_count(A.U));
+	TRY(check_offsets(A.uoffs, A.U));
+	A.n_ubases = A.uoffs[A.U];
+	TRY(resolve_args(m, A));
+	TRY(check_unitig_lengths(A.uoffs, A.U, A.k));
+	TRY(check_link_csr(A.loffs, A.links, A.n_links, A.U, true));
 	HIPCHK(hipSetDevice(m->device));
-	const hipStream_t st = m->stream;
+	const u64 U = A.U, n_ubases = A.n_ubases, n_links = A.n_links;
 	if (!U) {
-		if (rseq) roffsets[0] = rlink_offsets[0] = 0;
+		if (A.rseq) A.roffs[0] = A.rloffs[0] = 0;
 		return KMX_OK;
 	}
-	struct Staged {                                                // the call's own device buffers; the stream is drained before they go
-		kmx_model *m;
-		DevBuf<unsigned char> useq, rseq;
-		DevBuf<u64> uoffs, loffs, hits, through, roffs, rloffs, lorigin, rhits;
-		DevBuf<u32> links, origin, rlinks;
-		DevBuf<Unitig> urec, rrec;
-		DevBuf<ResPlace> rplace;
-		~Staged() { (void)hipStreamSynchronize(m->stream); }
-	} G{m};
-	if (G.useq.alloc(n_ubases) != hipSuccess || G.uoffs.alloc(U + 1) != hipSuccess || G.loffs.alloc(2 * U + 1) != hipSuccess || G.links.alloc(n_links) != hipSuccess || G.through.alloc(16 * U) != hipSuccess ||
-	    (urec && G.urec.alloc(U) != hipSuccess) || (link_hits && G.hits.alloc(n_links) != hipSuccess))
-		return res_nomem();
-	HIPCHK(hipMemcpyAsync(G.useq, useq, n_ubases, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.uoffs, uoffsets, (U + 1) * 8, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.loffs, link_offsets, (2 * U + 1) * 8, hipMemcpyHostToDevice, st));
-	if (n_links) HIPCHK(hipMemcpyAsync(G.links, links, n_links * 4, hipMemcpyHostToDevice, st));
-	HIPCHK(hipMemcpyAsync(G.through, through, 16 * U * 8, hipMemcpyHostToDevice, st));
-	if (urec) HIPCHK(hipMemcpyAsync(G.urec, urec, U * sizeof(Unitig), hipMemcpyHostToDevice, st));
-	if (link_hits && n_links) HIPCHK(hipMemcpyAsync(G.hits, link_hits, n_links * 8, hipMemcpyHostToDevice, st));
-	ResDev D{};
-	D.k = k; D.U = U; D.n_ubases = n_ubases; D.n_links = n_links;
-	D.useq = G.useq; D.uoffs = G.uoffs; D.urec = urec ? G.urec.get() : nullptr; D.loffs = G.loffs; D.links = G.links; D.hits = link_hits ? G.hits.get() : nullptr;
-	D.through = G.through; D.min_reads = params->min_reads; D.max_cross = params->max_cross;
-	if (!rseq) return resolve_core(m, D, n_unitigs_out, n_bases_out, stats);   // the sizing call
+	Staging G(m, kResWhat);
+	ResDev D = resolve_dev_of(A);
+	D.useq = G.in<unsigned char>(A.useq, n_ubases); D.uoffs = G.in<u64>(A.uoffs, U + 1); D.loffs = G.in<u64>(A.loffs, 2 * U + 1); D.links = G.in<u32>(A.links, n_links);
+	D.through = G.in<u64>(A.through, 16 * U); D.urec = A.urec ? G.in<Unitig>(A.urec, U) : nullptr; D.hits = A.hits ? G.in<u64>(A.hits, n_links) : nullptr;
+	TRY(G.status());
+	if (!A.rseq) return resolve_core(m, D, A.n_out, A.n_bases_out, A.stats);   // the sizing call: the inputs only
 	// the output is staged at what 4 U and 4 n_ubases bound, never beyond the caller's capacities
-	const u64 rcap = std::min<u64>(rec_capacity, 4 * U), scap = std::min<u64>(seq_capacity, 4 * n_ubases);
-	if (G.rseq.alloc(scap) != hipSuccess || G.roffs.alloc(rcap + 1) != hipSuccess || G.rloffs.alloc(2 * rcap + 1) != hipSuccess || G.lorigin.alloc(n_links) != hipSuccess ||
-	    (link_hits && G.rhits.alloc(n_links) != hipSuccess) || G.origin.alloc(rcap) != hipSuccess || G.rlinks.alloc(n_links) != hipSuccess || (urec && G.rrec.alloc(rcap) != hipSuccess) ||
-	    G.rplace.alloc(U) != hipSuccess)
-		return res_nomem();
-	D.rseq = G.rseq; D.seq_cap = scap; D.rec_cap = rcap; D.roffs = G.roffs; D.rrec = urec ? G.rrec.get() : nullptr; D.origin = G.origin; D.rplace = G.rplace;
-	D.rloffs = G.rloffs; D.rlinks = G.rlinks; D.lorigin = G.lorigin; D.rhits = link_hits ? G.rhits.get() : nullptr;
-	TRY(resolve_core(m, D, n_unitigs_out, n_bases_out, stats));
-	const u64 N = *n_unitigs_out, B = *n_bases_out;
-	if (B) HIPCHK(hipMemcpyAsync(rseq, G.rseq, B, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(roffsets, G.roffs, (N + 1) * 8, hipMemcpyDeviceToHost, st));
-	if (urec) HIPCHK(hipMemcpyAsync(rrec, G.rrec, N * sizeof(Unitig), hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(origin, G.origin, N * 4, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(rplace, G.rplace, U * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipMemcpyAsync(rlink_offsets, G.rloffs, (2 * N + 1) * 8, hipMemcpyDeviceToHost, st));
-	if (n_links) HIPCHK(hipMemcpyAsync(rlinks, G.rlinks, n_links * 4, hipMemcpyDeviceToHost, st));
-	if (n_links) HIPCHK(hipMemcpyAsync(link_origin, G.lorigin, n_links * 8, hipMemcpyDeviceToHost, st));
-	if (n_links && link_hits) HIPCHK(hipMemcpyAsync(rlink_hits, G.rhits, n_links * 8, hipMemcpyDeviceToHost, st));
-	HIPCHK(hipStreamSynchronize(st));
-	return KMX_OK;
+	D.rec_cap = std::min<u64>(A.rec_cap, 4 * U); D.seq_cap = std::min<u64>(A.seq_cap, 4 * n_ubases);
+	D.rseq = G.out<unsigned char>(D.seq_cap); D.roffs = G.out<u64>(D.rec_cap + 1); D.rloffs = G.out<u64>(2 * D.rec_cap + 1); D.lorigin = G.out<u64>(n_links);
+	D.rhits = A.hits ? G.out<u64>(n_links) : nullptr; D.origin = G.out<u32>(D.rec_cap); D.rlinks = G.out<u32>(n_links); D.rrec = A.urec ? G.out<Unitig>(D.rec_cap) : nullptr;
+	D.rplace = G.out<ResPlace>(U);
+	TRY(G.status());
+	TRY(resolve_core(m, D, A.n_out, A.n_bases_out, A.stats));
+	const u64 N = *A.n_out;
+	G.down(A.rseq, D.rseq, *A.n_bases_out);
+	G.down(A.roffs, D.roffs, N + 1);
+	if (A.urec) G.down(A.rrec, D.rrec, N);
+	G.down(A.origin, D.origin, N);
+	G.down(A.rplace, D.rplace, U);
+	G.down(A.rloffs, D.rloffs, 2 * N + 1);
+	G.down(A.rlinks, D.rlinks, n_links);
+	G.down(A.lorigin, D.lorigin, n_links);
+	if (A.hits) G.down(A.rhits, D.rhits, n_links);
+	return G.finish();
 }
 
 static int kmx_unitig_resolve_last_phases_impl(kmx_model *m, double *seconds)

@@ -19,6 +19,8 @@
 // unitig_link_emit link_offsets and links.  The work arrays stay on the handle by capacity; nothing here touches the model or
 // the listing.
 //
+// The phase clock (PhaseClock) and the test of k are shared with the later graph calls: graph_host.h.
+//
 // The phase figures (kmx_*_last_phases) are zeroed once where a call starts its work, and every lap of the phase clock adds to
 // them, so a cleaning call's figures are sums over its rounds; only its final emit into the caller's buffers is left out.
 static_assert(sizeof(kmx_unitig) == 40 && sizeof(Unitig) == 40, "kmx_unitig is 40 bytes");
@@ -82,7 +84,7 @@ struct UniRanked {
 
 static int unitig_args(int k, u64 n)
 {
-	if (k < 5 || k > 63 || !(k & 1)) return fail(KMX_E_ARG, "unitigs need an odd k in [5, 63], not %d (an even k has k-mers that are their own reverse complement)", k);
+	TRY(check_odd_k(k));
 	if (n >> 31) return fail(KMX_E_ARG, "%llu listing entries: unitigs take fewer than 2^31", (unsigned long long)n);
 	return KMX_OK;
 }
@@ -104,22 +106,7 @@ static int count_unitigs_listing(kmx_model *m, const char *who)
 	return KMX_OK;
 }
 
-static int uni_nomem() { (void)hipGetLastError(); return fail(KMX_E_NOMEM, "the buffers of the unitig construction could not be allocated"); }
-
-// a lap of the phase clock adds to the handle's figure: only under kmx_set_profile(m, 1), where every phase waits for the stream
-struct UniClock {
-	kmx_model *m;
-	std::chrono::steady_clock::time_point t0;
-	explicit UniClock(kmx_model *mm) : m(mm) { if (m->prof.on) { hipStreamSynchronize(m->stream); t0 = std::chrono::steady_clock::now(); } }
-	void lap(int phase)
-	{
-		if (!m->prof.on) return;
-		hipStreamSynchronize(m->stream);
-		const auto t1 = std::chrono::steady_clock::now();
-		m->uni.phase_s[phase] += std::chrono::duration<double>(t1 - t0).count();
-		t0 = t1;
-	}
-};
+static int uni_nomem() { return graph_nomem("the unitig construction"); }
 
 // the first half, on a device-resident listing at threshold thr.  On KMX_OK *r is what the second half takes.
 static int unitig_rank(kmx_model *m, const UniListing &L, u32 thr, bool links, UniRanked *r)
@@ -147,7 +134,7 @@ static int unitig_rank(kmx_model *m, const UniListing &L, u32 thr, bool links, U
 		HIPCHK(hipStreamSynchronize(st));
 		return (int)KMX_OK;
 	};
-	UniClock clk(m);
+	PhaseClock clk(m, m->uni.phase_s);
 	kmxk::unitig_index(*d, st);
 	u32 bad = 0;
 	TRY(word(0, &bad));
@@ -209,7 +196,7 @@ static int unitig_rank(kmx_model *m, const UniListing &L, u32 thr, bool links, U
 static int unitig_emit(kmx_model *m, const UniRanked &r, const UniBufs &b)
 {
 	if (!r.d.n) { HIPCHK(hipMemsetAsync(b.offs, 0, 8, m->stream)); return KMX_OK; }
-	UniClock clk(m);
+	PhaseClock clk(m, m->uni.phase_s);
 	kmxk::unitig_emit(r.d, m->uni.d_pair[r.cur], (const UniTot *)m->uni.d_mn.get(), r.n_uni, b.seq, b.seq_cap, b.offs, b.rec, b.rec_cap, m->stream);
 	HIPCHK(hipGetLastError());
 	clk.lap(3);
@@ -220,7 +207,7 @@ static int unitig_emit(kmx_model *m, const UniRanked &r, const UniBufs &b)
 static int unitig_link_emit(kmx_model *m, const UniRanked &r, const UniBufs &b)
 {
 	if (!r.d.n) { HIPCHK(hipMemsetAsync(b.loffs, 0, 8, m->stream)); return KMX_OK; }
-	UniClock clk(m);
+	PhaseClock clk(m, m->uni.phase_s);
 	kmxk::unitig_link_emit(r.d, m->uni.d_pair[r.cur], (const UniTot *)m->uni.d_mn.get(), m->uni.d_pair[r.cur ^ 1].get() + r.d.n + 1, r.n_uni, b.loffs, b.rec_cap, b.links, b.link_cap, m->stream);
 	HIPCHK(hipGetLastError());
 	clk.lap(4);
@@ -257,7 +244,7 @@ static int unitig_clean_rounds(kmx_model *m, const UniListing &L, u32 thr, const
 		const UniBufs staged{nullptr, 0, U.d_offs, U.d_rec, nu, U.d_loffs, U.d_links, nl};      // the records only: no byte of a string is stored
 		TRY(unitig_emit(m, *r, staged));
 		TRY(unitig_link_emit(m, *r, staged));
-		UniClock clk(m);
+		PhaseClock clk(m, m->uni.phase_s);
 		HIPCHK(hipMemsetAsync(U.d_cctr, 0, 4 * sizeof(unsigned long long), st));
 		const UniClean c{U.d_rec, U.d_loffs, U.d_links, nu, nl, P.ops, P.max_tip, P.max_bubble};
 		kmxk::unitig_clean(c, U.d_verdict, U.d_cctr, st);
