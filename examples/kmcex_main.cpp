@@ -30,6 +30,13 @@
 //          linked at a distance of at most max_dist windows, 1000 when omitted): pairs.insert.tsv (bin start, pairs; bins of 10
 //          bases up to 2000) and pairs.links.tsv (a, b, pairs, mean distance, min, max, link index or -).  A batch never splits a
 //          pair.  With -X the pairs per edge are added to the reads per edge before the contigs are built
+//     -S<min_pairs>[,<ratio>]  with -M -W -P: order and orient along the pair links that at least min_pairs pairs support (and, with
+//          ratio, whose pairs times ratio reach the best link at either end) and spell scaffolds with runs of N sized from the
+//          insert size (KModel::unitig_scaffold; inner is the floor of the mean d of the pairs on one unitig with frag >= 0, a run
+//          has at least 10 N and at most 2 max_dist): scaffolds.fa, scaffolds.paths.tsv (scaffold, step, unitig, strand, base
+//          offset, N in front, estimate) and scaffolds.agp (AGP 2.1).  Without -X it scaffolds the unitigs from pairs.links.tsv's
+//          list; with -X it reads the input a third time, maps the pairs onto the contigs with the contig graph and scaffolds the
+//          contigs ("unitig" in the two tables is then the contig).  Not with -R: a resolved set is no set to map onto
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -53,6 +60,8 @@ struct Params {
 	long ratio = 0;                                                // -X<min_reads>,<ratio>
 	long long res_min = -1, res_cross = 0;                         // -R<min_reads>[,<max_cross>], -1 = no resolution
 	long pair_dist = -2;                                           // -P: max_dist, -1 = 1000, -2 = no pairs
+	long long scaf_min = -1;                                       // -S: min_pairs, -1 = no scaffolds
+	long scaf_ratio = 0;                                           // -S<min_pairs>,<ratio>
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -100,6 +109,18 @@ static bool parse(int argc, char **argv, Params &p)
 			}
 			if (*end) return false;
 		}
+		else if (!strncmp(a, "-S", 2)) {
+			char *end = nullptr;
+			if (!a[2]) return false;
+			p.scaf_min = strtoll(a + 2, &end, 10);
+			if (end == a + 2 || p.scaf_min < 0) return false;
+			if (*end == ',') {
+				const char *r = end + 1;
+				p.scaf_ratio = strtol(r, &end, 10);
+				if (end == r || p.scaf_ratio < 0 || p.scaf_ratio > 65536) return false;
+			}
+			if (*end) return false;
+		}
 		else if (!strncmp(a, "-P", 2)) {
 			char *end = nullptr;
 			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
@@ -137,6 +158,14 @@ static bool parse(int argc, char **argv, Params &p)
 		std::cout << "-P needs -M -W: the mates of a pair are placed by their walks\n";
 		return false;
 	}
+	if (p.scaf_min >= 0 && p.pair_dist == -2) {                    // the scaffolds are built from the pair links
+		std::cout << "-S needs -M -W -P: the scaffolds are built from the links the pairs leave\n";
+		return false;
+	}
+	if (p.scaf_min >= 0 && p.res_min >= 0) {
+		std::cout << "-S does not go with -R: the pairs are mapped onto what is scaffolded, and a resolved set, where a k-mer lies on several copies, is no set to map onto\n";
+		return false;
+	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -169,6 +198,46 @@ static bool next_reads(std::istream &in, std::vector<std::string> &reads, size_t
 	return true;
 }
 
+// the typical d of a pair on one unitig: the floor of the mean over the SAME pairs with frag >= 0 (0 when there is none)
+struct InnerSum {
+	long double sum = 0;
+	uint64_t n = 0;
+	void add(const std::vector<kmx_pair> &pr)
+	{
+		for (size_t i = 0; i < pr.size(); i++)
+			if (pr[i].cls == KMX_PAIR_SAME && pr[i].frag >= 0) { sum += (long double)pr[i].d; n++; }
+	}
+	uint32_t inner() const
+	{
+		if (!n || sum <= 0) return 0;
+		const long double q = sum / (long double)n;
+		return q >= 4294967295.0L ? 0xFFFFFFFFu : (uint32_t)q;
+	}
+};
+
+// -S: the scaffolds of `strs` from `plinks`, written as scaffolds.fa, scaffolds.paths.tsv and scaffolds.agp
+static bool write_scaffolds(KModel *km, const std::string &dir, const std::vector<std::string> &strs, const std::vector<kmx_unitig> *rec, const std::vector<kmx_pair_link> &plinks, const Params &p,
+                            uint32_t inner, uint32_t max_dist, const char *what)
+{
+	const uint64_t max_n = 2 * (uint64_t)max_dist;
+	const kmx_scaffold_params sp = {(uint64_t)p.scaf_min, (uint32_t)p.scaf_ratio, inner, max_n < 10 ? (uint32_t)max_n : 10u, max_n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)max_n, 0};
+	const KModel::Scaffolds sc = km->unitig_scaffold(strs, rec, plinks, p.k, sp);
+	std::ofstream sf((dir + "/scaffolds.fa").c_str()), st((dir + "/scaffolds.paths.tsv").c_str()), sa((dir + "/scaffolds.agp").c_str());
+	KModel::write_scaffolds_fasta(sf, sc);
+	KModel::write_scaffold_paths_tsv(st, sc);
+	KModel::write_scaffolds_agp(sa, sc, strs);
+	sf.close();
+	st.close();
+	sa.close();
+	if (!sf || !st || !sa) { std::cout << "could not write " << dir << "/scaffolds.fa, scaffolds.paths.tsv or scaffolds.agp" << std::endl; return false; }
+	uint64_t gaps = 0;
+	for (size_t i = 0; i < sc.rec.size(); i++) gaps += sc.rec[i].n_gap_bases;
+	std::cout << "   scaffolds of " << what << " (links of >= " << p.scaf_min << " pairs" << (p.scaf_ratio ? ", ratio " : "") << (p.scaf_ratio ? std::to_string(p.scaf_ratio) : std::string()) << ", inner " << inner
+	          << ") :     " << sc.stats.n_scaffolds << " scaffolds (" << sc.stats.n_multi << " of several, " << sc.stats.n_circular << " circular), " << sc.stats.n_chain << " of " << sc.stats.n_links
+	          << " links joined, " << gaps << " N" << std::endl;
+	return true;
+}
+
 int main(int argc, char **argv)
 {
 	Params p;
@@ -189,7 +258,10 @@ int main(int argc, char **argv)
 		             "           origin, copy); contigs.* are built from the resolved graph\n"
 		             "       -P<max_dist>  with -M -W: the input is interleaved paired reads (forward-reverse); place the mates of every pair:\n"
 		             "           pairs.insert.tsv (insert sizes), pairs.links.tsv (unitigs linked at up to max_dist (1000) windows); with -X the\n"
-		             "           pairs per edge count as reads\n";
+		             "           pairs per edge count as reads\n"
+		             "       -S<min_pairs>[,<ratio>]  with -M -W -P, not with -R: join the unitigs (with -X: the contigs, from a second mapping of the\n"
+		             "           pairs onto them) along the links at least min_pairs pairs support, with runs of N sized from the insert size:\n"
+		             "           scaffolds.fa, scaffolds.paths.tsv (scaffold, step, unitig, strand, offset, N in front, estimate), scaffolds.agp\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -258,6 +330,7 @@ int main(int argc, char **argv)
 			std::vector<kmx_pair_link> plinks;
 			std::vector<uint64_t> insert_hist(pairs ? pp.n_bins : 0, 0), pair_hits(pairs ? links.size() : 0, 0);
 			std::vector<int64_t> frags;
+			InnerSum inner;
 			kmx_pair_stats pt = kmx_pair_stats();
 			std::string carry;                                           // with -P: the first mate of a pair the last batch ended inside
 			bool carried = false;
@@ -288,6 +361,7 @@ int main(int argc, char **argv)
 						const std::vector<kmx_pair> pr = km->seq_pairs(wk, walk_offsets, steps, link_offsets, links, pp, &plinks, &insert_hist, &pair_hits, &ps);
 						for (size_t i = 0; i < pr.size(); i++)
 							if (pr[i].cls == KMX_PAIR_SAME && pr[i].frag >= 0) frags.push_back(pr[i].frag);
+						inner.add(pr);
 						pt.n_pairs += ps.n_pairs; pt.n_none += ps.n_none; pt.n_single += ps.n_single; pt.n_same += ps.n_same; pt.n_negative += ps.n_negative;
 						pt.n_inverted += ps.n_inverted; pt.n_link += ps.n_link; pt.n_adjacent += ps.n_adjacent; pt.n_far += ps.n_far;
 					}
@@ -325,6 +399,7 @@ int main(int argc, char **argv)
 					          << pt.n_inverted << " inverted, " << pt.n_single << " single, " << pt.n_none << " unplaced" << std::endl;
 					for (size_t e = 0; e < link_hits.size() && e < pair_hits.size(); e++) link_hits[e] += pair_hits[e];   // what -X and -R judge the edges by
 				}
+				if (p.scaf_min >= 0 && p.min_reads < 0 && !write_scaffolds(km, dir, strs, &rec, plinks, p, inner.inner(), pp.max_dist, "unitigs")) return 1;
 				if (p.min_reads >= 0) {
 					const kmx_contig_params xp = {(uint64_t)p.min_reads, (uint32_t)p.ratio, 0};
 					KModel::Resolved rs;
@@ -356,6 +431,29 @@ int main(int argc, char **argv)
 						KModel::write_contigs_gfa(cg, ct, p.k, &cstrs, &crec);
 						cg.close();
 						if (!cg) { std::cout << "could not write " << dir << "/contigs.gfa" << std::endl; return 1; }
+					}
+					if (p.scaf_min >= 0) {                                   // the pairs once more, on the contigs and their graph
+						std::ifstream in2(p.input.c_str());
+						std::vector<kmx_pair_link> cplinks;
+						InnerSum cinner;
+						carried = false;
+						km->count_unitig_map_begin(ct.strs);
+						while (in2.peek() != EOF) {
+							if (!next_reads(in2, reads, size_t(1) << 26)) { std::cout << p.input << " is no FASTA / FASTQ file" << std::endl; return 1; }
+							if (carried) { reads.insert(reads.begin(), carry); carried = false; }
+							if (reads.size() % 2) {
+								if (in2.peek() == EOF) break;                     // (the first pass has refused an odd number of reads)
+								carry = reads.back();
+								reads.pop_back();
+								carried = true;
+								if (reads.empty()) continue;
+							}
+							const std::vector<kmx_map_segment> segs = km->seq_to_unitigs(reads, &seg_offsets);
+							const std::vector<kmx_walk> wk = km->seq_walks(segs, seg_offsets, ct.link_offsets, ct.links, wp, &walk_offsets, &steps);
+							cinner.add(km->seq_pairs(wk, walk_offsets, steps, ct.link_offsets, ct.links, pp, &cplinks));
+						}
+						km->unitig_map_end();
+						if (!write_scaffolds(km, dir, ct.strs, 0, cplinks, p, cinner.inner(), pp.max_dist, "contigs")) return 1;
 					}
 					std::cout << "   contigs (links of >= " << p.min_reads << " reads" << (p.ratio ? ", ratio " : "") << (p.ratio ? std::to_string(p.ratio) : std::string()) << ")    :     " << ct.stats.n_contigs
 					          << " contigs (" << ct.stats.n_multi << " of several unitigs, " << ct.stats.n_circular << " circular), " << ct.stats.n_kept << " of " << ct.stats.n_links << " edges kept" << std::endl;

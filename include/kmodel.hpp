@@ -661,6 +661,73 @@ public:
 		for (size_t i = 0; i < hist.size(); i++) out << (uint64_t)i * bin_width << "\t" << hist[i] << "\n";
 	}
 
+	// Scaffolds (the rule: kmx.h): unitigs or contigs ordered and oriented along the pair links seq_pairs left, spelled with runs of
+	// N sized from the insert size.  unitig_scaffold takes the strings (rec may be null: the scaffolds' counts are then 0) and the
+	// list; it needs no session.  The result holds the scaffolds, one kmx_scaffold each, steps (every scaffold's oriented unitigs
+	// back to back, each with the N in front of it and the estimate they were sized from) and place (one per unitig: its scaffold,
+	// strand, step and base offset there).  It sizes the bases with a first call, so it never comes back short.
+	struct Scaffolds {
+		std::vector<std::string> strs;
+		std::vector<kmx_scaffold> rec;
+		std::vector<kmx_scaffold_step> steps;
+		std::vector<kmx_scaffold_place> place;
+		kmx_scaffold_stats stats;
+	};
+	Scaffolds unitig_scaffold(const std::vector<std::string> &unitigs, const std::vector<kmx_unitig> *rec, const std::vector<kmx_pair_link> &plinks, int k, const kmx_scaffold_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), np = plinks.size();
+		if (rec && rec->size() != U) { std::cout << "unitig_scaffold: the records are not those of the unitigs" << std::endl; exit(1); }
+		Scaffolds s;
+		std::vector<uint64_t> soff(U + 1, 0);
+		s.rec.resize(U + 1); s.steps.resize(U + 1); s.place.resize(U + 1);
+		uint64_t ns = 0, nb = 0;
+		const int rc = kmx_unitig_scaffold(h_, k, f.bases.data(), f.off.data(), U, rec && U ? &(*rec)[0] : 0, np ? &plinks[0] : 0, np, &params, 0, 0, &soff[0], &s.rec[0], &s.steps[0], &s.place[0],
+		                                   &ns, &nb, &s.stats);                                               // the sizing call
+		if (rc != KMX_E_RANGE) check(rc);
+		std::string sseq((size_t)nb + 1, '\0');
+		if (rc == KMX_E_RANGE)
+			check(kmx_unitig_scaffold(h_, k, f.bases.data(), f.off.data(), U, rec && U ? &(*rec)[0] : 0, np ? &plinks[0] : 0, np, &params, &sseq[0], nb, &soff[0], &s.rec[0], &s.steps[0], &s.place[0],
+			                          &ns, &nb, &s.stats));
+		soff.resize((size_t)ns + 1);
+		s.strs = split(sseq, soff);
+		s.rec.resize((size_t)ns); s.steps.resize(U); s.place.resize(U);
+		return s;
+	}
+	// the scaffolds as FASTA, header ">s<index> n_bases=<b> n_steps=<s> n_gap_bases=<n> circular=<0|1>"
+	static void write_scaffolds_fasta(std::ostream &out, const Scaffolds &s)
+	{
+		for (size_t i = 0; i < s.strs.size(); i++)
+			out << ">s" << i << " n_bases=" << s.rec[i].n_bases << " n_steps=" << (s.rec[i].n_steps & ~KMX_SCAFFOLD_CIRCULAR) << " n_gap_bases=" << s.rec[i].n_gap_bases
+			    << " circular=" << (s.rec[i].n_steps >> 31) << "\n" << s.strs[i] << "\n";
+	}
+	// ... every step as a table, one "s<scaffold>\t<step>\tu<unitig>\t<+|->\t<base offset in the scaffold>\t<N in front>\t<estimate>" per step ...
+	static void write_scaffold_paths_tsv(std::ostream &out, const Scaffolds &s)
+	{
+		for (size_t i = 0; i < s.rec.size(); i++)
+			for (uint64_t j = 0; j < (s.rec[i].n_steps & ~KMX_SCAFFOLD_CIRCULAR) && s.rec[i].first_step + j < s.steps.size(); j++) {
+				const kmx_scaffold_step &t = s.steps[(size_t)(s.rec[i].first_step + j)];
+				out << "s" << i << "\t" << j << "\tu" << (t.o >> 1) << "\t" << ((t.o & 1) ? '-' : '+') << "\t" << ((t.o >> 1) < s.place.size() ? s.place[t.o >> 1].off : 0) << "\t" << t.n_gap << "\t"
+				    << (long long)t.est << "\n";
+			}
+	}
+	// ... and as AGP 2.1: per step "s<scaffold>\t<begin>\t<end>\t<part>\tW\tu<unitig>\t1\t<length>\t<+|->", and in front of a later
+	// step with N "s<scaffold>\t<begin>\t<end>\t<part>\tN\t<length>\tscaffold\tyes\tpaired-ends" (coordinates from 1, ends inclusive)
+	static void write_scaffolds_agp(std::ostream &out, const Scaffolds &s, const std::vector<std::string> &unitigs)
+	{
+		out << "##agp-version\t2.1\n";
+		for (size_t i = 0; i < s.rec.size(); i++) {
+			uint64_t part = 0;
+			for (uint64_t j = 0; j < (s.rec[i].n_steps & ~KMX_SCAFFOLD_CIRCULAR) && s.rec[i].first_step + j < s.steps.size(); j++) {
+				const kmx_scaffold_step &t = s.steps[(size_t)(s.rec[i].first_step + j)];
+				if ((t.o >> 1) >= s.place.size() || (t.o >> 1) >= unitigs.size()) continue;
+				const uint64_t off = s.place[t.o >> 1].off, len = unitigs[t.o >> 1].size();
+				if (j > 0 && t.n_gap > 0) out << "s" << i << "\t" << off - t.n_gap + 1 << "\t" << off << "\t" << ++part << "\tN\t" << t.n_gap << "\tscaffold\tyes\tpaired-ends\n";
+				out << "s" << i << "\t" << off + 1 << "\t" << off + len << "\t" << ++part << "\tW\tu" << (t.o >> 1) << "\t1\t" << len << "\t" << ((t.o & 1) ? '-' : '+') << "\n";
+			}
+		}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

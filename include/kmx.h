@@ -1146,7 +1146,7 @@ int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds /* [4] */);
  *   (c) cutting a batch at any pair boundary and merging into the same list gives the same bytes as one call;
  *   (d) for error-free pairs drawn from a genome that is one unitig every pair is SAME and frag is the true fragment length.
  * Out of scope: RF and FF libraries; mates in two separate files; pairs on a resolved graph, where a k-mer lies on several
- * copies; acting on the links (ordering and joining contigs, gap filling); choosing max_dist; several GPUs.                 */
+ * copies; choosing max_dist; several GPUs.  What acts on the links: kmx_unitig_scaffold below.                            */
 #define KMX_PAIR_NONE     0
 #define KMX_PAIR_SINGLE   1
 #define KMX_PAIR_SAME     2
@@ -1192,6 +1192,104 @@ int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_
                               uint64_t n_steps, const uint64_t *d_link_offsets /* [2 U + 1] */, const uint32_t *d_links, uint64_t n_links, const kmx_pair_params *params /* HOST */,
                               kmx_pair *d_pairs /* or NULL */, uint64_t *d_hist /* or NULL */, uint64_t *d_pair_hits /* or NULL */, kmx_pair_link *d_plinks /* or NULL */, uint64_t capacity,
                               uint64_t *n_plinks /* HOST */, kmx_pair_stats *stats /* HOST */);
+
+/* ---- scaffolds: unitigs or contigs ordered and oriented along the pair links, spelled with runs of 'N' sized from the insert
+ * size.  A repeat longer than a read, or a hole in the coverage, ends every contig; the pairs that span it are in the list
+ * kmx_unitig_pair_walks leaves.  This call keeps the links the pairs support and joins what has become the only way on.  The
+ * construction of the contig rule on another edge set: a list of unbounded degree instead of rows of at most 4, and bytes that
+ * carry gaps.
+ * Input: k, odd, in [5, 63]; a unitig set in the layout of kmx_query_seqs (useq, uoffsets[U + 1], U < 2^31, every unitig at least
+ *   k bytes of uppercase ACGT, not checked; a reverse step complements with the byte map of kmx_unitig_contigs, whose contigs are
+ *   such a set); optionally urec[U] (only sum_count, min_count and max_count are read); plinks[n_plinks] as
+ *   kmx_unitig_pair_walks leaves it, n_plinks < 2^31; and kmx_scaffold_params: ratio in [0, 65536], min_n <= max_n, reserved = 0.
+ *   Links.  Entry i is a PAIR LINK iff a < 2 U, b < 2 U, a >> 1 != b >> 1 and n_pairs >= 1; every other entry is ignored and
+ *     counted in n_ignored.  A pair link is one edge a -> b and its own mirror b ^ 1 -> a ^ 1, both with sup = n_pairs.  out(o) is
+ *     the multiset of edges out of oriented unitig o: in a list that is not canonical, two entries that give the same edge are
+ *     two edges.
+ *   Kept edges.  best(o) = the largest sup over out(o), 0 when it is empty.  An entry is below_min iff n_pairs < min_pairs;
+ *     otherwise below_ratio iff ratio > 0 and (n_pairs * ratio < best(a) or n_pairs * ratio < best(b ^ 1)), the product taken in
+ *     128 bits; otherwise KEPT.  nk(o) = the kept edges in out(o), a true count (below 2^31, as n_plinks is).
+ *   Chain links.  Entry i is a chain link iff it is kept, nk(a) == 1 and nk(b ^ 1) == 1; then a -> b and b ^ 1 -> a ^ 1.  The
+ *     argument of the contig rule holds unchanged, because a >> 1 != b >> 1 excludes o -> o ^ 1: the 2 U oriented unitigs fall
+ *     into mirror-paired paths and cycles, and no component holds both orientations of a unitig.
+ *   Gap of a chain link, in signed 64-bit arithmetic (two's complement, wrapping): D = sum_dist / n_pairs (unsigned floor
+ *     division); g = inner - 1 - D, where inner is the library's typical d of a KMX_PAIR_SAME pair: a pair across a hole of g
+ *     missing windows has d = dist + g + 1; est = g - (k - 1), the estimated bases between the two unitigs, negative when they
+ *     would overlap; n_gap = min(max(est, min_n), max_n), the 'N' bytes written.
+ *   Scaffolds: one per mirror pair, chosen exactly as contigs are (a single step takes d = 0; of a path and its mirror the one
+ *     whose first step has the smaller unitig index; a cycle starts at its smallest unitig in orientation 0 and is spelled open,
+ *     marked circular), in ascending unitig index of the first step.  The string is the WHOLE oriented string of o_1, then for each
+ *     later step n_gap bytes 'N' and the WHOLE oriented string of that step: pair links claim no overlap, so nothing is trimmed.
+ * Output.  sseq[seq_capacity] and soffsets[U + 1] in the layout of kmx_query_seqs (S + 1 offsets are written); srec[U], the
+ *   records below (S are written); steps[U], back to back in scaffold order: n_gap and est belong to the link IN FRONT of the
+ *   step, are 0 for the first step of a path, and for the first step of a cycle are the closing link's (not spelled, not counted
+ *   in n_gap_bases); place[U]: unitig u lies in scaffold os >> 1, os & 1 is 1 iff its step is 2 u + 1, step is the index of that
+ *   step inside its scaffold and off the base offset of the step's first byte there.  On the HOST: *n_scaffolds, *n_sbases and
+ *   kmx_scaffold_stats.  *n_sbases > seq_capacity: KMX_E_RANGE, everything but sseq complete, nothing written at or behind
+ *   sseq[seq_capacity]; n_ubases + (U - 1) * max_n always suffices.  sseq == NULL with seq_capacity == 0 is the sizing call (KMX_OK
+ *   when there is nothing to spell, KMX_E_RANGE otherwise), as in the unitig calls.  Everything is an integer sum, count, minimum
+ *   or maximum and a function of the input alone: byte-identical across runs and forms.
+ * Consequences:
+ *   (a) with n_plinks = 0, or min_pairs above every entry, every scaffold is one unitig and sseq and soffsets are the input byte
+ *       for byte;
+ *   (b) replacing any entry (a, b) by (b ^ 1, a ^ 1) changes nothing but which entry is counted in n_chain;
+ *   (c) place inverts steps; the n_steps sum to U; n_sbases = n_ubases + the sum of n_gap_bases;
+ *   (d) two islands of one genome that the pairs span come out as one scaffold with the hole as a run of 'N' of its true length,
+ *       when inner is the library's d.
+ * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; gap filling
+ * through the graph; links that skip a unitig (transitive reduction); RF and FF libraries; several GPUs; choosing min_pairs and
+ * inner.                                                                                                                    */
+typedef struct kmx_scaffold_params { uint64_t min_pairs; uint32_t ratio /* [0, 65536] */; uint32_t inner; uint32_t min_n, max_n /* min_n <= max_n */;
+                                     uint64_t reserved /* 0 */; } kmx_scaffold_params;                                  /* 32 bytes */
+#define KMX_SCAFFOLD_CIRCULAR 0x80000000u
+typedef struct kmx_scaffold {            /* one per scaffold; 64 bytes, no padding */
+	uint64_t n_bases;                    /* the bytes of its string, the N included */
+	uint64_t n_kmers;                    /* the sum of m_u over its steps */
+	uint64_t sum_count;                  /* from urec; 0 when urec is NULL */
+	uint32_t min_count, max_count;       /* from urec; 0 when urec is NULL */
+	uint32_t first_step;                 /* its steps are steps[first_step .. first_step + n_steps) */
+	uint32_t n_steps;                    /* below 2^31; KMX_SCAFFOLD_CIRCULAR is set above it for a cycle: circular = n_steps >> 31 */
+	uint64_t n_gap_bases;                /* the spelled N */
+	uint64_t min_pairs, sum_pairs;       /* n_pairs over its chain links, the closing link of a cycle included; 0 when it has none */
+} kmx_scaffold;
+typedef struct kmx_scaffold_step { uint32_t o; uint32_t n_gap; int64_t est; } kmx_scaffold_step;                         /* 16 bytes */
+typedef struct kmx_scaffold_place { uint32_t os; uint32_t step; uint64_t off; } kmx_scaffold_place;                      /* 16 bytes */
+typedef struct kmx_scaffold_stats { uint64_t n_entries, n_links, n_ignored, n_below_min, n_below_ratio, n_kept, n_chain /* entries of the list, each */,
+                                    n_scaffolds, n_circular, n_multi /* scaffolds of more than one step */; } kmx_scaffold_stats;   /* 80 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_unitig_contigs); it runs on the model's stream and is a
+ * build-class call.  urec may be NULL, plinks with n_plinks == 0, sseq with seq_capacity == 0; every other buffer is required
+ * (with U == 0 only soffsets, the two counts and stats).  KMX_E_ARG before anything runs: an even or out-of-range k, U >= 2^31,
+ * n_plinks >= 2^31, ratio > 65536, min_n > max_n, reserved != 0, a NULL required buffer, an output that overlaps an input or
+ * another output; uoffsets whose first entry is not 0, that decrease, or that give a unitig fewer than k bytes; a list that is
+ * not strictly ascending by a << 32 | b.  U == 0: KMX_OK, soffsets[0] = 0, all counts zero but n_entries and n_ignored.
+ * KMX_E_NOMEM leaves the handle usable.  The call returns when the output is complete.                                      */
+int kmx_unitig_scaffold(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_unitig *urec /* or NULL */,
+                        const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_scaffold_params *params, char *sseq /* [seq_capacity] or NULL */, uint64_t seq_capacity,
+                        uint64_t *soffsets /* [U + 1] */, kmx_scaffold *srec /* [U] */, kmx_scaffold_step *steps /* [U] */, kmx_scaffold_place *place /* [U] */,
+                        uint64_t *n_scaffolds, uint64_t *n_sbases, kmx_scaffold_stats *stats);
+/* The same on DEVICE buffers, read where the graph, contig and pair calls left them; params, the two counts and stats are on the
+ * HOST.  It checks k, U, n_plinks, the parameters, NULL and overlap, and validates nothing else on the host; the kernels clamp
+ * instead, exactly as the contig kernels do: uoffsets into [0, n_ubases]; an entry that is no pair link is ignored; the list is
+ * taken as it is (not ascending, not canonical, duplicate keys: every entry is its own edge); and the chain link is tested
+ * from both sides, so whatever the list holds the links form mirror-paired paths and cycles and the doubling ends within
+ * ceil(log2 2U) + 1 rounds, the cut, and as many again.  Every store is checked against U, seq_capacity or n_plinks.  Bad device
+ * input gives wrong scaffolds and never an access outside a buffer.
+ * It waits for the stream once per doubling round and once for the counts; the bytes are written only after that wait has
+ * shown that n_sbases fits (the N by a fill of sseq[0, n_sbases), the unitigs over it by the tile emit of the contigs), and a
+ * last wait behind them leaves nothing in flight.  Device memory, kept on the handle between calls through the owning types
+ * of hip_owned.h: 145 bytes per unitig (2 x 32 for the two copies of pointer, step rank and byte rank of both orientations, whose
+ * spare copy the marks reuse; 2 x 8 for the two copies of the running minimum; 24 for the scanned marks; 2 x 16 for best, the
+ * kept count and the smallest kept entry of both orientations; 1 for the cycle flag; 8 for where a unitig's bytes go) and none
+ * per entry, plus the scan's scratch.  The host form also stages its input and output there.                                 */
+int kmx_unitig_scaffold_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, uint64_t n_ubases,
+                            const kmx_unitig *d_urec /* or NULL */, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_scaffold_params *params /* HOST */,
+                            char *d_sseq /* [seq_capacity] or NULL */, uint64_t seq_capacity, uint64_t *d_soffsets /* [U + 1] */, kmx_scaffold *d_srec /* [U] */,
+                            kmx_scaffold_step *d_steps /* [U] */, kmx_scaffold_place *d_place /* [U] */, uint64_t *n_scaffolds /* HOST */, uint64_t *n_sbases /* HOST */,
+                            kmx_scaffold_stats *stats /* HOST */);
+/* where the last of these two calls on the handle spent its time, measured only under kmx_set_profile(m, 1) (every phase then
+ * waits for the stream): seconds[5] = verdicts, ranking (links, rounds, cut), marks and their scan, records with steps and
+ * places, the bytes; *rounds = its doubling rounds (counted always)                                                          */
+int kmx_unitig_scaffold_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_walk_through", "kmx_unitig_walk_through_dev",
     "kmx_unitig_resolve", "kmx_unitig_resolve_dev", "kmx_unitig_resolve_last_phases",
     "kmx_unitig_pair_walks", "kmx_unitig_pair_walks_dev",
+    "kmx_unitig_scaffold", "kmx_unitig_scaffold_dev", "kmx_unitig_scaffold_last_phases",
 ]
 
 
@@ -231,6 +232,36 @@ PAIR_LINK_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("n_pairs", "<u8"), ("su
 PAIR_CLASSES = {0: "NONE", 1: "SINGLE", 2: "SAME", 3: "INVERTED", 4: "LINK", 5: "FAR"}
 
 
+class ScaffoldParams(C.Structure):
+    """kmx_scaffold_params of include/kmx.h: 32 bytes"""
+    _fields_ = [("min_pairs", C.c_uint64), ("ratio", C.c_uint32), ("inner", C.c_uint32), ("min_n", C.c_uint32), ("max_n", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class ScaffoldStats(C.Structure):
+    """kmx_scaffold_stats of include/kmx.h: 80 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_entries", "n_links", "n_ignored", "n_below_min", "n_below_ratio", "n_kept", "n_chain", "n_scaffolds", "n_circular", "n_multi")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_scaffold, kmx_scaffold_step and kmx_scaffold_place as NumPy structured dtypes (what KModel.unitig_scaffold_flat returns): 64,
+# 16 and 16 bytes.  n_steps carries SCAFFOLD_CIRCULAR above the count: scaffold_n_steps and scaffold_circular take it apart.
+SCAFFOLD_DTYPE = np.dtype([("n_bases", "<u8"), ("n_kmers", "<u8"), ("sum_count", "<u8"), ("min_count", "<u4"), ("max_count", "<u4"), ("first_step", "<u4"), ("n_steps", "<u4"),
+                           ("n_gap_bases", "<u8"), ("min_pairs", "<u8"), ("sum_pairs", "<u8")])
+SCAFFOLD_STEP_DTYPE = np.dtype([("o", "<u4"), ("n_gap", "<u4"), ("est", "<i8")])
+SCAFFOLD_PLACE_DTYPE = np.dtype([("os", "<u4"), ("step", "<u4"), ("off", "<u8")])
+SCAFFOLD_CIRCULAR = 0x80000000
+
+
+def scaffold_n_steps(srec) -> np.ndarray:
+    return np.asarray(srec["n_steps"]) & np.uint32(SCAFFOLD_CIRCULAR - 1)
+
+
+def scaffold_circular(srec) -> np.ndarray:
+    return (np.asarray(srec["n_steps"]) >> np.uint32(31)).astype(np.uint8)
+
+
 class RingList(C.Structure):
     """kmx_ring_list of include/kmx.h"""
     _fields_ = [("list", C.c_int32), ("n_host", C.c_int32), ("src_kmers", C.c_void_p), ("src_counts", C.c_void_p),
@@ -382,6 +413,9 @@ def load_library():
     _sig(L, "kmx_unitig_walk_through_dev", [vp, vp, u64, vp, u64, vp, vp, u64, u64, vp, C.POINTER(ThroughStats)])
     _sig(L, "kmx_unitig_pair_walks", [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, C.POINTER(PairParams), vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PairStats)])
     _sig(L, "kmx_unitig_pair_walks_dev", [vp, vp, u64, vp, u64, vp, u64, vp, vp, u64, C.POINTER(PairParams), vp, vp, vp, vp, u64, C.POINTER(u64), C.POINTER(PairStats)])
+    _sig(L, "kmx_unitig_scaffold", [vp, C.c_int, vp, vp, u64, vp, vp, u64, C.POINTER(ScaffoldParams), vp, u64, vp, vp, vp, vp, p64, p64, C.POINTER(ScaffoldStats)])
+    _sig(L, "kmx_unitig_scaffold_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, u64, C.POINTER(ScaffoldParams), vp, u64, vp, vp, vp, vp, p64, p64, C.POINTER(ScaffoldStats)])
+    _sig(L, "kmx_unitig_scaffold_last_phases", [vp, C.POINTER(C.c_double), p64])
     _sig(L, "kmx_unitig_resolve", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1280,6 +1314,80 @@ class KModel:
         walks, wo, steps, _, _, _ = self.seq_to_walks(reads, link_offsets, links, max_gap, max_indel, link_hits=link_hits)
         rec, lst, st = self.unitig_pairs_flat(walks, wo, steps, link_offsets, links, max_dist, min_mapped, bin_width, n_bins, plinks=plinks, hist=hist, pair_hits=pair_hits)
         return rec, lst, st, walks, wo, steps
+
+    # ---- scaffolds: unitigs or contigs joined along the pair links, with runs of N (the rule: include/kmx.h); no model, no session
+    def unitig_scaffold_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, plinks: np.ndarray, inner: int, min_pairs: int = 2, ratio: int = 0, min_n: int = 10, max_n: int = 1000,
+                             urec=None, capacity=None):
+        """kmx_unitig_scaffold on a unitig set (uint8 bases, uint64 offsets [U + 1], optionally its UNITIG_DTYPE records) and the
+        PAIR_LINK_DTYPE list unitig_pairs_flat left -> (uint8 scaffold bases, uint64 soffsets [S + 1], SCAFFOLD_DTYPE records [S],
+        SCAFFOLD_STEP_DTYPE steps [U], SCAFFOLD_PLACE_DTYPE place [U], stats as a dict).  capacity None: n_ubases + (U - 1) * max_n,
+        which always suffices; a number: that many bytes, 0 being the sizing call (KmxError KMX_E_RANGE when short: its `needed`
+        the bytes needed, its `result` everything but the bases)."""
+        ubuf = np.ascontiguousarray(ubuf, dtype=np.uint8)
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        plinks = np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+        nu = uoffsets.size - 1
+        if urec is not None:
+            urec = np.ascontiguousarray(urec, dtype=UNITIG_DTYPE)
+            if urec.size != nu:
+                raise KmxError(-1, "urec holds one record per unitig")
+        cap = ubuf.size + max(nu - 1, 0) * int(max_n) if capacity is None else int(capacity)
+        sseq = np.zeros(cap, dtype=np.uint8) if cap else None
+        soffs = np.zeros(nu + 1, dtype=np.uint64)
+        srec = np.zeros(max(nu, 1), dtype=SCAFFOLD_DTYPE)
+        steps = np.zeros(max(nu, 1), dtype=SCAFFOLD_STEP_DTYPE)
+        place = np.zeros(max(nu, 1), dtype=SCAFFOLD_PLACE_DTYPE)
+        par, st = ScaffoldParams(int(min_pairs), int(ratio), int(inner), int(min_n), int(max_n), 0), ScaffoldStats()
+        ns, nb = C.c_uint64(0), C.c_uint64(0)
+        try:
+            _chk(self.L.kmx_unitig_scaffold(self.h, int(k), ubuf.ctypes.data, uoffsets.ctypes.data, nu, urec.ctypes.data if urec is not None else None, plinks.ctypes.data if plinks.size else None,
+                                            plinks.size, C.byref(par), sseq.ctypes.data if cap else None, cap, soffs.ctypes.data, srec.ctypes.data, steps.ctypes.data, place.ctypes.data,
+                                            C.byref(ns), C.byref(nb), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(nb.value)
+            e.result = (soffs[:ns.value + 1].copy(), srec[:ns.value].copy(), steps[:nu].copy(), place[:nu].copy(), st.as_dict())
+            raise
+        s, b = ns.value, nb.value
+        return (sseq[:b].copy() if cap else np.zeros(0, dtype=np.uint8)), soffs[:s + 1].copy(), srec[:s].copy(), steps[:nu].copy(), place[:nu].copy(), st.as_dict()
+
+    def unitig_scaffold_dev(self, k: int, d_ubuf, d_uoffsets, d_plinks, n_plinks: int, inner: int, min_pairs: int = 2, ratio: int = 0, min_n: int = 10, max_n: int = 1000, d_urec=None,
+                            capacity=None, out=None):
+        """kmx_unitig_scaffold_dev on torch tensors of the model's device, read where the graph, contig and pair calls left them:
+        d_ubuf uint8 [n_ubases], d_uoffsets int64 [U + 1], d_plinks uint8 [capacity, 32] holding n_plinks entries (or None),
+        d_urec uint8 [U, 40] or None.  out: the five output tensors (d_sseq uint8 [capacity] or None for the sizing call, d_soffsets
+        int64 [U + 1], d_srec uint8 [U, 64], d_steps uint8 [U, 16], d_place uint8 [U, 16]), allocated when None with `capacity`
+        bytes (None: n_ubases + (U - 1) * max_n) -> (out, (n_scaffolds, n_sbases), stats as a dict).  KmxError KMX_E_RANGE carries the
+        bytes needed in `needed` and everything else in `result`."""
+        import torch
+        nu, nb, dev = d_uoffsets.numel() - 1, d_ubuf.numel(), d_uoffsets.device
+        if out is None:
+            cap = nb + max(nu - 1, 0) * int(max_n) if capacity is None else int(capacity)
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            out = (z(cap, torch.uint8) if cap else None, z(nu + 1, torch.int64), z((max(nu, 1), 64), torch.uint8), z((max(nu, 1), 16), torch.uint8), z((max(nu, 1), 16), torch.uint8))
+        par, st = ScaffoldParams(int(min_pairs), int(ratio), int(inner), int(min_n), int(max_n), 0), ScaffoldStats()
+        ns, nsb = C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            _chk(self.L.kmx_unitig_scaffold_dev(self.h, int(k), d_ubuf.data_ptr(), d_uoffsets.data_ptr(), nu, nb, ptr(d_urec), ptr(d_plinks) if n_plinks else None, int(n_plinks), C.byref(par),
+                                                ptr(out[0]), out[0].numel() if out[0] is not None else 0, *[t.data_ptr() for t in out[1:]], C.byref(ns), C.byref(nsb), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(nsb.value)
+            e.result = (out, (ns.value, nsb.value), st.as_dict())
+            raise
+        return out, (ns.value, nsb.value), st.as_dict()
+
+    def scaffolds_from_pairs(self, k: int, strs, plinks: np.ndarray, inner: int, min_pairs: int = 2, ratio: int = 0, min_n: int = 10, max_n: int = 1000):
+        """unitig_scaffold_flat on a list of unitig or contig strings and a pair list -> (the scaffold strings as str, SCAFFOLD_DTYPE
+        records, SCAFFOLD_STEP_DTYPE steps, SCAFFOLD_PLACE_DTYPE place, stats as a dict)"""
+        _, _, ubuf, uoffs = _join_seqs(list(strs))
+        sseq, soffs, srec, steps, place, st = self.unitig_scaffold_flat(k, ubuf, uoffs, plinks, inner, min_pairs, ratio, min_n, max_n)
+        return [b.decode("latin-1") for b in _split_seqs(sseq, soffs)], srec, steps, place, st
+
+    def unitig_scaffold_phases(self) -> dict:
+        """kmx_unitig_scaffold_last_phases: seconds per phase of the last scaffold call (under set_profile(1)) and its doubling rounds"""
+        sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
+        _chk(self.L.kmx_unitig_scaffold_last_phases(self.h, sec, C.byref(rounds)))
+        return dict(zip(("verdicts", "ranking", "marks", "records", "bytes"), (float(x) for x in sec)), rounds=int(rounds.value))
 
     # ---- contigs: the unitigs merged along the edges the reads support (the rule: include/kmx.h); no model, no session
     def unitig_contigs_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, link_hits: np.ndarray, min_reads: int = 1, ratio: int = 0,

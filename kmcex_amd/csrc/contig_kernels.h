@@ -16,7 +16,8 @@
 //                 one binary search, the offsets and destinations of the unitigs that start in the tile into LDS, a scan of the
 //                 output words each of these pieces covers, then one lane per aligned 16-byte output word: forward pieces are
 //                 copies, reverse pieces are read backwards and complemented, and either way a wave stores consecutive aligned
-//                 words.  No lane's work grows with the length of a unitig or of a contig;
+//                 words.  No lane's work grows with the length of a unitig or of a contig.  Its body is ctg_emit_tile, which
+//                 k_scf_emit (scaffold_kernels.h) runs with nothing skipped and another capacity;
 //   k_ctg_clinks  after the scan of the end counts: one lane per oriented contig writes its row of the contig graph.
 // Every index read from the caller's arrays is clamped where it is read and every store is checked against its capacity: bad
 // device input gives wrong contigs, never an access outside a buffer.  The chain link is tested from both sides, so whatever
@@ -294,15 +295,16 @@ __device__ __forceinline__ u32 ctg_comp4(u32 w)
 	return w ^ 0x15151515u ^ (m | (m << 4));
 }
 
-// piece i of the tile [t0, t1): the bytes of unitig u0 + i that lie in the tile and are emitted (a later step never writes its first
-// k - 1 bytes).  They go to cseq[d0, d1); the byte at d0 is s_in[x0], the next one s_in[x0 + 1] (forward) or s_in[x0 - 1] (rev).
-__device__ __forceinline__ bool ctg_piece(const u64 *s_off, const u64 *s_base, u32 i, u64 t0, u64 t1, int k, u64 *d0, u64 *d1, u32 *x0, bool *rev)
+// piece i of the tile [t0, t1): the bytes of unitig u0 + i that lie in the tile and are emitted (a step that is not marked
+// CTG_FIRST never writes its first `later_skip` bytes: k - 1 for a contig, 0 for a scaffold).  They go to out[d0, d1); the byte at
+// d0 is s_in[x0], the next one s_in[x0 + 1] (forward) or s_in[x0 - 1] (rev).
+__device__ __forceinline__ bool ctg_piece(const u64 *s_off, const u64 *s_base, u32 i, u64 t0, u64 t1, u64 later_skip, u64 *d0, u64 *d1, u32 *x0, bool *rev)
 {
 	const u64 so = s_off[i], eo = s_off[i + 1];
 	if (eo <= so) return false;
 	const u64 len = eo - so, a = ctg_max(so, t0), b = ctg_min(eo, t1);
 	if (b <= a) return false;
-	const u64 ja = a - so, jb = b - so, w = s_base[i], base = w & (CTG_FIRST - 1), skip = (w & CTG_FIRST) ? 0 : (u64)(k - 1);
+	const u64 ja = a - so, jb = b - so, w = s_base[i], base = w & (CTG_FIRST - 1), skip = (w & CTG_FIRST) ? 0 : later_skip;
 	*rev = (w & CTG_REV) != 0;
 	if (!*rev) {
 		const u64 j0 = ctg_max(ja, skip);
@@ -316,8 +318,9 @@ __device__ __forceinline__ bool ctg_piece(const u64 *s_off, const u64 *s_base, u
 	return true;
 }
 
-// one block per tile of CTG_TILE input bytes
-__global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
+// The tile of block blockIdx.x of a unitig set (useq, uoffs, U, n_ubases) into out[cap]: ubase[u] says where the oriented string
+// of unitig u goes.  Shared by k_ctg_emit and k_scf_emit (scaffold_kernels.h).
+__device__ __forceinline__ void ctg_emit_tile(const unsigned char *useq, const u64 *uoffs, u64 U, u64 n_ubases, const u64 *ubase, u64 later_skip, unsigned char *out, u64 cap)
 {
 	__shared__ __align__(16) unsigned char s_in[CTG_TILE + 16];    // (a word is read behind the last byte)
 	__shared__ u64 s_off[CTG_NB + 1];
@@ -327,18 +330,18 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 	__shared__ u64 s_u0;
 	__shared__ u32 s_nseg;
 	const u32 tid = threadIdx.x;
-	const u64 t0 = (u64)blockIdx.x * CTG_TILE, t1 = ctg_min(t0 + CTG_TILE, D.n_ubases);
+	const u64 t0 = (u64)blockIdx.x * CTG_TILE, t1 = ctg_min(t0 + CTG_TILE, n_ubases);
 	{
 		const u64 p = t0 + (u64)tid * 16;
-		if (((size_t)D.useq & 15) == 0 && p + 16 <= D.n_ubases) *(uint4 *)(s_in + tid * 16) = *(const uint4 *)(D.useq + p);
+		if (((size_t)useq & 15) == 0 && p + 16 <= n_ubases) *(uint4 *)(s_in + tid * 16) = *(const uint4 *)(useq + p);
 		else
-			for (u32 b = 0; b < 16; b++) s_in[tid * 16 + b] = p + b < D.n_ubases ? D.useq[p + b] : (unsigned char)0;
+			for (u32 b = 0; b < 16; b++) s_in[tid * 16 + b] = p + b < n_ubases ? useq[p + b] : (unsigned char)0;
 	}
 	if (tid == 0) {                                              // the tile's first unitig: the last one that starts at or in front of t0
-		u64 lo = 0, hi = D.U;
+		u64 lo = 0, hi = U;
 		while (lo < hi) {
 			const u64 mid = (lo + hi) >> 1;
-			if (ctg_min(D.uoffs[mid], D.n_ubases) <= t0) lo = mid + 1; else hi = mid;
+			if (ctg_min(uoffs[mid], n_ubases) <= t0) lo = mid + 1; else hi = mid;
 		}
 		s_u0 = lo ? lo - 1 : 0;
 		s_nseg = 0;
@@ -346,11 +349,11 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 	__syncthreads();
 	const u64 u0 = s_u0;
 	for (u32 i = tid; i <= CTG_NB; i += 256) {
-		const u64 u = u0 + i, off = u <= D.U ? ctg_min(D.uoffs[u], D.n_ubases) : D.n_ubases;
+		const u64 u = u0 + i, off = u <= U ? ctg_min(uoffs[u], n_ubases) : n_ubases;
 		s_off[i] = off;
 		if (i < CTG_NB) {
-			s_base[i] = u < D.U ? D.ubase[u] : 0;
-			if (u < D.U && off < t1) atomicMax(&s_nseg, i + 1);
+			s_base[i] = u < U ? ubase[u] : 0;
+			if (u < U && off < t1) atomicMax(&s_nseg, i + 1);
 		}
 	}
 	__syncthreads();
@@ -361,7 +364,7 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 		u64 d0, d1;
 		u32 x0;
 		bool rev;
-		wn[j] = i < nseg && ctg_piece(s_off, s_base, i, t0, t1, D.k, &d0, &d1, &x0, &rev) ? (u32)(((d1 + 15) >> 4) - (d0 >> 4)) : 0;
+		wn[j] = i < nseg && ctg_piece(s_off, s_base, i, t0, t1, later_skip, &d0, &d1, &x0, &rev) ? (u32)(((d1 + 15) >> 4) - (d0 >> 4)) : 0;
 		sum += wn[j];
 	}
 	s_part[tid] = sum;
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 	if (tid == 255) s_pre[CTG_NB] = run;
 	__syncthreads();
 	const u32 total = s_pre[CTG_NB];
-	const bool wide = ((size_t)D.cseq & 15) == 0;
+	const bool wide = ((size_t)out & 15) == 0;
 	for (u32 w = tid; w < total; w += 256) {
 		u32 lo = 0, hi = CTG_NB;                                     // the last piece with s_pre[i] <= w: the one word w belongs to
 		while (lo < hi) {
@@ -388,7 +391,7 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 		u64 d0, d1;
 		u32 x0;
 		bool rev;
-		if (!ctg_piece(s_off, s_base, i, t0, t1, D.k, &d0, &d1, &x0, &rev)) continue;
+		if (!ctg_piece(s_off, s_base, i, t0, t1, later_skip, &d0, &d1, &x0, &rev)) continue;
 		const u64 A = ((d0 >> 4) + (w - s_pre[i])) << 4;
 		u32 word[4];
 		bool full[4];
@@ -411,16 +414,22 @@ __global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
 			}
 			word[g] = rev ? ctg_comp4(v) : v;
 		}
-		if (wide && full[0] && full[1] && full[2] && full[3] && A + 16 <= D.n_ubases) {
-			*(uint4 *)(D.cseq + A) = make_uint4(word[0], word[1], word[2], word[3]);
+		if (wide && full[0] && full[1] && full[2] && full[3] && A + 16 <= cap) {
+			*(uint4 *)(out + A) = make_uint4(word[0], word[1], word[2], word[3]);
 			continue;
 		}
 		for (u32 g = 0; g < 4; g++) {
-			if (wide && full[g] && A + 4 * g + 4 <= D.n_ubases) { *(u32 *)(D.cseq + A + 4 * g) = word[g]; continue; }
+			if (wide && full[g] && A + 4 * g + 4 <= cap) { *(u32 *)(out + A + 4 * g) = word[g]; continue; }
 			for (u32 b = 0; b < 4; b++) {
 				const u64 d = A + 4 * g + b;
-				if (d >= d0 && d < d1 && d < D.n_ubases) D.cseq[d] = (unsigned char)(word[g] >> (8 * b));
+				if (d >= d0 && d < d1 && d < cap) out[d] = (unsigned char)(word[g] >> (8 * b));
 			}
 		}
 	}
+}
+
+// one block per tile of CTG_TILE input bytes
+__global__ __launch_bounds__(256) void k_ctg_emit(CtgDev D)
+{
+	ctg_emit_tile(D.useq, D.uoffs, D.U, D.n_ubases, D.ubase, (u64)(D.k - 1), D.cseq, D.n_ubases);
 }

@@ -1,5 +1,5 @@
 // graph_checks.h -- what the host forms of the graph calls validate before anything runs, and the buffer check of every call
-// that takes more than one buffer.  No HIP: the includer provides fail(code, fmt, ...), TRY, the KMX_* codes, u32 and u64
+// that takes more than one buffer.  No HIP: the includer provides include/kmx.h, fail(code, fmt, ...), TRY, u32 and u64
 // (kmx_api.hip does; so does tests/graph_checks_driver.cpp, which runs these functions on the CPU under the sanitizers).
 #pragma once
 #include <cstdint>
@@ -54,6 +54,16 @@ static int check_link_csr(const uint64_t *link_offsets, const uint32_t *links, u
 			for (u64 f = link_offsets[b1]; f < link_offsets[b1 + 1]; f++) found = found || links[f] == (u32)(a ^ 1);
 			if (!found) return fail(KMX_E_ARG, "the edge %llu -> %u has no mirror %llu -> %llu", (unsigned long long)a, links[e], (unsigned long long)b1, (unsigned long long)(a ^ 1));
 		}
+	return KMX_OK;
+}
+
+// a list of pair links (kmx_unitig_pair_walks leaves it, kmx_unitig_scaffold reads it) is strictly ascending by a << 32 | b
+static int check_pair_list(const kmx_pair_link *plinks, u64 n)
+{
+	if (n && !plinks) return fail(KMX_E_ARG, "null argument");
+	for (u64 i = 1; i < n; i++)
+		if (((u64)plinks[i - 1].a << 32 | plinks[i - 1].b) >= ((u64)plinks[i].a << 32 | plinks[i].b))
+			return fail(KMX_E_ARG, "the list of pair links is not strictly ascending at entry %llu", (unsigned long long)i);
 	return KMX_OK;
 }
 

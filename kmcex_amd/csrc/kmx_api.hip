@@ -406,6 +406,17 @@ struct kmx_model {
 		DevBuf<unsigned long long> d_rcnt;                         // [RES_C_N]
 		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): verdicts, scan and records, links, bytes
 	} res;
+	// kmx_unitig_scaffold* (scaffold_host.h): the work arrays of a call, kept by capacity from call to call
+	struct ScfState {
+		DevBuf<u64> d_best, d_ubase;                               // best per oriented unitig; where a unitig's bytes go
+		DevBuf<u32> d_nk, d_mn, d_flag;                            // d_nk: [2][2 U] the kept count and the smallest kept entry; d_mn: [2][2 U] running minima; d_flag: [1 + t] round t moved
+		DevBuf<unsigned char> d_circ, d_tmp;                       // the cycle flag per unitig; rocPRIM scratch
+		DevBuf<CtgRank> d_rank[2];                                 // [2 U + 2] each: the rank state and its copy, later the marks
+		DevBuf<CtgTot> d_sc;                                       // [U + 1] the scanned marks
+		DevBuf<unsigned long long> d_cnt;                          // [SCF_C_N]
+		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): verdicts, ranking, marks, records, bytes
+		u64 rounds = 0;
+	} scf;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2938,6 +2949,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "contig_host.h"
 #include "resolve_host.h"
 #include "pair_host.h"
+#include "scaffold_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3476,6 +3488,9 @@ extern "C" int kmx_unitig_walk_through(kmx_model *m, const kmx_walk *walks, uint
 extern "C" int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, uint64_t n_unitigs, uint64_t *d_through, kmx_through_stats *stats) { return guarded([&] { return kmx_unitig_walk_through_dev_impl(m, ThroughArgs{d_walks, n_walks, d_steps, n_steps, d_link_offsets, d_links, n_links, n_unitigs, d_through, stats}); }); }
 extern "C" int kmx_unitig_pair_walks(kmx_model *m, const kmx_walk *walks, uint64_t n_walks, const uint64_t *walk_offsets, uint64_t n_seqs, const uint32_t *steps, uint64_t n_steps, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *pairs, uint64_t *hist, uint64_t *pair_hits, kmx_pair_link *plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_impl(m, PairArgs{walks, n_walks, walk_offsets, n_seqs, steps, n_steps, link_offsets, links, n_links, params, pairs, hist, pair_hits, plinks, capacity, n_plinks, stats}); }); }
 extern "C" int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_walks, const uint64_t *d_walk_offsets, uint64_t n_seqs, const uint32_t *d_steps, uint64_t n_steps, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_pair_params *params, kmx_pair *d_pairs, uint64_t *d_hist, uint64_t *d_pair_hits, kmx_pair_link *d_plinks, uint64_t capacity, uint64_t *n_plinks, kmx_pair_stats *stats) { return guarded([&] { return kmx_unitig_pair_walks_dev_impl(m, PairArgs{d_walks, n_walks, d_walk_offsets, n_seqs, d_steps, n_steps, d_link_offsets, d_links, n_links, params, d_pairs, d_hist, d_pair_hits, d_plinks, capacity, n_plinks, stats}); }); }
+extern "C" int kmx_unitig_scaffold(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_scaffold_params *params, char *sseq, uint64_t seq_capacity, uint64_t *soffsets, kmx_scaffold *srec, kmx_scaffold_step *steps, kmx_scaffold_place *place, uint64_t *n_scaffolds, uint64_t *n_sbases, kmx_scaffold_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_impl(m, ScfArgs{k, useq, uoffsets, n_unitigs, 0, urec, plinks, n_plinks, params, sseq, seq_capacity, soffsets, srec, steps, place, n_scaffolds, n_sbases, stats}); }); }
+extern "C" int kmx_unitig_scaffold_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_scaffold_params *params, char *d_sseq, uint64_t seq_capacity, uint64_t *d_soffsets, kmx_scaffold *d_srec, kmx_scaffold_step *d_steps, kmx_scaffold_place *d_place, uint64_t *n_scaffolds, uint64_t *n_sbases, kmx_scaffold_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_dev_impl(m, ScfArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_plinks, n_plinks, params, d_sseq, seq_capacity, d_soffsets, d_srec, d_steps, d_place, n_scaffolds, n_sbases, stats}); }); }
+extern "C" int kmx_unitig_scaffold_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_scaffold_last_phases_impl(m, seconds, rounds); }); }
 extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, ResArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, ResArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }

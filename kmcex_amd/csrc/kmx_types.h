@@ -587,6 +587,51 @@ struct PairDev {
 	u64 *sc;
 	PairLink *mrg;
 };
+// kmx_unitig_scaffold*: a scaffold, a step and a unitig's place, the layouts of kmx_scaffold, kmx_scaffold_step and
+// kmx_scaffold_place (include/kmx.h; scaffold_host.h asserts them) ...
+struct Scaffold {
+	u64 n_bases, n_kmers, sum_count;
+	u32 min_count, max_count;
+	u32 first_step, n_steps;     // n_steps | SCF_CIRCULAR
+	u64 n_gap_bases, min_pairs, sum_pairs;
+};
+struct ScfStep {
+	u32 o, n_gap;
+	long long est;
+};
+struct ScfPlace {
+	u32 os, step;
+	u64 off;
+};
+static constexpr u32 SCF_CIRCULAR = 0x80000000u;
+// ... the counters of a call, the first six per entry of the list ...
+enum { SCF_C_LINKS = 0, SCF_C_IGNORED, SCF_C_BELOW_MIN, SCF_C_BELOW_RATIO, SCF_C_KEPT, SCF_C_CHAIN, SCF_C_CIRCULAR, SCF_C_MULTI, SCF_C_N };
+// ... and the input, the work arrays and the output of one call (scaffold_kernels.h).  The rank state is the contigs' CtgRank, its
+// second rank in bytes, and the marks are their CtgTot.  Every array of the caller is read and written under the bounds given
+// here: U, n_ubases, n_plinks, seq_cap.
+struct ScfDev {
+	int k;
+	u64 U, n_ubases, n_plinks;
+	const unsigned char *useq;   // [n_ubases]
+	const u64 *uoffs;            // [U + 1]
+	const Unitig *urec;          // [U] or null
+	const PairLink *plinks;      // [n_plinks]
+	u64 min_pairs;
+	u32 ratio, inner, min_n, max_n;
+	u64 *best;                   // [2 U]
+	u32 *nk;                     // [2 U]: the kept edges out of o
+	u32 *only;                   // [2 U]: the smallest entry that gives a kept edge out of o, all ones for none
+	unsigned char *circ;         // [U]: the unitig lies on a cycle of chain links
+	CtgTot *sc;                  // [U + 1]: the scanned marks
+	u64 *ubase;                  // [U]: where the oriented string of u starts in sseq | CTG_REV
+	unsigned long long *cnt;     // [SCF_C_N]
+	unsigned char *sseq;         // [seq_cap] or null
+	u64 seq_cap;
+	u64 *soffs;                  // [U + 1]
+	Scaffold *srec;              // [U]
+	ScfStep *steps;              // [U]
+	ScfPlace *place;             // [U]
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

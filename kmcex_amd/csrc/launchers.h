@@ -109,4 +109,11 @@ hipError_t resolve_scan(const ResDev &, const CtgTot *, DevBuf<unsigned char> &t
 void resolve_records(const ResDev &, hipStream_t);
 void resolve_links(const ResDev &, hipStream_t);
 void resolve_bytes(const ResDev &, hipStream_t);
+// ... and kmx_unitig_scaffold* (scaffold_kernels.h): bests, verdicts and the rank state (the rounds are contig_round's); the cut;
+// marks + scan (the totals land in D.sc[D.U]); steps, places and records; the N fill and the bytes
+hipError_t scaffold_links(const ScfDev &, CtgRank *, u32 *, hipStream_t);
+void scaffold_cut(const ScfDev &, const CtgRank *, const u32 *, CtgRank *, hipStream_t);
+hipError_t scaffold_mark(const ScfDev &, const CtgRank *, CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);
+void scaffold_place(const ScfDev &, const CtgRank *, hipStream_t);
+hipError_t scaffold_bytes(const ScfDev &, u64 n_sbases, hipStream_t);
 }   // namespace kmxk

@@ -119,9 +119,7 @@ static int kmx_unitig_pair_walks_impl(kmx_model *m, const PairArgs &A)
 	TRY(check_offsets(A.wo, A.n_seqs));
 	if (A.wo[A.n_seqs] != A.n_walks) return fail(KMX_E_ARG, "walk_offsets end at %llu, not at n_walks = %llu", (unsigned long long)A.wo[A.n_seqs], (unsigned long long)A.n_walks);
 	TRY(check_link_csr(A.loffs, A.links, A.n_links, U, false));
-	for (u64 i = 1; i < n_in; i++)
-		if (((u64)A.plinks[i - 1].a << 32 | A.plinks[i - 1].b) >= ((u64)A.plinks[i].a << 32 | A.plinks[i].b))
-			return fail(KMX_E_ARG, "the list of pair links is not strictly ascending at entry %llu", (unsigned long long)i);
+	TRY(check_pair_list(A.plinks, n_in));
 	HIPCHK(hipSetDevice(m->device));
 	Staging G(m, kMapWhat);
 	PairDev D = pair_dev_of(A);

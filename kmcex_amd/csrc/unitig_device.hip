@@ -3,7 +3,8 @@
 // search the same listing through the same bucket index, and the launcher of walk_kernels.h (kmx_unitig_walk_segs*); their host side is map_host.h.
 // Then the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.  Last the launcher of
 // resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
-// (kmx_unitig_pair_walks*); its host side is pair_host.h.
+// (kmx_unitig_pair_walks*); its host side is pair_host.h.  Last the launchers of scaffold_kernels.h (kmx_unitig_scaffold*); their
+// host side is scaffold_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -12,6 +13,7 @@
 #include "contig_kernels.h"
 #include "resolve_kernels.h"
 #include "pair_kernels.h"
+#include "scaffold_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -300,6 +302,55 @@ hipError_t pair_walks(const PairDev &D, DevBuf<unsigned char> &tmp, hipStream_t 
 	hipLaunchKernelGGL(k_pair_fold, dim3(nblk(D.n_items)), dim3(256), 0, st, D);
 	const u64 n_store = D.n_items < D.cap ? D.n_items : D.cap;
 	if (n_store) hipLaunchKernelGGL(k_pair_store, dim3(nblk(n_store)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_scaffold* (scaffold_kernels.h); D.U > 0.  D.cnt and D.circ are zero before scaffold_links.
+
+// bests, verdicts with the five entry counters, the chain link in of every oriented unitig -> the rank state.  The rounds are
+// contig_round's.
+hipError_t scaffold_links(const ScfDev &D, CtgRank *rank, u32 *mn, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.best, 0, 2 * D.U * 8, st));
+	RCHK(hipMemsetAsync(D.nk, 0, 2 * D.U * 4, st));
+	RCHK(hipMemsetAsync(D.only, 0xFF, 2 * D.U * 4, st));
+	if (D.n_plinks) {
+		hipLaunchKernelGGL(k_scf_best, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+		hipLaunchKernelGGL(k_scf_keep, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	}
+	hipLaunchKernelGGL(k_scf_init, dim3(nblk(2 * D.U)), dim3(256), 0, st, D, rank, mn);
+	return hipGetLastError();
+}
+
+void scaffold_cut(const ScfDev &D, const CtgRank *pin, const u32 *mnin, CtgRank *pout, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_scf_cut, dim3(nblk(2 * D.U)), dim3(256), 0, st, D, pin, mnin, pout);
+}
+
+// marks into tot[U + 1], then their exclusive scan into D.sc: D.sc[u] = (scaffolds, bytes, steps) in front of unitig u
+hipError_t scaffold_mark(const ScfDev &D, const CtgRank *rank, CtgTot *tot, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_scf_mark, dim3(nblk(D.U + 1)), dim3(256), 0, st, D, rank, tot);
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const CtgTot *)tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const CtgTot *)tot, D.sc, CtgTot{0, 0, 0}, (size_t)(D.U + 1), CtgPlus(), st));
+	return hipGetLastError();
+}
+
+// behind the marks: records, steps, places and soffsets
+void scaffold_place(const ScfDev &D, const CtgRank *rank, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_scf_rec_init, dim3(nblk(D.U)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_scf_place, dim3(nblk(D.U + 1)), dim3(256), 0, st, D, rank);
+}
+
+// the bytes, n_sbases <= D.seq_cap of them: 'N' everywhere, then one block per tile of the flat input (D.ubase as scaffold_place
+// left it)
+hipError_t scaffold_bytes(const ScfDev &D, u64 n_sbases, hipStream_t st)
+{
+	if (n_sbases) RCHK(hipMemsetAsync(D.sseq, 'N', n_sbases, st));
+	if (D.n_ubases) hipLaunchKernelGGL(k_scf_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
