@@ -37,6 +37,12 @@
 //          offset, N in front, estimate) and scaffolds.agp (AGP 2.1).  Without -X it scaffolds the unitigs from pairs.links.tsv's
 //          list; with -X it reads the input a third time, maps the pairs onto the contigs with the contig graph and scaffolds the
 //          contigs ("unitig" in the two tables is then the contig).  Not with -R: a resolved set is no set to map onto
+//     -T[<tol>[,<max_steps>]]  with -M -W -P -X -R: after the last batch, find for every pair link the one path of the graph between
+//          its two unitigs whose windows fit the insert size within tol (k when omitted) in at most max_steps (8) unitigs
+//          (KModel::pair_paths; links of at least -R's min_reads pairs, inner as -S takes it, at most 4096 prefixes per link) and
+//          add the pairs of every such path to the reads through its unitigs and across its edges before -R and -X judge them,
+//          so that repeats longer than a read and shorter than a fragment no longer end the contigs: pairs.paths.tsv (entry, a,
+//          b, pairs, verdict, windows, steps)
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -62,6 +68,7 @@ struct Params {
 	long pair_dist = -2;                                           // -P: max_dist, -1 = 1000, -2 = no pairs
 	long long scaf_min = -1;                                       // -S: min_pairs, -1 = no scaffolds
 	long scaf_ratio = 0;                                           // -S<min_pairs>,<ratio>
+	long path_tol = -2, path_steps = 8;                            // -T[<tol>[,<max_steps>]]: tol, -1 = k, -2 = no pair paths
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -121,6 +128,20 @@ static bool parse(int argc, char **argv, Params &p)
 			}
 			if (*end) return false;
 		}
+		else if (!strncmp(a, "-T", 2)) {
+			char *end = nullptr;
+			p.path_tol = -1;
+			if (a[2]) {
+				p.path_tol = strtol(a + 2, &end, 10);
+				if (end == a + 2 || p.path_tol < 0 || p.path_tol > 0xFFFFFFFFL) return false;   // not a number of windows
+				if (*end == ',') {
+					const char *r = end + 1;
+					p.path_steps = strtol(r, &end, 10);
+					if (end == r || p.path_steps < 1 || p.path_steps > KMX_PATH_MAX_STEPS) return false;
+				}
+				if (*end) return false;
+			}
+		}
 		else if (!strncmp(a, "-P", 2)) {
 			char *end = nullptr;
 			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
@@ -164,6 +185,10 @@ static bool parse(int argc, char **argv, Params &p)
 	}
 	if (p.scaf_min >= 0 && p.res_min >= 0) {
 		std::cout << "-S does not go with -R: the pairs are mapped onto what is scaffolded, and a resolved set, where a k-mer lies on several copies, is no set to map onto\n";
+		return false;
+	}
+	if (p.path_tol > -2 && (p.pair_dist == -2 || p.res_min < 0)) {  // the paths are found for the pair links and credited to what -R reads
+		std::cout << "-T needs -M -W -P -X -R: the paths are found for the links the pairs leave, and their pairs are added to what the repeats are resolved from\n";
 		return false;
 	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
@@ -261,7 +286,9 @@ int main(int argc, char **argv)
 		             "           pairs per edge count as reads\n"
 		             "       -S<min_pairs>[,<ratio>]  with -M -W -P, not with -R: join the unitigs (with -X: the contigs, from a second mapping of the\n"
 		             "           pairs onto them) along the links at least min_pairs pairs support, with runs of N sized from the insert size:\n"
-		             "           scaffolds.fa, scaffolds.paths.tsv (scaffold, step, unitig, strand, offset, N in front, estimate), scaffolds.agp\n";
+		             "           scaffolds.fa, scaffolds.paths.tsv (scaffold, step, unitig, strand, offset, N in front, estimate), scaffolds.agp\n"
+		             "       -T[<tol>[,<max_steps>]]  with -M -W -P -X -R: find the one graph path every pair link stands for (windows within tol (k) of\n"
+		             "           the insert size, at most max_steps (8) unitigs) and count its pairs as reads through its unitigs: pairs.paths.tsv\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -398,6 +425,17 @@ int main(int argc, char **argv)
 					          << (frags.empty() ? 0 : frags[frags.size() / 2]) << "), " << pt.n_link << " links (" << pt.n_adjacent << " adjacent, " << plinks.size() << " distinct), " << pt.n_far << " far, "
 					          << pt.n_inverted << " inverted, " << pt.n_single << " single, " << pt.n_none << " unplaced" << std::endl;
 					for (size_t e = 0; e < link_hits.size() && e < pair_hits.size(); e++) link_hits[e] += pair_hits[e];   // what -X and -R judge the edges by
+				}
+				if (p.path_tol > -2) {                                      // the pairs that span a repeat, credited along the one path that fits
+					const kmx_pair_path_params tp = {(uint64_t)p.res_min, inner.inner(), (uint32_t)(p.path_tol >= 0 ? p.path_tol : p.k), (uint32_t)p.path_steps, 4096, 0};
+					const KModel::PairPaths pa = km->pair_paths(strs, link_offsets, links, plinks, p.k, tp, &through, &link_hits);
+					std::ofstream pf((dir + "/pairs.paths.tsv").c_str());
+					KModel::write_pair_paths_tsv(pf, plinks, pa);
+					pf.close();
+					if (!pf) { std::cout << "could not write " << dir << "/pairs.paths.tsv" << std::endl; return 1; }
+					std::cout << "   pair paths (tol " << tp.tol << ", <= " << tp.max_steps << " steps, inner " << tp.inner << ") :     " << pa.stats.n_path << " of " << pa.stats.n_entries << " links are one path ("
+					          << pa.stats.n_adjacent << " adjacent, " << pa.stats.n_no_path << " none, " << pa.stats.n_ambiguous << " ambiguous, " << pa.stats.n_complex << " complex, " << pa.stats.n_below_min
+					          << " below " << tp.min_pairs << " pairs, " << pa.stats.n_ignored << " ignored), " << pa.stats.n_added << " unitigs credited" << std::endl;
 				}
 				if (p.scaf_min >= 0 && p.min_reads < 0 && !write_scaffolds(km, dir, strs, &rec, plinks, p, inner.inner(), pp.max_dist, "unitigs")) return 1;
 				if (p.min_reads >= 0) {

@@ -728,6 +728,56 @@ public:
 		}
 	}
 
+	// Pair paths (the rule: kmx.h): for every entry of the list seq_pairs left, the one path of the unitig graph between its two
+	// ends whose windows fit the insert size.  pair_paths takes the unitig strings (only their lengths are used), the CSR and the
+	// list; through (16 per unitig) and path_hits (one per link) are ADDED to, so the arrays unitig_through and seq_walks filled can
+	// be passed as they are; an empty or shorter vector is grown with zeros first.  It needs no session, and it gives the steps
+	// room for every entry, so it never comes back short.
+	struct PairPaths {
+		std::vector<kmx_pair_path> rec;              // one per entry of the list
+		std::vector<uint32_t> steps;                 // the intermediates of the PATH entries, back to back
+		kmx_pair_path_stats stats;
+	};
+	PairPaths pair_paths(const std::vector<std::string> &unitigs, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links, const std::vector<kmx_pair_link> &plinks, int k,
+	                     const kmx_pair_path_params &params, std::vector<uint64_t> *through = 0, std::vector<uint64_t> *path_hits = 0)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), np = plinks.size(), nl = links.size();
+		if (link_offsets.size() != 2 * U + 1) { std::cout << "pair_paths: the vectors are not those of one graph" << std::endl; exit(1); }
+		if (through && through->size() < 16 * U) through->resize(16 * U, 0);
+		if (path_hits && path_hits->size() < nl) path_hits->resize(nl, 0);
+		PairPaths p;
+		p.stats = kmx_pair_path_stats();
+		p.rec.resize(np + 1);
+		const uint64_t cap = (uint64_t)np * params.max_steps;
+		p.steps.resize((size_t)cap + 1);
+		uint64_t n = 0;
+		check(kmx_unitig_pair_paths(h_, k, f.off.data(), U, &link_offsets[0], nl ? &links[0] : 0, nl, np ? &plinks[0] : 0, np, &params, &p.rec[0], &p.steps[0], cap, &n,
+		                            through && U ? &(*through)[0] : 0, path_hits && nl ? &(*path_hits)[0] : 0, &p.stats));
+		p.rec.resize(np);
+		p.steps.resize((size_t)n);
+		return p;
+	}
+	// the pair paths as a table, one "<entry>\tu<a><+|->\tu<b><+|->\t<pairs>\t<verdict>\t<windows>\t<steps>" per entry of the list: the
+	// steps of a PATH with the orientation signs of reads.gaf (">u3<u5"), "*" for every other verdict
+	static void write_pair_paths_tsv(std::ostream &out, const std::vector<kmx_pair_link> &plinks, const PairPaths &p)
+	{
+		static const char *const names[] = {"IGNORED", "BELOW_MIN", "NO_PATH", "ADJACENT", "PATH", "AMBIGUOUS", "COMPLEX"};
+		for (size_t i = 0; i < plinks.size() && i < p.rec.size(); i++) {
+			const kmx_pair_link &e = plinks[i];
+			const kmx_pair_path &r = p.rec[i];
+			out << i << "\tu" << (e.a >> 1) << ((e.a & 1) ? '-' : '+') << "\tu" << (e.b >> 1) << ((e.b & 1) ? '-' : '+') << "\t" << e.n_pairs << "\t" << (r.verdict <= KMX_PATH_COMPLEX ? names[r.verdict] : "?")
+			    << "\t" << r.windows << "\t";
+			uint64_t n = 0;
+			if (r.verdict == KMX_PATH_PATH)
+				for (uint64_t j = 0; j < r.n_steps && r.first_step + j < p.steps.size(); j++, n++) {
+					const uint32_t o = p.steps[(size_t)(r.first_step + j)];
+					out << ((o & 1) ? '<' : '>') << "u" << (o >> 1);
+				}
+			out << (n ? "\n" : "*\n");
+		}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

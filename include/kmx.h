@@ -1021,7 +1021,7 @@ int kmx_unitig_contigs_last_phases(kmx_model *m, double *seconds /* [5] */, uint
  *       link_hits[mir(e)] for e = entry a of L (both terms also where mir(e) = e: a hairpin join is the way in of one step and
  *       the way out of the step before, in the same row); the same holds for the columns and R;
  *   (d) a circular unitig gone round twice adds to cell (0, 0) of itself.
- * Out of scope: evidence from paired reads; several GPUs.                                                                   */
+ * Out of scope: several GPUs.  Evidence from paired reads is added to the same array by kmx_unitig_pair_paths below.         */
 typedef struct kmx_through_stats { uint64_t n_walks, n_steps, n_interior, n_added, n_missing, reserved[3]; } kmx_through_stats;   /* 64 bytes */
 /* On HOST buffers.  Needs no built model and no session (like kmx_unitig_contigs); it runs on the model's stream and is a
  * build-class call.  stats is required; every buffer of a non-zero count is required, link_offsets always.  KMX_E_ARG before
@@ -1070,7 +1070,8 @@ int kmx_unitig_walk_through_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t 
  *   (c) a k-mer of a resolved unitig now appears p times, so the output is NOT a valid set for kmx_unitig_map_begin (it refuses
  *       with KMX_E_ARG); through hits for a second round therefore cannot be had;
  *   (d) everything is an integer count and a function of the input alone, byte-identical across runs and variants.
- * Out of scope: iterating; p != q; repeats with a self edge; evidence from paired reads; choosing min_reads.                  */
+ * Out of scope: iterating; p != q; repeats with a self edge; choosing min_reads.  Evidence from paired reads reaches this
+ * call through the cells kmx_unitig_pair_paths below adds to.                                                               */
 typedef struct kmx_resolve_params { uint64_t min_reads, max_cross; } kmx_resolve_params;                                 /* 16 bytes */
 typedef struct kmx_resolve_place { uint32_t first, n_copies; } kmx_resolve_place;                                        /* 8 bytes */
 typedef struct kmx_resolve_stats { uint64_t n_candidates, n_resolved, n_crossed, n_unsupported, n_ambiguous, n_copies_added, n_unitigs_out, reserved; } kmx_resolve_stats;   /* 64 bytes */
@@ -1290,6 +1291,102 @@ int kmx_unitig_scaffold_dev(kmx_model *m, int k, const char *d_useq, const uint6
  * waits for the stream): seconds[5] = verdicts, ranking (links, rounds, cut), marks and their scan, records with steps and
  * places, the bytes; *rounds = its doubling rounds (counted always)                                                          */
 int kmx_unitig_scaffold_last_phases(kmx_model *m, double *seconds /* [5] */, uint64_t *rounds);
+
+/* ---- pair paths: for every entry of a pair list, the unique path of the unitig graph between its two ends whose length fits
+ * the library's insert size.  A repeat longer than a read but shorter than the fragment between the mates is crossed by no read,
+ * so kmx_unitig_walk_through leaves its cells at 0; the pairs that span it are entries of the list kmx_unitig_pair_walks leaves.
+ * This call finds the one graph path such an entry stands for and credits that path's interior unitigs (in the layout of
+ * through) and edges (in the layout of link_hits), so that kmx_unitig_resolve and kmx_unitig_contigs consume it unchanged.  It
+ * needs no model, no session and no bases.
+ * Input: k, odd, in [5, 63]; uoffsets[U + 1] of the unitig set, U < 2^31, with m_u = max(len_u - (k - 1), 0) the windows of
+ *   unitig u; the CSR (link_offsets[2 U + 1], links[n_links]; row(o) is the row of oriented unitig o): at most 4 entries of a row
+ *   are read, and an entry >= 2 U is skipped, neither matched nor extended; plinks[n_plinks] as kmx_unitig_pair_walks leaves it,
+ *   n_plinks < 2^31; and kmx_pair_path_params: max_steps in [1, KMX_PATH_MAX_STEPS], max_visits in [1, 65536], reserved = 0.
+ * Entry i = (a, b, n_pairs, sum_dist, ...), all arithmetic in signed 64 bits (two's complement, wrapping):
+ *   KMX_PATH_IGNORED    unless a < 2 U, b < 2 U, a >> 1 != b >> 1 and n_pairs >= 1: the scaffold call's pair link;
+ *   KMX_PATH_BELOW_MIN  otherwise, if n_pairs < min_pairs.
+ *   Otherwise D = sum_dist / n_pairs (unsigned floor division), g = inner - 1 - D (the g of kmx_unitig_scaffold: the windows
+ *   missing between a and b), lo = g - tol, hi = g + tol.  hi < 0: KMX_PATH_NO_PATH with n_visited = 0.
+ *   A PREFIX is a sequence v_1 .. v_t with 0 <= t <= max_steps, v_1 an entry of row(a), v_(j+1) an entry of row(v_j), and
+ *     W = the sum of m_(v_j >> 1) <= hi.  The empty prefix is one; every row position gives a prefix of its own (an edge listed
+ *     twice gives two); intermediates may repeat and may equal a or b.
+ *   A prefix is a HIT iff b is among the read entries of row(v_t) (row(a) for t = 0) and W >= lo; a prefix is at most one hit.
+ *   n_prefix = the number of prefixes, n_visited = min(n_prefix, max_visits + 1).  The verdict, in this order:
+ *   KMX_PATH_COMPLEX    n_prefix > max_visits; n_hits is then 0 and nothing else is reported;
+ *   KMX_PATH_NO_PATH    n_hits = 0;
+ *   KMX_PATH_AMBIGUOUS  n_hits >= 2;
+ *   KMX_PATH_ADJACENT   one hit with t = 0: kmx_unitig_pair_walks has counted it in pair_hits, nothing is added here;
+ *   KMX_PATH_PATH       one hit with t >= 1.
+ *   The definition counts sets, so no search order shows; a search that stops once its counter has passed max_visits gives the
+ *   same verdict.
+ * Effects of a PATH with steps v_1 .. v_t, v_0 = a and v_(t+1) = b.  For 1 <= j <= t, with x = v_j, P = v_(j-1), N = v_(j+1):
+ *   the cell is exactly that of kmx_unitig_walk_through (i_in the first match of P ^ 1 in row(x ^ 1), i_out that of N in row(x),
+ *   swapped for odd x) and through[16 (x >> 1) + 4 a + b] += n_pairs; an index not found is counted in n_missing and adds
+ *   nothing, every other one in n_added.  For 0 <= j <= t: path_hits[e] += n_pairs for e the first entry equal to v_(j+1) in
+ *   row(v_j): the traversed direction only, like link_hits.
+ * Output.  precs[n_plinks], the records below: n_steps = t, windows = W and first_step of the hit are set for PATH and ADJACENT
+ *   and are 0 otherwise; first_step is the number of steps of the PATH entries in front of the entry.  psteps[capacity]: the
+ *   intermediates of the PATH entries, back to back in entry order, with *n_psteps (HOST in both forms) their number.
+ *   through[16 U] and path_hits[n_links] are ADDED to; either may be NULL (n_added and n_missing are counted all the same).
+ *   stats is required and on the HOST in both forms.  More steps than capacity: KMX_E_RANGE with *n_psteps the number needed
+ *   and records, stats, through and path_hits complete, so a caller that repeats the call passes those two as NULL: the
+ *   convention of kmx_unitig_pair_walks.  n_plinks * max_steps always suffices.  psteps == NULL: no list is built and n_psteps
+ *   may be NULL (where it is given it is set).
+ * Consequences:
+ *   (a) n_ignored + n_below_min + n_no_path + n_adjacent + n_path + n_ambiguous + n_complex == n_entries; the n_steps of the PATH
+ *       entries sum to *n_psteps = n_added + n_missing;
+ *   (b) with a mirrored CSR and no COMPLEX in either direction, replacing an entry by its mirror (b ^ 1, a ^ 1) leaves verdict,
+ *       n_hits and windows as they are, gives the steps reversed and flipped (v_t ^ 1 .. v_1 ^ 1), adds to the SAME cells of
+ *       through (as the walk of a read's reverse complement does) and moves every path_hits increment to the mirror edge;
+ *   (c) through summed with the array of kmx_unitig_walk_through feeds kmx_unitig_resolve unchanged, and path_hits summed with
+ *       link_hits feeds kmx_unitig_contigs;
+ *   (d) every output is an integer count or sum and a function of the input alone: byte-identical across runs and forms.
+ * Out of scope: meeting in the middle; choosing among several paths, by coverage or by fit; spelling the path's bases into the
+ * gaps of kmx_unitig_scaffold (a scaffold link is such an entry); a search per pair instead of per entry; RF and FF libraries;
+ * several GPUs; choosing tol and inner.                                                                                      */
+#define KMX_PATH_IGNORED   0
+#define KMX_PATH_BELOW_MIN 1
+#define KMX_PATH_NO_PATH   2
+#define KMX_PATH_ADJACENT  3
+#define KMX_PATH_PATH      4
+#define KMX_PATH_AMBIGUOUS 5
+#define KMX_PATH_COMPLEX   6
+#define KMX_PATH_MAX_STEPS 16
+typedef struct kmx_pair_path_params { uint64_t min_pairs; uint32_t inner, tol, max_steps /* [1, KMX_PATH_MAX_STEPS] */, max_visits /* [1, 65536] */;
+                                      uint64_t reserved /* 0 */; } kmx_pair_path_params;                                /* 32 bytes */
+typedef struct kmx_pair_path {           /* one per entry of the list; 32 bytes, no padding */
+	uint32_t verdict;                    /* KMX_PATH_* */
+	uint32_t n_steps;                    /* t of the hit */
+	uint64_t first_step;                 /* its steps are psteps[first_step .. first_step + n_steps) */
+	uint64_t windows;                    /* W of the hit */
+	uint32_t n_hits, n_visited;
+} kmx_pair_path;
+typedef struct kmx_pair_path_stats { uint64_t n_entries, n_ignored, n_below_min, n_no_path, n_adjacent, n_path, n_ambiguous, n_complex, n_added, n_missing; } kmx_pair_path_stats;   /* 80 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_unitig_scaffold); it runs on the model's stream and is a
+ * build-class call.  psteps, through and path_hits may be NULL, links with n_links == 0, plinks and precs with n_plinks == 0;
+ * every other buffer is required.  KMX_E_ARG before anything runs: an even or out-of-range k, U >= 2^31, n_plinks >= 2^31,
+ * max_steps or max_visits out of range, reserved != 0, a NULL required buffer, an output that overlaps an input or another
+ * output; uoffsets whose first entry is not 0, that decrease, or that give a unitig fewer than k bytes; a CSR that
+ * kmx_unitig_walk_segs would refuse; a list that is not strictly ascending by a << 32 | b.  n_plinks == 0: KMX_OK, all-zero
+ * stats.  U == 0: KMX_OK, every entry is IGNORED.  KMX_E_NOMEM leaves the handle usable.                                      */
+int kmx_unitig_pair_paths(kmx_model *m, int k, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const uint64_t *link_offsets /* [2 U + 1] */, const uint32_t *links,
+                          uint64_t n_links, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_path_params *params, kmx_pair_path *precs /* [n_plinks] */,
+                          uint32_t *psteps /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_psteps, uint64_t *through /* [16 U] or NULL */, uint64_t *path_hits /* [n_links] or NULL */,
+                          kmx_pair_path_stats *stats);
+/* The same on DEVICE buffers, read where the graph and pair calls left them; params, *n_psteps and stats are on the HOST.  It
+ * checks k, U, n_plinks, the parameters, NULL and overlap, and validates nothing else; the kernels clamp instead: row bounds into
+ * [0, n_links], at most 4 entries of a row, an entry >= 2 U skipped, a unitig whose offsets decrease or that is shorter than k
+ * has m_u = 0, and the list is taken as it is.  Every store is checked against its capacity: bad device input gives wrong paths
+ * and never an access outside a buffer.  No entry costs more than max_visits + 1 visits.  It enqueues everything on the model's
+ * stream and waits once, for *n_psteps and the stats; the steps are stored only where they fit.  Device memory, kept on the
+ * handle between calls through the owning types of hip_owned.h: 4 max_steps + 8 bytes per entry plus the scan's scratch.  The
+ * host form also stages its input and output there.                                                                         */
+int kmx_unitig_pair_paths_dev(kmx_model *m, int k, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const uint64_t *d_link_offsets /* [2 U + 1] */,
+                              const uint32_t *d_links, uint64_t n_links, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_path_params *params /* HOST */,
+                              kmx_pair_path *d_precs /* [n_plinks] */, uint32_t *d_psteps /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_psteps /* HOST */,
+                              uint64_t *d_through /* [16 U] or NULL */, uint64_t *d_path_hits /* [n_links] or NULL */, kmx_pair_path_stats *stats /* HOST */);
+/* seconds[3] of the last of these two calls under kmx_set_profile(m, 1): the search, the scan, the additions with the wait */
+int kmx_unitig_pair_paths_last_phases(kmx_model *m, double *seconds /* [3] */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_resolve", "kmx_unitig_resolve_dev", "kmx_unitig_resolve_last_phases",
     "kmx_unitig_pair_walks", "kmx_unitig_pair_walks_dev",
     "kmx_unitig_scaffold", "kmx_unitig_scaffold_dev", "kmx_unitig_scaffold_last_phases",
+    "kmx_unitig_pair_paths", "kmx_unitig_pair_paths_dev", "kmx_unitig_pair_paths_last_phases",
 ]
 
 
@@ -262,6 +263,25 @@ def scaffold_circular(srec) -> np.ndarray:
     return (np.asarray(srec["n_steps"]) >> np.uint32(31)).astype(np.uint8)
 
 
+class PairPathParams(C.Structure):
+    """kmx_pair_path_params of include/kmx.h: 32 bytes"""
+    _fields_ = [("min_pairs", C.c_uint64), ("inner", C.c_uint32), ("tol", C.c_uint32), ("max_steps", C.c_uint32), ("max_visits", C.c_uint32), ("reserved", C.c_uint64)]
+
+
+class PairPathStats(C.Structure):
+    """kmx_pair_path_stats of include/kmx.h: 80 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_entries", "n_ignored", "n_below_min", "n_no_path", "n_adjacent", "n_path", "n_ambiguous", "n_complex", "n_added", "n_missing")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_pair_path as a NumPy structured dtype (what KModel.unitig_pair_paths_flat returns): 32 bytes
+PAIR_PATH_DTYPE = np.dtype([("verdict", "<u4"), ("n_steps", "<u4"), ("first_step", "<u8"), ("windows", "<u8"), ("n_hits", "<u4"), ("n_visited", "<u4")])
+PAIR_PATH_VERDICTS = {0: "IGNORED", 1: "BELOW_MIN", 2: "NO_PATH", 3: "ADJACENT", 4: "PATH", 5: "AMBIGUOUS", 6: "COMPLEX"}
+PAIR_PATH_MAX_STEPS = 16
+
+
 class RingList(C.Structure):
     """kmx_ring_list of include/kmx.h"""
     _fields_ = [("list", C.c_int32), ("n_host", C.c_int32), ("src_kmers", C.c_void_p), ("src_counts", C.c_void_p),
@@ -416,6 +436,9 @@ def load_library():
     _sig(L, "kmx_unitig_scaffold", [vp, C.c_int, vp, vp, u64, vp, vp, u64, C.POINTER(ScaffoldParams), vp, u64, vp, vp, vp, vp, p64, p64, C.POINTER(ScaffoldStats)])
     _sig(L, "kmx_unitig_scaffold_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, u64, C.POINTER(ScaffoldParams), vp, u64, vp, vp, vp, vp, p64, p64, C.POINTER(ScaffoldStats)])
     _sig(L, "kmx_unitig_scaffold_last_phases", [vp, C.POINTER(C.c_double), p64])
+    _sig(L, "kmx_unitig_pair_paths", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
+    _sig(L, "kmx_unitig_pair_paths_dev", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
+    _sig(L, "kmx_unitig_pair_paths_last_phases", [vp, C.POINTER(C.c_double)])
     _sig(L, "kmx_unitig_resolve", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1388,6 +1411,95 @@ class KModel:
         sec, rounds = (C.c_double * 5)(), C.c_uint64(0)
         _chk(self.L.kmx_unitig_scaffold_last_phases(self.h, sec, C.byref(rounds)))
         return dict(zip(("verdicts", "ranking", "marks", "records", "bytes"), (float(x) for x in sec)), rounds=int(rounds.value))
+
+    # ---- pair paths: the graph path every entry of a pair list stands for (the rule: include/kmx.h); no model, no session
+    def unitig_pair_paths_flat(self, k: int, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, plinks: np.ndarray, inner: int, tol: int, min_pairs: int = 2, max_steps: int = 8,
+                               max_visits: int = 4096, through=None, path_hits=None, capacity=None, steps: bool = True):
+        """kmx_unitig_pair_paths on the offsets of a unitig set (uint64 [U + 1]), the CSR of its graph and the PAIR_LINK_DTYPE list
+        unitig_pairs_flat left -> (PAIR_PATH_DTYPE records [n_plinks], uint32 psteps or None, stats as a dict).  through (uint64
+        [16 U]) and path_hits (uint64 [n_links]), both optional, are ADDED to.  capacity None: n_plinks * max_steps, which always
+        suffices; a number: that many steps (KmxError KMX_E_RANGE when short: its `needed` the steps needed, its `result` the
+        records and the stats).  steps False: no list is built."""
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        plinks = np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+        nu = uoffsets.size - 1
+        if link_offsets.size != 2 * nu + 1:
+            raise KmxError(-1, "link_offsets holds 2 U + 1 entries")
+        if through is not None and (through.dtype != np.uint64 or not through.flags.c_contiguous or through.size < 16 * nu):
+            raise KmxError(-1, "through must be a contiguous uint64 array with 16 entries per unitig")
+        if path_hits is not None and (path_hits.dtype != np.uint64 or not path_hits.flags.c_contiguous or path_hits.size < links.size):
+            raise KmxError(-1, "path_hits must be a contiguous uint64 array with one entry per link")
+        cap = plinks.size * int(max_steps) if capacity is None else int(capacity)
+        rec = np.zeros(max(plinks.size, 1), dtype=PAIR_PATH_DTYPE)
+        pst = np.zeros(max(cap, 1), dtype=np.uint32) if steps else None
+        par, st, n = PairPathParams(int(min_pairs), int(inner), int(tol), int(max_steps), int(max_visits), 0), PairPathStats(), C.c_uint64(0)
+        try:
+            _chk(self.L.kmx_unitig_pair_paths(self.h, int(k), uoffsets.ctypes.data, nu, link_offsets.ctypes.data, links.ctypes.data if links.size else None, links.size,
+                                              plinks.ctypes.data if plinks.size else None, plinks.size, C.byref(par), rec.ctypes.data, pst.ctypes.data if steps else None, cap if steps else 0,
+                                              C.byref(n), through.ctypes.data if through is not None else None, path_hits.ctypes.data if path_hits is not None else None, C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            e.result = (rec[:plinks.size].copy(), st.as_dict())
+            raise
+        return rec[:plinks.size].copy(), (pst[:n.value].copy() if steps else None), st.as_dict()
+
+    def unitig_pair_paths_dev(self, k: int, d_uoffsets, d_link_offsets, d_links, d_plinks, n_plinks: int, inner: int, tol: int, min_pairs: int = 2, max_steps: int = 8, max_visits: int = 4096,
+                              d_through=None, d_path_hits=None, capacity=None, out=None):
+        """kmx_unitig_pair_paths_dev on torch tensors of the model's device, read where the graph and pair calls left them:
+        d_uoffsets int64 [U + 1], d_link_offsets int64 [2 U + 1], d_links int32 [n_links], d_plinks uint8 [capacity, 32] holding
+        n_plinks entries; d_through int64 [16 U] and d_path_hits int64 [n_links] or None (added to).  out: (d_precs uint8
+        [n_plinks, 32], d_psteps int32 [capacity] or None for no list), allocated when None with `capacity` steps (None: n_plinks *
+        max_steps) -> (out, the steps the list holds, stats as a dict).  KmxError KMX_E_RANGE carries the steps needed in `needed`."""
+        import torch
+        nu, dev = d_uoffsets.numel() - 1, d_uoffsets.device
+        if out is None:
+            cap = int(n_plinks) * int(max_steps) if capacity is None else int(capacity)
+            out = (torch.zeros((max(int(n_plinks), 1), 32), dtype=torch.uint8, device=dev), torch.zeros(max(cap, 1), dtype=torch.int32, device=dev))
+        else:
+            cap = out[1].numel() if out[1] is not None and capacity is None else int(capacity or 0)
+        par, st, n = PairPathParams(int(min_pairs), int(inner), int(tol), int(max_steps), int(max_visits), 0), PairPathStats(), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            _chk(self.L.kmx_unitig_pair_paths_dev(self.h, int(k), d_uoffsets.data_ptr(), nu, d_link_offsets.data_ptr(), d_links.data_ptr() if d_links.numel() else None, d_links.numel(),
+                                                  ptr(d_plinks) if n_plinks else None, int(n_plinks), C.byref(par), out[0].data_ptr(), ptr(out[1]), cap if out[1] is not None else 0, C.byref(n),
+                                                  ptr(d_through), ptr(d_path_hits), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            raise
+        return out, int(n.value), st.as_dict()
+
+    def unitig_pair_paths_phases(self) -> dict:
+        """kmx_unitig_pair_paths_last_phases: seconds per phase of the last pair path call (under set_profile(1))"""
+        sec = (C.c_double * 3)()
+        _chk(self.L.kmx_unitig_pair_paths_last_phases(self.h, sec))
+        return dict(zip(("search", "scan", "apply"), (float(x) for x in sec)))
+
+    def resolved_contigs_from_pairs(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, reads, max_dist: int, tol=None, max_gap=None,
+                                    max_indel: int = 1, min_reads: int = 2, max_cross: int = 0, contig_min_reads: int = 1, ratio: int = 0, max_steps: int = 8, max_visits: int = 4096,
+                                    pair_paths: bool = True):
+        """inside a map session on these unitigs, on interleaved reads: seq_to_walks (the link hits), unitig_through_flat (the
+        through hits), unitig_pairs_flat (the list, the pair hits and inner: the floor of the mean d of the SAME pairs with frag >= 0), then
+        unitig_pair_paths_flat at min_pairs = min_reads and tol (None: k), whose through and path_hits are added to the walks'
+        arrays, unitig_resolve_flat and unitig_contigs_flat on the resolved graph -> (the contig strings as str, the resolve
+        stats, the pair path stats or None, the pair path records or None).  pair_paths False: the same chain without the new
+        call."""
+        link_offsets = np.ascontiguousarray(link_offsets, dtype=np.uint64)
+        links = np.ascontiguousarray(links, dtype=np.uint32)
+        hits = np.zeros(links.size, dtype=np.uint64)
+        walks, wo, steps, _, _, _ = self.seq_to_walks(reads, link_offsets, links, int(k) if max_gap is None else int(max_gap), max_indel, link_hits=hits)
+        through, _ = self.unitig_through_flat(walks, steps, link_offsets, links)
+        rec, lst, _ = self.unitig_pairs_flat(walks, wo, steps, link_offsets, links, max_dist, pair_hits=hits)
+        pst = prec = None
+        if pair_paths:
+            d = rec["d"][(rec["cls"] == 2) & (rec["frag"] >= 0)]
+            inner = int(d.sum()) // d.size if d.size and int(d.sum()) > 0 else 0
+            prec, _, pst = self.unitig_pair_paths_flat(k, uoffsets, link_offsets, links, lst, inner, int(k) if tol is None else int(tol), min_reads, max_steps, max_visits, through=through,
+                                                       path_hits=hits)
+        r = self.unitig_resolve_flat(k, ubuf, uoffsets, link_offsets, links, through, min_reads, max_cross, link_hits=hits)
+        c = self.unitig_contigs_flat(k, r[0], r[1], r[5], r[6], r[8], contig_min_reads, ratio)
+        return [b.decode("latin-1") for b in _split_seqs(c[0], c[1])], r[9], pst, prec
 
     # ---- contigs: the unitigs merged along the edges the reads support (the rule: include/kmx.h); no model, no session
     def unitig_contigs_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, link_hits: np.ndarray, min_reads: int = 1, ratio: int = 0,

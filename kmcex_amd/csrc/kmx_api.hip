@@ -417,6 +417,14 @@ struct kmx_model {
 		double phase_s[5] = {0, 0, 0, 0, 0};                       // under kmx_set_profile(m, 1): verdicts, ranking, marks, records, bytes
 		u64 rounds = 0;
 	} scf;
+	// kmx_unitig_pair_paths* (pair_path_host.h): the work arrays of a call, kept by capacity from call to call
+	struct PpState {
+		DevBuf<u32> d_work;                                        // [n_plinks][max_steps] the steps of every entry's first hit
+		DevBuf<u64> d_sc;                                          // [n_plinks + 1] the scanned steps of the PATH entries
+		DevBuf<unsigned long long> d_cnt;                          // [PP_C_N]
+		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
+		double phase_s[3] = {0, 0, 0};                             // under kmx_set_profile(m, 1): search, scan, additions
+	} ppath;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2950,6 +2958,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "resolve_host.h"
 #include "pair_host.h"
 #include "scaffold_host.h"
+#include "pair_path_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3491,6 +3500,9 @@ extern "C" int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, 
 extern "C" int kmx_unitig_scaffold(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_scaffold_params *params, char *sseq, uint64_t seq_capacity, uint64_t *soffsets, kmx_scaffold *srec, kmx_scaffold_step *steps, kmx_scaffold_place *place, uint64_t *n_scaffolds, uint64_t *n_sbases, kmx_scaffold_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_impl(m, ScfArgs{k, useq, uoffsets, n_unitigs, 0, urec, plinks, n_plinks, params, sseq, seq_capacity, soffsets, srec, steps, place, n_scaffolds, n_sbases, stats}); }); }
 extern "C" int kmx_unitig_scaffold_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_scaffold_params *params, char *d_sseq, uint64_t seq_capacity, uint64_t *d_soffsets, kmx_scaffold *d_srec, kmx_scaffold_step *d_steps, kmx_scaffold_place *d_place, uint64_t *n_scaffolds, uint64_t *n_sbases, kmx_scaffold_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_dev_impl(m, ScfArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_plinks, n_plinks, params, d_sseq, seq_capacity, d_soffsets, d_srec, d_steps, d_place, n_scaffolds, n_sbases, stats}); }); }
 extern "C" int kmx_unitig_scaffold_last_phases(kmx_model *m, double *seconds, uint64_t *rounds) { return guarded([&] { return kmx_unitig_scaffold_last_phases_impl(m, seconds, rounds); }); }
+extern "C" int kmx_unitig_pair_paths(kmx_model *m, int k, const uint64_t *uoffsets, uint64_t n_unitigs, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_path_params *params, kmx_pair_path *precs, uint32_t *psteps, uint64_t capacity, uint64_t *n_psteps, uint64_t *through, uint64_t *path_hits, kmx_pair_path_stats *stats) { return guarded([&] { return kmx_unitig_pair_paths_impl(m, PathArgs{k, uoffsets, n_unitigs, link_offsets, links, n_links, plinks, n_plinks, params, precs, psteps, capacity, n_psteps, through, path_hits, stats}); }); }
+extern "C" int kmx_unitig_pair_paths_dev(kmx_model *m, int k, const uint64_t *d_uoffsets, uint64_t n_unitigs, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_path_params *params, kmx_pair_path *d_precs, uint32_t *d_psteps, uint64_t capacity, uint64_t *n_psteps, uint64_t *d_through, uint64_t *d_path_hits, kmx_pair_path_stats *stats) { return guarded([&] { return kmx_unitig_pair_paths_dev_impl(m, PathArgs{k, d_uoffsets, n_unitigs, d_link_offsets, d_links, n_links, d_plinks, n_plinks, params, d_precs, d_psteps, capacity, n_psteps, d_through, d_path_hits, stats}); }); }
+extern "C" int kmx_unitig_pair_paths_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_pair_paths_last_phases_impl(m, seconds); }); }
 extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, ResArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, ResArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }

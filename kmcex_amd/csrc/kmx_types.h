@@ -632,6 +632,36 @@ struct ScfDev {
 	ScfStep *steps;              // [U]
 	ScfPlace *place;             // [U]
 };
+// kmx_unitig_pair_paths*: the record of a list entry, the layout of kmx_pair_path (include/kmx.h; pair_path_host.h asserts it) ...
+struct PairPath {
+	u32 verdict, n_steps;
+	u64 first_step, windows;
+	u32 n_hits, n_visited;
+};
+// ... the verdicts (KMX_PATH_* of include/kmx.h), which are also the first seven counters of a call, in the order of
+// kmx_pair_path_stats behind n_entries ...
+enum { PP_IGNORED = 0, PP_BELOW_MIN, PP_NO_PATH, PP_ADJACENT, PP_PATH, PP_AMBIGUOUS, PP_COMPLEX, PP_C_ADDED, PP_C_MISSING, PP_C_N };
+static constexpr u32 PP_MAX_STEPS = 16;                          // KMX_PATH_MAX_STEPS
+// ... and the input, the work arrays and the output of one call (pair_path_kernels.h).  work[n_plinks * max_steps]: the steps of an
+// entry's first hit; sc[n_plinks + 1]: the steps of the PATH entries in front of an entry, sc[n_plinks] their total.  Every array
+// of the caller is read and written under the bounds given here: U, n_links, n_plinks, cap.
+struct PathDev {
+	int k;
+	u64 U, n_links, n_plinks, cap;
+	const u64 *uoffs;            // [U + 1]
+	const u64 *loffs;            // [2 U + 1]
+	const u32 *links;            // [n_links]
+	const PairLink *plinks;      // [n_plinks]
+	u64 min_pairs;
+	u32 inner, tol, max_steps, max_visits;
+	PairPath *precs;             // [n_plinks]
+	u32 *psteps;                 // [cap] or null
+	unsigned long long *through; // [16 U] or null, added to
+	unsigned long long *path_hits;   // [n_links] or null, added to
+	u32 *work;
+	u64 *sc;
+	unsigned long long *cnt;     // [PP_C_N]
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

@@ -116,4 +116,8 @@ void scaffold_cut(const ScfDev &, const CtgRank *, const u32 *, CtgRank *, hipSt
 hipError_t scaffold_mark(const ScfDev &, const CtgRank *, CtgTot *, DevBuf<unsigned char> &tmp, hipStream_t);
 void scaffold_place(const ScfDev &, const CtgRank *, hipStream_t);
 hipError_t scaffold_bytes(const ScfDev &, u64 n_sbases, hipStream_t);
+// ... and kmx_unitig_pair_paths* (pair_path_kernels.h): the search per list entry, the scan of the paths' steps, the additions
+hipError_t pair_path_search(const PathDev &, hipStream_t);
+hipError_t pair_path_scan(const PathDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t pair_path_apply(const PathDev &, hipStream_t);
 }   // namespace kmxk

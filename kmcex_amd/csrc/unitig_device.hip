@@ -4,7 +4,8 @@
 // Then the launchers of contig_kernels.h (kmx_unitig_contigs*); their host side is contig_host.h.  Last the launcher of
 // resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
 // (kmx_unitig_pair_walks*); its host side is pair_host.h.  Last the launchers of scaffold_kernels.h (kmx_unitig_scaffold*); their
-// host side is scaffold_host.h.
+// host side is scaffold_host.h.  Behind them the launchers of pair_path_kernels.h (kmx_unitig_pair_paths*); their host side is
+// pair_path_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -14,6 +15,7 @@
 #include "resolve_kernels.h"
 #include "pair_kernels.h"
 #include "scaffold_kernels.h"
+#include "pair_path_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -351,6 +353,34 @@ hipError_t scaffold_bytes(const ScfDev &D, u64 n_sbases, hipStream_t st)
 {
 	if (n_sbases) RCHK(hipMemsetAsync(D.sseq, 'N', n_sbases, st));
 	if (D.n_ubases) hipLaunchKernelGGL(k_scf_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_pair_paths* (pair_path_kernels.h); D.U > 0 and D.n_plinks > 0
+
+// the verdict of every entry with its seven counters; the first hit's steps into D.work
+hipError_t pair_path_search(const PathDev &D, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.cnt, 0, PP_C_N * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(k_pp_search, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the exclusive scan of the PATH entries' steps into D.sc[n_plinks + 1]: D.sc[n_plinks] is what psteps has to hold
+hipError_t pair_path_scan(const PathDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	auto t = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), PairPathSteps{D.precs, D.n_plinks});
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, t, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, t, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	return hipGetLastError();
+}
+
+// first_step, the steps where they fit, the additions to through and path_hits, n_added and n_missing
+hipError_t pair_path_apply(const PathDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_pp_apply, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
