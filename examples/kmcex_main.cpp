@@ -43,6 +43,12 @@
 //          add the pairs of every such path to the reads through its unitigs and across its edges before -R and -X judge them,
 //          so that repeats longer than a read and shorter than a fragment no longer end the contigs: pairs.paths.tsv (entry, a,
 //          b, pairs, verdict, windows, steps)
+//     -F[<kinds>]  with -S: spell the scaffolds again with the graph's own bases in the gaps (KModel::scaffold_fill).  After the
+//          scaffolds it finds, for every pair link, the one path through the graph of what was scaffolded (the unitig graph, with
+//          -X the contig graph; KModel::pair_paths at -S's min_pairs and inner, tol = k, at most 8 unitigs and 4096 prefixes per
+//          link: -T's conventions) and fills the links the bits of kinds ask for (3 when omitted; 1: links with a path, 2: links
+//          along one graph edge, whose two strings overlap by k - 1): scaffolds.filled.fa and scaffolds.fill.tsv (scaffold, step,
+//          unitig, strand, kind, entry, offset, bytes in front, path).  scaffolds.fa stays as it is
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -69,6 +75,7 @@ struct Params {
 	long long scaf_min = -1;                                       // -S: min_pairs, -1 = no scaffolds
 	long scaf_ratio = 0;                                           // -S<min_pairs>,<ratio>
 	long path_tol = -2, path_steps = 8;                            // -T[<tol>[,<max_steps>]]: tol, -1 = k, -2 = no pair paths
+	long fill_kinds = -1;                                          // -F[<kinds>]: the links to fill, -1 = no filled scaffolds
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -142,6 +149,11 @@ static bool parse(int argc, char **argv, Params &p)
 				if (*end) return false;
 			}
 		}
+		else if (!strncmp(a, "-F", 2)) {
+			char *end = nullptr;
+			p.fill_kinds = a[2] ? strtol(a + 2, &end, 10) : 3;
+			if (a[2] && (*end || p.fill_kinds < 0 || p.fill_kinds > 3)) return false;   // not a set of kinds
+		}
 		else if (!strncmp(a, "-P", 2)) {
 			char *end = nullptr;
 			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
@@ -189,6 +201,10 @@ static bool parse(int argc, char **argv, Params &p)
 	}
 	if (p.path_tol > -2 && (p.pair_dist == -2 || p.res_min < 0)) {  // the paths are found for the pair links and credited to what -R reads
 		std::cout << "-T needs -M -W -P -X -R: the paths are found for the links the pairs leave, and their pairs are added to what the repeats are resolved from\n";
+		return false;
+	}
+	if (p.fill_kinds >= 0 && p.scaf_min < 0) {                     // the filled scaffolds are the scaffolds spelled again
+		std::cout << "-F needs -S: it fills the gaps of the scaffolds\n";
 		return false;
 	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
@@ -240,9 +256,10 @@ struct InnerSum {
 	}
 };
 
-// -S: the scaffolds of `strs` from `plinks`, written as scaffolds.fa, scaffolds.paths.tsv and scaffolds.agp
+// -S: the scaffolds of `strs` from `plinks`, written as scaffolds.fa, scaffolds.paths.tsv and scaffolds.agp; with -F also the
+// scaffolds filled along the paths of the graph (link_offsets, links) of `strs`: scaffolds.filled.fa and scaffolds.fill.tsv
 static bool write_scaffolds(KModel *km, const std::string &dir, const std::vector<std::string> &strs, const std::vector<kmx_unitig> *rec, const std::vector<kmx_pair_link> &plinks, const Params &p,
-                            uint32_t inner, uint32_t max_dist, const char *what)
+                            uint32_t inner, uint32_t max_dist, const char *what, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links)
 {
 	const uint64_t max_n = 2 * (uint64_t)max_dist;
 	const kmx_scaffold_params sp = {(uint64_t)p.scaf_min, (uint32_t)p.scaf_ratio, inner, max_n < 10 ? (uint32_t)max_n : 10u, max_n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)max_n, 0};
@@ -260,6 +277,19 @@ static bool write_scaffolds(KModel *km, const std::string &dir, const std::vecto
 	std::cout << "   scaffolds of " << what << " (links of >= " << p.scaf_min << " pairs" << (p.scaf_ratio ? ", ratio " : "") << (p.scaf_ratio ? std::to_string(p.scaf_ratio) : std::string()) << ", inner " << inner
 	          << ") :     " << sc.stats.n_scaffolds << " scaffolds (" << sc.stats.n_multi << " of several, " << sc.stats.n_circular << " circular), " << sc.stats.n_chain << " of " << sc.stats.n_links
 	          << " links joined, " << gaps << " N" << std::endl;
+	if (p.fill_kinds < 0) return true;
+	const kmx_pair_path_params tp = {(uint64_t)p.scaf_min, inner, (uint32_t)p.k, 8, 4096, 0};
+	const kmx_fill_params fp = {(uint32_t)p.fill_kinds, 0};
+	const KModel::PairPaths pa = km->pair_paths(strs, link_offsets, links, plinks, p.k, tp);
+	const KModel::FilledScaffolds fs = km->scaffold_fill(strs, sc, plinks, pa, p.k, fp);
+	std::ofstream ff((dir + "/scaffolds.filled.fa").c_str()), ft((dir + "/scaffolds.fill.tsv").c_str());
+	KModel::write_filled_scaffolds_fasta(ff, fs);
+	KModel::write_scaffold_fill_tsv(ft, fs);
+	ff.close();
+	ft.close();
+	if (!ff || !ft) { std::cout << "could not write " << dir << "/scaffolds.filled.fa or scaffolds.fill.tsv" << std::endl; return false; }
+	std::cout << "   filled scaffolds of " << what << " (kinds " << p.fill_kinds << ", tol " << tp.tol << ") :     " << fs.stats.n_path << " links filled along a path, " << fs.stats.n_adjacent << " along an edge, "
+	          << fs.stats.n_n << " left as N (" << fs.stats.n_no_entry << " without an entry), " << fs.stats.n_removed << " N removed, " << fs.stats.n_filled << " bases filled" << std::endl;
 	return true;
 }
 
@@ -288,7 +318,10 @@ int main(int argc, char **argv)
 		             "           pairs onto them) along the links at least min_pairs pairs support, with runs of N sized from the insert size:\n"
 		             "           scaffolds.fa, scaffolds.paths.tsv (scaffold, step, unitig, strand, offset, N in front, estimate), scaffolds.agp\n"
 		             "       -T[<tol>[,<max_steps>]]  with -M -W -P -X -R: find the one graph path every pair link stands for (windows within tol (k) of\n"
-		             "           the insert size, at most max_steps (8) unitigs) and count its pairs as reads through its unitigs: pairs.paths.tsv\n";
+		             "           the insert size, at most max_steps (8) unitigs) and count its pairs as reads through its unitigs: pairs.paths.tsv\n"
+		             "       -F[<kinds>]  with -S: fill the scaffolds' gaps with the bases of the one graph path that fits (kinds & 1) and trim the overlap\n"
+		             "           of two steps along one edge (kinds & 2; 3 when omitted): scaffolds.filled.fa, scaffolds.fill.tsv (scaffold, step,\n"
+		             "           unitig, strand, kind, entry, offset, bytes in front, path)\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -437,7 +470,7 @@ int main(int argc, char **argv)
 					          << pa.stats.n_adjacent << " adjacent, " << pa.stats.n_no_path << " none, " << pa.stats.n_ambiguous << " ambiguous, " << pa.stats.n_complex << " complex, " << pa.stats.n_below_min
 					          << " below " << tp.min_pairs << " pairs, " << pa.stats.n_ignored << " ignored), " << pa.stats.n_added << " unitigs credited" << std::endl;
 				}
-				if (p.scaf_min >= 0 && p.min_reads < 0 && !write_scaffolds(km, dir, strs, &rec, plinks, p, inner.inner(), pp.max_dist, "unitigs")) return 1;
+				if (p.scaf_min >= 0 && p.min_reads < 0 && !write_scaffolds(km, dir, strs, &rec, plinks, p, inner.inner(), pp.max_dist, "unitigs", link_offsets, links)) return 1;
 				if (p.min_reads >= 0) {
 					const kmx_contig_params xp = {(uint64_t)p.min_reads, (uint32_t)p.ratio, 0};
 					KModel::Resolved rs;
@@ -491,7 +524,7 @@ int main(int argc, char **argv)
 							cinner.add(km->seq_pairs(wk, walk_offsets, steps, ct.link_offsets, ct.links, pp, &cplinks));
 						}
 						km->unitig_map_end();
-						if (!write_scaffolds(km, dir, ct.strs, 0, cplinks, p, cinner.inner(), pp.max_dist, "contigs")) return 1;
+						if (!write_scaffolds(km, dir, ct.strs, 0, cplinks, p, cinner.inner(), pp.max_dist, "contigs", ct.link_offsets, ct.links)) return 1;
 					}
 					std::cout << "   contigs (links of >= " << p.min_reads << " reads" << (p.ratio ? ", ratio " : "") << (p.ratio ? std::to_string(p.ratio) : std::string()) << ")    :     " << ct.stats.n_contigs
 					          << " contigs (" << ct.stats.n_multi << " of several unitigs, " << ct.stats.n_circular << " circular), " << ct.stats.n_kept << " of " << ct.stats.n_links << " edges kept" << std::endl;

@@ -778,6 +778,75 @@ public:
 		}
 	}
 
+	// Filled scaffolds (the rule: kmx.h): the scaffolds spelled again, with the graph's own bases in every gap that pair_paths found
+	// the one path for (kinds bit 0) and the k - 1 overlap trimmed where two steps share a graph edge (bit 1).  scaffold_fill takes
+	// the unitig strings the scaffolds were made of, what unitig_scaffold and pair_paths returned on the same list, and the list;
+	// it needs no session and no graph.  The result holds the strings, one kmx_scaffold_fill each, one kmx_fill_step per step in the
+	// order of the scaffold's steps, and the oriented unitigs of every filled path back to back.  It sizes the bases with a first
+	// call, so it never comes back short.
+	struct FilledScaffolds {
+		std::vector<std::string> strs;
+		std::vector<kmx_scaffold_fill> rec;
+		std::vector<kmx_fill_step> steps;
+		std::vector<uint32_t> pieces;
+		std::vector<uint32_t> n_steps;               // of the scaffold, with its circular bit
+		std::vector<uint32_t> first_step;
+		kmx_fill_stats stats;
+	};
+	FilledScaffolds scaffold_fill(const std::vector<std::string> &unitigs, const Scaffolds &scaffolds, const std::vector<kmx_pair_link> &plinks, const PairPaths &paths, int k, const kmx_fill_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), S = scaffolds.rec.size(), np = plinks.size(), ns = paths.steps.size();
+		if (scaffolds.steps.size() != U || paths.rec.size() != np) { std::cout << "scaffold_fill: the scaffolds and paths are not those of the unitigs and the list" << std::endl; exit(1); }
+		FilledScaffolds r;
+		r.stats = kmx_fill_stats();
+		std::vector<uint64_t> foff(S + 1, 0);
+		r.rec.resize(S + 1); r.steps.resize(U + 1);
+		const uint64_t pcap = (uint64_t)ns;                      // a link has one entry, so no step of a path is spelled twice
+		r.pieces.resize((size_t)pcap + 1);
+		uint64_t nb = 0, npc = 0;
+		const int rc = kmx_unitig_scaffold_fill(h_, k, f.bases.data(), f.off.data(), U, S ? &scaffolds.rec[0] : 0, S, U ? &scaffolds.steps[0] : 0, np ? &plinks[0] : 0, np, np ? &paths.rec[0] : 0,
+		                                        ns ? &paths.steps[0] : 0, ns, &params, 0, 0, &foff[0], &r.rec[0], &r.steps[0], &r.pieces[0], pcap, &nb, &npc, &r.stats);   // the sizing call
+		if (rc != KMX_E_RANGE) check(rc);
+		std::string fseq((size_t)nb + 1, '\0');
+		if (rc == KMX_E_RANGE)
+			check(kmx_unitig_scaffold_fill(h_, k, f.bases.data(), f.off.data(), U, S ? &scaffolds.rec[0] : 0, S, U ? &scaffolds.steps[0] : 0, np ? &plinks[0] : 0, np, np ? &paths.rec[0] : 0,
+			                               ns ? &paths.steps[0] : 0, ns, &params, &fseq[0], nb, &foff[0], &r.rec[0], &r.steps[0], &r.pieces[0], pcap, &nb, &npc, &r.stats));
+		r.strs = split(fseq, foff);
+		r.rec.resize(S); r.steps.resize(U); r.pieces.resize((size_t)npc);
+		for (size_t i = 0; i < S; i++) { r.n_steps.push_back(scaffolds.rec[i].n_steps); r.first_step.push_back(scaffolds.rec[i].first_step); }
+		return r;
+	}
+	// the filled scaffolds as FASTA, header ">s<index> n_bases=<b> n_steps=<s> n_gap_bases=<n> n_fill_bases=<f> circular=<0|1>"
+	static void write_filled_scaffolds_fasta(std::ostream &out, const FilledScaffolds &s)
+	{
+		for (size_t i = 0; i < s.strs.size() && i < s.rec.size() && i < s.n_steps.size(); i++)
+			out << ">s" << i << " n_bases=" << s.rec[i].n_bases << " n_steps=" << (s.n_steps[i] & ~KMX_SCAFFOLD_CIRCULAR) << " n_gap_bases=" << s.rec[i].n_gap_bases << " n_fill_bases=" << s.rec[i].n_fill_bases
+			    << " circular=" << (s.n_steps[i] >> 31) << "\n" << s.strs[i] << "\n";
+	}
+	// ... and every step as a table, one "s<scaffold>\t<step>\tu<unitig>\t<+|->\t<kind>\t<entry>\t<off>\t<bytes in front>\t<path>" per
+	// step: "*" for no entry; the path with the orientation signs of reads.gaf (">u3<u5"), "*" for none
+	static void write_scaffold_fill_tsv(std::ostream &out, const FilledScaffolds &s)
+	{
+		static const char *const names[] = {"HEAD", "N", "ADJACENT", "PATH"};
+		for (size_t i = 0; i < s.rec.size() && i < s.n_steps.size(); i++) {
+			uint64_t at = s.rec[i].first_piece;
+			for (uint64_t j = 0; j < (s.n_steps[i] & ~KMX_SCAFFOLD_CIRCULAR) && s.first_step[i] + j < s.steps.size(); j++) {
+				const kmx_fill_step &t = s.steps[(size_t)(s.first_step[i] + j)];
+				out << "s" << i << "\t" << j << "\tu" << (t.o >> 1) << "\t" << ((t.o & 1) ? '-' : '+') << "\t" << (t.kind <= KMX_FILL_PATH ? names[t.kind] : "?") << "\t";
+				if (t.entry == KMX_FILL_NO_ENTRY) out << "*"; else out << t.entry;
+				out << "\t" << t.off << "\t" << t.n_front << "\t";
+				uint64_t n = 0;
+				for (uint64_t p = 0; p < t.n_pieces && at + p < s.pieces.size(); p++, n++) {
+					const uint32_t o = s.pieces[(size_t)(at + p)];
+					out << ((o & 1) ? '<' : '>') << "u" << (o >> 1);
+				}
+				at += t.n_pieces;
+				out << (n ? "\n" : "*\n");
+			}
+		}
+	}
+
 	void save(std::string save_dir) { check(kmx_save(h_, save_dir.c_str())); }       // kmodel.hpp:173
 	void save_model(std::string save_dir) { save(save_dir); }                          // README.md:78
 

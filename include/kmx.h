@@ -1237,9 +1237,9 @@ int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_
  *   (c) place inverts steps; the n_steps sum to U; n_sbases = n_ubases + the sum of n_gap_bases;
  *   (d) two islands of one genome that the pairs span come out as one scaffold with the hole as a run of 'N' of its true length,
  *       when inner is the library's d.
- * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; gap filling
- * through the graph; links that skip a unitig (transitive reduction); RF and FF libraries; several GPUs; choosing min_pairs and
- * inner.                                                                                                                    */
+ * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; links that skip
+ * a unitig (transitive reduction); RF and FF libraries; several GPUs; choosing min_pairs and inner.  Gaps the graph can spell:
+ * kmx_unitig_scaffold_fill below.                                                                                           */
 typedef struct kmx_scaffold_params { uint64_t min_pairs; uint32_t ratio /* [0, 65536] */; uint32_t inner; uint32_t min_n, max_n /* min_n <= max_n */;
                                      uint64_t reserved /* 0 */; } kmx_scaffold_params;                                  /* 32 bytes */
 #define KMX_SCAFFOLD_CIRCULAR 0x80000000u
@@ -1341,9 +1341,9 @@ int kmx_unitig_scaffold_last_phases(kmx_model *m, double *seconds /* [5] */, uin
  *   (c) through summed with the array of kmx_unitig_walk_through feeds kmx_unitig_resolve unchanged, and path_hits summed with
  *       link_hits feeds kmx_unitig_contigs;
  *   (d) every output is an integer count or sum and a function of the input alone: byte-identical across runs and forms.
- * Out of scope: meeting in the middle; choosing among several paths, by coverage or by fit; spelling the path's bases into the
- * gaps of kmx_unitig_scaffold (a scaffold link is such an entry); a search per pair instead of per entry; RF and FF libraries;
- * several GPUs; choosing tol and inner.                                                                                      */
+ * Out of scope: meeting in the middle; choosing among several paths, by coverage or by fit; a search per pair instead of per
+ * entry; RF and FF libraries; several GPUs; choosing tol and inner.  A scaffold link is such an entry: kmx_unitig_scaffold_fill
+ * below spells its path into the scaffold's gap.                                                                             */
 #define KMX_PATH_IGNORED   0
 #define KMX_PATH_BELOW_MIN 1
 #define KMX_PATH_NO_PATH   2
@@ -1387,6 +1387,111 @@ int kmx_unitig_pair_paths_dev(kmx_model *m, int k, const uint64_t *d_uoffsets /*
                               uint64_t *d_through /* [16 U] or NULL */, uint64_t *d_path_hits /* [n_links] or NULL */, kmx_pair_path_stats *stats /* HOST */);
 /* seconds[3] of the last of these two calls under kmx_set_profile(m, 1): the search, the scan, the additions with the wait */
 int kmx_unitig_pair_paths_last_phases(kmx_model *m, double *seconds /* [3] */);
+
+/* ---- filled scaffolds: the scaffolds of kmx_unitig_scaffold spelled again, with the bases of the graph in every gap that
+ * kmx_unitig_pair_paths found the one path for.  A scaffold writes a run of 'N' between two steps even where the unitig graph
+ * holds the real bases of that gap, and writes two whole strings with at least min_n 'N' between them even where the two steps
+ * share a graph edge and so overlap by k - 1 bases.  This call takes what the two calls returned and needs no model, no session
+ * and no CSR.
+ * Input: k, odd, in [5, 63]; the unitig set the scaffold call was given (useq, uoffsets[U + 1], U < 2^31, every unitig at least k
+ *   bytes); srec[S] and steps[U] as the scaffold call left them (of srec only first_step and n_steps with its circular bit are
+ *   read: every scaffold holds a step, first_step is the number of steps of the scaffolds in front of it, and the steps sum to
+ *   U; of steps, o and n_gap); plinks[n_plinks], strictly ascending by a << 32 | b, n_plinks < 2^31; precs[n_plinks] and
+ *   psteps[n_psteps] as kmx_unitig_pair_paths left them on that list and the graph's CSR; and kmx_fill_params: kinds in [0, 3]
+ *   (bit 0: fill PATH links, bit 1: fill ADJACENT links), reserved = 0.
+ *   The entry of a link.  Take step j >= 1 of a scaffold, p = steps[first_step + j - 1].o and q = steps[first_step + j].o.  F is
+ *     the entry with (a, b) = (p, q), M the entry with (a, b) = (q ^ 1, p ^ 1), each found by a lower-bound search on the key.
+ *     The link's entry is F if it exists, else M, else none.
+ *   The path of a link.  Through F it is psteps[first_step .. first_step + t) of the entry's record as it stands; through M it is
+ *     reversed and flipped, v_t ^ 1 .. v_1 ^ 1: consequence (b) of the pair-path contract.
+ *   The kind of a step.  KMX_FILL_HEAD: step 0 of its scaffold (the closing link of a cycle is never spelled, as in the scaffold
+ *     call).  KMX_FILL_PATH: the entry's verdict is KMX_PATH_PATH, kinds & 1, 1 <= t <= KMX_PATH_MAX_STEPS, first_step + t <=
+ *     n_psteps and every v < 2 U.  KMX_FILL_ADJACENT: the verdict is KMX_PATH_ADJACENT and kinds & 2; then t = 0.  KMX_FILL_N:
+ *     everything else.
+ *   The bytes.  A HEAD step writes the whole oriented string of its unitig.  An N step writes steps[].n_gap bytes 'N', then the
+ *     whole oriented string of q: exactly what the scaffold call writes.  A PATH or ADJACENT step writes, for each v_j in turn,
+ *     the LAST m_v = len_v - (k - 1) bytes of the oriented string of v_j (a PIECE), then the last len_q - (k - 1) bytes of the
+ *     oriented string of q: consecutive unitigs along a graph edge overlap by k - 1 bytes.  The rule is defined on lengths
+ *     alone; overlaps are not checked.  A reverse step or piece complements with the byte map of kmx_unitig_contigs.
+ * Output.  fseq[seq_capacity] and foffsets[S + 1] in the layout of kmx_query_seqs; frec[S] and fsteps[U], the records below, the
+ *   steps in the order of steps[]: off is where the step's WHOLE oriented string starts inside its scaffold (for a filled step
+ *   k - 1 bytes in front of its first written byte), n_front the 'N' or the piece bytes in front of the step; pieces[
+ *   piece_capacity]: the oriented unitigs of every filled path, back to back in scaffold order (frec.first_piece, fsteps.
+ *   n_pieces); it may be NULL.  On the HOST: *n_fbases, *n_pieces and kmx_fill_stats.  *n_fbases > seq_capacity: KMX_E_RANGE,
+ *   everything but fseq complete, nothing written at or behind fseq[seq_capacity]; *n_fbases is the scaffold call's n_sbases less
+ *   n_gap + (k - 1) per filled link plus W, the windows of its path, per PATH link, so n_ubases + (U - 1) * (the largest n_gap) +
+ *   the sum of W over the filled links suffices.  fseq == NULL with seq_capacity == 0 is the sizing call, as in the
+ *   scaffold call.  More pieces than piece_capacity: KMX_E_RANGE with *n_pieces the number needed and everything else, fseq
+ *   included, complete: the convention of psteps; pieces == NULL: no list is built and n_pieces may be NULL.  Everything is an
+ *   integer sum or count and a function of the input alone: byte-identical across runs and forms.
+ * Consequences:
+ *   (a) with kinds = 0, or no PATH / ADJACENT entry among the chain links, fseq and foffsets are the scaffold call's sseq and
+ *       soffsets byte for byte;
+ *   (b) where every edge of the CSR is a true k - 1 overlap, fseq[foffsets[s] + off, + len) is the oriented string of the step,
+ *       for every step;
+ *   (c) replacing an entry and its record and steps by their mirror changes nothing in fseq;
+ *   (d) per scaffold, n_bases = the sum of len over its steps - (k - 1) * its filled links + n_gap_bases + n_fill_bases.
+ * Out of scope: choosing among several paths (an AMBIGUOUS entry stays a run of 'N'); comparing bases when est < 0 or along a
+ * filled link; filling the closing link of a cycle; several GPUs.                                                             */
+#define KMX_FILL_HEAD     0
+#define KMX_FILL_N        1
+#define KMX_FILL_ADJACENT 2
+#define KMX_FILL_PATH     3
+#define KMX_FILL_NO_ENTRY 0xFFFFFFFFu
+typedef struct kmx_fill_params { uint32_t kinds /* [0, 3] */; uint32_t reserved /* 0 */; } kmx_fill_params;                    /* 8 bytes */
+typedef struct kmx_scaffold_fill {       /* one per scaffold; 64 bytes, no padding */
+	uint64_t n_bases;                    /* the bytes of its string */
+	uint64_t n_gap_bases;                /* the 'N' still written */
+	uint64_t n_fill_bases;               /* the bytes of its path pieces */
+	uint64_t n_path_links, n_adjacent_links, n_n_links;   /* its steps behind the first, by kind */
+	uint64_t n_pieces;                   /* its pieces are pieces[first_piece .. first_piece + n_pieces) */
+	uint64_t first_piece;
+} kmx_scaffold_fill;
+typedef struct kmx_fill_step {           /* one per step; 32 bytes, no padding */
+	uint32_t o;                          /* the oriented unitig, steps[].o */
+	uint32_t kind;                       /* KMX_FILL_* */
+	uint32_t entry;                      /* the entry of the link in front, KMX_FILL_NO_ENTRY for none and at a HEAD */
+	uint32_t n_pieces;                   /* t of a PATH step, else 0 */
+	uint64_t off;                        /* where the step's whole oriented string starts inside its scaffold */
+	uint64_t n_front;                    /* the 'N' (N step) or the piece bytes (PATH step) in front of it */
+} kmx_fill_step;
+typedef struct kmx_fill_stats { uint64_t n_head, n_path, n_adjacent, n_n /* steps of each kind */, n_no_entry /* links without an entry */,
+                                n_mirror /* links whose entry is M */, n_removed /* the 'N' of the filled links */, n_filled /* the piece bytes */, reserved[2]; } kmx_fill_stats;   /* 80 bytes */
+/* On HOST buffers; it stages through the handle, runs on the model's stream and is a build-class call.  pieces may be NULL,
+ * plinks and precs with n_plinks == 0, psteps with n_psteps == 0, fseq with seq_capacity == 0; every other buffer is required
+ * (with U == 0 only foffsets, n_fbases and stats).  KMX_E_ARG before anything runs: an even or out-of-range k, U >= 2^31,
+ * n_plinks >= 2^31, S > U, kinds > 3, reserved != 0, a NULL required buffer, an output that overlaps an input or another output;
+ * uoffsets whose first entry is not 0, that decrease, or that give a unitig fewer than k bytes; a list that is not strictly
+ * ascending by a << 32 | b; a scaffold with first_step + n_steps > U, without a step, or whose first_step is not the number of
+ * steps in front of it; steps that do not sum to U.  U == 0: KMX_OK, foffsets[0] = 0, all counts zero.  KMX_E_NOMEM leaves the
+ * handle usable.  The call returns when the output is complete.                                                            */
+int kmx_unitig_scaffold_fill(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_scaffold *srec /* [n_scaffolds] */,
+                             uint64_t n_scaffolds, const kmx_scaffold_step *steps /* [U] */, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_path *precs /* [n_plinks] */,
+                             const uint32_t *psteps, uint64_t n_psteps, const kmx_fill_params *params, char *fseq /* [seq_capacity] or NULL */, uint64_t seq_capacity,
+                             uint64_t *foffsets /* [S + 1] */, kmx_scaffold_fill *frec /* [S] */, kmx_fill_step *fsteps /* [U] */, uint32_t *pieces /* [piece_capacity] or NULL */,
+                             uint64_t piece_capacity, uint64_t *n_fbases, uint64_t *n_pieces, kmx_fill_stats *stats);
+/* The same on DEVICE buffers, read where the scaffold and pair-path calls left them; params, the two counts and stats are on the
+ * HOST.  It checks k, U, n_plinks, S <= U, the parameters, NULL and overlap, and validates nothing else; the kernels clamp
+ * instead: uoffsets into [0, n_ubases]; step 0 starts a scaffold whatever srec says, and so does every step a first_step < U
+ * names; a step with o >= 2 U writes no byte; a link whose lookups fail any bound is an N step, and so is a link beside a
+ * unitig shorter than k or with such a unitig on its path; a list that is not ascending is searched all the same.  Every store
+ * is checked against S, U, seq_capacity or piece_capacity.  Bad device input gives wrong strings and never an access outside a
+ * buffer.  It enqueues the kinds and one scan on the model's stream and waits ONCE, for the counts; steps, records and pieces
+ * follow, and the bytes only when that wait has shown that n_fbases fits: 'N' over fseq[0, n_fbases), the steps' own bytes by
+ * the tile emit of the contigs with k - 1 bytes skipped at a filled step, then the pieces by a gather emit tiled over the
+ * piece bytes, because a repeat unitig is written once per path that crosses it.  A last wait leaves nothing in flight.  Device
+ * memory, kept on the handle between calls through the owning types of hip_owned.h: 88 bytes per unitig (2 x 40 for what a step
+ * writes and its scan, 8 for where a unitig's bytes go) and 20 per piece, plus the scan's scratch.  The host form also stages
+ * its input and output there.                                                                                               */
+int kmx_unitig_scaffold_fill_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, uint64_t n_ubases,
+                                 const kmx_scaffold *d_srec /* [n_scaffolds] */, uint64_t n_scaffolds, const kmx_scaffold_step *d_steps /* [U] */, const kmx_pair_link *d_plinks,
+                                 uint64_t n_plinks, const kmx_pair_path *d_precs /* [n_plinks] */, const uint32_t *d_psteps, uint64_t n_psteps, const kmx_fill_params *params /* HOST */,
+                                 char *d_fseq /* [seq_capacity] or NULL */, uint64_t seq_capacity, uint64_t *d_foffsets /* [S + 1] */, kmx_scaffold_fill *d_frec /* [S] */,
+                                 kmx_fill_step *d_fsteps /* [U] */, uint32_t *d_pieces /* [piece_capacity] or NULL */, uint64_t piece_capacity, uint64_t *n_fbases /* HOST */,
+                                 uint64_t *n_pieces /* HOST */, kmx_fill_stats *stats /* HOST */);
+/* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): the kinds, the scan with the wait, steps with records
+ * and pieces, the bytes */
+int kmx_unitig_scaffold_fill_last_phases(kmx_model *m, double *seconds /* [4] */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

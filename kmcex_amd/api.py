@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_pair_walks", "kmx_unitig_pair_walks_dev",
     "kmx_unitig_scaffold", "kmx_unitig_scaffold_dev", "kmx_unitig_scaffold_last_phases",
     "kmx_unitig_pair_paths", "kmx_unitig_pair_paths_dev", "kmx_unitig_pair_paths_last_phases",
+    "kmx_unitig_scaffold_fill", "kmx_unitig_scaffold_fill_dev", "kmx_unitig_scaffold_fill_last_phases",
 ]
 
 
@@ -282,6 +283,26 @@ PAIR_PATH_VERDICTS = {0: "IGNORED", 1: "BELOW_MIN", 2: "NO_PATH", 3: "ADJACENT",
 PAIR_PATH_MAX_STEPS = 16
 
 
+class FillParams(C.Structure):
+    """kmx_fill_params of include/kmx.h: 8 bytes"""
+    _fields_ = [("kinds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class FillStats(C.Structure):
+    """kmx_fill_stats of include/kmx.h: 80 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_head", "n_path", "n_adjacent", "n_n", "n_no_entry", "n_mirror", "n_removed", "n_filled")] + [("reserved", C.c_uint64 * 2)]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_[:8]}
+
+
+# kmx_scaffold_fill and kmx_fill_step as NumPy structured dtypes (what KModel.unitig_scaffold_fill_flat returns): 64 and 32 bytes
+SCAFFOLD_FILL_DTYPE = np.dtype([(f, "<u8") for f in ("n_bases", "n_gap_bases", "n_fill_bases", "n_path_links", "n_adjacent_links", "n_n_links", "n_pieces", "first_piece")])
+FILL_STEP_DTYPE = np.dtype([("o", "<u4"), ("kind", "<u4"), ("entry", "<u4"), ("n_pieces", "<u4"), ("off", "<u8"), ("n_front", "<u8")])
+FILL_KINDS = {0: "HEAD", 1: "N", 2: "ADJACENT", 3: "PATH"}
+FILL_NO_ENTRY = 0xFFFFFFFF
+
+
 class RingList(C.Structure):
     """kmx_ring_list of include/kmx.h"""
     _fields_ = [("list", C.c_int32), ("n_host", C.c_int32), ("src_kmers", C.c_void_p), ("src_counts", C.c_void_p),
@@ -439,6 +460,9 @@ def load_library():
     _sig(L, "kmx_unitig_pair_paths", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
     _sig(L, "kmx_unitig_pair_paths_dev", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
     _sig(L, "kmx_unitig_pair_paths_last_phases", [vp, C.POINTER(C.c_double)])
+    _sig(L, "kmx_unitig_scaffold_fill", [vp, C.c_int, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
+    _sig(L, "kmx_unitig_scaffold_fill_dev", [vp, C.c_int, vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
+    _sig(L, "kmx_unitig_scaffold_fill_last_phases", [vp, C.POINTER(C.c_double)])
     _sig(L, "kmx_unitig_resolve", [vp, C.c_int, vp, vp, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_dev", [vp, C.c_int, vp, vp, u64, u64, vp, vp, vp, u64, vp, vp, C.POINTER(ResolveParams), vp, u64, vp, u64, vp, vp, vp, vp, vp, vp, vp, p64, p64, C.POINTER(ResolveStats)])
     _sig(L, "kmx_unitig_resolve_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1475,6 +1499,99 @@ class KModel:
         sec = (C.c_double * 3)()
         _chk(self.L.kmx_unitig_pair_paths_last_phases(self.h, sec))
         return dict(zip(("search", "scan", "apply"), (float(x) for x in sec)))
+
+    # ---- filled scaffolds: the scaffolds spelled again with the graph's bases in the gaps the pair paths cross (the rule:
+    # include/kmx.h); no model, no session, no CSR
+    def unitig_scaffold_fill_flat(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, srec: np.ndarray, steps: np.ndarray, plinks: np.ndarray, precs: np.ndarray, psteps, kinds: int = 3,
+                                  capacity=None, piece_capacity=None, pieces: bool = True):
+        """kmx_unitig_scaffold_fill on the unitig set the scaffold call was given, the SCAFFOLD_DTYPE records [S] and
+        SCAFFOLD_STEP_DTYPE steps [U] it returned, the PAIR_LINK_DTYPE list, and the PAIR_PATH_DTYPE records and uint32 steps
+        unitig_pair_paths_flat returned on it -> (uint8 bases, uint64 foffsets [S + 1], SCAFFOLD_FILL_DTYPE records [S],
+        FILL_STEP_DTYPE steps [U], uint32 pieces or None, stats as a dict).  capacity None: a sizing call first, then the bytes it
+        asked for; a number: that many bytes, 0 being the sizing call.  piece_capacity None: the
+        size of psteps.  KmxError KMX_E_RANGE when either is short: its `needed` the bytes needed, its `needed_pieces` the
+        pieces, its `result` everything but the bases.  pieces False: no list is built."""
+        ubuf = np.ascontiguousarray(ubuf, dtype=np.uint8)
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        srec = np.ascontiguousarray(srec, dtype=SCAFFOLD_DTYPE)
+        steps = np.ascontiguousarray(steps, dtype=SCAFFOLD_STEP_DTYPE)
+        plinks = np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+        precs = np.ascontiguousarray(precs, dtype=PAIR_PATH_DTYPE)
+        psteps = np.zeros(0, dtype=np.uint32) if psteps is None else np.ascontiguousarray(psteps, dtype=np.uint32)
+        nu, ns = uoffsets.size - 1, srec.size
+        if steps.size != nu or precs.size != plinks.size:
+            raise KmxError(-1, "steps holds one entry per unitig and precs one per pair link")
+        if capacity is None:                                      # the sizing call says what is needed
+            try:
+                return self.unitig_scaffold_fill_flat(k, ubuf, uoffsets, srec, steps, plinks, precs, psteps, kinds, 0, piece_capacity, pieces)
+            except KmxError as e:
+                if e.code != -5 or not getattr(e, "needed", 0):
+                    raise
+                capacity = e.needed
+        cap = int(capacity)
+        pcap = (psteps.size if piece_capacity is None else int(piece_capacity)) if pieces else 0
+        fseq = np.zeros(cap, dtype=np.uint8) if cap else None
+        foffs = np.zeros(ns + 1, dtype=np.uint64)
+        frec = np.zeros(max(ns, 1), dtype=SCAFFOLD_FILL_DTYPE)
+        fst = np.zeros(max(nu, 1), dtype=FILL_STEP_DTYPE)
+        pcs = np.zeros(max(pcap, 1), dtype=np.uint32) if pieces else None
+        par, st, nb, npc = FillParams(int(kinds), 0), FillStats(), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data if a is not None and a.size else None
+        try:
+            _chk(self.L.kmx_unitig_scaffold_fill(self.h, int(k), ubuf.ctypes.data, uoffsets.ctypes.data, nu, ptr(srec), ns, ptr(steps), ptr(plinks), plinks.size, ptr(precs), ptr(psteps), psteps.size,
+                                                 C.byref(par), ptr(fseq), cap, foffs.ctypes.data, frec.ctypes.data, fst.ctypes.data, pcs.ctypes.data if pieces else None, pcap, C.byref(nb),
+                                                 C.byref(npc), C.byref(st)))
+        except KmxError as e:
+            e.needed, e.needed_pieces = int(nb.value), int(npc.value)
+            e.result = (foffs.copy(), frec[:ns].copy(), fst[:nu].copy(), (pcs[:min(npc.value, pcap)].copy() if pieces else None), st.as_dict())
+            raise
+        return ((fseq[:nb.value].copy() if cap else np.zeros(0, dtype=np.uint8)), foffs.copy(), frec[:ns].copy(), fst[:nu].copy(), (pcs[:npc.value].copy() if pieces else None), st.as_dict())
+
+    def unitig_scaffold_fill_dev(self, k: int, d_ubuf, d_uoffsets, d_srec, n_scaffolds: int, d_steps, d_plinks, n_plinks: int, d_precs, d_psteps, n_psteps: int, kinds: int = 3, capacity: int = 0,
+                                 piece_capacity: int = 0, out=None):
+        """kmx_unitig_scaffold_fill_dev on torch tensors of the model's device, read where the scaffold and pair-path calls left
+        them: d_ubuf uint8 [n_ubases], d_uoffsets int64 [U + 1], d_srec uint8 [>= S, 64], d_steps uint8 [U, 16], d_plinks uint8
+        [>= n_plinks, 32], d_precs uint8 [>= n_plinks, 32], d_psteps int32 [>= n_psteps].  out: the five output tensors (d_fseq
+        uint8 [capacity] or None for the sizing call, d_foffsets int64 [S + 1], d_frec uint8 [S, 64], d_fsteps uint8 [U, 32],
+        d_pieces int32 [piece_capacity] or None for no list), allocated when None from `capacity` and `piece_capacity` ->
+        (out, (n_fbases, n_pieces), stats as a dict).  KmxError KMX_E_RANGE carries the bytes needed in `needed`, the pieces in
+        `needed_pieces` and everything else in `result`."""
+        import torch
+        nu, nb, dev, ns = d_uoffsets.numel() - 1, d_ubuf.numel(), d_uoffsets.device, int(n_scaffolds)
+        if out is None:
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            out = (z(int(capacity), torch.uint8) if capacity else None, z(ns + 1, torch.int64), z((max(ns, 1), 64), torch.uint8), z((max(nu, 1), 32), torch.uint8),
+                   z(int(piece_capacity), torch.int32) if piece_capacity else None)
+        par, st, nf, npc = FillParams(int(kinds), 0), FillStats(), C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        try:
+            _chk(self.L.kmx_unitig_scaffold_fill_dev(self.h, int(k), d_ubuf.data_ptr(), d_uoffsets.data_ptr(), nu, nb, ptr(d_srec) if ns else None, ns, ptr(d_steps) if nu else None,
+                                                     ptr(d_plinks) if n_plinks else None, int(n_plinks), ptr(d_precs) if n_plinks else None, ptr(d_psteps) if n_psteps else None, int(n_psteps),
+                                                     C.byref(par), ptr(out[0]), out[0].numel() if out[0] is not None else 0, out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), ptr(out[4]),
+                                                     out[4].numel() if out[4] is not None else 0, C.byref(nf), C.byref(npc), C.byref(st)))
+        except KmxError as e:
+            e.needed, e.needed_pieces = int(nf.value), int(npc.value)
+            e.result = (out, (nf.value, npc.value), st.as_dict())
+            raise
+        return out, (nf.value, npc.value), st.as_dict()
+
+    def filled_scaffolds_from_pairs(self, k: int, strs, link_offsets: np.ndarray, links: np.ndarray, plinks: np.ndarray, inner: int, min_pairs: int = 2, ratio: int = 0, min_n: int = 10,
+                                    max_n: int = 1000, tol=None, max_steps: int = 8, max_visits: int = 4096, kinds: int = 3):
+        """on a list of unitig strings, the CSR of their graph and a pair list: unitig_scaffold_flat, unitig_pair_paths_flat at the
+        same min_pairs and inner and tol (None: k), then unitig_scaffold_fill_flat -> (the filled scaffold strings as str,
+        SCAFFOLD_FILL_DTYPE records, FILL_STEP_DTYPE steps, uint32 pieces, fill stats as a dict, what unitig_scaffold_flat
+        returned, what unitig_pair_paths_flat returned)"""
+        _, _, ubuf, uoffs = _join_seqs(list(strs))
+        scf = self.unitig_scaffold_flat(k, ubuf, uoffs, plinks, inner, min_pairs, ratio, min_n, max_n)
+        pth = self.unitig_pair_paths_flat(k, uoffs, link_offsets, links, plinks, inner, int(k) if tol is None else int(tol), min_pairs, max_steps, max_visits)
+        fseq, foffs, frec, fst, pcs, st = self.unitig_scaffold_fill_flat(k, ubuf, uoffs, scf[2], scf[3], plinks, pth[0], pth[1], kinds)
+        return [b.decode("latin-1") for b in _split_seqs(fseq, foffs)], frec, fst, pcs, st, scf, pth
+
+    def unitig_scaffold_fill_phases(self) -> dict:
+        """kmx_unitig_scaffold_fill_last_phases: seconds per phase of the last fill call (under set_profile(1))"""
+        sec = (C.c_double * 4)()
+        _chk(self.L.kmx_unitig_scaffold_fill_last_phases(self.h, sec))
+        return dict(zip(("kinds", "scan", "records", "bytes"), (float(x) for x in sec)))
 
     def resolved_contigs_from_pairs(self, k: int, ubuf: np.ndarray, uoffsets: np.ndarray, link_offsets: np.ndarray, links: np.ndarray, reads, max_dist: int, tol=None, max_gap=None,
                                     max_indel: int = 1, min_reads: int = 2, max_cross: int = 0, contig_min_reads: int = 1, ratio: int = 0, max_steps: int = 8, max_visits: int = 4096,

@@ -662,6 +662,53 @@ struct PathDev {
 	u64 *sc;
 	unsigned long long *cnt;     // [PP_C_N]
 };
+// kmx_unitig_scaffold_fill*: a filled scaffold's record and a step, the layouts of kmx_scaffold_fill and kmx_fill_step
+// (include/kmx.h; fill_host.h asserts them) ...
+struct ScfFill {
+	u64 n_bases, n_gap_bases, n_fill_bases, n_path_links, n_adjacent_links, n_n_links, n_pieces, first_piece;
+};
+struct FillStep {
+	u32 o, kind, entry, n_pieces;
+	u64 off, n_front;
+};
+// ... the kinds of a step (KMX_FILL_* of include/kmx.h), which are also the first four counters of a call, in the order of
+// kmx_fill_stats ...
+enum { FILL_HEAD = 0, FILL_N, FILL_ADJACENT, FILL_PATH, FILL_C_NO_ENTRY, FILL_C_MIRROR, FILL_C_REMOVED, FILL_C_FILLED, FILL_C_N };
+// ... what the scan carries per step: the scaffolds that start, the bytes, the pieces and the piece bytes in front of it, and the
+// last step in front of it that starts a scaffold ...
+struct FillTot {
+	u64 n, len, np, pb, first;
+};
+// ... and the input, the work arrays and the output of one call (fill_kernels.h).  pc_*: the n_pc pieces of the filled paths in
+// scaffold order: the oriented unitig, where its bytes go in fseq, and the piece bytes in front of it (pc_pre[n_pc] their total,
+// pbytes).  Every array of the caller is read and written under the bounds given here: U, n_ubases, S, n_plinks, n_psteps,
+// seq_cap, piece_cap.
+struct FillDev {
+	int k;
+	u32 kinds;
+	u64 U, n_ubases, S, n_plinks, n_psteps;
+	const unsigned char *useq;   // [n_ubases]
+	const u64 *uoffs;            // [U + 1]
+	const Scaffold *srec;        // [S]
+	const ScfStep *steps;        // [U]
+	const PairLink *plinks;      // [n_plinks]
+	const PairPath *precs;       // [n_plinks]
+	const u32 *psteps;           // [n_psteps]
+	FillTot *tot, *sc;           // [U + 1] each: per step, and scanned
+	u64 *ubase;                  // [U]: where the oriented string of u starts in fseq | CTG_REV | CTG_FIRST
+	unsigned long long *cnt;     // [FILL_C_N]
+	u32 *pc_o;                   // [n_pc]
+	u64 *pc_dst;                 // [n_pc]
+	u64 *pc_pre;                 // [n_pc + 1]
+	u64 n_pc, pbytes;
+	unsigned char *fseq;         // [seq_cap] or null
+	u64 seq_cap;
+	u64 *foffs;                  // [S + 1]
+	ScfFill *frec;               // [S]
+	FillStep *fsteps;            // [U]
+	u32 *pieces;                 // [piece_cap] or null
+	u64 piece_cap;
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

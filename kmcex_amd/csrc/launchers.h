@@ -120,4 +120,10 @@ hipError_t scaffold_bytes(const ScfDev &, u64 n_sbases, hipStream_t);
 hipError_t pair_path_search(const PathDev &, hipStream_t);
 hipError_t pair_path_scan(const PathDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t pair_path_apply(const PathDev &, hipStream_t);
+// ... and kmx_unitig_scaffold_fill* (fill_kernels.h): the kinds with the counters, the scan (its totals in D.sc[D.U]), steps,
+// records and pieces, the N fill and the two emits
+hipError_t fill_kinds(const FillDev &, hipStream_t);
+hipError_t fill_scan(const FillDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t fill_place(const FillDev &, hipStream_t);
+hipError_t fill_bytes(const FillDev &, u64 n_fbases, hipStream_t);
 }   // namespace kmxk

@@ -5,7 +5,7 @@
 // resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
 // (kmx_unitig_pair_walks*); its host side is pair_host.h.  Last the launchers of scaffold_kernels.h (kmx_unitig_scaffold*); their
 // host side is scaffold_host.h.  Behind them the launchers of pair_path_kernels.h (kmx_unitig_pair_paths*); their host side is
-// pair_path_host.h.
+// pair_path_host.h.  Last the launchers of fill_kernels.h (kmx_unitig_scaffold_fill*); their host side is fill_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -16,6 +16,7 @@
 #include "pair_kernels.h"
 #include "scaffold_kernels.h"
 #include "pair_path_kernels.h"
+#include "fill_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -28,6 +29,10 @@ struct TotPlus {
 };
 struct CtgPlus {
 	__host__ __device__ CtgTot operator()(const CtgTot &a, const CtgTot &b) const { return CtgTot{a.n + b.n, a.len + b.len, a.steps + b.steps}; }
+};
+
+struct FillPlus {
+	__host__ __device__ FillTot operator()(const FillTot &a, const FillTot &b) const { return FillTot{a.n + b.n, a.len + b.len, a.np + b.np, a.pb + b.pb, a.first > b.first ? a.first : b.first}; }
 };
 
 }   // namespace
@@ -381,6 +386,48 @@ hipError_t pair_path_scan(const PathDev &D, DevBuf<unsigned char> &tmp, hipStrea
 hipError_t pair_path_apply(const PathDev &D, hipStream_t st)
 {
 	hipLaunchKernelGGL(k_pp_apply, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_scaffold_fill* (fill_kernels.h); D.U > 0
+
+// the kind of every step with the call's counters, and what it writes: D.tot[U + 1]
+hipError_t fill_kinds(const FillDev &D, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.tot, 0, (D.U + 1) * sizeof(FillTot), st));
+	RCHK(hipMemsetAsync(D.cnt, 0, FILL_C_N * sizeof(unsigned long long), st));
+	if (D.S) hipLaunchKernelGGL(k_fill_heads, dim3(nblk(D.S)), dim3(256), 0, st, D);
+	hipLaunchKernelGGL(k_fill_kind, dim3(nblk(D.U)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the exclusive scan of D.tot into D.sc[U + 1]: D.sc[U] holds the scaffolds, the bytes, the pieces and the piece bytes of the call
+hipError_t fill_scan(const FillDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, (const FillTot *)D.tot, D.sc, FillTot{0, 0, 0, 0, 0}, (size_t)(D.U + 1), FillPlus(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, (const FillTot *)D.tot, D.sc, FillTot{0, 0, 0, 0, 0}, (size_t)(D.U + 1), FillPlus(), st));
+	return hipGetLastError();
+}
+
+// behind the scan and the host's wait for its totals (D.n_pc, D.pbytes and the piece arrays are set): steps, records, foffsets,
+// the words of the step emit and the pieces
+hipError_t fill_place(const FillDev &D, hipStream_t st)
+{
+	if (D.S) RCHK(hipMemsetAsync(D.frec, 0, D.S * sizeof(ScfFill), st));
+	RCHK(hipMemsetAsync(D.ubase, 0xFF, D.U * 8, st));
+	hipLaunchKernelGGL(k_fill_place, dim3(nblk(D.U + 1)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the bytes, n_fbases <= D.seq_cap of them: 'N' everywhere, the steps' own bytes by the tile emit over the flat input, the path
+// pieces by the gather emit over the piece bytes
+hipError_t fill_bytes(const FillDev &D, u64 n_fbases, hipStream_t st)
+{
+	if (n_fbases) RCHK(hipMemsetAsync(D.fseq, 'N', n_fbases, st));
+	if (D.n_ubases) hipLaunchKernelGGL(k_fill_step_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
+	if (D.pbytes && D.n_pc) hipLaunchKernelGGL(k_fill_emit, dim3((unsigned)((D.pbytes + FILL_TILE - 1) / FILL_TILE)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
