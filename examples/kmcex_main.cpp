@@ -49,6 +49,11 @@
 //          link: -T's conventions) and fills the links the bits of kinds ask for (3 when omitted; 1: links with a path, 2: links
 //          along one graph edge, whose two strings overlap by k - 1): scaffolds.filled.fa and scaffolds.fill.tsv (scaffold, step,
 //          unitig, strand, kind, entry, offset, bytes in front, path).  scaffolds.fa stays as it is
+//     -L[<tol>]  with -S: after the last batch, drop from the list that -S scaffolds the links that skip a unitig
+//          (KModel::pair_reduce at -S's min_pairs and inner; a link a -> c goes when links a -> b and b -> c explain its distance
+//          within tol windows, k when omitted; rows of more than 64 links are not searched: tol = k and 64 are conventions, not
+//          measured choices): pairs.reduced.tsv (entry, a, b, pairs, verdict, via, witnesses, g, delta).  The scaffolds, and with -F
+//          the pair paths and the fill, are then built from the reduced list.  -T keeps the full list
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -76,6 +81,7 @@ struct Params {
 	long scaf_ratio = 0;                                           // -S<min_pairs>,<ratio>
 	long path_tol = -2, path_steps = 8;                            // -T[<tol>[,<max_steps>]]: tol, -1 = k, -2 = no pair paths
 	long fill_kinds = -1;                                          // -F[<kinds>]: the links to fill, -1 = no filled scaffolds
+	long reduce_tol = -2;                                          // -L[<tol>]: tol, -1 = k, -2 = the list is scaffolded as it is
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -154,6 +160,11 @@ static bool parse(int argc, char **argv, Params &p)
 			p.fill_kinds = a[2] ? strtol(a + 2, &end, 10) : 3;
 			if (a[2] && (*end || p.fill_kinds < 0 || p.fill_kinds > 3)) return false;   // not a set of kinds
 		}
+		else if (!strncmp(a, "-L", 2)) {
+			char *end = nullptr;
+			p.reduce_tol = a[2] ? strtol(a + 2, &end, 10) : -1;
+			if (a[2] && (*end || p.reduce_tol < 0 || p.reduce_tol > 0xFFFFFFFFL)) return false;   // not a number of windows
+		}
 		else if (!strncmp(a, "-P", 2)) {
 			char *end = nullptr;
 			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
@@ -207,6 +218,10 @@ static bool parse(int argc, char **argv, Params &p)
 		std::cout << "-F needs -S: it fills the gaps of the scaffolds\n";
 		return false;
 	}
+	if (p.reduce_tol > -2 && p.scaf_min < 0) {                     // the reduced list is the one the scaffolds are built from
+		std::cout << "-L needs -S: it reduces the list of pair links the scaffolds are built from\n";
+		return false;
+	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
 }
 
@@ -258,9 +273,22 @@ struct InnerSum {
 
 // -S: the scaffolds of `strs` from `plinks`, written as scaffolds.fa, scaffolds.paths.tsv and scaffolds.agp; with -F also the
 // scaffolds filled along the paths of the graph (link_offsets, links) of `strs`: scaffolds.filled.fa and scaffolds.fill.tsv
-static bool write_scaffolds(KModel *km, const std::string &dir, const std::vector<std::string> &strs, const std::vector<kmx_unitig> *rec, const std::vector<kmx_pair_link> &plinks, const Params &p,
+static bool write_scaffolds(KModel *km, const std::string &dir, const std::vector<std::string> &strs, const std::vector<kmx_unitig> *rec, const std::vector<kmx_pair_link> &full, const Params &p,
                             uint32_t inner, uint32_t max_dist, const char *what, const std::vector<uint64_t> &link_offsets, const std::vector<uint32_t> &links)
 {
+	KModel::PairReduced red;
+	if (p.reduce_tol > -2) {                                       // -L: the links that skip a unitig go first
+		const kmx_pair_reduce_params rp = {(uint64_t)p.scaf_min, inner, p.reduce_tol < 0 ? (uint32_t)p.k : (uint32_t)p.reduce_tol, 64, 0};
+		red = km->pair_reduce(strs, full, p.k, rp);
+		std::ofstream rt((dir + "/pairs.reduced.tsv").c_str());
+		KModel::write_pair_reduce_tsv(rt, full, red);
+		rt.close();
+		if (!rt) { std::cout << "could not write " << dir << "/pairs.reduced.tsv" << std::endl; return false; }
+		std::cout << "   pair links of " << what << " reduced (tol " << rp.tol << ", rows of <= " << rp.max_row << ", inner " << inner << ") :     " << red.stats.n_transitive << " of " << red.stats.n_entries
+		          << " links skip a unitig (" << red.stats.n_kept << " kept, " << red.stats.n_complex << " complex, " << red.stats.n_below_min << " below " << p.scaf_min << " pairs, " << red.stats.n_ignored
+		          << " ignored), " << red.stats.n_out << " links stay" << std::endl;
+	}
+	const std::vector<kmx_pair_link> &plinks = p.reduce_tol > -2 ? red.list : full;
 	const uint64_t max_n = 2 * (uint64_t)max_dist;
 	const kmx_scaffold_params sp = {(uint64_t)p.scaf_min, (uint32_t)p.scaf_ratio, inner, max_n < 10 ? (uint32_t)max_n : 10u, max_n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)max_n, 0};
 	const KModel::Scaffolds sc = km->unitig_scaffold(strs, rec, plinks, p.k, sp);
@@ -321,7 +349,10 @@ int main(int argc, char **argv)
 		             "           the insert size, at most max_steps (8) unitigs) and count its pairs as reads through its unitigs: pairs.paths.tsv\n"
 		             "       -F[<kinds>]  with -S: fill the scaffolds' gaps with the bases of the one graph path that fits (kinds & 1) and trim the overlap\n"
 		             "           of two steps along one edge (kinds & 2; 3 when omitted): scaffolds.filled.fa, scaffolds.fill.tsv (scaffold, step,\n"
-		             "           unitig, strand, kind, entry, offset, bytes in front, path)\n";
+		             "           unitig, strand, kind, entry, offset, bytes in front, path)\n"
+		             "       -L[<tol>]  with -S: first drop the pair links that skip a unitig (a -> c where a -> b and b -> c explain its distance within tol\n"
+		             "           (k) windows; rows of more than 64 links are not searched; both are conventions, not measured choices):\n"
+		             "           pairs.reduced.tsv (entry, a, b, pairs, verdict, via, witnesses, g, delta); -S and -F then work on the reduced list\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");

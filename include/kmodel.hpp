@@ -778,6 +778,48 @@ public:
 		}
 	}
 
+	// Reduced pair lists (the rule: kmx.h): the list seq_pairs left without the entries that skip a unitig, so that the entries on
+	// both sides of a short unitig become the scaffold's chain links.  pair_reduce takes the unitig strings (only their lengths are
+	// used) and the list; it needs no session and no graph, and it gives the list room for every entry, so it never comes back
+	// short.  unitig_scaffold, pair_paths and scaffold_fill take `list` as they take the full one.
+	struct PairReduced {
+		std::vector<kmx_pair_reduce> rec;            // one per entry of the input list
+		std::vector<kmx_pair_link> list;             // the entries that stay, in input order
+		std::vector<uint32_t> origin;                // the input index of every entry of list
+		kmx_pair_reduce_stats stats;
+	};
+	PairReduced pair_reduce(const std::vector<std::string> &unitigs, const std::vector<kmx_pair_link> &plinks, int k, const kmx_pair_reduce_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), np = plinks.size();
+		PairReduced r;
+		r.stats = kmx_pair_reduce_stats();
+		r.rec.resize(np + 1);
+		r.list.resize(np + 1);
+		r.origin.resize(np + 1);
+		uint64_t n = 0;
+		check(kmx_unitig_pair_reduce(h_, k, f.off.data(), U, np ? &plinks[0] : 0, np, &params, &r.rec[0], &r.list[0], &r.origin[0], np, &n, &r.stats));
+		r.rec.resize(np);
+		r.list.resize((size_t)n);
+		r.origin.resize((size_t)n);
+		return r;
+	}
+	// the verdicts as a table, one "<entry>\tu<a><+|->\tu<b><+|->\t<pairs>\t<verdict>\t<via>\t<n_via>\t<g>\t<delta>" per entry of the
+	// input list: via with the orientation signs of reads.gaf (">u3", "<u3"), "*" for none
+	static void write_pair_reduce_tsv(std::ostream &out, const std::vector<kmx_pair_link> &plinks, const PairReduced &p)
+	{
+		static const char *const names[] = {"IGNORED", "BELOW_MIN", "KEPT", "TRANSITIVE", "COMPLEX"};
+		for (size_t i = 0; i < plinks.size() && i < p.rec.size(); i++) {
+			const kmx_pair_link &e = plinks[i];
+			const kmx_pair_reduce &r = p.rec[i];
+			out << i << "\tu" << (e.a >> 1) << ((e.a & 1) ? '-' : '+') << "\tu" << (e.b >> 1) << ((e.b & 1) ? '-' : '+') << "\t" << e.n_pairs << "\t" << (r.verdict <= KMX_REDUCE_COMPLEX ? names[r.verdict] : "?")
+			    << "\t";
+			if (r.via == 0xFFFFFFFFu) out << "*";
+			else out << ((r.via & 1) ? '<' : '>') << "u" << (r.via >> 1);
+			out << "\t" << r.n_via << "\t" << (long long)r.g << "\t" << (long long)r.delta << "\n";
+		}
+	}
+
 	// Filled scaffolds (the rule: kmx.h): the scaffolds spelled again, with the graph's own bases in every gap that pair_paths found
 	// the one path for (kinds bit 0) and the k - 1 overlap trimmed where two steps share a graph edge (bit 1).  scaffold_fill takes
 	// the unitig strings the scaffolds were made of, what unitig_scaffold and pair_paths returned on the same list, and the list;

@@ -1237,9 +1237,9 @@ int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_
  *   (c) place inverts steps; the n_steps sum to U; n_sbases = n_ubases + the sum of n_gap_bases;
  *   (d) two islands of one genome that the pairs span come out as one scaffold with the hole as a run of 'N' of its true length,
  *       when inner is the library's d.
- * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; links that skip
- * a unitig (transitive reduction); RF and FF libraries; several GPUs; choosing min_pairs and inner.  Gaps the graph can spell:
- * kmx_unitig_scaffold_fill below.                                                                                           */
+ * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; RF and FF
+ * libraries; several GPUs; choosing min_pairs and inner.  Gaps the graph can spell: kmx_unitig_scaffold_fill below.  Links that
+ * skip a unitig: kmx_unitig_pair_reduce below drops them from the list before this call.                                    */
 typedef struct kmx_scaffold_params { uint64_t min_pairs; uint32_t ratio /* [0, 65536] */; uint32_t inner; uint32_t min_n, max_n /* min_n <= max_n */;
                                      uint64_t reserved /* 0 */; } kmx_scaffold_params;                                  /* 32 bytes */
 #define KMX_SCAFFOLD_CIRCULAR 0x80000000u
@@ -1492,6 +1492,95 @@ int kmx_unitig_scaffold_fill_dev(kmx_model *m, int k, const char *d_useq, const 
 /* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): the kinds, the scan with the wait, steps with records
  * and pieces, the bytes */
 int kmx_unitig_scaffold_fill_last_phases(kmx_model *m, double *seconds /* [4] */);
+
+/* ---- reduced pair lists: a pair list without the entries that skip a unitig.  The scaffold call joins two unitigs only where a
+ * pair link is the one kept edge out of a and the one kept edge into c.  A fragment that is longer than a short unitig b spans
+ * it, so the list of kmx_unitig_pair_walks holds a -> b, b -> c and the skipping entry a -> c; then nk(a) = 2 and nk(c ^ 1) = 2,
+ * none of the three is a chain link, and the scaffold breaks at exactly the place the pairs describe best.  This call returns the
+ * same list without the entries that two other entries explain (its transitive reduction, one unitig deep).
+ * kmx_unitig_scaffold, kmx_unitig_pair_paths and kmx_unitig_scaffold_fill consume the result unchanged.  It needs no built model,
+ * no session, no bases and no CSR; uoffsets is read only for m_u = len_u - k + 1 (0 for what is shorter than k).
+ * Input: k, odd, in [5, 63]; uoffsets[U + 1], U < 2^31; plinks[n_plinks] as kmx_unitig_pair_walks leaves it, n_plinks < 2^31; and
+ *   kmx_pair_reduce_params: max_row in [1, 65536], reserved = 0.  All arithmetic is signed 64-bit, two's complement, wrapping.
+ *   ELIGIBLE.  Entry i = (a, c, n_pairs, sum_dist, ...) is eligible iff it is a pair link by the scaffold's definition (a < 2 U,
+ *     c < 2 U, a >> 1 != c >> 1, n_pairs >= 1) and n_pairs >= min_pairs.  An entry that is no pair link is KMX_REDUCE_IGNORED, a
+ *     pair link below min_pairs KMX_REDUCE_BELOW_MIN; neither is examined and neither serves as a witness.
+ *   g(i) = inner - 1 - sum_dist / n_pairs (unsigned floor division): the scaffold's g, the windows missing between the two.
+ *   TABLE.  Every eligible entry gives two rows, (a, c, i) and (c ^ 1, a ^ 1, i).  The rows are sorted ascending by (src, dst, i).
+ *     out(o) is the contiguous run of rows with src = o; first(x, y) is the first row with src = x and dst = y, or none.  In a
+ *     canonical list every oriented edge has exactly one row; the definition holds as it stands for the lists that are not
+ *     canonical or carry duplicate keys, which the _dev form accepts.
+ *   SIDE.  r_a = |out(a)|, r_c = |out(c ^ 1)|; side = 0 if r_a <= r_c, else 1.  min(r_a, r_c) > max_row: KMX_REDUCE_COMPLEX; the
+ *     entry stays, with n_via = 0, via = 0xFFFFFFFF and delta = 0 (side and g are reported).
+ *   WITNESSES.  On side 0, for every row (a, b, j) of out(a) with F = first(b, c) present:
+ *     delta = g(i) - (g(j) + m_(b >> 1) + g(F.i)).  On side 1, for every row (c ^ 1, y, j) of out(c ^ 1), with b = y ^ 1 and
+ *     F = first(a, b) present: delta = g(i) - (g(F.i) + m_(b >> 1) + g(j)).  The row is a witness iff -tol <= delta <= tol
+ *     (signed).  The entry's own rows never qualify: first(c, c) does not exist.  n_via = the witness rows on the enumerated
+ *     side; via = the smallest b over them; delta = the delta of that witness: of the first such row in table order on side 0,
+ *     of the last on side 1.
+ *   VERDICT.  KMX_REDUCE_TRANSITIVE iff n_via >= 1, otherwise KMX_REDUCE_KEPT.  Every verdict is taken on the INPUT list at once:
+ *     a transitive entry still serves as a witness, so no order shows.
+ * Output.  rrecs[n_plinks], the records below; for an entry that is not examined g and delta are 0 and via is all ones.
+ *   lout[capacity]: every entry whose verdict is not TRANSITIVE, byte-identical and in input order, so a strictly ascending list
+ *   stays one; origin[capacity]: origin[j] is the input index of output entry j.  Either may be NULL; with both NULL no list is
+ *   built and the call gives the verdicts only (the sizing call: KMX_OK, *n_out what a list would hold).  Otherwise
+ *   *n_out > capacity: KMX_E_RANGE with rrecs, stats and *n_out complete and nothing written to lout or origin; capacity =
+ *   n_plinks always suffices.  On the HOST in both forms: *n_out and kmx_pair_reduce_stats; n_rows = the rows of the table,
+ *   n_examined = the rows enumerated (min(r_a, r_c) summed over the KEPT and TRANSITIVE entries).
+ * Consequences:
+ *   (a) with min_pairs above every entry, or n_plinks < 3, lout is the input byte for byte;
+ *   (b) n_ignored + n_below_min + n_kept + n_transitive + n_complex == n_entries, and n_out = n_entries - n_transitive;
+ *   (c) in a canonical list in which no unitig is a witness in both orientations, replacing an entry by its mirror (c ^ 1, a ^ 1)
+ *       changes none of verdict, n_via, g, delta for any entry, and changes via only by ^ 1 for that entry;
+ *   (d) lout is a valid input for the scaffold, pair-path and fill calls;
+ *   (e) three islands of one genome, the middle one shorter than the fragment, come out of kmx_unitig_scaffold on lout as one
+ *       scaffold with both holes as runs of 'N' of their true length; on the full list they stay three.
+ *   (f) every output is an integer count, sum or minimum and a function of the input alone: byte-identical across runs and forms.
+ * Out of scope: crediting a removed entry's pairs to its two witnesses; skips of more than one unitig without the intermediate
+ * skips (a -> d with only a -> b -> c -> d stays KEPT); iterating; choosing tol; RF and FF libraries; several GPUs.           */
+#define KMX_REDUCE_IGNORED    0
+#define KMX_REDUCE_BELOW_MIN  1
+#define KMX_REDUCE_KEPT       2
+#define KMX_REDUCE_TRANSITIVE 3
+#define KMX_REDUCE_COMPLEX    4
+typedef struct kmx_pair_reduce_params { uint64_t min_pairs; uint32_t inner, tol, max_row /* [1, 65536] */, reserved /* 0 */; } kmx_pair_reduce_params;   /* 24 bytes */
+typedef struct kmx_pair_reduce {         /* one per entry of the list; 32 bytes, no padding */
+	uint32_t verdict;                    /* KMX_REDUCE_* */
+	uint32_t via;                        /* the smallest witness b, 0xFFFFFFFF for none */
+	uint32_t n_via;                      /* the witness rows on the enumerated side */
+	uint32_t side;                       /* 0: out(a) was enumerated, 1: out(c ^ 1) */
+	int64_t g;                           /* g(i) */
+	int64_t delta;                       /* the delta of via's witness */
+} kmx_pair_reduce;
+typedef struct kmx_pair_reduce_stats { uint64_t n_entries, n_ignored, n_below_min, n_kept, n_transitive, n_complex, n_out, n_rows, n_examined /* rows enumerated */,
+                                       reserved; } kmx_pair_reduce_stats;                                               /* 80 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_unitig_scaffold); it runs on the model's stream and is a
+ * build-class call.  lout and origin may be NULL, plinks and rrecs with n_plinks == 0; every other buffer is required.
+ * KMX_E_ARG before anything runs: an even or out-of-range k, U >= 2^31, n_plinks >= 2^31, max_row outside [1, 65536],
+ * reserved != 0, a NULL required buffer, an output that overlaps an input or another output; uoffsets whose first entry is not 0,
+ * that decrease, or that give a unitig fewer than k bytes; a list that is not strictly ascending by a << 32 | b.  U == 0: KMX_OK,
+ * every entry is IGNORED and lout is the input.  n_plinks == 0: KMX_OK, all counts zero.  KMX_E_NOMEM leaves the handle usable.
+ * The call returns when the output is complete.                                                                             */
+int kmx_unitig_pair_reduce(kmx_model *m, int k, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_pair_link *plinks, uint64_t n_plinks,
+                           const kmx_pair_reduce_params *params, kmx_pair_reduce *rrecs /* [n_plinks] */, kmx_pair_link *lout /* [capacity] or NULL */,
+                           uint32_t *origin /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_out, kmx_pair_reduce_stats *stats);
+/* The same on DEVICE buffers, read where the pair call left them; params, *n_out and stats are on the HOST.  It checks k, U,
+ * n_plinks, the parameters, NULL and overlap, and validates nothing else; the kernels clamp instead: uoffsets into
+ * [0, n_ubases], and the list is taken as it is (not ascending, not canonical, duplicate keys, an entry beside its mirror: the
+ * table above is defined for all of them).  Every store is checked against its capacity: bad device input gives wrong verdicts
+ * and never an access outside a buffer.  No entry costs more than max_row rows.  It enqueues the rows, one stable radix sort of
+ * the 2 n_plinks (key, row) pairs, the verdicts (8 lanes per entry) and the scan of the keep flags on the model's stream and
+ * waits once, for *n_out and the counters; the entries that stay are copied only after that wait has shown that they fit, and a
+ * last wait behind the copy leaves nothing in flight.  Device memory, kept on the handle between calls through the owning
+ * types of hip_owned.h: 60 bytes per entry (2 x (8 + 4) x 2 for the sort's double buffers of the two rows, 4 for the keep flag,
+ * 8 for its scan) plus rocPRIM's scratch.  The host form also stages its input and output there.                             */
+int kmx_unitig_pair_reduce_dev(kmx_model *m, int k, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, uint64_t n_ubases, const kmx_pair_link *d_plinks,
+                               uint64_t n_plinks, const kmx_pair_reduce_params *params /* HOST */, kmx_pair_reduce *d_rrecs /* [n_plinks] */,
+                               kmx_pair_link *d_lout /* [capacity] or NULL */, uint32_t *d_origin /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_out /* HOST */,
+                               kmx_pair_reduce_stats *stats /* HOST */);
+/* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): the rows, the sort, the verdicts, the scan with the
+ * wait and the compaction */
+int kmx_unitig_pair_reduce_last_phases(kmx_model *m, double *seconds /* [4] */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_pair_walks", "kmx_unitig_pair_walks_dev",
     "kmx_unitig_scaffold", "kmx_unitig_scaffold_dev", "kmx_unitig_scaffold_last_phases",
     "kmx_unitig_pair_paths", "kmx_unitig_pair_paths_dev", "kmx_unitig_pair_paths_last_phases",
+    "kmx_unitig_pair_reduce", "kmx_unitig_pair_reduce_dev", "kmx_unitig_pair_reduce_last_phases",
     "kmx_unitig_scaffold_fill", "kmx_unitig_scaffold_fill_dev", "kmx_unitig_scaffold_fill_last_phases",
 ]
 
@@ -303,6 +304,25 @@ FILL_KINDS = {0: "HEAD", 1: "N", 2: "ADJACENT", 3: "PATH"}
 FILL_NO_ENTRY = 0xFFFFFFFF
 
 
+class PairReduceParams(C.Structure):
+    """kmx_pair_reduce_params of include/kmx.h: 24 bytes"""
+    _fields_ = [("min_pairs", C.c_uint64), ("inner", C.c_uint32), ("tol", C.c_uint32), ("max_row", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PairReduceStats(C.Structure):
+    """kmx_pair_reduce_stats of include/kmx.h: 80 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_entries", "n_ignored", "n_below_min", "n_kept", "n_transitive", "n_complex", "n_out", "n_rows", "n_examined", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_pair_reduce as a NumPy structured dtype (what KModel.unitig_pair_reduce_flat returns): 32 bytes
+PAIR_REDUCE_DTYPE = np.dtype([("verdict", "<u4"), ("via", "<u4"), ("n_via", "<u4"), ("side", "<u4"), ("g", "<i8"), ("delta", "<i8")])
+PAIR_REDUCE_VERDICTS = {0: "IGNORED", 1: "BELOW_MIN", 2: "KEPT", 3: "TRANSITIVE", 4: "COMPLEX"}
+PAIR_REDUCE_NO_VIA = 0xFFFFFFFF
+
+
 class RingList(C.Structure):
     """kmx_ring_list of include/kmx.h"""
     _fields_ = [("list", C.c_int32), ("n_host", C.c_int32), ("src_kmers", C.c_void_p), ("src_counts", C.c_void_p),
@@ -460,6 +480,9 @@ def load_library():
     _sig(L, "kmx_unitig_pair_paths", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
     _sig(L, "kmx_unitig_pair_paths_dev", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairPathParams), vp, vp, u64, p64, vp, vp, C.POINTER(PairPathStats)])
     _sig(L, "kmx_unitig_pair_paths_last_phases", [vp, C.POINTER(C.c_double)])
+    _sig(L, "kmx_unitig_pair_reduce", [vp, C.c_int, vp, u64, vp, u64, C.POINTER(PairReduceParams), vp, vp, vp, u64, p64, C.POINTER(PairReduceStats)])
+    _sig(L, "kmx_unitig_pair_reduce_dev", [vp, C.c_int, vp, u64, u64, vp, u64, C.POINTER(PairReduceParams), vp, vp, vp, u64, p64, C.POINTER(PairReduceStats)])
+    _sig(L, "kmx_unitig_pair_reduce_last_phases", [vp, C.POINTER(C.c_double)])
     _sig(L, "kmx_unitig_scaffold_fill", [vp, C.c_int, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
     _sig(L, "kmx_unitig_scaffold_fill_dev", [vp, C.c_int, vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
     _sig(L, "kmx_unitig_scaffold_fill_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1499,6 +1522,68 @@ class KModel:
         sec = (C.c_double * 3)()
         _chk(self.L.kmx_unitig_pair_paths_last_phases(self.h, sec))
         return dict(zip(("search", "scan", "apply"), (float(x) for x in sec)))
+
+    # ---- reduced pair lists: a pair list without the entries that skip a unitig (the rule: include/kmx.h); no model, no session
+    def unitig_pair_reduce_flat(self, k: int, uoffsets: np.ndarray, plinks: np.ndarray, inner: int, tol: int, min_pairs: int = 2, max_row: int = 64, capacity=None, lists: bool = True):
+        """kmx_unitig_pair_reduce on the offsets of a unitig set (uint64 [U + 1]) and the PAIR_LINK_DTYPE list unitig_pairs_flat left
+        -> (PAIR_REDUCE_DTYPE records [n_plinks], the PAIR_LINK_DTYPE list that stays or None, uint32 origin or None, stats as a
+        dict).  capacity None: n_plinks, which always suffices; a number: that many entries (KmxError KMX_E_RANGE when short: its
+        `needed` the entries needed, its `result` the records and the stats).  lists False: the verdicts only."""
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        plinks = np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+        nu, np_ = uoffsets.size - 1, plinks.size
+        cap = np_ if capacity is None else int(capacity)
+        rec = np.zeros(max(np_, 1), dtype=PAIR_REDUCE_DTYPE)
+        lout = np.zeros(max(cap, 1), dtype=PAIR_LINK_DTYPE) if lists else None
+        org = np.zeros(max(cap, 1), dtype=np.uint32) if lists else None
+        par, st, n = PairReduceParams(int(min_pairs), int(inner), int(tol), int(max_row), 0), PairReduceStats(), C.c_uint64(0)
+        try:
+            _chk(self.L.kmx_unitig_pair_reduce(self.h, int(k), uoffsets.ctypes.data, nu, plinks.ctypes.data if np_ else None, np_, C.byref(par), rec.ctypes.data,
+                                               lout.ctypes.data if lists else None, org.ctypes.data if lists else None, cap if lists else 0, C.byref(n), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            e.result = (rec[:np_].copy(), st.as_dict())
+            raise
+        return rec[:np_].copy(), (lout[:n.value].copy() if lists else None), (org[:n.value].copy() if lists else None), st.as_dict()
+
+    def unitig_pair_reduce_dev(self, k: int, d_uoffsets, n_ubases: int, d_plinks, n_plinks: int, inner: int, tol: int, min_pairs: int = 2, max_row: int = 64, capacity=None, out=None):
+        """kmx_unitig_pair_reduce_dev on torch tensors of the model's device, read where the pair call left them: d_uoffsets int64
+        [U + 1], d_plinks uint8 [>= n_plinks, 32].  out: (d_rrecs uint8 [n_plinks, 32], d_lout uint8 [capacity, 32] or None, d_origin
+        int32 [capacity] or None; both None: the verdicts only), allocated when None with `capacity` entries (None: n_plinks) ->
+        (out, the entries that stay, stats as a dict).  KmxError KMX_E_RANGE carries the entries needed in `needed` and the stats
+        in `result`."""
+        import torch
+        nu, dev = d_uoffsets.numel() - 1, d_uoffsets.device
+        if out is None:
+            cap = int(n_plinks) if capacity is None else int(capacity)
+            out = (torch.zeros((max(int(n_plinks), 1), 32), dtype=torch.uint8, device=dev), torch.zeros((max(cap, 1), 32), dtype=torch.uint8, device=dev),
+                   torch.zeros(max(cap, 1), dtype=torch.int32, device=dev))
+        else:
+            cap = min(t.shape[0] for t in out[1:] if t is not None) if capacity is None and (out[1] is not None or out[2] is not None) else int(capacity or 0)
+        par, st, n = PairReduceParams(int(min_pairs), int(inner), int(tol), int(max_row), 0), PairReduceStats(), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            _chk(self.L.kmx_unitig_pair_reduce_dev(self.h, int(k), d_uoffsets.data_ptr(), nu, int(n_ubases), ptr(d_plinks) if n_plinks else None, int(n_plinks), C.byref(par), out[0].data_ptr(),
+                                                   ptr(out[1]), ptr(out[2]), cap, C.byref(n), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            e.result = st.as_dict()
+            raise
+        return out, int(n.value), st.as_dict()
+
+    def unitig_pair_reduce_phases(self) -> dict:
+        """kmx_unitig_pair_reduce_last_phases: seconds per phase of the last reduce call (under set_profile(1))"""
+        sec = (C.c_double * 4)()
+        _chk(self.L.kmx_unitig_pair_reduce_last_phases(self.h, sec))
+        return dict(zip(("rows", "sort", "verdicts", "compact"), (float(x) for x in sec)))
+
+    def reduced_scaffolds_from_pairs(self, k: int, strs, plinks: np.ndarray, inner: int, min_pairs: int = 2, ratio: int = 0, min_n: int = 10, max_n: int = 1000, tol=None, max_row: int = 64):
+        """on a list of unitig or contig strings and a pair list: unitig_pair_reduce_flat at min_pairs and inner with tol (None: k),
+        then scaffolds_from_pairs on the list that stays -> (what scaffolds_from_pairs returns, then the reduce records, the
+        reduced list and the reduce stats)"""
+        _, _, _, uoffs = _join_seqs(list(strs))
+        rec, lout, _, rst = self.unitig_pair_reduce_flat(k, uoffs, plinks, inner, int(k) if tol is None else int(tol), min_pairs, max_row)
+        return self.scaffolds_from_pairs(k, strs, lout, inner, min_pairs, ratio, min_n, max_n) + (rec, lout, rst)
 
     # ---- filled scaffolds: the scaffolds spelled again with the graph's bases in the gaps the pair paths cross (the rule:
     # include/kmx.h); no model, no session, no CSR

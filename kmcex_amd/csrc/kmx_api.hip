@@ -435,6 +435,14 @@ struct kmx_model {
 		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
 		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): kinds, scan with the wait, records, bytes
 	} fill;
+	// kmx_unitig_pair_reduce* (reduce_host.h): the work arrays of a call, kept by capacity from call to call
+	struct ReduceState {
+		DevBuf<u64> d_key, d_sc;                                   // d_key: [2][2 E] the rows' keys and their sorted copy; d_sc: [E + 1] the scanned keep flags
+		DevBuf<u32> d_val, d_flag;                                 // d_val: [2][2 E] the rows' numbers and their sorted copy; d_flag: [E] the entry stays
+		DevBuf<unsigned long long> d_cnt;                          // [RED_C_N]
+		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
+		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): rows, sort, verdicts, scan with the wait and the compaction
+	} red;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2970,6 +2978,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "scaffold_host.h"
 #include "pair_path_host.h"
 #include "fill_host.h"
+#include "reduce_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3517,6 +3526,9 @@ extern "C" int kmx_unitig_pair_paths_last_phases(kmx_model *m, double *seconds) 
 extern "C" int kmx_unitig_scaffold_fill(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_scaffold *srec, uint64_t n_scaffolds, const kmx_scaffold_step *steps, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_path *precs, const uint32_t *psteps, uint64_t n_psteps, const kmx_fill_params *params, char *fseq, uint64_t seq_capacity, uint64_t *foffsets, kmx_scaffold_fill *frec, kmx_fill_step *fsteps, uint32_t *pieces, uint64_t piece_capacity, uint64_t *n_fbases, uint64_t *n_pieces, kmx_fill_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_fill_impl(m, FillArgs{k, useq, uoffsets, n_unitigs, 0, srec, n_scaffolds, steps, plinks, n_plinks, precs, psteps, n_psteps, params, fseq, seq_capacity, foffsets, frec, fsteps, pieces, piece_capacity, n_fbases, n_pieces, stats}); }); }
 extern "C" int kmx_unitig_scaffold_fill_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_scaffold *d_srec, uint64_t n_scaffolds, const kmx_scaffold_step *d_steps, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_path *d_precs, const uint32_t *d_psteps, uint64_t n_psteps, const kmx_fill_params *params, char *d_fseq, uint64_t seq_capacity, uint64_t *d_foffsets, kmx_scaffold_fill *d_frec, kmx_fill_step *d_fsteps, uint32_t *d_pieces, uint64_t piece_capacity, uint64_t *n_fbases, uint64_t *n_pieces, kmx_fill_stats *stats) { return guarded([&] { return kmx_unitig_scaffold_fill_dev_impl(m, FillArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_srec, n_scaffolds, d_steps, d_plinks, n_plinks, d_precs, d_psteps, n_psteps, params, d_fseq, seq_capacity, d_foffsets, d_frec, d_fsteps, d_pieces, piece_capacity, n_fbases, n_pieces, stats}); }); }
 extern "C" int kmx_unitig_scaffold_fill_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_scaffold_fill_last_phases_impl(m, seconds); }); }
+extern "C" int kmx_unitig_pair_reduce(kmx_model *m, int k, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_reduce_params *params, kmx_pair_reduce *rrecs, kmx_pair_link *lout, uint32_t *origin, uint64_t capacity, uint64_t *n_out, kmx_pair_reduce_stats *stats) { return guarded([&] { return kmx_unitig_pair_reduce_impl(m, RedArgs{k, uoffsets, n_unitigs, 0, plinks, n_plinks, params, rrecs, lout, origin, capacity, n_out, stats}); }); }
+extern "C" int kmx_unitig_pair_reduce_dev(kmx_model *m, int k, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_reduce_params *params, kmx_pair_reduce *d_rrecs, kmx_pair_link *d_lout, uint32_t *d_origin, uint64_t capacity, uint64_t *n_out, kmx_pair_reduce_stats *stats) { return guarded([&] { return kmx_unitig_pair_reduce_dev_impl(m, RedArgs{k, d_uoffsets, n_unitigs, n_ubases, d_plinks, n_plinks, params, d_rrecs, d_lout, d_origin, capacity, n_out, stats}); }); }
+extern "C" int kmx_unitig_pair_reduce_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_pair_reduce_last_phases_impl(m, seconds); }); }
 extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, ResArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, ResArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }

@@ -709,6 +709,36 @@ struct FillDev {
 	u32 *pieces;                 // [piece_cap] or null
 	u64 piece_cap;
 };
+// kmx_unitig_pair_reduce*: the record of a list entry, the layout of kmx_pair_reduce (include/kmx.h; reduce_host.h asserts it) ...
+struct PairReduce {
+	u32 verdict, via, n_via, side;
+	long long g, delta;
+};
+// ... the verdicts (KMX_REDUCE_* of include/kmx.h), which are also the first five counters of a call, in the order of
+// kmx_pair_reduce_stats behind n_entries ...
+enum { RED_IGNORED = 0, RED_BELOW_MIN, RED_KEPT, RED_TRANSITIVE, RED_COMPLEX, RED_C_EXAMINED, RED_C_N };
+static constexpr u64 RED_NO_KEY = ~0ULL;                         // the row key of an entry that gives no rows: behind every real row
+// ... and the input, the work arrays and the output of one call (reduce_kernels.h).  The table: key[2 n_plinks] = src << 32 | dst
+// of the rows 2 i and 2 i + 1 of entry i (RED_NO_KEY for an entry that is not eligible), val = the row's number; skey, sval: the
+// same sorted by key, stably, so rows of one key are in entry order.  flag[n_plinks]: 1 for an entry that stays; sc[n_plinks + 1]:
+// its exclusive scan, sc[n_plinks] is n_out.  Every array of the caller is read and written under the bounds given
+// here: U, n_ubases, n_plinks, cap.
+struct RedDev {
+	int k;
+	u64 U, n_ubases, n_plinks, cap;
+	const u64 *uoffs;            // [U + 1]
+	const PairLink *plinks;      // [n_plinks]
+	u64 min_pairs;
+	u32 inner, tol, max_row;
+	PairReduce *rrecs;           // [n_plinks]
+	PairLink *lout;              // [cap] or null
+	u32 *origin;                 // [cap] or null
+	u64 *key, *skey;             // [2 n_plinks] each
+	u32 *val, *sval;             // [2 n_plinks] each
+	u32 *flag;                   // [n_plinks]
+	u64 *sc;                     // [n_plinks + 1]
+	unsigned long long *cnt;     // [RED_C_N]
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

@@ -126,4 +126,11 @@ hipError_t fill_kinds(const FillDev &, hipStream_t);
 hipError_t fill_scan(const FillDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t fill_place(const FillDev &, hipStream_t);
 hipError_t fill_bytes(const FillDev &, u64 n_fbases, hipStream_t);
+// ... and kmx_unitig_pair_reduce* (reduce_kernels.h): the rows and their sort, the verdicts with the keep flags, the scan (its
+// total in D.sc[D.n_plinks]), the entries that stay
+hipError_t reduce_rows(const RedDev &, hipStream_t);
+hipError_t reduce_sort(const RedDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t reduce_verdicts(const RedDev &, hipStream_t);
+hipError_t reduce_scan(const RedDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t reduce_compact(const RedDev &, hipStream_t);
 }   // namespace kmxk

@@ -5,7 +5,8 @@
 // resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
 // (kmx_unitig_pair_walks*); its host side is pair_host.h.  Last the launchers of scaffold_kernels.h (kmx_unitig_scaffold*); their
 // host side is scaffold_host.h.  Behind them the launchers of pair_path_kernels.h (kmx_unitig_pair_paths*); their host side is
-// pair_path_host.h.  Last the launchers of fill_kernels.h (kmx_unitig_scaffold_fill*); their host side is fill_host.h.
+// pair_path_host.h.  Then the launchers of fill_kernels.h (kmx_unitig_scaffold_fill*); their host side is fill_host.h.  Last the
+// launchers of reduce_kernels.h (kmx_unitig_pair_reduce*); their host side is reduce_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -17,6 +18,7 @@
 #include "scaffold_kernels.h"
 #include "pair_path_kernels.h"
 #include "fill_kernels.h"
+#include "reduce_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -428,6 +430,51 @@ hipError_t fill_bytes(const FillDev &D, u64 n_fbases, hipStream_t st)
 	if (n_fbases) RCHK(hipMemsetAsync(D.fseq, 'N', n_fbases, st));
 	if (D.n_ubases) hipLaunchKernelGGL(k_fill_step_emit, dim3((unsigned)((D.n_ubases + CTG_TILE - 1) / CTG_TILE)), dim3(256), 0, st, D);
 	if (D.pbytes && D.n_pc) hipLaunchKernelGGL(k_fill_emit, dim3((unsigned)((D.pbytes + FILL_TILE - 1) / FILL_TILE)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_pair_reduce* (reduce_kernels.h); D.n_plinks > 0
+
+// eligibility and g of every entry with the two counters, and its two rows
+hipError_t reduce_rows(const RedDev &D, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.cnt, 0, RED_C_N * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(k_red_rows, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the table sorted by src << 32 | dst: the sort is stable, so rows of one key stay in entry order
+hipError_t reduce_sort(const RedDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	RCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.key, D.skey, D.val, D.sval, (size_t)(2 * D.n_plinks), 0, 64, st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::radix_sort_pairs(tmp.get(), bytes, D.key, D.skey, D.val, D.sval, (size_t)(2 * D.n_plinks), 0, 64, st));
+	return hipGetLastError();
+}
+
+// the verdict of every entry with its counters and its keep flag, 8 lanes per entry
+hipError_t reduce_verdicts(const RedDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_red_verdict, dim3(nblk(8 * D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the exclusive scan of the keep flags into D.sc[n_plinks + 1]: D.sc[n_plinks] is what lout has to hold
+hipError_t reduce_scan(const RedDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	auto t = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), RedFlag{D.flag, D.n_plinks});
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, t, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, t, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	return hipGetLastError();
+}
+
+// behind the host's wait for D.sc[n_plinks] <= D.cap: the entries that stay, in input order, and where they came from
+hipError_t reduce_compact(const RedDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_red_compact, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
