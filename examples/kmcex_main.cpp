@@ -54,6 +54,11 @@
 //          within tol windows, k when omitted; rows of more than 64 links are not searched: tol = k and 64 are conventions, not
 //          measured choices): pairs.reduced.tsv (entry, a, b, pairs, verdict, via, witnesses, g, delta).  The scaffolds, and with -F
 //          the pair paths and the fill, are then built from the reduced list.  -T keeps the full list
+//     -J   with -X -S: the contigs are scaffolded from the list of the first pass, lifted to contig coordinates through the place of
+//          every unitig (KModel::pair_lift at -P's max_dist), instead of reading the input once more and mapping every pair onto
+//          the contigs: pairs.lifted.tsv (entry, a, b, pairs, class, A, B, shift, out).  inner is the floor of (the sum of d over
+//          the first pass's pairs on one unitig + the lifted d of the forward SAME entries) / (their number + the pairs of those
+//          entries): what the second pass would have averaged.  -L and -F work on the lifted list as on a mapped one.  Not with -R
 //
 // Same flow: run the KMC counter on the FASTQ input (the reference shells out to ./kmc_api/kmc, main.cpp:137-140;
 // here the binary is taken from $KMC_BIN or ./kmc_api/kmc and skipped when absent so that an existing KMC
@@ -82,6 +87,7 @@ struct Params {
 	long path_tol = -2, path_steps = 8;                            // -T[<tol>[,<max_steps>]]: tol, -1 = k, -2 = no pair paths
 	long fill_kinds = -1;                                          // -F[<kinds>]: the links to fill, -1 = no filled scaffolds
 	long reduce_tol = -2;                                          // -L[<tol>]: tol, -1 = k, -2 = the list is scaffolded as it is
+	bool lift = false;                                             // -J: the contigs' pair list is lifted from the unitigs', not mapped again
 	std::string input, output, workdir = "/tmp";
 };
 
@@ -165,6 +171,7 @@ static bool parse(int argc, char **argv, Params &p)
 			p.reduce_tol = a[2] ? strtol(a + 2, &end, 10) : -1;
 			if (a[2] && (*end || p.reduce_tol < 0 || p.reduce_tol > 0xFFFFFFFFL)) return false;   // not a number of windows
 		}
+		else if (!strcmp(a, "-J")) p.lift = true;
 		else if (!strncmp(a, "-P", 2)) {
 			char *end = nullptr;
 			p.pair_dist = a[2] ? strtol(a + 2, &end, 10) : -1;
@@ -220,6 +227,14 @@ static bool parse(int argc, char **argv, Params &p)
 	}
 	if (p.reduce_tol > -2 && p.scaf_min < 0) {                     // the reduced list is the one the scaffolds are built from
 		std::cout << "-L needs -S: it reduces the list of pair links the scaffolds are built from\n";
+		return false;
+	}
+	if (p.lift && (p.scaf_min < 0 || p.min_reads < 0)) {           // the lifted list is the one the contigs are scaffolded from
+		std::cout << "-J needs -X -S: it lifts the list of pair links to the contigs that are scaffolded\n";
+		return false;
+	}
+	if (p.lift && p.res_min >= 0) {
+		std::cout << "-J does not go with -R: a resolved set, where a unitig lies on several copies, has no place to lift through\n";
 		return false;
 	}
 	return !p.input.empty() && !p.output.empty() && !p.workdir.empty();
@@ -352,7 +367,9 @@ int main(int argc, char **argv)
 		             "           unitig, strand, kind, entry, offset, bytes in front, path)\n"
 		             "       -L[<tol>]  with -S: first drop the pair links that skip a unitig (a -> c where a -> b and b -> c explain its distance within tol\n"
 		             "           (k) windows; rows of more than 64 links are not searched; both are conventions, not measured choices):\n"
-		             "           pairs.reduced.tsv (entry, a, b, pairs, verdict, via, witnesses, g, delta); -S and -F then work on the reduced list\n";
+		             "           pairs.reduced.tsv (entry, a, b, pairs, verdict, via, witnesses, g, delta); -S and -F then work on the reduced list\n"
+		             "       -J   with -X -S: scaffold the contigs from the first pass's pair list lifted to contig coordinates, instead of reading the\n"
+		             "           input once more: pairs.lifted.tsv (entry, a, b, pairs, class, A, B, shift, out); not with -R\n";
 		return 2;
 	}
 	const char *env = getenv("KMC_BIN");
@@ -534,7 +551,22 @@ int main(int argc, char **argv)
 						cg.close();
 						if (!cg) { std::cout << "could not write " << dir << "/contigs.gfa" << std::endl; return 1; }
 					}
-					if (p.scaf_min >= 0) {                                   // the pairs once more, on the contigs and their graph
+					if (p.scaf_min >= 0 && p.lift) {                         // -J: the first pass's list in contig coordinates
+						const kmx_pair_lift_params lp = {pp.max_dist, 0};
+						const KModel::PairLifted lf = km->pair_lift(strs, ct.place, ct.rec, plinks, p.k, lp);
+						std::ofstream lt2((dir + "/pairs.lifted.tsv").c_str());
+						KModel::write_pair_lift_tsv(lt2, plinks, lf);
+						lt2.close();
+						if (!lt2) { std::cout << "could not write " << dir << "/pairs.lifted.tsv" << std::endl; return 1; }
+						InnerSum linner = inner;                             // what the pairs on one contig would have averaged
+						linner.sum += (long double)lf.stats.sum_same_d;
+						linner.n += lf.stats.pairs_same - lf.stats.pairs_same_back;
+						std::cout << "   pair links lifted to the contigs (at most " << lp.max_dist << " windows) :     " << lf.stats.n_link << " of " << lf.stats.n_entries << " links lie between contigs ("
+						          << lf.stats.n_same << " on one contig, " << lf.stats.n_same_back << " of them backward, " << lf.stats.n_inverted << " inverted, " << lf.stats.n_far << " far, "
+						          << lf.stats.n_ignored << " ignored), " << lf.stats.n_out << " distinct" << std::endl;
+						if (!write_scaffolds(km, dir, ct.strs, 0, lf.list, p, linner.inner(), pp.max_dist, "contigs", ct.link_offsets, ct.links)) return 1;
+					}
+					else if (p.scaf_min >= 0) {                              // the pairs once more, on the contigs and their graph
 						std::ifstream in2(p.input.c_str());
 						std::vector<kmx_pair_link> cplinks;
 						InnerSum cinner;

@@ -820,6 +820,50 @@ public:
 		}
 	}
 
+	// Lifted pair lists (the rule: kmx.h): the list seq_pairs left on a unitig set, rewritten in the coordinates of the contigs that
+	// unitig_contigs chained those unitigs into, so that the pairs need not be mapped a second time.  pair_lift takes the unitig
+	// strings (only their lengths are used), place and rec as unitig_contigs returned them and the list; it needs no session and no
+	// graph, and it gives the list room for every entry, so it never comes back short.  unitig_scaffold, pair_reduce, pair_paths and
+	// scaffold_fill on the contigs take `list` as they take a list mapped there.
+	struct PairLifted {
+		std::vector<kmx_pair_lift> rec;              // one per entry of the input list
+		std::vector<kmx_pair_link> list;             // the list in contig coordinates, strictly ascending
+		kmx_pair_lift_stats stats;
+	};
+	PairLifted pair_lift(const std::vector<std::string> &unitigs, const std::vector<kmx_contig_place> &place, const std::vector<kmx_contig> &crec, const std::vector<kmx_pair_link> &plinks, int k,
+	                     const kmx_pair_lift_params &params)
+	{
+		const Flat f(unitigs);
+		const size_t U = unitigs.size(), np = plinks.size();
+		if (place.size() < U) die("pair_lift: place holds one entry per unitig");
+		PairLifted r;
+		r.stats = kmx_pair_lift_stats();
+		r.rec.resize(np + 1);
+		r.list.resize(np + 1);
+		uint64_t n = 0;
+		check(kmx_unitig_pair_lift(h_, k, f.off.data(), U, U ? &place[0] : 0, crec.empty() ? 0 : &crec[0], crec.size(), np ? &plinks[0] : 0, np, &params, &r.rec[0], &r.list[0], np, &n, &r.stats));
+		r.rec.resize(np);
+		r.list.resize((size_t)n);
+		return r;
+	}
+	// the classes as a table, one "<entry>\tu<a><+|->\tu<b><+|->\t<pairs>\t<class>\tc<A><+|->\tc<B><+|->\t<shift>\t<out>" per entry of the
+	// input list: "*" for the contigs of an IGNORED entry and for the out of an entry that is no LINK
+	static void write_pair_lift_tsv(std::ostream &out, const std::vector<kmx_pair_link> &plinks, const PairLifted &p)
+	{
+		static const char *const names[] = {"IGNORED", "SAME", "INVERTED", "LINK", "FAR"};
+		for (size_t i = 0; i < plinks.size() && i < p.rec.size(); i++) {
+			const kmx_pair_link &e = plinks[i];
+			const kmx_pair_lift &r = p.rec[i];
+			out << i << "\tu" << (e.a >> 1) << ((e.a & 1) ? '-' : '+') << "\tu" << (e.b >> 1) << ((e.b & 1) ? '-' : '+') << "\t" << e.n_pairs << "\t" << (r.cls <= KMX_LIFT_FAR ? names[r.cls] : "?") << "\t";
+			if (r.cls == KMX_LIFT_IGNORED) out << "*\t*";
+			else out << "c" << (r.A >> 1) << ((r.A & 1) ? '-' : '+') << "\tc" << (r.B >> 1) << ((r.B & 1) ? '-' : '+');
+			out << "\t" << (long long)r.shift << "\t";
+			if (r.out == 0xFFFFFFFFu) out << "*";
+			else out << r.out;
+			out << "\n";
+		}
+	}
+
 	// Filled scaffolds (the rule: kmx.h): the scaffolds spelled again, with the graph's own bases in every gap that pair_paths found
 	// the one path for (kinds bit 0) and the k - 1 overlap trimmed where two steps share a graph edge (bit 1).  scaffold_fill takes
 	// the unitig strings the scaffolds were made of, what unitig_scaffold and pair_paths returned on the same list, and the list;

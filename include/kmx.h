@@ -1237,9 +1237,9 @@ int kmx_unitig_pair_walks_dev(kmx_model *m, const kmx_walk *d_walks, uint64_t n_
  *   (c) place inverts steps; the n_steps sum to U; n_sbases = n_ubases + the sum of n_gap_bases;
  *   (d) two islands of one genome that the pairs span come out as one scaffold with the hole as a run of 'N' of its true length,
  *       when inner is the library's d.
- * Out of scope: lifting a unitig-level list to contig coordinates through place; comparing bases when est < 0; RF and FF
- * libraries; several GPUs; choosing min_pairs and inner.  Gaps the graph can spell: kmx_unitig_scaffold_fill below.  Links that
- * skip a unitig: kmx_unitig_pair_reduce below drops them from the list before this call.                                    */
+ * Out of scope: comparing bases when est < 0; RF and FF libraries; several GPUs; choosing min_pairs and inner.  Gaps the graph can
+ * spell: kmx_unitig_scaffold_fill below.  Links that skip a unitig: kmx_unitig_pair_reduce below drops them from the list before
+ * this call.  A unitig-level list in contig coordinates through place: kmx_unitig_pair_lift below.                           */
 typedef struct kmx_scaffold_params { uint64_t min_pairs; uint32_t ratio /* [0, 65536] */; uint32_t inner; uint32_t min_n, max_n /* min_n <= max_n */;
                                      uint64_t reserved /* 0 */; } kmx_scaffold_params;                                  /* 32 bytes */
 #define KMX_SCAFFOLD_CIRCULAR 0x80000000u
@@ -1581,6 +1581,110 @@ int kmx_unitig_pair_reduce_dev(kmx_model *m, int k, const uint64_t *d_uoffsets /
 /* seconds[4] of the last of these two calls under kmx_set_profile(m, 1): the rows, the sort, the verdicts, the scan with the
  * wait and the compaction */
 int kmx_unitig_pair_reduce_last_phases(kmx_model *m, double *seconds /* [4] */);
+
+/* ---- lifted pair lists: a pair list with unitig keys and unitig distances, rewritten in the coordinates of the contigs those
+ * unitigs were chained into.  kmx_unitig_contigs returns place[u], the contig, strand and k-mer offset of every unitig; the
+ * distance of a list entry moves by a constant that depends only on its two unitigs.  So the list that a second mapping of the
+ * same pairs onto the contigs would build is a function of the first list, place and the contigs' lengths, and the pairs need
+ * not be read and mapped again.  kmx_unitig_scaffold, kmx_unitig_pair_reduce, kmx_unitig_pair_paths and
+ * kmx_unitig_scaffold_fill on the contig set consume the result unchanged.  It needs no built model, no session, no bases and no
+ * CSR.
+ * Input: k, odd, in [5, 63]; uoffsets[U + 1], U < 2^31, read only for m_u = len_u - k + 1 (0 for what is shorter than k); place[U]
+ *   and crec[C] as kmx_unitig_contigs left them (of crec only n_kmers is read), C <= U; plinks[n_plinks] as
+ *   kmx_unitig_pair_walks leaves it, n_plinks < 2^31; and kmx_pair_lift_params, reserved = 0.  All arithmetic is signed 64-bit.
+ *   WHERE AN ORIENTED UNITIG LIES.  o = 2 u + d < 2 U, P = place[u], c = P.oc >> 1, s = P.oc & 1, M = crec[c].n_kmers, m = m_u.
+ *     o is PLACED iff c < C, M < 2^32 and P.off + m <= M.  It lies along the oriented contig O(o) = 2 c + (d ^ s), and
+ *     start(o) = P.off when d ^ s = 0, else M - P.off - m: the windows of O(o) in front of it.  head(o) = start(o) and
+ *     tail(o) = M - start(o) - m, the windows behind it.
+ *   CLASS of entry i = (a, b, n_pairs, sum_dist, min_dist, max_dist); the first that applies:
+ *   KMX_LIFT_IGNORED   a >= 2 U, b >= 2 U, a >> 1 == b >> 1, n_pairs == 0, or an end that is not placed;
+ *   with A = O(a) and B = O(b):
+ *   KMX_LIFT_SAME      A == B: both mates lie on one oriented contig.  shift = start(b) - start(a) - m_a + 1, so that the d of
+ *                      every pair of the entry at the contig level is its dist + shift.  The entry is FORWARD when
+ *                      min_dist + shift >= 0; otherwise its pairs contradict the order of the contig and n_same_back counts it;
+ *   KMX_LIFT_INVERTED  A == B ^ 1.  shift = 0;
+ *   otherwise shift = tail(a) + head(b), lo = min_dist + shift, hi = max_dist + shift, and
+ *   KMX_LIFT_FAR       lo > max_dist (of the parameters) or hi >= 2^32: no pair of the entry is within reach, or the maximum
+ *                      cannot be stored;
+ *   KMX_LIFT_LINK      otherwise.  It contributes (key, n_pairs, sum_dist + n_pairs * shift wrapping in 64 bits, lo, hi), where key
+ *                      is canonical as in the pair call: (A, B) when A << 32 | B is smaller than (B ^ 1) << 32 | (A ^ 1), else
+ *                      (B ^ 1, A ^ 1).  The two are never equal: that would be an INVERTED entry.
+ * Output.  lout[capacity] with *n_out: the LINK contributions, strictly ascending by key, equal keys folded by sum, sum, minimum
+ *   and maximum: exactly a list kmx_unitig_pair_walks could have left for the contig set.  lrec[n_plinks], one record below per
+ *   input entry: cls; out, the index of the output entry it was folded into, 0xFFFFFFFF when it is no LINK; A and B before
+ *   canonicalisation, 0 for an IGNORED entry; shift (0 when IGNORED); flipped, 1 when a LINK's key is the mirror; reserved = 0.
+ *   *n_out > capacity with a list: KMX_E_RANGE with *n_out the number needed, lout untouched, and lrec and stats complete;
+ *   capacity = n_plinks always suffices.  lout == NULL with capacity 0 is the sizing call: KMX_OK, *n_out what a list would
+ *   hold, lrec and stats complete.  On the HOST in both forms: *n_out and kmx_pair_lift_stats: the entries of each class (n_same
+ *   includes the n_same_back backward ones), n_out, the n_pairs of the entries of each class (sums modulo 2^64), pairs_same_back,
+ *   and sum_same_d = the sum of (sum_dist + n_pairs * shift) over the FORWARD SAME entries: the lifted d of their pairs.
+ * Consequences:
+ *   (a) with a place from a contig call that merged nothing (every contig one unitig: c = u, s = 0, off = 0) and
+ *       max_dist = 2^32 - 1, lout is the input byte for byte, for a canonical list of pair links;
+ *   (b) replacing an entry by its mirror (b ^ 1, a ^ 1) changes A, B and flipped of its record and nothing in lout (head and tail
+ *       swap under the mirror, and start(b ^ 1) - start(a ^ 1) - m_b = start(b) - start(a) - m_a); permuting the input entries
+ *       (_dev form) changes only the order of lrec;
+ *   (c) pairs are conserved: the pairs of the five classes sum to the n_pairs of the input, and the n_pairs of lout to pairs_link;
+ *   (d) re-mapping equivalence: for pairs whose every read is one walk on the unitigs and one walk on the contigs, with no pair
+ *       FAR at either level, lout equals byte for byte the list kmx_unitig_pair_walks builds when the same pairs are mapped onto
+ *       the contigs (same max_dist), and (the sum of d over the SAME pairs on the unitigs) + sum_same_d is the sum of d over the
+ *       SAME pairs on the contigs;
+ *   (e) every output is an integer count, sum, minimum or maximum and a function of the input alone: byte-identical across runs,
+ *       forms and fold variants.
+ * Out of scope: lifting to scaffold coordinates (kmx_scaffold_place, base offsets with 'N'); lifting `through` or walks;
+ * splitting an entry whose pairs straddle max_dist (the entry is a LINK with its whole count as soon as its nearest pair is
+ * within reach); insert-size histograms from SAME entries; several GPUs; choosing max_dist.                                  */
+#define KMX_LIFT_IGNORED  0
+#define KMX_LIFT_SAME     1
+#define KMX_LIFT_INVERTED 2
+#define KMX_LIFT_LINK     3
+#define KMX_LIFT_FAR      4
+typedef struct kmx_pair_lift_params { uint32_t max_dist; uint32_t reserved /* 0 */; } kmx_pair_lift_params;                 /* 8 bytes */
+typedef struct kmx_pair_lift {           /* one per entry of the input list; 32 bytes, no padding */
+	uint32_t cls;                        /* KMX_LIFT_* */
+	uint32_t out;                        /* the entry of lout it was folded into, 0xFFFFFFFF for none */
+	uint32_t A, B;                       /* O(a), O(b); 0 when IGNORED */
+	int64_t shift;                       /* what the entry's distances move by; 0 when IGNORED or INVERTED */
+	uint32_t flipped;                    /* 1: the key in lout is (B ^ 1, A ^ 1) */
+	uint32_t reserved;                   /* 0 */
+} kmx_pair_lift;
+typedef struct kmx_pair_lift_stats { uint64_t n_entries, n_ignored, n_same, n_inverted, n_link, n_far, n_same_back, n_out,
+                                     pairs_ignored, pairs_same, pairs_inverted, pairs_link, pairs_far, pairs_same_back;
+                                     int64_t sum_same_d; uint64_t reserved; } kmx_pair_lift_stats;                       /* 128 bytes */
+/* On HOST buffers.  Needs no built model and no session (like kmx_unitig_pair_reduce); it runs on the model's stream and is a
+ * build-class call.  lout may be NULL (with capacity 0); plinks and lrec with n_plinks == 0, place with U == 0 and crec with
+ * C == 0; every other buffer is required.  KMX_E_ARG before anything runs: an even or out-of-range k, U >= 2^31,
+ * n_plinks >= 2^31, C > U, reserved != 0, a NULL required buffer, a capacity without a list, an output that overlaps an input or
+ * another output; uoffsets whose first entry is not 0, that decrease, or that give a unitig fewer than k bytes; a place[u] that is
+ * not placed; a list that is not strictly ascending by a << 32 | b.  n_plinks == 0: KMX_OK, an empty list and all counts zero.
+ * U == 0: KMX_OK, an empty list; every entry is IGNORED and counted as such, so that (c) holds.  KMX_E_NOMEM leaves the handle
+ * usable.  The call returns when the output is complete.                                                                    */
+int kmx_unitig_pair_lift(kmx_model *m, int k, const uint64_t *uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, const kmx_contig_place *place /* [n_unitigs] */,
+                         const kmx_contig *crec /* [n_contigs] */, uint64_t n_contigs, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_lift_params *params,
+                         kmx_pair_lift *lrec /* [n_plinks] */, kmx_pair_link *lout /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_out, kmx_pair_lift_stats *stats);
+/* The same on DEVICE buffers, read where the contig and pair calls left them; params, *n_out and stats are on the HOST.  It
+ * checks k, U, C, n_plinks, the parameters, NULL and overlap, and validates nothing else; the kernels clamp instead: uoffsets
+ * into [0, n_ubases]; an end that is not placed (an oc beyond C included) makes the entry IGNORED; and the list is taken as it is
+ * (not ascending, duplicate keys, an entry beside its mirror: all of them fold into the same lout).  Every store is checked
+ * against its capacity: bad device input gives wrong classes and never an access outside a buffer.  It enqueues the classes,
+ * one stable radix sort of the n_plinks (key, index) pairs, the scan of the key changes, the fold and the store on the model's
+ * stream and waits once, for *n_out and the counters; the store writes lout only where the merged count fits, which it checks
+ * on the device.  Device memory, kept on the handle between calls through the owning types of hip_owned.h: 96 bytes per entry
+ * (2 x (8 + 4) for the sort's double buffers, 32 for the shifted item, 32 for the merged record, 8 for the scan) plus rocPRIM's
+ * scratch.  The host form also stages its input and output there.                                                           */
+int kmx_unitig_pair_lift_dev(kmx_model *m, int k, const uint64_t *d_uoffsets /* [n_unitigs + 1] */, uint64_t n_unitigs, uint64_t n_ubases, const kmx_contig_place *d_place /* [n_unitigs] */,
+                             const kmx_contig *d_crec /* [n_contigs] */, uint64_t n_contigs, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_lift_params *params /* HOST */,
+                             kmx_pair_lift *d_lrec /* [n_plinks] */, kmx_pair_link *d_lout /* [capacity] or NULL */, uint64_t capacity, uint64_t *n_out /* HOST */,
+                             kmx_pair_lift_stats *stats /* HOST */);
+/* which fold kernel the next lift calls on the handle run: the segmented reduction inside a wavefront or the plain fold with
+ * four atomics per item.  Both give the same bytes; the call exists so that the two can be measured on the same buffers
+ * (tools/bench_unitig_pair_lift.py).  A handle starts with the library's default.                          */
+#define KMX_LIFT_FOLD_WAVE  0
+#define KMX_LIFT_FOLD_PLAIN 1
+int kmx_unitig_pair_lift_fold_variant(kmx_model *m, int variant);
+/* seconds[4] of the last of the two lift calls under kmx_set_profile(m, 1): the classes, the sort, the scan with the fold, the
+ * store with the wait */
+int kmx_unitig_pair_lift_last_phases(kmx_model *m, double *seconds /* [4] */);
 
 /* KModel::save(dir) -> header, km.bin, rest.bin (dir must exist)           kmodel.hpp:173-206 */
 int kmx_save(kmx_model *m, const char *dir);

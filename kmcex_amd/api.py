@@ -64,6 +64,7 @@ ABI_SYMBOLS = [
     "kmx_unitig_scaffold", "kmx_unitig_scaffold_dev", "kmx_unitig_scaffold_last_phases",
     "kmx_unitig_pair_paths", "kmx_unitig_pair_paths_dev", "kmx_unitig_pair_paths_last_phases",
     "kmx_unitig_pair_reduce", "kmx_unitig_pair_reduce_dev", "kmx_unitig_pair_reduce_last_phases",
+    "kmx_unitig_pair_lift", "kmx_unitig_pair_lift_dev", "kmx_unitig_pair_lift_fold_variant", "kmx_unitig_pair_lift_last_phases",
     "kmx_unitig_scaffold_fill", "kmx_unitig_scaffold_fill_dev", "kmx_unitig_scaffold_fill_last_phases",
 ]
 
@@ -323,6 +324,27 @@ PAIR_REDUCE_VERDICTS = {0: "IGNORED", 1: "BELOW_MIN", 2: "KEPT", 3: "TRANSITIVE"
 PAIR_REDUCE_NO_VIA = 0xFFFFFFFF
 
 
+class PairLiftParams(C.Structure):
+    """kmx_pair_lift_params of include/kmx.h: 8 bytes"""
+    _fields_ = [("max_dist", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PairLiftStats(C.Structure):
+    """kmx_pair_lift_stats of include/kmx.h: 128 bytes"""
+    _fields_ = [(f, C.c_uint64) for f in ("n_entries", "n_ignored", "n_same", "n_inverted", "n_link", "n_far", "n_same_back", "n_out", "pairs_ignored", "pairs_same", "pairs_inverted",
+                                          "pairs_link", "pairs_far", "pairs_same_back")] + [("sum_same_d", C.c_int64), ("reserved", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+# kmx_pair_lift as a NumPy structured dtype (what KModel.unitig_pair_lift_flat returns): 32 bytes
+PAIR_LIFT_DTYPE = np.dtype([("cls", "<u4"), ("out", "<u4"), ("A", "<u4"), ("B", "<u4"), ("shift", "<i8"), ("flipped", "<u4"), ("reserved", "<u4")])
+PAIR_LIFT_CLASSES = {0: "IGNORED", 1: "SAME", 2: "INVERTED", 3: "LINK", 4: "FAR"}
+PAIR_LIFT_NO_OUT = 0xFFFFFFFF
+PAIR_LIFT_FOLDS = {"wave": 0, "plain": 1}
+
+
 class RingList(C.Structure):
     """kmx_ring_list of include/kmx.h"""
     _fields_ = [("list", C.c_int32), ("n_host", C.c_int32), ("src_kmers", C.c_void_p), ("src_counts", C.c_void_p),
@@ -483,6 +505,10 @@ def load_library():
     _sig(L, "kmx_unitig_pair_reduce", [vp, C.c_int, vp, u64, vp, u64, C.POINTER(PairReduceParams), vp, vp, vp, u64, p64, C.POINTER(PairReduceStats)])
     _sig(L, "kmx_unitig_pair_reduce_dev", [vp, C.c_int, vp, u64, u64, vp, u64, C.POINTER(PairReduceParams), vp, vp, vp, u64, p64, C.POINTER(PairReduceStats)])
     _sig(L, "kmx_unitig_pair_reduce_last_phases", [vp, C.POINTER(C.c_double)])
+    _sig(L, "kmx_unitig_pair_lift", [vp, C.c_int, vp, u64, vp, vp, u64, vp, u64, C.POINTER(PairLiftParams), vp, vp, u64, p64, C.POINTER(PairLiftStats)])
+    _sig(L, "kmx_unitig_pair_lift_dev", [vp, C.c_int, vp, u64, u64, vp, vp, u64, vp, u64, C.POINTER(PairLiftParams), vp, vp, u64, p64, C.POINTER(PairLiftStats)])
+    _sig(L, "kmx_unitig_pair_lift_fold_variant", [vp, C.c_int])
+    _sig(L, "kmx_unitig_pair_lift_last_phases", [vp, C.POINTER(C.c_double)])
     _sig(L, "kmx_unitig_scaffold_fill", [vp, C.c_int, vp, vp, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
     _sig(L, "kmx_unitig_scaffold_fill_dev", [vp, C.c_int, vp, vp, u64, u64, vp, u64, vp, vp, u64, vp, vp, u64, C.POINTER(FillParams), vp, u64, vp, vp, vp, vp, u64, p64, p64, C.POINTER(FillStats)])
     _sig(L, "kmx_unitig_scaffold_fill_last_phases", [vp, C.POINTER(C.c_double)])
@@ -1584,6 +1610,77 @@ class KModel:
         _, _, _, uoffs = _join_seqs(list(strs))
         rec, lout, _, rst = self.unitig_pair_reduce_flat(k, uoffs, plinks, inner, int(k) if tol is None else int(tol), min_pairs, max_row)
         return self.scaffolds_from_pairs(k, strs, lout, inner, min_pairs, ratio, min_n, max_n) + (rec, lout, rst)
+
+    # ---- lifted pair lists: a unitig-level pair list in contig coordinates (the rule: include/kmx.h); no model, no session
+    def unitig_pair_lift_flat(self, k: int, uoffsets: np.ndarray, place: np.ndarray, crec: np.ndarray, plinks: np.ndarray, max_dist: int, capacity=None, lists: bool = True):
+        """kmx_unitig_pair_lift on the offsets of a unitig set (uint64 [U + 1]), the CONTIG_PLACE_DTYPE place [U] and CONTIG_DTYPE
+        records [C] unitig_contigs_flat returned for it, and the PAIR_LINK_DTYPE list unitig_pairs_flat left on the unitigs ->
+        (PAIR_LIFT_DTYPE records [n_plinks], the PAIR_LINK_DTYPE list in contig coordinates or None, stats as a dict).  capacity
+        None: n_plinks, which always suffices; a number: that many entries (KmxError KMX_E_RANGE when short: its `needed` the
+        entries needed, its `result` the records and the stats).  lists False: the sizing call."""
+        uoffsets = np.ascontiguousarray(uoffsets, dtype=np.uint64)
+        place = np.ascontiguousarray(place, dtype=CONTIG_PLACE_DTYPE)
+        crec = np.ascontiguousarray(crec, dtype=CONTIG_DTYPE)
+        plinks = np.ascontiguousarray(plinks, dtype=PAIR_LINK_DTYPE)
+        nu, nc, np_ = uoffsets.size - 1, crec.size, plinks.size
+        if place.size != nu:
+            raise KmxError(-1, "place holds one entry per unitig")
+        cap = np_ if capacity is None else int(capacity)
+        rec = np.zeros(max(np_, 1), dtype=PAIR_LIFT_DTYPE)
+        lout = np.zeros(max(cap, 1), dtype=PAIR_LINK_DTYPE) if lists else None
+        par, st, n = PairLiftParams(int(max_dist), 0), PairLiftStats(), C.c_uint64(0)
+        try:
+            _chk(self.L.kmx_unitig_pair_lift(self.h, int(k), uoffsets.ctypes.data, nu, place.ctypes.data if nu else None, crec.ctypes.data if nc else None, nc,
+                                             plinks.ctypes.data if np_ else None, np_, C.byref(par), rec.ctypes.data, lout.ctypes.data if lists else None, cap if lists else 0, C.byref(n),
+                                             C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            e.result = (rec[:np_].copy(), st.as_dict())
+            raise
+        return rec[:np_].copy(), (lout[:n.value].copy() if lists else None), st.as_dict()
+
+    def unitig_pair_lift_dev(self, k: int, d_uoffsets, n_ubases: int, d_place, d_crec, n_contigs: int, d_plinks, n_plinks: int, max_dist: int, capacity=None, out=None):
+        """kmx_unitig_pair_lift_dev on torch tensors of the model's device, read where the contig and pair calls left them:
+        d_uoffsets int64 [U + 1], d_place int32 [U, 2], d_crec uint8 [>= n_contigs, 64], d_plinks uint8 [>= n_plinks, 32].  out:
+        (d_lrec uint8 [n_plinks, 32], d_lout uint8 [capacity, 32] or None for the sizing call), allocated when None with
+        `capacity` entries (None: n_plinks) -> (out, the entries of the lifted list, stats as a dict).  KmxError KMX_E_RANGE
+        carries the entries needed in `needed` and the stats in `result`."""
+        import torch
+        nu, dev = d_uoffsets.numel() - 1, d_uoffsets.device
+        if out is None:
+            cap = int(n_plinks) if capacity is None else int(capacity)
+            out = (torch.zeros((max(int(n_plinks), 1), 32), dtype=torch.uint8, device=dev), torch.zeros((max(cap, 1), 32), dtype=torch.uint8, device=dev))
+        else:
+            cap = (out[1].shape[0] if out[1] is not None else 0) if capacity is None else int(capacity)
+        par, st, n = PairLiftParams(int(max_dist), 0), PairLiftStats(), C.c_uint64(0)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        try:
+            _chk(self.L.kmx_unitig_pair_lift_dev(self.h, int(k), d_uoffsets.data_ptr(), nu, int(n_ubases), ptr(d_place) if nu else None, ptr(d_crec) if n_contigs else None, int(n_contigs),
+                                                 ptr(d_plinks) if n_plinks else None, int(n_plinks), C.byref(par), out[0].data_ptr(), ptr(out[1]), cap, C.byref(n), C.byref(st)))
+        except KmxError as e:
+            e.needed = int(n.value)
+            e.result = st.as_dict()
+            raise
+        return out, int(n.value), st.as_dict()
+
+    def unitig_pair_lift_fold(self, variant) -> None:
+        """kmx_unitig_pair_lift_fold_variant: "wave" or "plain" (or its number), the fold kernel of the next lift calls; for measuring"""
+        _chk(self.L.kmx_unitig_pair_lift_fold_variant(self.h, int(PAIR_LIFT_FOLDS.get(variant, variant))))
+
+    def unitig_pair_lift_phases(self) -> dict:
+        """kmx_unitig_pair_lift_last_phases: seconds per phase of the last lift call (under set_profile(1))"""
+        sec = (C.c_double * 4)()
+        _chk(self.L.kmx_unitig_pair_lift_last_phases(self.h, sec))
+        return dict(zip(("classify", "sort", "fold", "store"), (float(x) for x in sec)))
+
+    def lifted_scaffolds_from_pairs(self, k: int, ustrs, place: np.ndarray, crec: np.ndarray, cstrs, plinks: np.ndarray, inner: int, max_dist: int, min_pairs: int = 2, ratio: int = 0,
+                                    min_n: int = 10, max_n: int = 1000):
+        """on the unitig strings a pair list was built on, the place and records unitig_contigs_flat returned for them and the contig
+        strings: unitig_pair_lift_flat at max_dist, then scaffolds_from_pairs of the contigs on the lifted list -> (what
+        scaffolds_from_pairs returns, then the lift records, the lifted list and the lift stats)"""
+        _, _, _, uoffs = _join_seqs(list(ustrs))
+        rec, lout, lst = self.unitig_pair_lift_flat(k, uoffs, place, crec, plinks, max_dist)
+        return self.scaffolds_from_pairs(k, cstrs, lout, inner, min_pairs, ratio, min_n, max_n) + (rec, lout, lst)
 
     # ---- filled scaffolds: the scaffolds spelled again with the graph's bases in the gaps the pair paths cross (the rule:
     # include/kmx.h); no model, no session, no CSR

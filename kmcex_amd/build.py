@@ -10,7 +10,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libkmx.so")
 SOURCES = ["kernels.hip", "rest_device.hip", "count_device.hip", "edit_device.hip", "polish_device.hip", "unitig_device.hip", "kmx_api.hip", "kmc_reader.cpp", "reads_reader.cpp", "strpack.cpp"]
-HEADERS = ["device_common.h", "kmx_types.h", "hip_owned.h", "launchers.h", "kmc_reader.h", "strpack.h", "range_kernels.h", "multi_build.h", "rank_crew.h", "range_host.h", "count_kernels.h", "correct_kernels.h", "edit_kernels.h", "extend_kernels.h", "count_host.h", "graph_checks.h", "graph_host.h", "unitig_kernels.h", "unitig_host.h", "map_kernels.h", "walk_kernels.h", "map_host.h", "contig_kernels.h", "contig_host.h", "resolve_kernels.h", "resolve_host.h", "pair_kernels.h", "pair_host.h", "scaffold_kernels.h", "scaffold_host.h", "pair_path_kernels.h", "pair_path_host.h", "fill_kernels.h", "fill_host.h", "reduce_kernels.h", "reduce_host.h", "reads_reader.h", os.path.join("..", "..", "include", "kmx.h")]
+HEADERS = ["device_common.h", "kmx_types.h", "hip_owned.h", "launchers.h", "kmc_reader.h", "strpack.h", "range_kernels.h", "multi_build.h", "rank_crew.h", "range_host.h", "count_kernels.h", "correct_kernels.h", "edit_kernels.h", "extend_kernels.h", "count_host.h", "graph_checks.h", "graph_host.h", "unitig_kernels.h", "unitig_host.h", "map_kernels.h", "walk_kernels.h", "map_host.h", "contig_kernels.h", "contig_host.h", "resolve_kernels.h", "resolve_host.h", "pair_kernels.h", "pair_host.h", "scaffold_kernels.h", "scaffold_host.h", "pair_path_kernels.h", "pair_path_host.h", "fill_kernels.h", "fill_host.h", "reduce_kernels.h", "reduce_host.h", "lift_kernels.h", "lift_host.h", "reads_reader.h", os.path.join("..", "..", "include", "kmx.h")]
 
 
 def hipcc() -> str:

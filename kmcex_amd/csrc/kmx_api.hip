@@ -154,6 +154,14 @@ struct RestEnt { u64 w[2]; int c; };
 // ------------------------------------------------------------------------------------------ the model
 enum { ST_EMPTY = 0, ST_BUILDING = 1, ST_READY = 2 };
 
+// The fold kernel a handle starts with in kmx_unitig_pair_lift* (lift_kernels.h): the fold inside the wavefront, or with
+// -DKMX_LIFT_PLAIN_FOLD the lane-per-item fold it was measured against.
+#ifdef KMX_LIFT_PLAIN_FOLD
+#define KMX_LIFT_FOLD_DEFAULT KMX_LIFT_FOLD_PLAIN
+#else
+#define KMX_LIFT_FOLD_DEFAULT KMX_LIFT_FOLD_WAVE
+#endif
+
 // Ownership: every device / pinned buffer, stream and event below is a member that releases itself (hip_owned.h), so
 // kmx_destroy is `delete` once the caller's stream has drained.  Members go in reverse order of declaration, and a Stream
 // drains before it is destroyed: inside KmcFeed, QueryFeed and the probe the streams are declared AFTER the events and the
@@ -443,6 +451,16 @@ struct kmx_model {
 		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
 		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): rows, sort, verdicts, scan with the wait and the compaction
 	} red;
+	// kmx_unitig_pair_lift* (lift_host.h): the work arrays of a call, kept by capacity from call to call
+	struct LiftState {
+		DevBuf<u64> d_key, d_sc;                                   // d_key: [2][E] the items' keys and their sorted copy; d_sc: [E + 1] the scanned key changes
+		DevBuf<u32> d_idx;                                         // [2][E] the items' indices and their sorted copy
+		DevBuf<PairLink> d_item;                                   // [2][E] the shifted items, then the merged records
+		DevBuf<unsigned long long> d_cnt;                          // [LIFT_C_N]
+		DevBuf<unsigned char> d_tmp;                               // rocPRIM scratch
+		int fold = KMX_LIFT_FOLD_DEFAULT;                          // the fold kernel of the next call (kmx_unitig_pair_lift_fold_variant)
+		double phase_s[4] = {0, 0, 0, 0};                          // under kmx_set_profile(m, 1): classes, sort, scan and fold, store with the wait
+	} lift;
 };
 
 // the end of a map session: its index and work arrays go (after the stream has drained)
@@ -2979,6 +2997,7 @@ static int kmx_extend_seqs_impl(kmx_model *m, const char *seq, const uint64_t *o
 #include "pair_path_host.h"
 #include "fill_host.h"
 #include "reduce_host.h"
+#include "lift_host.h"
 
 // ------------------------------------------------------------------------------------------ persistence
 static int download_array(kmx_model *m, int which, int index, std::vector<unsigned char> &out)
@@ -3529,6 +3548,10 @@ extern "C" int kmx_unitig_scaffold_fill_last_phases(kmx_model *m, double *second
 extern "C" int kmx_unitig_pair_reduce(kmx_model *m, int k, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_reduce_params *params, kmx_pair_reduce *rrecs, kmx_pair_link *lout, uint32_t *origin, uint64_t capacity, uint64_t *n_out, kmx_pair_reduce_stats *stats) { return guarded([&] { return kmx_unitig_pair_reduce_impl(m, RedArgs{k, uoffsets, n_unitigs, 0, plinks, n_plinks, params, rrecs, lout, origin, capacity, n_out, stats}); }); }
 extern "C" int kmx_unitig_pair_reduce_dev(kmx_model *m, int k, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_reduce_params *params, kmx_pair_reduce *d_rrecs, kmx_pair_link *d_lout, uint32_t *d_origin, uint64_t capacity, uint64_t *n_out, kmx_pair_reduce_stats *stats) { return guarded([&] { return kmx_unitig_pair_reduce_dev_impl(m, RedArgs{k, d_uoffsets, n_unitigs, n_ubases, d_plinks, n_plinks, params, d_rrecs, d_lout, d_origin, capacity, n_out, stats}); }); }
 extern "C" int kmx_unitig_pair_reduce_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_pair_reduce_last_phases_impl(m, seconds); }); }
+extern "C" int kmx_unitig_pair_lift(kmx_model *m, int k, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_contig_place *place, const kmx_contig *crec, uint64_t n_contigs, const kmx_pair_link *plinks, uint64_t n_plinks, const kmx_pair_lift_params *params, kmx_pair_lift *lrec, kmx_pair_link *lout, uint64_t capacity, uint64_t *n_out, kmx_pair_lift_stats *stats) { return guarded([&] { return kmx_unitig_pair_lift_impl(m, LiftArgs{k, uoffsets, n_unitigs, 0, place, crec, n_contigs, plinks, n_plinks, params, lrec, lout, capacity, n_out, stats}); }); }
+extern "C" int kmx_unitig_pair_lift_dev(kmx_model *m, int k, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_contig_place *d_place, const kmx_contig *d_crec, uint64_t n_contigs, const kmx_pair_link *d_plinks, uint64_t n_plinks, const kmx_pair_lift_params *params, kmx_pair_lift *d_lrec, kmx_pair_link *d_lout, uint64_t capacity, uint64_t *n_out, kmx_pair_lift_stats *stats) { return guarded([&] { return kmx_unitig_pair_lift_dev_impl(m, LiftArgs{k, d_uoffsets, n_unitigs, n_ubases, d_place, d_crec, n_contigs, d_plinks, n_plinks, params, d_lrec, d_lout, capacity, n_out, stats}); }); }
+extern "C" int kmx_unitig_pair_lift_fold_variant(kmx_model *m, int variant) { return guarded([&] { return kmx_unitig_pair_lift_fold_variant_impl(m, variant); }); }
+extern "C" int kmx_unitig_pair_lift_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_pair_lift_last_phases_impl(m, seconds); }); }
 extern "C" int kmx_unitig_resolve(kmx_model *m, int k, const char *useq, const uint64_t *uoffsets, uint64_t n_unitigs, const kmx_unitig *urec, const uint64_t *link_offsets, const uint32_t *links, uint64_t n_links, const uint64_t *link_hits, const uint64_t *through, const kmx_resolve_params *params, char *rseq, uint64_t seq_capacity, uint64_t *roffsets, uint64_t rec_capacity, kmx_unitig *rrec, uint32_t *origin, kmx_resolve_place *rplace, uint64_t *rlink_offsets, uint32_t *rlinks, uint64_t *link_origin, uint64_t *rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_impl(m, ResArgs{k, useq, uoffsets, n_unitigs, 0, urec, link_offsets, links, n_links, link_hits, through, params, rseq, seq_capacity, roffsets, rec_capacity, rrec, origin, rplace, rlink_offsets, rlinks, link_origin, rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_dev(kmx_model *m, int k, const char *d_useq, const uint64_t *d_uoffsets, uint64_t n_unitigs, uint64_t n_ubases, const kmx_unitig *d_urec, const uint64_t *d_link_offsets, const uint32_t *d_links, uint64_t n_links, const uint64_t *d_link_hits, const uint64_t *d_through, const kmx_resolve_params *params, char *d_rseq, uint64_t seq_capacity, uint64_t *d_roffsets, uint64_t rec_capacity, kmx_unitig *d_rrec, uint32_t *d_origin, kmx_resolve_place *d_rplace, uint64_t *d_rlink_offsets, uint32_t *d_rlinks, uint64_t *d_link_origin, uint64_t *d_rlink_hits, uint64_t *n_unitigs_out, uint64_t *n_bases_out, kmx_resolve_stats *stats) { return guarded([&] { return kmx_unitig_resolve_dev_impl(m, ResArgs{k, d_useq, d_uoffsets, n_unitigs, n_ubases, d_urec, d_link_offsets, d_links, n_links, d_link_hits, d_through, params, d_rseq, seq_capacity, d_roffsets, rec_capacity, d_rrec, d_origin, d_rplace, d_rlink_offsets, d_rlinks, d_link_origin, d_rlink_hits, n_unitigs_out, n_bases_out, stats}); }); }
 extern "C" int kmx_unitig_resolve_last_phases(kmx_model *m, double *seconds) { return guarded([&] { return kmx_unitig_resolve_last_phases_impl(m, seconds); }); }

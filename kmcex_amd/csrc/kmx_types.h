@@ -739,6 +739,39 @@ struct RedDev {
 	u64 *sc;                     // [n_plinks + 1]
 	unsigned long long *cnt;     // [RED_C_N]
 };
+// kmx_unitig_pair_lift*: the record of a list entry, the layout of kmx_pair_lift (include/kmx.h; lift_host.h asserts it) ...
+struct PairLift {
+	u32 cls, out, A, B;
+	long long shift;
+	u32 flipped, reserved;
+};
+// ... the classes (KMX_LIFT_* of include/kmx.h), which are also the first five counters of a call; behind them the backward SAME
+// entries, the pairs of the five classes and of the backward SAME entries, and the lifted d of the forward SAME entries ...
+enum { LIFT_IGNORED = 0, LIFT_SAME, LIFT_INVERTED, LIFT_LINK, LIFT_FAR, LIFT_C_SAME_BACK, LIFT_C_PAIRS /* + class */, LIFT_C_PAIRS_SAME_BACK = LIFT_C_PAIRS + 5, LIFT_C_SUM_SAME_D, LIFT_C_N };
+static constexpr u64 LIFT_NO_KEY = ~0ULL;                        // the key of an entry that is no LINK: behind every real key
+enum { LIFT_FOLD_WAVE = 0, LIFT_FOLD_PLAIN = 1 };
+// ... and the input, the work arrays and the output of one call (lift_kernels.h).  The work item of entry i: key[i] = its canonical
+// contig key A << 32 | B (LIFT_NO_KEY when it is no LINK), idx[i] = i, item[i] = (A, B, n, sum, lo, hi) after the shift; skey, sidx:
+// key and idx sorted by key, stably; sc[n_plinks + 1]: the key changes in front of a sorted item, sc[n_plinks] is n_out;
+// mrg[n_plinks]: the merged records, their min_dist inverted so that all zero is the neutral element.  Every array of the caller is
+// read and written under the bounds given here: U, n_ubases, C, n_plinks, cap.
+struct LiftDev {
+	int k, fold;                 // fold: LIFT_FOLD_*
+	u64 U, n_ubases, C, n_plinks, cap;
+	const u64 *uoffs;            // [U + 1]
+	const CtgPlace *place;       // [U]
+	const Contig *crec;          // [C]
+	const PairLink *plinks;      // [n_plinks]
+	u32 max_dist;
+	PairLift *lrec;              // [n_plinks]
+	PairLink *lout;              // [cap] or null
+	u64 *key, *skey;             // [n_plinks] each
+	u32 *idx, *sidx;             // [n_plinks] each
+	PairLink *item;              // [n_plinks]
+	PairLink *mrg;               // [n_plinks]
+	u64 *sc;                     // [n_plinks + 1]
+	unsigned long long *cnt;     // [LIFT_C_N]
+};
 // rank state per oriented node: pair = pointer << 32 | rank (a head points at itself with rank 0), mn = the smallest listing
 // index among the `rank` nodes from this one back (what a cycle is cut at)
 

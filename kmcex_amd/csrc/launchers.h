@@ -133,4 +133,10 @@ hipError_t reduce_sort(const RedDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t reduce_verdicts(const RedDev &, hipStream_t);
 hipError_t reduce_scan(const RedDev &, DevBuf<unsigned char> &tmp, hipStream_t);
 hipError_t reduce_compact(const RedDev &, hipStream_t);
+// ... and kmx_unitig_pair_lift* (lift_kernels.h): the classes with the work items, their sort, the scan of the key changes (its
+// total in D.sc[D.n_plinks]) with the fold, the records' run indices with the list
+hipError_t lift_classify(const LiftDev &, hipStream_t);
+hipError_t lift_sort(const LiftDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t lift_fold(const LiftDev &, DevBuf<unsigned char> &tmp, hipStream_t);
+hipError_t lift_store(const LiftDev &, hipStream_t);
 }   // namespace kmxk

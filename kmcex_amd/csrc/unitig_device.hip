@@ -5,8 +5,9 @@
 // resolve_kernels.h (kmx_unitig_walk_through*); its host side is resolve_host.h.  Behind them the launcher of pair_kernels.h
 // (kmx_unitig_pair_walks*); its host side is pair_host.h.  Last the launchers of scaffold_kernels.h (kmx_unitig_scaffold*); their
 // host side is scaffold_host.h.  Behind them the launchers of pair_path_kernels.h (kmx_unitig_pair_paths*); their host side is
-// pair_path_host.h.  Then the launchers of fill_kernels.h (kmx_unitig_scaffold_fill*); their host side is fill_host.h.  Last the
-// launchers of reduce_kernels.h (kmx_unitig_pair_reduce*); their host side is reduce_host.h.
+// pair_path_host.h.  Then the launchers of fill_kernels.h (kmx_unitig_scaffold_fill*); their host side is fill_host.h.  Then the
+// launchers of reduce_kernels.h (kmx_unitig_pair_reduce*); their host side is reduce_host.h.  Last the launchers of lift_kernels.h
+// (kmx_unitig_pair_lift*); their host side is lift_host.h.
 #include "hip_owned.h"
 #include "launchers.h"
 #include "unitig_kernels.h"
@@ -19,6 +20,7 @@
 #include "pair_path_kernels.h"
 #include "fill_kernels.h"
 #include "reduce_kernels.h"
+#include "lift_kernels.h"
 #include <cstring>
 #include <rocprim/rocprim.hpp>
 
@@ -475,6 +477,48 @@ hipError_t reduce_scan(const RedDev &D, DevBuf<unsigned char> &tmp, hipStream_t 
 hipError_t reduce_compact(const RedDev &D, hipStream_t st)
 {
 	hipLaunchKernelGGL(k_red_compact, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// ---- kmx_unitig_pair_lift* (lift_kernels.h); D.n_plinks > 0
+
+// the class and the record of every entry with the call's counters, and its work item
+hipError_t lift_classify(const LiftDev &D, hipStream_t st)
+{
+	RCHK(hipMemsetAsync(D.cnt, 0, LIFT_C_N * sizeof(unsigned long long), st));
+	hipLaunchKernelGGL(k_lift_classify, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// the work items sorted by their contig key: the sort is stable, and the entries that are no LINK come last
+hipError_t lift_sort(const LiftDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	RCHK(rocprim::radix_sort_pairs(nullptr, bytes, D.key, D.skey, D.idx, D.sidx, (size_t)D.n_plinks, 0, 64, st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::radix_sort_pairs(tmp.get(), bytes, D.key, D.skey, D.idx, D.sidx, (size_t)D.n_plinks, 0, 64, st));
+	return hipGetLastError();
+}
+
+// the exclusive scan of the key changes into D.sc[n_plinks + 1] (D.sc[n_plinks] is what lout has to hold), then the fold of
+// every run into D.mrg: whole wavefronts, since every lane takes part in the shuffles of the wave fold
+hipError_t lift_fold(const LiftDev &D, DevBuf<unsigned char> &tmp, hipStream_t st)
+{
+	size_t bytes = 0;
+	auto flags = rocprim::make_transform_iterator(rocprim::counting_iterator<u64>(0), LiftKeyFlag{D.skey, D.n_plinks});
+	RCHK(rocprim::exclusive_scan(nullptr, bytes, flags, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	RCHK(tmp.ensure(bytes, st));
+	RCHK(rocprim::exclusive_scan(tmp.get(), bytes, flags, D.sc, (u64)0, (size_t)(D.n_plinks + 1), rocprim::plus<u64>(), st));
+	RCHK(hipMemsetAsync(D.mrg, 0, D.n_plinks * sizeof(PairLink), st));
+	if (D.fold == LIFT_FOLD_PLAIN) hipLaunchKernelGGL(k_lift_fold<LIFT_FOLD_PLAIN>, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	else hipLaunchKernelGGL(k_lift_fold<LIFT_FOLD_WAVE>, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
+	return hipGetLastError();
+}
+
+// lrec[].out of every LINK entry, and the merged records into lout where their count fits D.cap
+hipError_t lift_store(const LiftDev &D, hipStream_t st)
+{
+	hipLaunchKernelGGL(k_lift_store, dim3(nblk(D.n_plinks)), dim3(256), 0, st, D);
 	return hipGetLastError();
 }
 
